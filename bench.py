@@ -12,15 +12,24 @@ model is broadcast once over RCCL before timing and the outputs are all-gathered
   --config 5   configs[4]: random 128-body tree, RNEA + ABA, fp32, 1 048 576 sharded       (strong scaling)
   (no flag)    the metric: humanoid RNEA + ABA, fp64, 4096 per GPU                       (weak scaling)
 
-Timing: --ramp-ms (100) milliseconds of untimed steps for the device's clocks, W warm-up steps, then R (25; at least 5 for the long-running configurations) timed REGIONS of exactly K steps each, every region bracketed by barrier + synchronize on both
-sides; `value` and `ms_per_step` come from the MEDIAN region (max over ranks per region), all regions are listed in `region_ms`.  Each is
-followed by a region of the same K steps with HIP events recorded on the launch stream (`event_region_ms`): the roofline's kernel
-durations come from those, `value` from the regions that carry nothing but the steps.  After
-the timed regions the outputs the last step left in HBM are checked against the CPU oracle on a strided sample (`check`).
+Timing: --ramp-ms (100) milliseconds of untimed steps for the device's clocks, W warm-up steps, then ONE timed region of exactly K steps,
+bracketed by barrier + synchronize on both sides (max over ranks); `value` and `ms_per_step` come from it.  Nothing else runs in a plain
+invocation: it sets up, warms up, times the K steps, writes the outputs of the last step when --dump-outputs DIR is given, and prints the
+line.
 
-Prints ONE JSON line on rank 0 (see the contract in the task description), including
+--full adds everything beside the headline figure, as measured before it existed: R (25; at least 5 for the long-running configurations)
+timed REGIONS of K steps each, `value` and `ms_per_step` from the MEDIAN region, all regions listed in `region_ms`; each region followed by
+a region of the same K steps with HIP events recorded on the launch stream (`event_region_ms`), the roofline's kernel durations come from
+those; rocprofv3 counter passes of the dominant kernel in child processes (plain runs of this script) before this process touches the GPU;
+after the timed regions the outputs the last step left in HBM checked against the CPU oracle on a strided sample (`check`); and
   "roofline":     algorithmic bytes of the dominant kernel / its mean launch duration (HIP events on the launch stream)
   "cpu_baseline": the CPU oracle (a port, not Mecano/JVM) timed on the host cores (one thread each) on a bounded sample of the same workload.
+
+--dump-outputs DIR: after the timed steps, the arrays the timed call returned in its last step (rank 0's rows), one DIR/<name>.npy each
+(rnea_tau, aba_qdd, crba_H; float64, float32 for config 5); beyond DUMP_BYTES in all, the same fixed seeded sample of rows of each.  The
+inputs are drawn from fixed seeds, so two builds run with the same arguments can be compared output for output.
+
+Prints ONE JSON line on rank 0 (see the contract in the task description).
 """
 from __future__ import annotations
 
@@ -41,6 +50,8 @@ HBM_PEAK_GBS = 8000.0        # MI355X_MICROARCH.md: 8 TB/s spec
 MEASURED_COPY_GBS = 6290.0   # device copy kernel measured on this pool (profiles/r01_integrate_rates.txt)
 CLOCK_HZ, N_SIMDS = 2.4e9, 1024  # MI355X_MICROARCH.md: 256 CUs x 4 SIMDs
 REGIONS = 25  # 25 regions of the driver's 20 steps are 8 ms of the headline: the median of 25 rests on more than 1.6 ms of GPU time
+DUMP_BYTES = 60_000_000  # --dump-outputs: at most this many bytes of array data in all (a seeded sample of rows beyond it)
+DUMP_SEED = 7
 
 
 def cpu_baseline(desc, q, qd, qdd, tau, gravity, jobs, target_s=20.0):
@@ -146,7 +157,7 @@ def _pmc_pass(counters, B, pick, config=0):
     try:
         env = dict(os.environ, TMPDIR="/tmp", MH_BENCH_PMC_INNER="1")
         subprocess.run([exe, "--pmc"] + list(counters) + ["-d", out, "-o", "pmc", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__),
-                        "--steps", "20", "--warmup", "5", "--regions", "1", "--no-cpu-baseline", "--batch", str(B)] + (["--config", str(config)] if config else []),
+                        "--steps", "20", "--warmup", "5", "--batch", str(B)] + (["--config", str(config)] if config else []),
                        cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=150, check=True)
         vals = {c: [] for c in counters}
         for f in glob.glob(os.path.join(out, "**", "*counter_collection.csv"), recursive=True):
@@ -211,7 +222,7 @@ def _pmc_call_sum(counter, B, config, per_call, parts, min_grid=65536):
     try:
         env = dict(os.environ, TMPDIR="/tmp", MH_BENCH_PMC_INNER="1")
         subprocess.run([exe, "--pmc", counter, "-d", out, "-o", "pmc", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__),
-                        "--steps", "5", "--warmup", "2", "--regions", "1", "--ramp-ms", "0", "--no-cpu-baseline", "--batch", str(B), "--config", str(config)],
+                        "--steps", "5", "--warmup", "2", "--ramp-ms", "0", "--batch", str(B), "--config", str(config)],
                        cwd="/tmp", env=env, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=200, check=True)
         total, calls = 0.0, 0
         for f in glob.glob(os.path.join(out, "**", "*counter_collection.csv"), recursive=True):
@@ -253,6 +264,23 @@ def live_issue_counters(B, config=0):
     return _pmc_pass(["SQ_INSTS_VALU", "SQ_WAVE_CYCLES", "SQ_WAIT_ANY", "SQ_WAVES"], B, config4_kernel_pick(B) if config == 4 else headline_kernel_pick(B), config)
 
 
+def dump_outputs(out_dir, outputs, budget=DUMP_BYTES):
+    """--dump-outputs: every tensor of `outputs` ({name: [B, ...]}, rows = configurations) as out_dir/<name>.npy in its own dtype.  When
+    they hold more than `budget` bytes in all, the same sorted sample of rows of each, drawn from DUMP_SEED, so that two runs with the same
+    arguments write the same rows.  Returns the row indices written (None: all of them)."""
+    import torch
+    B = next(iter(outputs.values())).shape[0]
+    row_bytes = sum(t[0].numel() * t.element_size() for t in outputs.values())
+    rows = None
+    if B * row_bytes > budget:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(B, budget // row_bytes, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in outputs.items():
+        part = t if rows is None else t[torch.as_tensor(rows, device=t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), part.cpu().numpy())
+    return rows
+
+
 def self_launch(n):
     """One rank process per GPU, started from a parent that never touches the GPU (no torch import, no HIP call, no exec of an
     initialised process): RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in each child's environment, rank 0's stdout (the JSON line) relayed,
@@ -286,10 +314,15 @@ def main():
     ap.add_argument("--config", type=int, default=0, choices=(0, 3, 4, 5), help="BASELINE.json configuration (1-based); default 0 = the metric")
     ap.add_argument("--batch", type=int, default=0, help="configurations per step: per GPU for the weak-scaling workloads, in total for --config 4 / 5")
     ap.add_argument("--ramp-ms", type=float, default=100.0, help="untimed steps for this long before the W warm-up steps (device clocks; 0: none)")
-    ap.add_argument("--regions", type=int, default=0, help=f"timed regions of --steps steps each; the median is reported.  0 (default): {REGIONS}, fewer (>= 5) when 2 x regions x steps would take longer than ~12 s")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="everything beside the headline figure: the median of --regions timed regions with HIP-event "
+                    "regions between them (kernels_ms, roofline, rocprofv3 counter passes), the check against the CPU oracle, the CPU baseline")
+    ap.add_argument("--regions", type=int, default=0, help=f"--full: timed regions of --steps steps each; the median is reported.  0 (default): {REGIONS}, fewer (>= 5) when 2 x regions x steps would take longer than ~12 s")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baseline")
     ap.add_argument("--separate", action="store_true", help="two calls per step (mh_rnea_f64, then mh_aba_f64 / mh_crba_f64) instead of mh_rnea_aba_f64 / mh_rnea_crba_f64")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the outputs of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.regions and not args.full:
+        ap.error("--regions needs --full (a plain run times exactly one region of --steps steps)")
 
     # `python3 bench.py --gpus N` without a launcher: this process becomes a GPU-free parent of N fresh rank processes
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -299,12 +332,13 @@ def main():
     if env_world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={env_world}: launch with torch.distributed.run --nproc-per-node {args.gpus}, or unset WORLD_SIZE")
 
-    # roofline.traffic measured for this run (N = 1, the metric's configuration), in child processes, before this one touches the GPU
-    headline = args.gpus == 1 and args.config in (0, 4) and not args.separate
+    # --full: roofline.traffic measured for this run (N = 1, the metric's configuration), in child processes, before this one touches the GPU
+    full = args.full
+    headline = full and args.gpus == 1 and args.config in (0, 4) and not args.separate
     pmc_batch = args.batch or (262144 if args.config == 4 else BATCH)
     pmc_bytes = live_traffic(pmc_batch, args.config) if headline else None
     call_bytes = None
-    if args.gpus == 1 and args.config in (3, 5) and not args.separate:
+    if full and args.gpus == 1 and args.config in (3, 5) and not args.separate:
         call_bytes = live_traffic_of_call(args.batch or (1048576 if args.config == 5 else BATCH), args.config)
     sq = live_issue_counters(pmc_batch, args.config) if headline else None
 
@@ -419,8 +453,11 @@ def main():
     # the roofline's kernel durations come from (`kernels_ms`, `event_region_ms`).  The events are instrumentation with a cost of their
     # own inside a region -- an event pair around 20 steps of the headline: 7-8 us of 340 (profiles/r04_region_overhead.txt) -- so the
     # figure the metric is quoted on is taken where they are absent, and the host clock of the event regions is printed beside it.
+    # A plain run is ONE clock region of exactly K steps; the regions below are --full's.
     K, R = args.steps, args.regions
-    if R <= 0:  # every rank must loop the same number of times: rank 0 decides
+    if not full:
+        R = 1
+    elif R <= 0:  # every rank must loop the same number of times: rank 0 decides
         R = max(5, min(REGIONS, int(12.0 / max(1e-9, 2 * K * step_s_estimate))))
         if world > 1:
             r_t = torch.tensor([R], dtype=torch.int64, device="cuda" if dist.get_backend() == "nccl" else "cpu")
@@ -471,10 +508,20 @@ def main():
 
     for r in range(R):
         region(False)
-        region(True)
+        if full:
+            region(True)
     elapsed = float(np.sort(region_s)[len(region_s) // 2])
-    med = int(np.argsort(event_region_s)[len(event_region_s) // 2])
-    kernels_ms = {j: v[med] for j, v in kernel_ms.items()}
+    kernels_ms = None
+    if full:
+        med = int(np.argsort(event_region_s)[len(event_region_s) // 2])
+        kernels_ms = {j: v[med] for j, v in kernel_ms.items()}
+
+    # ---- what the timed call returned in its last step, as its caller receives it (rank 0's rows; a fixed seeded sample of rows beyond
+    # DUMP_BYTES: the same rows of every output)
+    results = {"rnea": tau if fused else outs.get("rnea"), "aba": acc if fused else outs.get("aba"), "crba": Hm if fused else outs.get("crba")}
+    if args.dump_outputs and rank == 0:
+        files = {"rnea": "rnea_tau", "aba": "aba_qdd", "crba": "crba_H"}
+        dump_outputs(args.dump_outputs, {files[j]: results[j] for j in jobs})
 
     # ---- after the timed regions: one all-gather of the outputs over xGMI (north_star: "a final gather"), per-rank kernel times
     gather_ms, per_rank = None, None
@@ -482,10 +529,10 @@ def main():
         last = (acc if cfg == 0 else tau) if fused else outs.get("aba", outs.get("rnea"))
         torch.cuda.synchronize()
         t1 = time.perf_counter()
-        full = mdist.all_gather_rows(last, B_total)
+        gathered = mdist.all_gather_rows(last, B_total)
         torch.cuda.synchronize()
         gather_ms = (time.perf_counter() - t1) * 1e3
-        assert full.shape[0] == B_total
+        assert gathered.shape[0] == B_total
         per_rank = [None] * world
         dist.all_gather_object(per_rank, {"rank": rank, "batch": B, "kernels_ms": kernels_ms, "device": device_id})
 
@@ -501,52 +548,6 @@ def main():
             dist.destroy_process_group()
         return
 
-    # ---- the outputs of the launches that were timed, against the CPU oracle on a strided sample (outside the timed regions).
-    # fp64: ABSOLUTE 1e-10 on every entry (north_star's bar; what tests/test_gpu_parity.py asserts on configs 2-4).  fp32: the bounds of
-    # tests/helpers.py (u = 2^-24, rounding errors of ~8 n operations adding up like a random walk): forward 4 sqrt(8 n) u max(1, |ref|)
-    # for RNEA / CRBA; forward dynamics by its backward error, as the tests do: the fp64 inverse dynamics of the fp32 answer must
-    # reproduce the given efforts within 16 sqrt(8 n) u (|tau| + |RNEA bias|) (its forward error is conditioning-bound and reported only).
-    idx = np.arange(0, B, max(1, B // 64))[:64]
-    check = {"rows": int(len(idx)), "tol": 1e-10 if word == 8 else None}
-    got = {"rnea": tau if fused else outs.get("rnea"), "aba": acc if fused else outs.get("aba"), "crba": Hm if fused else outs.get("crba")}
-    ok = True
-    try:
-        from oracle.cpu_oracle import OracleModel
-        om = OracleModel(desc)
-    except Exception as exc:  # no oracle build on this host (it is test infrastructure): the check is skipped, not failed
-        om, check = None, {"ok": None, "skipped": True, "reason": f"oracle unavailable: {exc}"}  # null, never a truthy placeholder: an unverified run is not a passed one
-    if om is not None:
-        q64, qd64, qdd64, tau64 = (np.asarray(x[idx % base], dtype=np_dt).astype(np.float64) for x in (q, qd, qdd, tau_in))
-        u32 = 2.0 ** -24
-        for job in jobs:
-            ref = {"rnea": lambda: om.rnea(q64, qd64, qdd64, gravity), "aba": lambda: om.aba(q64, qd64, tau64, gravity), "crba": lambda: om.crba(q64)}[job]()
-            mine = got[job][torch.as_tensor(idx, device="cuda")].cpu().numpy().astype(np.float64)
-            err = float(np.abs(mine - ref).max())
-            check[f"max_err_{job}"] = err
-            if word == 8:
-                ok = ok and err <= 1e-10
-            elif job == "aba":
-                back = om.rnea(q64, qd64, mine, gravity)
-                bias = om.rnea(q64, qd64, np.zeros_like(mine), gravity)
-                check["backward_err_aba"] = float(np.abs(back - tau64).max())
-                check["bound_aba"] = 16 * (8 * desc.n_joints) ** 0.5 * u32 * (float(np.abs(tau64).max()) + float(np.abs(bias).max()))
-                ok = ok and np.isfinite(err) and check["backward_err_aba"] <= check["bound_aba"]
-            else:
-                check[f"bound_{job}"] = 4 * (8 * desc.n_joints) ** 0.5 * u32 * max(1.0, float(np.abs(ref).max()))
-                ok = ok and err <= check[f"bound_{job}"]
-        check["ok"] = bool(ok)
-
-    fused_launch = fused and model.kernel_variant.startswith("topo:") and 2 * ((B + 63) // 64) <= 256  # one launch computes both outputs
-    bytes_of = {"rnea": bytes_rnea, "aba": bytes_aba, "crba": bytes_crba, "rnea_aba": bytes_rnea + bytes_aba, "rnea_crba": bytes_rnea + bytes_crba}
-    if fused:  # one launch computing both: 968 + 968 (config 3: 968 + 7448) algorithmic bytes per configuration
-        dom, dom_name = fused_key, fused_key.replace("_", "+") + (" fused" if fused_launch else " (two launches)")
-        if cfg == 5:  # mh_rnea_aba_f32 on a big AoS batch: transposed copies in, ONE depth-first walk for both algorithms, results transposed back
-            dom_name = "rnea+aba, the whole call (one fused depth-first walk + six AoS <-> SoA transposes)"
-    else:      # dominant kernel = the slowest launch of a step
-        dom = max(kernels_ms, key=kernels_ms.get)
-        dom_name = dom
-    dom_ms, dom_bytes = kernels_ms[dom], bytes_of[dom]
-    achieved = (dom_bytes * B) / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
     value = B_total * K / elapsed if elapsed > 0 else 0.0
     names = {0: "robot-configs/sec (RNEA+ABA), 30-DoF humanoid batch=4096", 3: "robot-configs/sec (RNEA+CRBA), 30-DoF humanoid batch=4096",
              4: "robot-configs/sec (ABA), 30-DoF humanoid batch=262144 sharded", 5: "robot-configs/sec (RNEA+ABA), random 128-body tree fp32 batch=1M sharded"}
@@ -554,32 +555,6 @@ def main():
                  3: "30-DoF humanoid, RNEA and CRBA (30 x 30 mass matrix) of every configuration per step, fp64, AoS",
                  4: "30-DoF humanoid, ABA of every configuration per step, fp64, AoS, batch sharded over the GPUs",
                  5: "random 128-body tree (revolute / prismatic / 6-DoF joints), RNEA and ABA per step, fp32, AoS, batch sharded over the GPUs"}
-    one_launch = fused_launch or (cfg == 4 and model.kernel_variant.startswith("topo:") and (B + 63) // 64 > 256)  # the counters were picked for that launch
-    if pmc_bytes is not None and one_launch:
-        traffic, traffic_source = pmc_bytes, "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, child processes of this run), 2 x FETCH + WRITE"
-    elif call_bytes is not None:
-        traffic, traffic_source = call_bytes, "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, child processes of this run), 2 x FETCH + WRITE summed over the kernels of one call"
-    else:
-        traffic, traffic_source = committed_traffic(fused_launch and cfg == 0, B)
-    # The bounding roofline is HBM by north_star's reporting rule; what actually limits the launch is read off the counters: a launch
-    # whose HBM traffic is near its algorithmic bytes and far below the bandwidth roof, with few waves per SIMD, is bound by one wave's
-    # instruction issue.  valu_busy_frac prices a wave64 instruction at 4 cycles of its SIMD (1024 SIMDs, 2.4 GHz: MI355X_MICROARCH.md).
-    roofline = {"bound": "hbm", "kernel": dom_name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_copy": achieved / MEASURED_COPY_GBS, "measured_copy": MEASURED_COPY_GBS,
-                "traffic": traffic, "traffic_source": traffic_source, "bytes_per_config": dom_bytes, "launch_ms": dom_ms}
-    if sq is not None and one_launch and dom_ms > 0:
-        simd_cycles = dom_ms * 1e-3 * CLOCK_HZ * N_SIMDS
-        roofline.update({"valu_insts_per_launch": sq["SQ_INSTS_VALU"], "waves_per_launch": sq["SQ_WAVES"],
-                         "valu_busy_frac": 4.0 * sq["SQ_INSTS_VALU"] / simd_cycles,
-                         "wait_frac": sq["SQ_WAIT_ANY"] / sq["SQ_WAVE_CYCLES"] if sq["SQ_WAVE_CYCLES"] else None,
-                         "issue_counters_source": "rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAVES (child process of this run)"})
-        few_waves = sq["SQ_WAVES"] <= N_SIMDS
-        roofline["limited_by"] = ("instruction issue of single waves (at most one wave per SIMD, traffic far below the HBM roof)"
-                                  if few_waves and roofline["frac"] < 0.25 else ("hbm" if roofline["frac"] >= 0.5 else "vector issue / latency"))
-        if cfg == 4:  # launch geometry: persistent workgroups of four waves, two per CU (240 registers, 78 KB of LDS each), resident for the whole launch
-            roofline["waves_per_simd"] = min((B + 63) // 64, 512) * 4 / N_SIMDS
-    else:
-        roofline["limited_by"] = None
     line = {
         "metric": names[cfg],
         "value": value, "unit": "configs/s", "n_gpus": world, "steps": K, "warmup": args.warmup,
@@ -590,24 +565,99 @@ def main():
                    "batch_per_gpu": B, "global_batch": B_total, "nq": nq, "nv": nv, "bodies": desc.n_joints,
                    "parallelism": f"dp{world} (batch sharded, no data-path collective)", "kernel_variant": model.kernel_variant,
                    "model_seed": MODEL_SEED if cfg != 5 else 128, "state_seed": STATE_SEED},
-        "ramp_ms": args.ramp_ms, "regions": R, "region_ms": [s * 1e3 for s in region_s], "reported_region": "median",
+        "full": full,
+        "ramp_ms": args.ramp_ms, "regions": R, "region_ms": [s * 1e3 for s in region_s], "reported_region": "median" if full else "single",
         "region_ms_min": min(region_s) * 1e3, "region_ms_max": max(region_s) * 1e3,
         "devices_distinct": (len({(d["host"], d["pci"] or d["uuid"] or d["device_index"]) for d in devices}) == world),
         "shared_gpu_rehearsal": bool(shared_gpu_rehearsal),
-        "event_region_ms": [s * 1e3 for s in event_region_s],  # the same K steps with the HIP events of `kernels_ms` / `roofline` recorded around them
-        "roofline": roofline,
-        "kernels_ms": kernels_ms,
         "per_rank": per_rank,
         "rccl_ranks": rccl_ranks,
         "dist_backend": (dist.get_backend() if world > 1 else None),
         "gather_ms": gather_ms,
-        "check": check,
     }
-    # CPU baseline beside it: rank 0 at N = 1 only (a reported baseline, not the optimisation target)
-    line["cpu_baseline"] = None
-    if world == 1 and not args.no_cpu_baseline:
-        jvm = mecano_jvm_baseline() if cfg == 0 else None  # the true Mecano figure when a JVM and the jars are on the box ...
-        line["cpu_baseline"] = jvm or cpu_baseline(desc, q, qd, qdd, tau_in, gravity, jobs)  # ... else the C restatement ("port")
+    ok = True
+    if full:
+        # ---- the outputs of the launches that were timed, against the CPU oracle on a strided sample (outside the timed regions).
+        # fp64: ABSOLUTE 1e-10 on every entry (north_star's bar; what tests/test_gpu_parity.py asserts on configs 2-4).  fp32: the bounds of
+        # tests/helpers.py (u = 2^-24, rounding errors of ~8 n operations adding up like a random walk): forward 4 sqrt(8 n) u max(1, |ref|)
+        # for RNEA / CRBA; forward dynamics by its backward error, as the tests do: the fp64 inverse dynamics of the fp32 answer must
+        # reproduce the given efforts within 16 sqrt(8 n) u (|tau| + |RNEA bias|) (its forward error is conditioning-bound and reported only).
+        idx = np.arange(0, B, max(1, B // 64))[:64]
+        check = {"rows": int(len(idx)), "tol": 1e-10 if word == 8 else None}
+        try:
+            from oracle.cpu_oracle import OracleModel
+            om = OracleModel(desc)
+        except Exception as exc:  # no oracle build on this host (it is test infrastructure): the check is skipped, not failed
+            om, check = None, {"ok": None, "skipped": True, "reason": f"oracle unavailable: {exc}"}  # null, never a truthy placeholder: an unverified run is not a passed one
+        if om is not None:
+            q64, qd64, qdd64, tau64 = (np.asarray(x[idx % base], dtype=np_dt).astype(np.float64) for x in (q, qd, qdd, tau_in))
+            u32 = 2.0 ** -24
+            for job in jobs:
+                ref = {"rnea": lambda: om.rnea(q64, qd64, qdd64, gravity), "aba": lambda: om.aba(q64, qd64, tau64, gravity), "crba": lambda: om.crba(q64)}[job]()
+                mine = results[job][torch.as_tensor(idx, device="cuda")].cpu().numpy().astype(np.float64)
+                err = float(np.abs(mine - ref).max())
+                check[f"max_err_{job}"] = err
+                if word == 8:
+                    ok = ok and err <= 1e-10
+                elif job == "aba":
+                    back = om.rnea(q64, qd64, mine, gravity)
+                    bias = om.rnea(q64, qd64, np.zeros_like(mine), gravity)
+                    check["backward_err_aba"] = float(np.abs(back - tau64).max())
+                    check["bound_aba"] = 16 * (8 * desc.n_joints) ** 0.5 * u32 * (float(np.abs(tau64).max()) + float(np.abs(bias).max()))
+                    ok = ok and np.isfinite(err) and check["backward_err_aba"] <= check["bound_aba"]
+                else:
+                    check[f"bound_{job}"] = 4 * (8 * desc.n_joints) ** 0.5 * u32 * max(1.0, float(np.abs(ref).max()))
+                    ok = ok and err <= check[f"bound_{job}"]
+            check["ok"] = bool(ok)
+
+        fused_launch = fused and model.kernel_variant.startswith("topo:") and 2 * ((B + 63) // 64) <= 256  # one launch computes both outputs
+        bytes_of = {"rnea": bytes_rnea, "aba": bytes_aba, "crba": bytes_crba, "rnea_aba": bytes_rnea + bytes_aba, "rnea_crba": bytes_rnea + bytes_crba}
+        if fused:  # one launch computing both: 968 + 968 (config 3: 968 + 7448) algorithmic bytes per configuration
+            dom, dom_name = fused_key, fused_key.replace("_", "+") + (" fused" if fused_launch else " (two launches)")
+            if cfg == 5:  # mh_rnea_aba_f32 on a big AoS batch: transposed copies in, ONE depth-first walk for both algorithms, results transposed back
+                dom_name = "rnea+aba, the whole call (one fused depth-first walk + six AoS <-> SoA transposes)"
+        else:      # dominant kernel = the slowest launch of a step
+            dom = max(kernels_ms, key=kernels_ms.get)
+            dom_name = dom
+        dom_ms, dom_bytes = kernels_ms[dom], bytes_of[dom]
+        achieved = (dom_bytes * B) / (dom_ms * 1e-3) / 1e9 if dom_ms > 0 else 0.0
+        one_launch = fused_launch or (cfg == 4 and model.kernel_variant.startswith("topo:") and (B + 63) // 64 > 256)  # the counters were picked for that launch
+        if pmc_bytes is not None and one_launch:
+            traffic, traffic_source = pmc_bytes, "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, child processes of this run), 2 x FETCH + WRITE"
+        elif call_bytes is not None:
+            traffic, traffic_source = call_bytes, "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes, child processes of this run), 2 x FETCH + WRITE summed over the kernels of one call"
+        else:
+            traffic, traffic_source = committed_traffic(fused_launch and cfg == 0, B)
+        # The bounding roofline is HBM by north_star's reporting rule; what actually limits the launch is read off the counters: a launch
+        # whose HBM traffic is near its algorithmic bytes and far below the bandwidth roof, with few waves per SIMD, is bound by one wave's
+        # instruction issue.  valu_busy_frac prices a wave64 instruction at 4 cycles of its SIMD (1024 SIMDs, 2.4 GHz: MI355X_MICROARCH.md).
+        roofline = {"bound": "hbm", "kernel": dom_name, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                    "frac": achieved / HBM_PEAK_GBS, "frac_of_measured_copy": achieved / MEASURED_COPY_GBS, "measured_copy": MEASURED_COPY_GBS,
+                    "traffic": traffic, "traffic_source": traffic_source, "bytes_per_config": dom_bytes, "launch_ms": dom_ms}
+        if sq is not None and one_launch and dom_ms > 0:
+            simd_cycles = dom_ms * 1e-3 * CLOCK_HZ * N_SIMDS
+            roofline.update({"valu_insts_per_launch": sq["SQ_INSTS_VALU"], "waves_per_launch": sq["SQ_WAVES"],
+                             "valu_busy_frac": 4.0 * sq["SQ_INSTS_VALU"] / simd_cycles,
+                             "wait_frac": sq["SQ_WAIT_ANY"] / sq["SQ_WAVE_CYCLES"] if sq["SQ_WAVE_CYCLES"] else None,
+                             "issue_counters_source": "rocprofv3 --pmc SQ_INSTS_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAVES (child process of this run)"})
+            few_waves = sq["SQ_WAVES"] <= N_SIMDS
+            roofline["limited_by"] = ("instruction issue of single waves (at most one wave per SIMD, traffic far below the HBM roof)"
+                                      if few_waves and roofline["frac"] < 0.25 else ("hbm" if roofline["frac"] >= 0.5 else "vector issue / latency"))
+            if cfg == 4:  # launch geometry: persistent workgroups of four waves, two per CU (240 registers, 78 KB of LDS each), resident for the whole launch
+                roofline["waves_per_simd"] = min((B + 63) // 64, 512) * 4 / N_SIMDS
+        else:
+            roofline["limited_by"] = None
+        line.update({
+            "event_region_ms": [s * 1e3 for s in event_region_s],  # the same K steps with the HIP events of `kernels_ms` / `roofline` recorded around them
+            "roofline": roofline,
+            "kernels_ms": kernels_ms,
+            "check": check,
+        })
+        # CPU baseline beside it: rank 0 at N = 1 only (a reported baseline, not the optimisation target)
+        line["cpu_baseline"] = None
+        if world == 1 and not args.no_cpu_baseline:
+            jvm = mecano_jvm_baseline() if cfg == 0 else None  # the true Mecano figure when a JVM and the jars are on the box ...
+            line["cpu_baseline"] = jvm or cpu_baseline(desc, q, qd, qdd, tau_in, gravity, jobs)  # ... else the C restatement ("port")
     print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -1602,7 +1602,7 @@ def test_bench_launches_its_own_ranks(torch_cuda):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(MECANO_DIST_BACKEND="gloo", MH_BENCH_NO_PMC="1")
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--regions", "1",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--full", "--regions", "1",
                         "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -1630,7 +1630,7 @@ def test_bench_refuses_more_ranks_than_devices_under_rccl(torch_cuda):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "MECANO_DIST_BACKEND")}
     env.update(MH_BENCH_NO_PMC="1")
-    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--regions", "1",
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--full", "--regions", "1",
                         "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode != 0
     assert "HIP device(s) visible" in p.stderr and not [l for l in p.stdout.splitlines() if l.startswith("{")], (p.stdout, p.stderr[-1500:])
@@ -1650,7 +1650,7 @@ def test_config4_strong_scaling_path_on_five_ranks_with_a_ragged_total(torch_cud
     env.update(MECANO_DIST_BACKEND="gloo", MH_BENCH_NO_PMC="1")
     total = 262144 + 5
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "5", "--config", "4", "--batch", str(total), "--steps", "3", "--warmup", "1",
-                        "--regions", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--regions", "1", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout

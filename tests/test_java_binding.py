@@ -130,7 +130,9 @@ def with_natural_padding(fields):
     return out, ofs
 
 
-@pytest.mark.parametrize("c_name, text, const", [("mh_options", NATIVE, "OPTIONS"), ("mh_model_desc", MODEL, "DESC")])
+# explicit ids: without them pytest names each case after the whole Java source it is given (12-16 KB per id)
+@pytest.mark.parametrize("c_name, text, const", [("mh_options", NATIVE, "OPTIONS"), ("mh_model_desc", MODEL, "DESC")],
+                         ids=["mh_options", "mh_model_desc"])
 def test_struct_layouts_match_the_header(c_name, text, const):
     want, _ = with_natural_padding(c_struct(c_name))
     assert java_struct(text, const) == want

@@ -10,10 +10,10 @@ if has rates; then
     timeout -k 10 200 python tools/exp_zvb2.py 8192 16384 24576 32768 49152 65536 131072 262144 2>&1 | grep "B=" || exit 1; } > $out/r04_zvf_vs_others.txt || exit 1
 fi
 if has bench; then
-  timeout -k 10 400 python bench.py --config 4 > $out/r04_bench_config4.json 2> $out/r04_bench_config4.err || exit 1
-  timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $out/r04_bench_line_driver_flags.json 2> $out/r04_bench_line.err || exit 1
-  timeout -k 10 400 python bench.py > $out/r04_bench_line.json 2>> $out/r04_bench_line.err || exit 1
-  timeout -k 10 400 python bench.py --config 3 > $out/r04_bench_config3.json 2>> $out/r04_bench_line.err || exit 1
+  timeout -k 10 400 python bench.py --full --config 4 > $out/r04_bench_config4.json 2> $out/r04_bench_config4.err || exit 1
+  timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $out/r04_bench_line_driver_flags.json 2> $out/r04_bench_line.err || exit 1
+  timeout -k 10 400 python bench.py --full > $out/r04_bench_line.json 2>> $out/r04_bench_line.err || exit 1
+  timeout -k 10 400 python bench.py --full --config 3 > $out/r04_bench_config3.json 2>> $out/r04_bench_line.err || exit 1
 fi
 if has stamps; then
   MH_SPEC_DIR=$root/exp_probe MH_ZVF=2 MH_ZV=0 timeout -k 10 120 python tools/exp_zvf_probe.py 262144 2>&1 | grep -v "self-check\|amdgpu.ids" > $out/r04_zvf_phase_stamps.txt || exit 1

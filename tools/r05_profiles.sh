@@ -5,11 +5,11 @@ set -o pipefail
 parts=${@:-bench trace pair counters c2 all}
 has() { [[ " $parts " == *" $1 "* ]]; }
 if has bench; then
-  timeout -k 10 400 python bench.py > $out/r05_bench_line_final.json 2> $out/r05_bench_line.err || exit 1
-  timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $out/r05_bench_line_driver_flags.json 2>> $out/r05_bench_line.err || exit 1
-  timeout -k 10 400 python bench.py --config 3 > $out/r05_bench_config3.json 2>> $out/r05_bench_line.err || exit 1
-  timeout -k 10 400 python bench.py --config 4 > $out/r05_bench_config4.json 2>> $out/r05_bench_line.err || exit 1
-  timeout -k 10 600 python bench.py --config 5 > $out/r05_bench_config5.json 2>> $out/r05_bench_line.err || exit 1
+  timeout -k 10 400 python bench.py --full > $out/r05_bench_line_final.json 2> $out/r05_bench_line.err || exit 1
+  timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $out/r05_bench_line_driver_flags.json 2>> $out/r05_bench_line.err || exit 1
+  timeout -k 10 400 python bench.py --full --config 3 > $out/r05_bench_config3.json 2>> $out/r05_bench_line.err || exit 1
+  timeout -k 10 400 python bench.py --full --config 4 > $out/r05_bench_config4.json 2>> $out/r05_bench_line.err || exit 1
+  timeout -k 10 600 python bench.py --full --config 5 > $out/r05_bench_config5.json 2>> $out/r05_bench_line.err || exit 1
   echo "bench lines done"
 fi
 if has trace; then
