@@ -255,9 +255,12 @@ mh_status mh_context_reserve(mh_context_t ctx, int64_t max_batch);
 mh_status mh_model_check(mh_model_t model, mh_context_t ctx, void *stream);
 
 /* Pre-allocate device workspace for batches up to max_batch so that compute calls allocate nothing.  After it (and one first call of
- * each entry point, which sets kernel attributes once) the device-pointer entry points only enqueue work on opts->stream -- kernels,
- * memsets, and for a pair call without a fused kernel an event fork / join with a stream of the model's own: they can be captured in a
- * HIP graph and replayed (tests/test_gpu_parity.py::test_entry_points_are_graph_capturable). */
+ * each entry point, which sets kernel attributes once; a call at any batch size up to max_batch will do) the device-pointer entry points
+ * with B <= max_batch only enqueue work on opts->stream -- kernels, memsets, and for a pair call without a fused kernel an event fork /
+ * join with a stream of the model's own: they can be captured in a HIP graph and replayed.  The depth-first frame plans of every batch
+ * size up to max_batch (both algorithms, both precisions, both layouts, the fp32 fused pair walk) are uploaded here, not at a call
+ * (tests/test_gpu_parity.py::test_entry_points_are_graph_capturable,
+ * tests/test_gpu_persistent_loops.py::test_reserve_then_capture_every_batch_class). */
 mh_status mh_reserve(mh_model_t model, int64_t max_batch);
 
 /*

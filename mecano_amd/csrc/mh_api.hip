@@ -1159,12 +1159,23 @@ bool dfs_windows(const mh_model *model, Algo algo, size_t elem, bool aos)
 { // AoS matrices with identity index maps and rows that span many cache lines: RNEA reads them through LDS windows (mh_dfs_kernels.h)
    return algo == ALGO_RNEA && aos && model->ident_maps && model->use_win && (long)model->nv * (long)elem >= 512;
 }
-// pair: the fused RNEA + ABA walk (aba_dfs_kernel<.., PAIR>; algo = ALGO_ABA, A.in3 = qdd, A.out = tau, A.in3b = tau in, A.outb = qdd out)
+// Everything of a depth-first launch but the launch itself: the frame plan (uploaded at its first use), the grid, the global blocks
+// behind it in model->ws and the kernel with its LDS attribute.  launch_dfs runs it for the call at hand, mh_reserve for every plan a
+// batch up to its max_batch may get -- so that such a call finds all of it in place and only enqueues its kernel.
+struct DfsSetup
+{
+   const mh_model::DfsPlan *plan;
+   const void *kern;
+   long lds, gslots;
+   int grid;
+   bool win;
+};
+// aos: the state rows are AoS (q_es == v_es == 1); pair: the fused RNEA + ABA walk (fp32 only)
 template <typename T>
-mh_status launch_dfs(Algo algo, mh_model *model, int64_t B, mh::Args<T> &A, hipStream_t stream, bool pair = false)
+mh_status dfs_setup(Algo algo, mh_model *model, int64_t B, bool aos, bool pair, DfsSetup &S)
 {
    const long waves = (B + 63) / 64;
-   const bool win = !pair && dfs_windows(model, algo, sizeof(T), A.q_es == 1 && A.v_es == 1);
+   const bool win = !pair && dfs_windows(model, algo, sizeof(T), aos);
    const DfsChoice ch = dfs_choose(model, algo, sizeof(T), B, win, pair);
    const long b_win = ch.b_win, slot_bytes = ch.slot_bytes, hand = ch.hand, budget = ch.budget, cus = model->cu_count;
    long per_cu = ch.per_cu;
@@ -1180,18 +1191,9 @@ mh_status launch_dfs(Algo algo, mh_model *model, int64_t B, mh::Args<T> &A, hipS
    mh_status st = ensure_bytes(model->ws, (size_t)gslots * (size_t)grid * 64 * sizeof(T));
    if (st != MH_OK)
       return st;
-   A.ws = (T *)model->ws.ptr;
-   A.ws_stride = gslots * 64; // per-wave block of the global workspace: [grid][slots][64 lanes] -- the same constant slot stride as in LDS
-   A.m.meta = plan->d_meta;
-   if (algo == ALGO_RNEA)
-      A.m.rnea_stack = plan->lds_slots;
-   else
-      A.m.aba_stack = plan->lds_slots;
    // every frame in LDS / every frame global: builds without the per-group branch
    const int mode = plan->glb_frames == 0 ? 0 : (plan->lds_slots == 0 ? 1 : 2);
    const void *kern = nullptr;
-   if (win)
-      A.m.prog = model->d_prog_seq; // (the windows follow the matrices in engine order)
    if (algo == ALGO_RNEA)
    {
       if (win)
@@ -1232,8 +1234,28 @@ mh_status launch_dfs(Algo algo, mh_model *model, int64_t B, mh::Args<T> &A, hipS
       HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
       model->lds_attr[kern] = (size_t)lds;
    }
+   S.plan = plan, S.kern = kern, S.lds = lds, S.gslots = gslots, S.grid = grid, S.win = win;
+   return MH_OK;
+}
+// pair: the fused RNEA + ABA walk (aba_dfs_kernel<.., PAIR>; algo = ALGO_ABA, A.in3 = qdd, A.out = tau, A.in3b = tau in, A.outb = qdd out)
+template <typename T>
+mh_status launch_dfs(Algo algo, mh_model *model, int64_t B, mh::Args<T> &A, hipStream_t stream, bool pair = false)
+{
+   DfsSetup S{};
+   const mh_status st = dfs_setup<T>(algo, model, B, A.q_es == 1 && A.v_es == 1, pair, S);
+   if (st != MH_OK)
+      return st;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = S.gslots * 64; // per-wave block of the global workspace: [grid][slots][64 lanes] -- the same constant slot stride as in LDS
+   A.m.meta = S.plan->d_meta;
+   if (algo == ALGO_RNEA)
+      A.m.rnea_stack = S.plan->lds_slots;
+   else
+      A.m.aba_stack = S.plan->lds_slots;
+   if (S.win)
+      A.m.prog = model->d_prog_seq; // (the windows follow the matrices in engine order)
    void *args[] = {(void *)&A};
-   HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(64), args, (size_t)lds, stream));
+   HIP_TRY(hipLaunchKernel(S.kern, dim3(S.grid), dim3(64), args, (size_t)S.lds, stream));
    return MH_OK;
 }
 
@@ -3012,23 +3034,33 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       st = ensure_bytes(m->tr, (size_t)max_batch * ((size_t)m->nq + 3 * (size_t)m->nv) * sizeof(double));
    if (st != MH_OK)
       return st;
-   // the depth-first kernels: the frame plans a batch of this size gets (both algorithms, both precisions, both layouts) and the
-   // global blocks behind them; the second workspace of the side-by-side pair call
+   // the depth-first kernels: every frame plan a batch of up to max_batch configurations can get, with the global blocks behind it and
+   // its kernel's LDS attribute (dfs_setup).  A plan is cached per LDS budget, and dfs_choose picks the budget from the waves per CU: all
+   // batches of one count of waves per CU get the same plans, the largest of them the largest grid -- so one setup per class, both
+   // algorithms, both precisions, both layouts, and the fp32 fused pair walk of mh_rnea_aba_f32 (batches from 8192 configurations on).
+   // Largest class first: the workspace is allocated once, at its final size, where it can be.
    size_t dfs_bytes = 0;
-   for (int a = 0; a < 2 && m->use_dfs; a++)
-      for (size_t elem : {sizeof(double), sizeof(float)})
+   if (m->use_dfs)
+   {
+      const long cus = m->cu_count, classes = ((max_batch + 63) / 64 + cus - 1) / cus;
+      for (long wpc = classes; wpc >= 1; wpc--)
+      {
+         const int64_t B = std::min<int64_t>(max_batch, (int64_t)wpc * cus * 64);
          for (int aos = 0; aos < 2; aos++)
          {
-            const Algo algo = a == 0 ? ALGO_RNEA : ALGO_ABA;
-            const DfsChoice ch = dfs_choose(m, algo, elem, max_batch, dfs_windows(m, algo, elem, aos != 0));
-            const mh_model::DfsPlan *plan = dfs_plan(m, a, (int)ch.budget);
-            if (!plan)
-               return fail(MH_ERR_HIP, "depth-first kernels: the body records of the frame plan could not be uploaded");
-            const long lds = (plan->lds_slots + (ch.hand_lds ? ch.hand : 0)) * ch.slot_bytes + ch.b_win;
-            const long per_cu = lds > 0 ? std::max<long>(1, std::min<long>(ch.per_cu, (160 * 1024) / lds)) : ch.per_cu;
-            const long grid = std::max<long>(1, std::min<long>((max_batch + 63) / 64, (long)m->cu_count * per_cu));
-            dfs_bytes = std::max(dfs_bytes, (size_t)((ch.hand_lds ? 0 : ch.hand) + plan->glb_slots) * (size_t)grid * 64 * elem);
+            DfsSetup S{};
+            for (Algo algo : {ALGO_RNEA, ALGO_ABA})
+            {
+               if ((st = dfs_setup<double>(algo, m, B, aos != 0, false, S)) != MH_OK)
+                  return st;
+               if ((st = dfs_setup<float>(algo, m, B, aos != 0, false, S)) != MH_OK)
+                  return st;
+            }
+            if (B >= 8192 && m->use_dfs_pair && m->nq + m->nv >= 64 && (st = dfs_setup<float>(ALGO_ABA, m, B, aos != 0, true, S)) != MH_OK)
+               return st;
          }
+      }
+   }
    if (m->split_rt.usable) // the run-time tree split: one workspace block per workgroup
       dfs_bytes = std::max(dfs_bytes, (size_t)m->split_rt.slots * (size_t)std::max<long>(1, std::min<long>((max_batch + 63) / 64, 2L * m->cu_count)) * 64 * sizeof(double));
    if (dfs_bytes > 0)

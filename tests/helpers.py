@@ -78,19 +78,150 @@ def f32_aba_forward_factor(n_bodies):
     return 8.0 * (8.0 * n_bodies) ** 0.5
 
 
-def close_aba(actual, ref, H_ref, n_bodies, u=2.0 ** -53, label=None):
+def close_aba(actual, ref, H_ref, n_bodies, u=2.0 ** -53, label=None, conds=None):
     """Forward dynamics against the oracle with a bound per ROW instead of one loosened tolerance for a whole family: the solve
     H qdd = tau - h amplifies rounding by cond(H), and random mixed trees reach cond_inf(H) of 1e6 .. 1e9 on some rows while most stay
     near 1e2.  |qdd - ref|_inf <= 8 sqrt(8 n) cond_inf(H) u max(1, |ref|_inf) on every row, H from the oracle's own mass matrix (u: the unit
-    roundoff of the precision under test).  Logs the worst err / (cond u scale) against the factor."""
-    actual, ref, H_ref = np.asarray(actual, dtype=np.float64), np.asarray(ref, dtype=np.float64), np.asarray(H_ref, dtype=np.float64)
-    assert actual.shape == ref.shape and H_ref.shape[0] == ref.shape[0]
+    roundoff of the precision under test).  Logs the worst err / (cond u scale) against the factor.  conds: cond_inf(H) of the rows, if
+    known already (H_ref is not read then)."""
+    actual, ref = np.asarray(actual, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    if conds is None:
+        H_ref = np.asarray(H_ref, dtype=np.float64)
+        assert H_ref.shape[0] == ref.shape[0]
+        conds = np.array([np.linalg.cond(H_ref[k], np.inf) for k in range(len(H_ref))])
+    assert actual.shape == ref.shape and len(conds) == ref.shape[0]
     if ref.size == 0:
         return 0.0
-    conds = np.array([np.linalg.cond(H_ref[k], np.inf) for k in range(len(H_ref))])
     rel = np.abs(actual - ref).max(axis=1) / np.maximum(1.0, np.abs(ref).max(axis=1))
     ratio = float((rel / (conds * u)).max())
     factor = f32_aba_forward_factor(n_bodies)
     record_parity(ratio, factor, (label or "aba") + " forward error / (cond_inf(H) u)")
     assert ratio <= factor, f"worst row: err / (cond u) = {ratio:.3e} > {factor:.3e} (cond_inf(H) {conds.min():.1e} .. {conds.max():.1e})"
     return ratio
+
+
+# ---- row cover of persistent / grid-stride loops.  A workgroup of such a loop takes group g of 64 rows, then g + grid, g + 2 grid, ...
+# Two things hide a stride or indexing bug from a parity check: inputs tiled with a period that divides the stride (a row read from the
+# wrong iteration holds the same state), and sampled rows that skip most groups.  DistinctRows makes every row of a device batch a
+# different state whose exact input the host can rebuild for any row; group_cover picks rows that touch every group of 64; poisoned
+# outputs with a guard row behind the last one show rows that were never written and writes past the end.
+GROUP = 64
+ROW_OFFSET_SCALE = 2.0 ** -10  # a power of two: c (1 + r // N) w_j is exact in fp32 and fp64 for |w_j| <= 3 and r // N < 2^20
+
+
+def free_q_mask(system):
+    """True for the entries of q that are not quaternion parts (revolute / prismatic coordinates, planar and floating positions)."""
+    from mecano_amd.multibody import SixDoFJoint, SphericalJoint
+    provider = system.getJointMatrixIndexProvider()
+    joints = provider.getIndexedJointsInOrder()
+    nq = max((max(provider.getJointConfigurationIndices(j), default=-1) for j in joints), default=-1) + 1
+    mask = np.ones(nq, dtype=bool)
+    for j in joints:
+        ci = list(provider.getJointConfigurationIndices(j))
+        if isinstance(j, SixDoFJoint):
+            mask[ci[:4]] = False
+        elif isinstance(j, SphericalJoint):
+            mask[ci] = False
+    return mask
+
+
+def _row_weights(n, mask=None):
+    w = np.array([1.0, -2.0, 3.0, -1.0, 2.0, -3.0])[np.arange(n) % 6] * ROW_OFFSET_SCALE
+    return w if mask is None else np.where(mask, w, 0.0)
+
+
+class DistinctRows:
+    """B distinct states from a host base of N: row r is base[r % N] + c (1 + r // N) w, w a small integer per entry (0 on quaternion
+    parts), c = ROW_OFFSET_SCALE.  The offset is exact in the dtype, so the one rounding of the sum is the same on the device (torch) and on
+    the host (numpy): rows(r) is bit for bit the input the device holds in row r."""
+
+    def __init__(self, system, n_base, seed):
+        self.q, self.qd, self.qdd, self.tau = rt.nextState(np.random.default_rng(seed), system, n_base)
+        self.N = n_base
+        self.wq = _row_weights(self.q.shape[1], free_q_mask(system))
+        self.wv = _row_weights(self.qd.shape[1])
+
+    def _fields(self):
+        return ((self.q, self.wq), (self.qd, self.wv), (self.qdd, self.wv), (self.tau, self.wv))
+
+    def rows(self, idx, dtype=np.float64):
+        """(q, qd, qdd, tau) of rows idx, as fp64 arrays holding exactly the values of precision `dtype` the device gets."""
+        idx = np.asarray(idx, dtype=np.int64)
+        m = (1 + idx // self.N).astype(dtype)[:, None]
+        return tuple((base.astype(dtype)[idx % self.N] + m * w.astype(dtype)[None, :]).astype(np.float64) for base, w in self._fields())
+
+    def device(self, torch, B, dtype=None, device="cuda"):
+        """(q, qd, qdd, tau) of rows 0 .. B-1 as contiguous [B, n] tensors on the HIP device (built there: no B-row host arrays)."""
+        dtype = dtype or torch.float64
+        r = torch.arange(B, device=device, dtype=torch.int64)
+        m = (1 + r // self.N).to(dtype)[:, None]
+        out = []
+        for base, w in self._fields():
+            b = torch.tensor(base, device=device, dtype=dtype)[r % self.N]
+            off = m * torch.tensor(w, device=device, dtype=dtype)[None, :]  # exact: small integer times a power of two
+            out.append((b + off).contiguous())
+        return tuple(out)
+
+
+def group_cover(B, grid=None, group=GROUP):
+    """Rows that touch every group of `group` rows of a batch of B: one row per group at a lane that rotates with the group ((37 g + 11)
+    mod 64, clipped to the ragged tail), every row of the first group, of the last full group and of the ragged last group, and with
+    `grid` (workgroups of a loop over the groups) every row of the first group of each of the loop's iterations."""
+    if B <= 0:
+        return np.zeros(0, dtype=np.int64)
+    ng = (B + group - 1) // group
+    g = np.arange(ng, dtype=np.int64)
+    width = np.minimum(group, B - g * group)
+    parts = [g * group + (37 * g + 11) % group % width, np.arange(min(group, B))]
+    if B >= group:
+        last_full = B // group - 1
+        parts.append(last_full * group + np.arange(group))
+    if B % group:
+        parts.append(np.arange(B // group * group, B))
+    if grid:
+        for first in range(0, ng, int(grid)):
+            parts.append(np.arange(first * group, min(B, (first + 1) * group)))
+    return np.unique(np.concatenate(parts))
+
+
+def _take(x, idx):
+    if hasattr(x, "cpu"):  # a torch tensor: gather on its device
+        import torch
+        return x[torch.as_tensor(np.asarray(idx), device=x.device)].cpu().numpy()
+    return np.asarray(x)[np.asarray(idx)]
+
+
+def _isnan(x):
+    if hasattr(x, "cpu"):
+        import torch
+        return bool(torch.isnan(x).any().item()) if x.numel() else False
+    return bool(np.isnan(np.asarray(x)).any())
+
+
+def poisoned(torch, rows, row_shape, dtype, guard=1):
+    """An output of `rows` rows of `row_shape` and `guard` rows behind them, all NaN: (rows view, guard view) -- contiguous, so the rows
+    view is what a call writes and the guard is the memory right behind it."""
+    n = int(np.prod(row_shape)) if row_shape else 1
+    buf = torch.full(((rows + guard) * n,), float("nan"), device="cuda", dtype=dtype)
+    return buf[: rows * n].view(rows, *row_shape), buf[rows * n:]
+
+
+def check_cover(out, guard, idx, ref, tol=1.0e-10, absolute=False, label=None, record=True, every_row=True):
+    """Rows idx of `out` (a [B, ...] torch tensor or array) against `ref` (the reference of exactly those rows), after the guard (memory
+    behind the last row) is found untouched (all NaN) and no row -- every row of the batch with every_row, else the covered ones -- is left
+    unwritten (NaN).  record=False keeps the check out of PARITY_LOG (self-tests on synthetic outputs)."""
+    if guard is not None:
+        g = guard.cpu().numpy() if hasattr(guard, "cpu") else np.asarray(guard)
+        assert np.isnan(g).all(), f"{label}: wrote past the last row"
+    got = _take(out, idx).astype(np.float64)
+    bad = np.isnan(got.reshape(len(idx), -1)).any(axis=1)
+    assert not bad.any(), f"{label}: rows left unwritten (NaN), e.g. {np.asarray(idx)[bad][:8].tolist()}"
+    if every_row:
+        assert not _isnan(out), f"{label}: rows outside the cover left unwritten (NaN)"
+    ref = np.asarray(ref, dtype=np.float64).reshape(got.shape)  # (SoA rows come flat)
+    if record:
+        return close(got, ref, tol, absolute, label)
+    err = float(np.abs(got - ref).max()) if ref.size else 0.0
+    bound = tol if absolute else tol * max(1.0, float(np.abs(ref).max()) if ref.size else 0.0)
+    assert err <= bound, f"{label}: max err {err:.3e} > {bound:.3e}"
+    return err

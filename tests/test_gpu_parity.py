@@ -1848,6 +1848,27 @@ def test_config5_at_its_full_per_gpu_shard(torch_cuda, layout_name):
         rt2 = (back2 - ttau).abs().max().item()
         record_parity(rt2, 2 * f32_aba_backward_tol(n) * scale, f"fp32 pair call, round trip {layout_name} 131072 MH_DFS_PAIR={env}")
         assert rt2 <= 2 * f32_aba_backward_tol(n) * scale, (env, rt2, scale)
+    # distinct rows (tests/helpers.py: DistinctRows): the 8 192-row tiles above divide the depth-first grids' stride (cu per_cu groups of
+    # 64), so a row computed in another iteration would hold the same state; here no two rows are the same.  The oracle on a row of every
+    # group of 64 (and every row of each iteration's first group), the round trip RNEA(ABA(tau)) = tau on every row.
+    from helpers import DistinctRows, check_cover, group_cover
+    drows = DistinctRows(sys_, 2048, 2342)
+    dq, dqd, dqdd, dtau = drows.device(torch, B, f32)
+    idx = group_cover(B, 8 * torch.cuda.get_device_properties(0).multi_processor_count)
+    hq, hqd, hqdd, htau = drows.rows(idx, np.float32)
+    dt32 = rows(hm.rnea(put(dq), put(dqd), put(dqdd), g, layout=layout))
+    check_cover(dt32, None, idx, om.rnea(hq, hqd, hqdd, g), f32_forward_tol(n), label=f"rnea_f32 {layout_name} 131072 distinct rows")
+    da32 = rows(hm.aba(put(dq), put(dqd), put(dtau), g, layout=layout))
+    check_cover(da32, None, idx, np.zeros((len(idx), d.nv)), np.inf, label="aba_f32 distinct rows written", record=False)
+    a_s = da32[torch.as_tensor(idx, device="cuda")].cpu().numpy().astype(np.float64)
+    dscale = np.abs(htau).max() + np.abs(om.rnea(hq, hqd, np.zeros_like(hqdd), g)).max()
+    berr = np.abs(om.rnea(hq, hqd, a_s, g) - htau).max()
+    record_parity(berr, f32_aba_backward_tol(n) * dscale, f"aba_f32 backward error {layout_name} 131072 distinct rows")
+    assert berr <= f32_aba_backward_tol(n) * dscale, (berr, dscale)
+    back = rows(hm.rnea(put(dq), put(dqd), put(da32.contiguous()), g, layout=layout))
+    rt_err = (back - dtau).abs().max().item()
+    record_parity(rt_err, 2 * f32_aba_backward_tol(n) * dscale, f"fp32 round trip RNEA(ABA(tau)) {layout_name} 131072 distinct rows")
+    assert rt_err <= 2 * f32_aba_backward_tol(n) * dscale, (rt_err, dscale)
 
 
 def test_config4_at_full_size_on_one_gpu(torch_cuda):
@@ -1891,6 +1912,21 @@ def test_config4_at_full_size_on_one_gpu(torch_cuda):
     finally:
         os.environ.pop("MH_RNEA_AHEAD", None)
     assert torch.equal(plain, back)
+    # distinct rows (tests/helpers.py: DistinctRows): the tiles above repeat with a period that divides the loop's stride (2 cu groups of
+    # 64), so a row computed in another iteration would hold the same state; here no two rows are the same.  Poisoned output with a guard
+    # row, the oracle on a row of every group of 64 and on every row of the first group of each iteration, the round trip on every row.
+    import ctypes
+    from mecano_amd import _lib
+    from helpers import DistinctRows, check_cover, group_cover, poisoned
+    rows = DistinctRows(sys_, 1024, 2342)
+    dq, dqd, _, dtau = rows.device(torch, B)
+    out, guard = poisoned(torch, B, (d.nv,), torch.float64)
+    _lib.check(_lib.load().mh_aba_f64(hm._h, B, dq.data_ptr(), dqd.data_ptr(), dtau.data_ptr(), (ctypes.c_double * 3)(*g), None, None, out.data_ptr()))
+    torch.cuda.synchronize()
+    idx = group_cover(B, 2 * torch.cuda.get_device_properties(0).multi_processor_count)
+    hq, hqd, _, htau = rows.rows(idx)
+    check_cover(out, guard, idx, OracleModel(d).aba(hq, hqd, htau, g), 1e-10, absolute=True, label="aba 262144 distinct rows")
+    assert (hm.rnea(dq, dqd, out.contiguous(), g) - dtau).abs().max().item() <= 1e-9
 
 
 def test_pair_call_of_device_filling_batches_is_one_launch(torch_cuda, monkeypatch):
