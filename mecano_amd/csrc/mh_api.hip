@@ -30,11 +30,6 @@ extern char **environ;
 #include <string>
 #include <vector>
 
-// Per-joint constants of the generic kernels: staged in LDS (1) or read through scalar loads (0).
-#ifndef MH_GENERIC_LDS_CONSTS
-#define MH_GENERIC_LDS_CONSTS 0
-#endif
-
 namespace
 {
 thread_local char g_err[512] = "";
@@ -232,7 +227,6 @@ struct mh_model
    int *d_prog_seq = nullptr;
    int rnea_stack = 0, aba_stack = 0, aba_hand = 0; // per-lane slots: depth stacks, ABA hand-over
    int pair_stack = 0;    // ... of the fused RNEA + ABA walk (aba_dfs_kernel<.., PAIR>)
-   int dfs_aba_occ3 = 1;  // MH_DFS_ABA_OCC3=0: never the three-waves-per-SIMD build of the fp32 depth-first forward dynamics
    int use_dfs_pair = 1;  // MH_DFS_PAIR=0: mh_rnea_aba_f32 on big batches issues the two depth-first kernels one after the other, as before round 5
    int use_dfs = 1;       // MH_DFS=0: the sweep kernels of mh_kernels.h serve plain RNEA / ABA calls too (A/B measurements)
    FreshOnCopy<std::map<const void *, size_t>> lds_attr; // dynamic-LDS limit already raised per kernel (the model lives on one device, one host thread at a time)
@@ -256,13 +250,11 @@ struct mh_model
    mh_model *parent = nullptr;
    int n_contexts = 0; // live contexts of this model (guarded by g_context_mutex)
    bool destroy_pending = false; // mh_model_destroy was called while contexts were alive: the last mh_context_destroy releases the model
-   int use_win = 1;       // MH_DFS_WIN=0: AoS rows are read per lane instead of through LDS windows (A/B measurements)
    int dfs_place = -1;    // MH_DFS_PLACE = 0 | 1 | 2: force all-LDS / stack in LDS + hand-over global / all global
    bool dfs_place_greedy = false; // MH_DFS_GREEDY=1: the frames' homes from the leaves upwards as in rounds 2-4 (A/B measurements; dfs_plan)
    int dfs_budget = -1;   // MH_DFS_BUDGET: cap of the stack's LDS budget in slots per wave (measurements)
    int dfs_aba64 = 0;     // fp64 forward dynamics on the depth-first kernel too: bushy trees (below), or MH_DFS_ABA64=0|1
    int n_nonadjacent = 0; // bodies whose parent is not the body before them in engine order (branch points of the tree)
-   int dfs_transpose = -1; // MH_DFS_TRANSPOSE = 0 | 1: depth-first kernels on big AoS batches never / always through transposed scratch copies
    double *d_consts64 = nullptr;
    float *d_consts32 = nullptr;
    Workspace ws;
@@ -276,7 +268,6 @@ struct mh_model
    hipStream_t pair_stream = nullptr;
    hipEvent_t pair_fork = nullptr, pair_join = nullptr;
    Workspace ws_pair;
-   int use_pair = 1; // MH_DISABLE_PAIR=1: always one after the other
    // bias-split forward dynamics (mh_zv_kernels.h): tau - h(q, qd) rows, one flag per 64 configurations (a launch stores its epoch there),
    // an error word in mapped host memory that a timed-out wait sets (read at the next call of the model)
    Workspace zv_tau, zv_flags;
@@ -307,7 +298,6 @@ struct mh_model
       std::vector<int> xl;       // exchange slots of the limbs attached to the trunk bodies (plain slot numbers)
    } split_rt;
    int use_split_rt = -1; // MH_SPLIT_RT = 0 | 1: never / whenever usable (default: small batches)
-   int split_rt_lds = -1; // MH_SPLIT_RT_LDS = 0 | 1: the split kernels' workspace never / always with its LDS share (measurements)
    // AoS -> SoA scratch copies of the state matrices for the run-time-topology kernels (big batches of wide matrices); tr_pair: the
    // copies of the forward dynamics call that runs beside the inverse dynamics call on pair_stream (they would share addresses otherwise)
    Workspace tr, tr_pair;
@@ -320,18 +310,12 @@ struct mh_model
    uint32_t warnings = 0;    // MH_WARN_* bits set by mh_model_create (mh_model_warnings)
    std::string warning_text; // ... and what they mean for this model
    int use_split = -1;      // MH_SPEC_SPLIT = 0 | 1: never / whenever possible use the tree-split kernels (default: small batches)
-   int use_fused = 1;       // MH_DISABLE_FUSED=1: mh_rnea_aba_f64 always issues two launches
-   int fused_factor = 4;    // one launch for RNEA + ABA while 2 * ceil(B / 64) workgroups <= cu_count * factor (MH_FUSED_FACTOR)
    int use_spec = 1;        // MH_DISABLE_SPEC=1 in the environment forces the generic kernels (A/B measurements)
    bool spec_minimal = false; // the loaded code object is a minimal (fast) build
-   int lds_wave_factor = 1; // ABA hand-over in LDS while waves <= cu_count * factor (MH_ABA_LDS_FACTOR)
    int ident_maps = 0;      // the engine-order index maps are the identity
    int dense_maps = 0;      // nq / nv equal the joints' totals (no unused matrix rows): rows can be staged as dense blocks
    int force_io = -1, force_st = -1; // MH_SPEC_IO / MH_SPEC_ST = 0 | 1 override the heuristics (measurements)
    int n_locked = 0;        // joints in MH_ACCELERATION_SOURCE mode (mh_model_set_joint_source_modes)
-   int lds_consts = 0;      // run-time-topology kernels: per-joint constants staged in LDS (large models: they overflow the scalar cache) or read by scalar loads
-   int waves_per_cu = 8;    // resident waves per CU the run-time-topology kernels are launched with (MH_WAVES_PER_CU)
-   bool waves_per_cu_set = false; // MH_WAVES_PER_CU given: the depth-first kernels take it instead of what their registers allow (dfs_reg_cap)
 };
 
 struct mh_context
@@ -353,6 +337,14 @@ mh_status ensure_bytes(Workspace &w, size_t bytes)
    return MH_OK;
 }
 
+// resident waves per CU the run-time-topology sweep kernels are launched with (plan_launch; the depth-first kernels take what their
+// registers allow instead: dfs_choose)
+constexpr int kWavesPerCu = 8;
+// one launch for RNEA + ABA (and the tree-split RNEA / ABA of a code object) while 2 * ceil(B / 64) workgroups <= cu_count * kFusedFactor
+constexpr int kFusedFactor = 4;
+// whole-tree forward dynamics of a code object: hand-over in LDS while waves <= cu_count * kAbaLdsFactor
+constexpr int kAbaLdsFactor = 1;
+
 struct Launch
 {
    int block, grid;
@@ -363,7 +355,7 @@ Launch plan_launch(const mh_model *m, int64_t B)
    Launch L;
    L.block = 64; // one wave per workgroup: a small batch spreads over as many CUs as it has waves
    long waves = (B + 63) / 64;
-   long cap = (long)m->cu_count * m->waves_per_cu; // resident waves: the workspace is sized by the grid, not by B
+   long cap = (long)m->cu_count * kWavesPerCu; // resident waves: the workspace is sized by the grid, not by B
    L.grid = (int)std::max<long>(1, std::min(waves, cap));
    L.lanes = (long)L.grid * L.block;
    return L;
@@ -379,10 +371,7 @@ mh_status ensure_workspace(mh_model *m, int64_t B, size_t elem)
 // wave per SIMD (measured: profiles/r02_regressor_rates.txt, profiles/r02_column_parts.txt)
 static int regressor_parts(const mh_model *model, const Launch &L)
 {
-   int parts = (int)std::max<long>(1, std::min<long>(std::min<long>(8, model->n), (long)model->cu_count * 4 / L.grid));
-   if (const char *e = getenv("MH_REGRESSOR_PARTS"))
-      parts = std::max(1, std::min(64, atoi(e)));
-   return parts;
+   return (int)std::max<long>(1, std::min<long>(std::min<long>(8, model->n), (long)model->cu_count * 4 / L.grid));
 }
 static mh_status ensure_parts_workspace(mh_model *m, const Launch &L, int parts, size_t elem)
 {
@@ -465,7 +454,7 @@ bool split_ok(const mh_model *m, int algo, int64_t B, bool soa)
                    // wrenches -- both measured faster than the whole-tree kernels at every batch size and in both layouts
    const long groups = (B + 63) / 64;
    const long waves = groups * 4 * (algo == 2 ? 2 : 1);
-   return waves <= (long)m->cu_count * 4 * m->fused_factor; // fused: while the batch cannot give every SIMD a wave of its own
+   return waves <= (long)m->cu_count * 4 * kFusedFactor; // fused: while the batch cannot give every SIMD a wave of its own
 }
 
 // Bias-split forward dynamics (mh_zv_kernels.h): AoS matrices, dense index maps, every joint an effort source, no per-body outputs.
@@ -861,7 +850,7 @@ void split_rt_plan(mh_model *m)
       const int pe = MI(e, mh::MI_PARENT);
       (pe >= 0 ? ch[pe] : roots).push_back(e);
    }
-   const int trunk_weight = getenv("MH_SPLIT_RT_TRUNK_WEIGHT") ? atoi(getenv("MH_SPLIT_RT_TRUNK_WEIGHT")) : 2; // in half bodies; measured (tools/exp_split_rt_weight.py): 1..3 tie, 4+ splits too little
+   const int trunk_weight = 2; // in half bodies; measured in round 2 (DESIGN_HISTORY.md, run-time tree split): 1..3 tie, 4+ splits too little
    std::vector<char> trunk(n, 0);
    std::vector<int> limbs = roots;
    auto estimate = [&](const std::vector<int> &L, int nt, std::vector<int> *owner) {
@@ -1020,17 +1009,14 @@ mh_status launch_split_rt(Algo algo, mh_model *model, int64_t B, mh::Args<T> &A,
    const mh_model::SplitRt &S = model->split_rt;
    const long groups = (B + 63) / 64;
    // workgroups per CU: the fp64 ABA holds ~300 registers (one wave per SIMD), the others fit two workgroups (measured on the humanoid at
-   // B = 32768, two groups per CU: RNEA 47 us with two resident workgroups against 66 looping one; tools/exp_split_rt_wgs.py)
-   static const int forced_wgs = getenv("MH_SPLIT_RT_WGS") ? std::max(1, atoi(getenv("MH_SPLIT_RT_WGS"))) : 0;
-   const int wgs = forced_wgs ? forced_wgs : ((algo == ALGO_ABA && sizeof(T) == 8) ? 1 : 2);
+   // B = 32768, two groups per CU: RNEA 47 us with two resident workgroups against 66 looping one; round 2, DESIGN_HISTORY.md)
+   const int wgs = (algo == ALGO_ABA && sizeof(T) == 8) ? 1 : 2;
    const int grid = (int)std::max<long>(1, std::min<long>(groups, (long)model->cu_count * wgs));
    // Which record set: everything in LDS when the block fits (no branches); else a share in LDS once the blocks of the workgroups of an
    // XCD outgrow its L2 (measured on the fp64 humanoid: 44 us all-global vs 47 with a share at B = 4096, 71 vs 50 at 8192); else all global.
    int k = sizeof(T) == 4 ? 0 : 1;
    if (S.lds_slots[k] < S.slots && (size_t)S.slots * 64 * sizeof(T) * ((size_t)grid / 8 + 1) <= (size_t)3 << 20)
       k = 2;
-   if (model->split_rt_lds >= 0)
-      k = model->split_rt_lds ? (sizeof(T) == 4 ? 0 : 1) : 2;
    if (grid > model->cu_count && (size_t)std::min(S.slots, S.lds_slots[k] + mh::SPLIT_LDS_MARGIN) * 64 * sizeof(T) > 80 * 1024)
       k = 2; // two workgroups per CU: an LDS share above half the CU's would serialise them
    const int mode = S.lds_slots[k] >= S.slots ? 0 : (S.lds_slots[k] == 0 ? 1 : 2);
@@ -1077,8 +1063,6 @@ mh_status launch_split_rt_pair(mh_model *model, int64_t B, mh::Args<double> &A, 
    int k = 1;
    if (S.lds_slots[k] < S.slots && (size_t)S.slots * 64 * sizeof(T) * ((size_t)groups / 8 + 1) <= (size_t)3 << 20)
       k = 2;
-   if (model->split_rt_lds >= 0)
-      k = model->split_rt_lds ? 1 : 2;
    const int mode = S.lds_slots[k] >= S.slots ? 0 : (S.lds_slots[k] == 0 ? 1 : 2);
    mh_status st = ensure_bytes(model->ws, (size_t)S.slots * (size_t)grid * 64 * sizeof(T));
    if (st != MH_OK)
@@ -1128,10 +1112,8 @@ DfsChoice dfs_choose(const mh_model *model, Algo algo, size_t elem, int64_t B, b
    const bool twelve_pays = ((wpc + 11) / 12) * 132 < ((wpc + 7) / 8) * 100;
    if (elem == 4 && algo == ALGO_RNEA && !win && twelve_pays)
       reg_cap = 12;
-   if (elem == 4 && algo == ALGO_ABA && !pair && model->dfs_aba_occ3 && twelve_pays)
+   if (elem == 4 && algo == ALGO_ABA && !pair && twelve_pays)
       reg_cap = 12, c.occ3 = true; // the build with a register budget for three waves per SIMD (mh_dfs_kernels.h: OCC3)
-   if (model->waves_per_cu_set)
-      reg_cap = std::min<long>(reg_cap, model->waves_per_cu);
    c.per_cu = std::max<long>(1, std::min<long>(reg_cap, (waves + cus - 1) / cus));
    const long full_stack = pair ? model->pair_stack : (algo == ALGO_RNEA ? model->rnea_stack : model->aba_stack);
    c.hand = algo == ALGO_RNEA ? 0 : model->aba_hand;
@@ -1157,7 +1139,7 @@ DfsChoice dfs_choose(const mh_model *model, Algo algo, size_t elem, int64_t B, b
 }
 bool dfs_windows(const mh_model *model, Algo algo, size_t elem, bool aos)
 { // AoS matrices with identity index maps and rows that span many cache lines: RNEA reads them through LDS windows (mh_dfs_kernels.h)
-   return algo == ALGO_RNEA && aos && model->ident_maps && model->use_win && (long)model->nv * (long)elem >= 512;
+   return algo == ALGO_RNEA && aos && model->ident_maps && (long)model->nv * (long)elem >= 512;
 }
 // Everything of a depth-first launch but the launch itself: the frame plan (uploaded at its first use), the grid, the global blocks
 // behind it in model->ws and the kernel with its LDS attribute.  launch_dfs runs it for the call at hand, mh_reserve for every plan a
@@ -1310,10 +1292,6 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
    A.f_bs = soa ? 1 : (long)model->n * 6, A.f_es = soa ? B : 1;
    set_root_acceleration(A, opts, gravity);
    A.coriolis = opts.consider_coriolis, A.accel = opts.consider_accelerations;
-   const bool ldsc = MH_GENERIC_LDS_CONSTS || model->lds_consts;
-   const size_t lds = ldsc ? (size_t)model->n * mh::MC_STRIDE * sizeof(T) : 0;
-   if (lds > 160 * 1024)
-      return fail(MH_ERR_BAD_DIMENSION, "model constants (%zu B) exceed the 160 KiB LDS of a gfx950 CU", lds);
 
    if (bodies && algo != ALGO_CRBA)
    { // per-body outputs: run-time-topology kernels (the model's joint source modes must all be effort sources)
@@ -1335,16 +1313,16 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
       if (model->split_rt.usable && model->n_locked == 0 && (model->use_split_rt == 1 || (B + 63) / 64 <= (long)model->cu_count * 2))
          return launch_split_rt<T>(algo, model, B, A, stream); // small batches: the run-time tree split writes the per-body outputs too
       if (algo == ALGO_RNEA)
-         { if (ldsc) hipLaunchKernelGGL((mh::rnea_kernel<T, true, true>), dim3(L.grid), dim3(L.block), lds, stream, A); else hipLaunchKernelGGL((mh::rnea_kernel<T, false, true>), dim3(L.grid), dim3(L.block), lds, stream, A); }
+         hipLaunchKernelGGL((mh::rnea_kernel<T, true>), dim3(L.grid), dim3(L.block), 0, stream, A);
       else
-         { if (ldsc) hipLaunchKernelGGL((mh::aba_kernel<T, true, false, true>), dim3(L.grid), dim3(L.block), lds, stream, A); else hipLaunchKernelGGL((mh::aba_kernel<T, false, false, true>), dim3(L.grid), dim3(L.block), lds, stream, A); }
+         hipLaunchKernelGGL((mh::aba_kernel<T, false, true>), dim3(L.grid), dim3(L.block), 0, stream, A);
       HIP_TRY(hipGetLastError());
       return MH_OK;
    }
    if (algo == ALGO_ABA && model->n_locked > 0)
    { // acceleration-source joints: run-time flags per joint, generic kernel only
       A.in3b = locked_in, A.outb = locked_out;
-      { if (ldsc) hipLaunchKernelGGL((mh::aba_kernel<T, true, true>), dim3(L.grid), dim3(L.block), lds, stream, A); else hipLaunchKernelGGL((mh::aba_kernel<T, false, true>), dim3(L.grid), dim3(L.block), lds, stream, A); }
+      hipLaunchKernelGGL((mh::aba_kernel<T, true>), dim3(L.grid), dim3(L.block), 0, stream, A);
       HIP_TRY(hipGetLastError());
       return MH_OK;
    }
@@ -1450,7 +1428,7 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
          flags |= SPEC_IO_LDS;
       if (algo == ALGO_ABA)
       {
-         bool st = model->spec.lds_bytes(a, flags | SPEC_ST_LDS, model->nq, model->nv) <= LDS_MAX && waves <= (long)model->cu_count * model->lds_wave_factor;
+         bool st = model->spec.lds_bytes(a, flags | SPEC_ST_LDS, model->nq, model->nv) <= LDS_MAX && waves <= (long)model->cu_count * kAbaLdsFactor;
          if (model->force_st >= 0)
             st = model->force_st && model->spec.lds_bytes(a, flags | SPEC_ST_LDS, model->nq, model->nv) <= LDS_MAX;
          if (st && !model->spec.supports(a, flags | SPEC_ST_LDS))
@@ -1485,13 +1463,13 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
       return launch_split_rt<T>(algo, model, B, A, stream);
    // Run-time-topology RNEA / ABA on AoS matrices: for big batches of wide matrices go through transposed scratch copies
    // (mh::transpose_kernel).  External wrenches keep their own strides.  The depth-first RNEA reads AoS rows through LDS windows instead
-   // (mh_dfs_kernels.h, RowWindow) unless MH_DFS_TRANSPOSE=1; the depth-first ABA has no registers left for windows and takes the copies.
+   // (mh_dfs_kernels.h, RowWindow); the depth-first ABA has no registers left for windows and takes the copies.
    T *t_out = nullptr;
    if (algo != ALGO_CRBA && !soa)
    {
       bool want = model->use_transpose >= 0 ? model->use_transpose != 0 : (B >= 8192 && model->nq + model->nv >= 64);
       if (dfs && want)
-         want = model->dfs_transpose >= 0 ? model->dfs_transpose != 0 : (algo == ALGO_ABA || !(model->ident_maps && model->use_win));
+         want = algo == ALGO_ABA || !model->ident_maps;
       if (want)
       {
          const size_t nq = model->nq, nv = model->nv;
@@ -1517,10 +1495,10 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
    switch (algo)
    {
       case ALGO_RNEA:
-         { if (ldsc) hipLaunchKernelGGL((mh::rnea_kernel<T, true>), dim3(L.grid), dim3(L.block), lds, stream, A); else hipLaunchKernelGGL((mh::rnea_kernel<T, false>), dim3(L.grid), dim3(L.block), lds, stream, A); }
+         hipLaunchKernelGGL((mh::rnea_kernel<T>), dim3(L.grid), dim3(L.block), 0, stream, A);
          break;
       case ALGO_ABA:
-         { if (ldsc) hipLaunchKernelGGL((mh::aba_kernel<T, true>), dim3(L.grid), dim3(L.block), lds, stream, A); else hipLaunchKernelGGL((mh::aba_kernel<T, false>), dim3(L.grid), dim3(L.block), lds, stream, A); }
+         hipLaunchKernelGGL((mh::aba_kernel<T>), dim3(L.grid), dim3(L.block), 0, stream, A);
          break;
       case ALGO_CRBA:
       {
@@ -1566,7 +1544,7 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
             if (const mh_status sp = ensure_parts_workspace(model, L, parts, sizeof(T)); sp != MH_OK)
                return sp;
             A.ws = (T *)model->ws.ptr;
-            if (ldsc) hipLaunchKernelGGL((mh::crba_kernel<T, true>), dim3(L.grid, parts), dim3(L.block), lds, stream, A); else hipLaunchKernelGGL((mh::crba_kernel<T, false>), dim3(L.grid, parts), dim3(L.block), lds, stream, A);
+            hipLaunchKernelGGL((mh::crba_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, stream, A);
          }
          break;
       }
@@ -1927,8 +1905,6 @@ mh_status coriolis_impl(mh_model_t model, int64_t B, const T *q, const T *qd, co
    A.q_bs = soa ? 1 : model->nq, A.q_es = soa ? B : 1;
    A.v_bs = soa ? 1 : model->nv, A.v_es = soa ? B : 1;
    A.f_bs = soa ? 1 : (long)model->nv * model->nv, A.f_es = soa ? B : 1; // strides of H and C
-   const bool ldsc = MH_GENERIC_LDS_CONSTS || model->lds_consts;
-   const size_t lds = ldsc ? (size_t)model->n * mh::MC_STRIDE * sizeof(T) : 0;
    const size_t hbytes = (size_t)B * model->nv * model->nv * sizeof(T);
    HIP_TRY(hipMemsetAsync(H_out, 0, hbytes, stream)); // the kernel writes the entries of related joints only (:298-300)
    HIP_TRY(hipMemsetAsync(C_out, 0, hbytes, stream));
@@ -1949,7 +1925,7 @@ mh_status coriolis_impl(mh_model_t model, int64_t B, const T *q, const T *qd, co
             return fail(MH_ERR_HIP, "specialised Coriolis kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
       }
    }
-   { if (ldsc) hipLaunchKernelGGL((mh::coriolis_kernel<T, true>), dim3(L.grid, parts), dim3(L.block), lds, stream, A); else hipLaunchKernelGGL((mh::coriolis_kernel<T, false>), dim3(L.grid, parts), dim3(L.block), lds, stream, A); }
+   hipLaunchKernelGGL((mh::coriolis_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, stream, A);
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
@@ -1989,21 +1965,16 @@ mh_status regressor_impl(mh_model_t model, int64_t B, const T *q, const T *qd, c
    A.f_bs = soa ? 1 : ysize, A.f_es = soa ? B : 1; // strides of Y
    set_root_acceleration(A, opts, gravity);
    A.coriolis = opts.consider_coriolis, A.accel = opts.consider_accelerations;
-   const bool ldsc = MH_GENERIC_LDS_CONSTS || model->lds_consts;
-   const size_t lds = ldsc ? (size_t)model->n * mh::MC_STRIDE * sizeof(T) : 0;
    // entries of joints that do not support a body are zero, and so are the reference's centre-of-mass columns (mh_kernels.h)
    HIP_TRY(hipMemsetAsync(Y_out, 0, (size_t)B * ysize * sizeof(T), stream));
    // the centre-of-mass columns: d tau / d (m c) on request; else the reference's -- zero, or e x a once the twist is switched off
    const int mode = first_moment_columns ? 1 : (opts.consider_coriolis ? 0 : 2);
-#define MH_REG_LAUNCH(MODE) \
-   { if (ldsc) hipLaunchKernelGGL((mh::regressor_kernel<T, true, MODE>), dim3(L.grid, parts), dim3(L.block), lds, stream, A); else hipLaunchKernelGGL((mh::regressor_kernel<T, false, MODE>), dim3(L.grid, parts), dim3(L.block), lds, stream, A); }
    if (mode == 0)
-      MH_REG_LAUNCH(0)
+      hipLaunchKernelGGL((mh::regressor_kernel<T, 0>), dim3(L.grid, parts), dim3(L.block), 0, stream, A);
    else if (mode == 1)
-      MH_REG_LAUNCH(1)
+      hipLaunchKernelGGL((mh::regressor_kernel<T, 1>), dim3(L.grid, parts), dim3(L.block), 0, stream, A);
    else
-      MH_REG_LAUNCH(2)
-#undef MH_REG_LAUNCH
+      hipLaunchKernelGGL((mh::regressor_kernel<T, 2>), dim3(L.grid, parts), dim3(L.block), 0, stream, A);
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
@@ -2048,8 +2019,6 @@ mh_status centroidal_impl(mh_model_t model, int64_t B, const T *q, const T *qd, 
    for (int k = 0; k < 3; k++)
       A.fp[k] = frame ? (T)frame[9 + k] : T(0);
    A.at_com = frame_mode == MH_CENTROIDAL_FRAME_AT_COM;
-   const bool ldsc = MH_GENERIC_LDS_CONSTS || model->lds_consts;
-   const size_t lds = ldsc ? (size_t)model->n * mh::MC_STRIDE * sizeof(T) : 0;
    HIP_TRY(hipMemsetAsync(A_out, 0, (size_t)B * 6 * model->nv * sizeof(T), stream)); // columns no considered joint owns stay zero
    if constexpr (sizeof(T) == 8)
    {
@@ -2068,7 +2037,7 @@ mh_status centroidal_impl(mh_model_t model, int64_t B, const T *q, const T *qd, 
             return fail(MH_ERR_HIP, "specialised centroidal kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
       }
    }
-   { if (ldsc) hipLaunchKernelGGL((mh::centroidal_kernel<T, true>), dim3(L.grid, parts), dim3(L.block), lds, stream, A); else hipLaunchKernelGGL((mh::centroidal_kernel<T, false>), dim3(L.grid, parts), dim3(L.block), lds, stream, A); }
+   hipLaunchKernelGGL((mh::centroidal_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, stream, A);
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
@@ -2512,7 +2481,7 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
                prog[pop_at[e]] |= mh::EV_ACC_USED;
          }
       };
-      build_program(!getenv("MH_DFS_ENGINE_ORDER"), m->prog); // (MH_DFS_ENGINE_ORDER=1: the siblings in engine order everywhere, for measurements)
+      build_program(true, m->prog);
       build_program(false, m->prog_seq);
    }
 
@@ -2563,8 +2532,6 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
       m->use_spec = atoi(e) ? 0 : 1;
    if (const char *e = getenv("MH_SPEC_SPLIT"))
       m->use_split = atoi(e);
-   if (const char *e = getenv("MH_DISABLE_FUSED"))
-      m->use_fused = atoi(e) ? 0 : 1;
    if (const char *e = getenv("MH_ZV"))
       m->use_zv = atoi(e);
    if (const char *e = getenv("MH_ZV_SAME_L2"))
@@ -2583,31 +2550,18 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
       m->use_zv_step = atoi(e) ? 1 : 0;
    if (const char *e = getenv("MH_ZVB_WHICH"))
       m->zvb_which = std::max(1, std::min(3, atoi(e)));
-   if (const char *e = getenv("MH_ABA_LDS_FACTOR"))
-      m->lds_wave_factor = atoi(e);
    if (const char *e = getenv("MH_SPEC_IO"))
       m->force_io = atoi(e);
    if (const char *e = getenv("MH_FAKE_CU_COUNT")) // measurements: shrink every grid so that one workgroup loops over the batch
       m->cu_count = std::max(1, atoi(e));
-   m->lds_consts = 0; // measured on the 128-body tree (fp32, B = 131072): no difference to scalar loads
-   if (const char *e = getenv("MH_GENERIC_LDS"))
-      m->lds_consts = atoi(e) != 0;
-   if (const char *e = getenv("MH_FUSED_FACTOR"))
-      m->fused_factor = std::max(1, atoi(e));
    if (const char *e = getenv("MH_GENERIC_TRANSPOSE"))
       m->use_transpose = atoi(e) != 0;
-   if (const char *e = getenv("MH_WAVES_PER_CU"))
-      m->waves_per_cu = std::max(1, std::min(32, atoi(e))), m->waves_per_cu_set = true;
    if (const char *e = getenv("MH_SPEC_ST"))
       m->force_st = atoi(e);
    if (const char *e = getenv("MH_DFS"))
       m->use_dfs = atoi(e) != 0;
    if (const char *e = getenv("MH_DFS_PAIR"))
       m->use_dfs_pair = atoi(e) != 0;
-   if (const char *e = getenv("MH_DFS_ABA_OCC3"))
-      m->dfs_aba_occ3 = atoi(e) != 0;
-   if (const char *e = getenv("MH_DFS_TRANSPOSE"))
-      m->dfs_transpose = atoi(e) != 0;
    // fp64 forward dynamics at device-filling batches: the sweep kernel accumulates the children of a branching body through the workspace
    // (read-modify-write per extra child), the depth-first one keeps them on its stack -- measured on the reference's 30-joint shapes at
    // B = 262 144 (profiles/r02_generic_fp64_rates.txt): random trees 1253 -> 989 us and 1384 -> 1288 us on the depth-first kernel, chains
@@ -2621,16 +2575,10 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
       m->dfs_place = atoi(e);
    if (const char *e = getenv("MH_DFS_GREEDY"))
       m->dfs_place_greedy = atoi(e) != 0;
-   if (const char *e = getenv("MH_DFS_WIN"))
-      m->use_win = atoi(e) != 0;
-   if (getenv("MH_DISABLE_PAIR"))
-      m->use_pair = 0;
    if (const char *e = getenv("MH_HOST_CHUNK"))
       m->host_chunk = std::max(0, atoi(e));
    if (const char *e = getenv("MH_SPLIT_RT"))
       m->use_split_rt = atoi(e);
-   if (const char *e = getenv("MH_SPLIT_RT_LDS"))
-      m->split_rt_lds = atoi(e) != 0;
    if (m->use_split_rt != 0)
       split_rt_plan(m);
    try_load_spec(m, P);
@@ -3065,7 +3013,7 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       dfs_bytes = std::max(dfs_bytes, (size_t)m->split_rt.slots * (size_t)std::max<long>(1, std::min<long>((max_batch + 63) / 64, 2L * m->cu_count)) * 64 * sizeof(double));
    if (dfs_bytes > 0)
       st = ensure_bytes(m->ws, dfs_bytes);
-   if (st == MH_OK && m->use_pair && (max_batch + 63) / 64 <= (long)m->cu_count)
+   if (st == MH_OK && (max_batch + 63) / 64 <= (long)m->cu_count)
       st = ensure_bytes(m->ws_pair, m->ws.bytes);
    // round 3's plans: the bias-split launches (their scratch for the largest batch they serve: two jobs on every group of 64 within the
    // CUs), the one-launch pair of the run-time tree split (twice the workgroups of a single call), the shared transposed copies of
@@ -3327,8 +3275,8 @@ mh_status mh_rnea_aba_f64(mh_model_t model, int64_t B, const double *q, const do
    if (pair_outputs_overlap(q, qd, qdd, tau, tau_out, qdd_out, (size_t)B * model->nq * sizeof(double), (size_t)B * model->nv * sizeof(double)))
       return fail(MH_ERR_INVALID_ARGUMENT, "mh_rnea_aba_f64: tau_out / qdd_out must not overlap q, qd, qdd, tau or each other (the two algorithms run concurrently)");
    const long waves = (B + 63) / 64;
-   const bool fusable = model->n_locked == 0 && model->spec.launch_fused && model->use_spec && model->use_fused && model->dense_maps && opts.layout == MH_LAYOUT_AOS
-                        && opts.consider_coriolis && opts.consider_accelerations && 2 * waves <= (long)model->cu_count * model->fused_factor
+   const bool fusable = model->n_locked == 0 && model->spec.launch_fused && model->use_spec && model->dense_maps && opts.layout == MH_LAYOUT_AOS
+                        && opts.consider_coriolis && opts.consider_accelerations && 2 * waves <= (long)model->cu_count * kFusedFactor
                         && model->spec.fused_lds_bytes(model->nq, model->nv) <= 160 * 1024
                         // beyond one group per CU the fused forward-dynamics kernel behind mh_aba_f64 is worth more than one launch for both
                         // (humanoid: 43.1 against 56.6 us at 32 768, 40.0 against 45.5 at 24 576; profiles/r04_pair_call_rates.txt)
@@ -3341,7 +3289,7 @@ mh_status mh_rnea_aba_f64(mh_model_t model, int64_t B, const double *q, const do
       hipStream_t s = (hipStream_t)opts.stream;
       // no code object would serve either call and the run-time tree split serves both: one launch, half the grid each
       const bool no_spec = !model->use_spec || !model->spec.launch_split || !model->spec.split_usable || !model->spec.split_usable();
-      if (no_spec && model->use_pair && model->split_rt.usable && model->n_locked == 0 && model->use_split_rt != 0 && 2 * waves <= (long)model->cu_count)
+      if (no_spec && model->split_rt.usable && model->n_locked == 0 && model->use_split_rt != 0 && 2 * waves <= (long)model->cu_count)
       {
          mh::Args<double> P{};
          P.m = dev_model<double>(model);
@@ -3356,7 +3304,7 @@ mh_status mh_rnea_aba_f64(mh_model_t model, int64_t B, const double *q, const do
          P.coriolis = opts.consider_coriolis, P.accel = opts.consider_accelerations;
          return launch_split_rt_pair(model, B, P, s);
       }
-      if (!model->use_pair || waves > (long)model->cu_count) // measured: pays up to one wave per CU (profiles/r02_generic_pair_side_by_side.txt)
+      if (waves > (long)model->cu_count) // measured: pays up to one wave per CU (profiles/r02_generic_pair_side_by_side.txt)
       {
          mh_status r = mh_rnea_f64(model, B, q, qd, qdd, gravity, f_ext, &opts, tau_out);
          return r != MH_OK ? r : mh_aba_f64(model, B, q, qd, tau, gravity, f_ext, &opts, qdd_out);
@@ -3463,7 +3411,7 @@ mh_status mh_rnea_crba_f64(mh_model_t model, int64_t B, const double *q, const d
    const long groups = (B + 63) / 64;
    // one launch: tree-split RNEA groups and tree-split CRBA groups side by side (code object with identity maps, AoS, no switches, no
    // external wrenches through this path; batches that leave room for both on the device)
-   if (model->spec.launch_rnea_crba && model->use_spec && model->use_fused && model->ident_maps && model->dense_maps && opts.layout == MH_LAYOUT_AOS
+   if (model->spec.launch_rnea_crba && model->use_spec && model->ident_maps && model->dense_maps && opts.layout == MH_LAYOUT_AOS
        && opts.consider_coriolis && opts.consider_accelerations && model->use_split != 0 && model->spec.split_usable && model->spec.split_usable()
        && model->spec.crba_split_usable && model->spec.crba_split_usable() && groups <= (long)model->cu_count * 2)
    {
@@ -3496,8 +3444,6 @@ mh_status mh_rnea_crba_f64(mh_model_t model, int64_t B, const double *q, const d
          if (fit >= 16 && fit <= 64 && fit > lpg)
             lpg = (int)fit;
       }
-      if (const char *e = getenv("MH_RNEA_CRBA_LPG")) // experiments: 16 ... 64
-         lpg = std::max(16, std::min(64, atoi(e)));
       const long ng = std::min<long>((B + lpg - 1) / lpg, (long)model->cu_count * 2);
       const int rc = model->spec.launch_rnea_crba(&A, (int)groups, (int)ng, lpg, (void *)s);
       if (rc == 0)
@@ -3507,7 +3453,7 @@ mh_status mh_rnea_crba_f64(mh_model_t model, int64_t B, const double *q, const d
    }
    // two launches; side by side while the batch leaves most of the device idle (the CRBA on the model's own stream; it needs no workspace
    // of the RNEA's kind when a code object serves it, and gets its own otherwise)
-   if (!model->use_pair || groups > (long)model->cu_count)
+   if (groups > (long)model->cu_count)
    {
       st = mh_rnea_f64(model, B, q, qd, qdd, gravity, f_ext, &opts, tau_out);
       return st != MH_OK ? st : mh_crba_f64(model, B, q, &opts, H_out);
@@ -3561,7 +3507,7 @@ mh_status mh_rnea_aba_f32(mh_model_t model, int64_t B, const float *q, const flo
        && pair_outputs_overlap(q, qd, qdd, tau, tau_out, qdd_out, (size_t)B * model->nq * sizeof(float), (size_t)B * model->nv * sizeof(float)))
       return fail(MH_ERR_INVALID_ARGUMENT, "mh_rnea_aba_f32: tau_out / qdd_out must not overlap q, qd, qdd, tau or each other (the two algorithms run concurrently)");
    const bool big = model && B >= 8192 && q && qd && qdd && tau && tau_out && qdd_out && !f_ext && model->use_dfs && model->n_locked == 0
-                    && model->use_transpose < 0 && model->dfs_transpose < 0 && model->nq + model->nv >= 64 && opts.consider_coriolis
+                    && model->use_transpose < 0 && model->nq + model->nv >= 64 && opts.consider_coriolis
                     && opts.consider_accelerations;
    const bool shared = big && opts.layout == MH_LAYOUT_AOS;
    // ONE walk for both (round 5; mh_dfs_kernels.h: aba_dfs_kernel<.., PAIR>) unless a run-time tree split or a code object serves the model
@@ -3574,7 +3520,7 @@ mh_status mh_rnea_aba_f32(mh_model_t model, int64_t B, const float *q, const flo
    {
       const long wpc = ((B + 63) / 64 + model->cu_count - 1) / model->cu_count, r8 = (wpc + 7) / 8, r12 = (wpc + 11) / 12;
       const long two = (r12 * 132 < r8 * 100 ? r12 * 132 : r8 * 100) * 125; // (x 1e4)
-      rounds_favour_two = !model->waves_per_cu_set && two < r8 * 10000;
+      rounds_favour_two = two < r8 * 10000;
    }
    const bool fused = big && model->use_dfs_pair && !rounds_favour_two && !(model->spec.handle && model->use_spec)
                       && !(model->split_rt.usable && (model->use_split_rt == 1 || (B + 63) / 64 <= (long)model->cu_count * 2));
@@ -3842,8 +3788,8 @@ mh_status mh_timer_create(mh_timer_t *out)
    mh_timer *t = new mh_timer();
    // timing only: without the system-scope fence (cache write-back) a default event performs when it becomes recorded -- measured on the
    // headline's regions of 20 steps: 8 us per region with default events (profiles/r04_region_overhead.txt)
-   const unsigned flags = getenv("MH_TIMER_DEFAULT_EVENTS") ? hipEventDefault : hipEventDisableSystemFence;
-   if (hipEventCreateWithFlags(&t->start, flags) != hipSuccess || hipEventCreateWithFlags(&t->stop, flags) != hipSuccess)
+   if (hipEventCreateWithFlags(&t->start, hipEventDisableSystemFence) != hipSuccess
+       || hipEventCreateWithFlags(&t->stop, hipEventDisableSystemFence) != hipSuccess)
    {
       delete t;
       return fail(MH_ERR_NO_DEVICE, "cannot create HIP events");

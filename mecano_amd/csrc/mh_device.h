@@ -479,18 +479,12 @@ MH_DEV T ldc(const T *p)
 }
 typedef const int __attribute__((address_space(4))) *ciptr;
 MH_DEV ciptr as_const(const int *p) { return (ciptr)(unsigned long long)p; }
-// accessor of one joint's constants: LDS copy (broadcast ds_read) or scalar loads from global memory
-template <typename T, bool LDS>
+// accessor of one joint's constants: scalar loads from global memory
+template <typename T>
 struct CRef
 {
    const T *p;
-   MH_DEV T operator[](int k) const
-   {
-      if constexpr (LDS)
-         return p[k];
-      else
-         return ldc(p + k);
-   }
+   MH_DEV T operator[](int k) const { return ldc(p + k); }
 };
 
 // ---- sincos.  fp64: Cody-Waite reduction by pi/2 (exact products through FMA) + the classic minimax kernels on

@@ -390,7 +390,7 @@ __global__ void __launch_bounds__(64) rnea_dfs_kernel(Args<T> A)
             // every test below: the run-time form was a maze of ~150 basic blocks per event)
             auto body = [&](auto kind) {
             const int type = kind; // a compile-time constant after inlining, except for KindRt
-            const CRef<T, false> c{CB + j * MC_STRIDE};
+            const CRef<T> c{CB + j * MC_STRIDE};
             const XF<T> Xb = load_xb<T>(c);
             const In<T> in = nxt;
             JX<T> jxm;
@@ -593,7 +593,7 @@ __global__ void __launch_bounds__(64, OCC3 ? 3 : 1) aba_dfs_kernel(Args<T> A)
             auto body = [&](auto kind) { // one dispatch on the joint kind per event (rnea_dfs_kernel)
             const int type = kind;
             const int jxs = jx_slots(type);
-            const CRef<T, false> c{CB + j * MC_STRIDE};
+            const CRef<T> c{CB + j * MC_STRIDE};
             const XF<T> Xb = load_xb<T>(c);
             const In<T> in = nxt;
             JX<T> jxm;
@@ -851,7 +851,7 @@ __global__ void __launch_bounds__(64, OCC3 ? 3 : 1) aba_dfs_kernel(Args<T> A)
             const int parent = mi[MI_PARENT], type_rt = mi[MI_TYPE], nch = mi[MI_NCH], fr = mi[MI_DFS_A], hf = mi[MI_HAND];
             auto body = [&](auto kind) {
             const int type = kind;
-            const CRef<T, false> c{CB + j * MC_STRIDE};
+            const CRef<T> c{CB + j * MC_STRIDE};
             const In<T> in = nxt;
             prefetch_q(j + 1);
             SV<T> ap;

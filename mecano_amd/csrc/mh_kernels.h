@@ -79,7 +79,7 @@ enum : int
    MF_HAS_ACC = 8,    // some child c != j + 1 exists: its inertia contribution arrives through the workspace
    MF_LOCKED = 16     // JointSourceMode.ACCELERATION_SOURCE (ForwardDynamicsCalculator.java:45-57): qdd is an input, tau an output
 };
-// ---- per-joint real constants (LDS)
+// ---- per-joint real constants (global memory, read through scalar loads: CRef)
 enum : int
 {
    MC_RB = 0,  // 9: rotation of the canonical before-joint frame in the parent's canonical after-joint frame, row-major
@@ -477,15 +477,6 @@ MH_DEV void store_joint_wrench(const CR &c, T *row, long f_es, int ext, const SV
    row[(e + 3) * f_es] = b.l.x, row[(e + 4) * f_es] = b.l.y, row[(e + 5) * f_es] = b.l.z;
 }
 
-template <typename T>
-MH_DEV void stage_consts(const DevModel &m, T *lds)
-{
-   const T *g = (const T *)m.consts;
-   for (int i = threadIdx.x; i < m.n * MC_STRIDE; i += blockDim.x)
-      lds[i] = g[i];
-   __syncthreads();
-}
-
 // ============================================================================================ layout staging
 // src [rows][cols] -> dst [cols][rows], 64 x 64 tiles through LDS, coalesced on both sides.  The run-time-topology kernels read one
 // matrix entry per lane: with AoS matrices ([B][n], lanes n * sizeof(T) bytes apart) every wave-load touches 64 cache lines and the
@@ -529,25 +520,21 @@ MH_DEV void lds_only_barrier()
 }
 constexpr int ROW_BLOCK_MAX_N = 512; // 128 n bytes of LDS <= 64 KB; 16 vectors of 16 bytes per thread and block
 // Non-temporal accesses (tools/proto_transpose.hip, profiles/r05_proto_transpose.txt: 131 072 x 323 floats, rows -> columns 5.2 -> 6.5 TB/s
-// with nt stores, columns -> rows 4.7 -> 6.3; a float4 copy of the same bytes 5.2-5.8 plain, 5.7-6.3 nt)
-template <bool NT, class VT, typename T>
+// with nt stores, columns -> rows 4.7 -> 6.3; a float4 copy of the same bytes 5.2-5.8 plain, 5.7-6.3 nt).  Both directions load and store
+// non-temporally: in the pair call of the 128-body tree that is ahead of nt stores only and of plain accesses by about 1 %
+// (profiles/r05_c5_transpose_nt.txt).
+template <class VT, typename T>
 MH_DEV VT row_block_load(const T *p)
 {
-   if constexpr (NT)
-      return __builtin_nontemporal_load((const VT *)p);
-   else
-      return *(const VT *)p;
+   return __builtin_nontemporal_load((const VT *)p);
 }
-template <bool NT, class VT, typename T>
+template <class VT, typename T>
 MH_DEV void row_block_store(T *p, VT v)
 {
-   if constexpr (NT)
-      __builtin_nontemporal_store(v, (VT *)p);
-   else
-      *(VT *)p = v;
+   __builtin_nontemporal_store(v, (VT *)p);
 }
 // src [B][n] (AoS) -> dst [n][B] (SoA)
-template <typename T, bool NTL, bool NTS>
+template <typename T>
 __global__ void __launch_bounds__(256) rows_to_columns_kernel(const T *__restrict__ src, T *__restrict__ dst, long B, int n, long blocks)
 {
    using RB = RowBlock<T>;
@@ -564,7 +551,7 @@ __global__ void __launch_bounds__(256) rows_to_columns_kernel(const T *__restric
 #pragma unroll
       for (int u = 0; u < NU; u++)
          if ((threadIdx.x + 256 * u) * V + V <= len)
-            reg[u] = row_block_load<NTL, VT>(flat + (threadIdx.x + 256 * u) * V);
+            reg[u] = row_block_load<VT>(flat + (threadIdx.x + 256 * u) * V);
    };
    long b = blockIdx.x;
    if (b < blocks)
@@ -587,13 +574,13 @@ __global__ void __launch_bounds__(256) rows_to_columns_kernel(const T *__restric
 #pragma unroll
             for (int k = 0; k < V; k++)
                w[k] = blk[(rb + k) * n + j];
-            row_block_store<NTS, VT>(dst + (long)j * B + r0 + rb, w);
+            row_block_store<VT>(dst + (long)j * B + r0 + rb, w);
          }
       lds_only_barrier(); // the block is free for the next one
    }
 }
 // src [n][B] (SoA) -> dst [B][n] (AoS)
-template <typename T, bool NTL, bool NTS>
+template <typename T>
 __global__ void __launch_bounds__(256) columns_to_rows_kernel(const T *__restrict__ src, T *__restrict__ dst, long B, int n, long blocks)
 {
    using RB = RowBlock<T>;
@@ -611,7 +598,7 @@ __global__ void __launch_bounds__(256) columns_to_rows_kernel(const T *__restric
 #pragma unroll
          for (int u = 0; u < NU; u++)
             if (jl + (256 / LPC) * u < n)
-               reg[u] = row_block_load<NTL, VT>(src + (long)(jl + (256 / LPC) * u) * B + r0 + rb);
+               reg[u] = row_block_load<VT>(src + (long)(jl + (256 / LPC) * u) * B + r0 + rb);
       }
    };
    long b = blockIdx.x;
@@ -637,7 +624,7 @@ __global__ void __launch_bounds__(256) columns_to_rows_kernel(const T *__restric
          request(b + gridDim.x);
       T *const flat = dst + r0 * n;
       for (int i = threadIdx.x * V; i + V <= len; i += 256 * V)
-         row_block_store<NTS, VT>(flat + i, *(const VT *)(blk + i));
+         row_block_store<VT>(flat + i, *(const VT *)(blk + i));
       lds_only_barrier();
    }
 }
@@ -657,24 +644,10 @@ inline void transpose_rows(const T *src, T *dst, long B, long n, bool to_columns
       }();
       const long blocks = (B + RB::R - 1) / RB::R, per_cu = std::max<long>(1, (long)(160 * 1024 / lds));
       const dim3 grid((unsigned)std::min<long>(blocks, cus * per_cu));
-      static const int nt = [] { // MH_TRANSPOSE_NT: bit 0 non-temporal stores, bit 1 non-temporal loads (measurements)
-         const char *e = getenv("MH_TRANSPOSE_NT");
-         return e ? atoi(e) : 3; // (in the pair call of the 128-body tree 3 is ahead of 1 and 0 by about 1 %: profiles/r05_c5_transpose_nt.txt)
-      }();
-      auto go = [&](auto ntl, auto nts) {
-         if (to_columns)
-            hipLaunchKernelGGL((rows_to_columns_kernel<T, decltype(ntl)::value, decltype(nts)::value>), grid, dim3(256), lds, stream, src, dst, B, (int)n, blocks);
-         else
-            hipLaunchKernelGGL((columns_to_rows_kernel<T, decltype(ntl)::value, decltype(nts)::value>), grid, dim3(256), lds, stream, src, dst, B, (int)n, blocks);
-      };
-      if (nt == 3)
-         go(std::true_type{}, std::true_type{});
-      else if (nt == 2)
-         go(std::true_type{}, std::false_type{});
-      else if (nt == 1)
-         go(std::false_type{}, std::true_type{});
+      if (to_columns)
+         hipLaunchKernelGGL((rows_to_columns_kernel<T>), grid, dim3(256), lds, stream, src, dst, B, (int)n, blocks);
       else
-         go(std::false_type{}, std::false_type{});
+         hipLaunchKernelGGL((columns_to_rows_kernel<T>), grid, dim3(256), lds, stream, src, dst, B, (int)n, blocks);
       return;
    }
    const dim3 grid((unsigned)(((B + 63) / 64) * ((n + 63) / 64)));
@@ -685,18 +658,11 @@ inline void transpose_rows(const T *src, T *dst, long B, long n, bool to_columns
 }
 
 // ============================================================================================ RNEA
-template <typename T, bool LDSC, bool BODIES = false>
+template <typename T, bool BODIES = false>
 __global__ void __launch_bounds__(256) rnea_kernel(Args<T> A)
 {
-   extern __shared__ double lds_raw[];
    const DevModel &m = A.m;
    const T *CB = (const T *)m.consts;
-   if constexpr (LDSC)
-   {
-      T *C = (T *)lds_raw;
-      stage_consts<T>(m, C);
-      CB = C;
-   }
    const ciptr meta = as_const(m.meta), dof_map = as_const(m.dof_map), cfg_map = as_const(m.cfg_map);
    const long lane = (long)blockIdx.x * blockDim.x + threadIdx.x;
    const long nlanes = (long)gridDim.x * blockDim.x;
@@ -720,7 +686,7 @@ __global__ void __launch_bounds__(256) rnea_kernel(Args<T> A)
       {
          ciptr mi = meta + j * MI_STRIDE;
          const int parent = mi[MI_PARENT], type = mi[MI_TYPE], flags = mi[MI_FLAGS];
-         const CRef<T, LDSC> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          SV<T> vp, ap;
          if (parent < 0)
          {
@@ -771,7 +737,7 @@ __global__ void __launch_bounds__(256) rnea_kernel(Args<T> A)
       {
          ciptr mi = meta + j * MI_STRIDE;
          const int parent = mi[MI_PARENT], type = mi[MI_TYPE], flags = mi[MI_FLAGS];
-         const CRef<T, LDSC> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          SV<T> f = ws_load6(ws, ws_stride, mi[MI_SLOT_F]);
          if (have_carry)
             f = f + carry;
@@ -984,18 +950,11 @@ MH_DEV SV<T> spd6_solve(const LDL6<T> &F, SV<T> b)
 #ifndef MH_SWEEP_AHEAD
 #define MH_SWEEP_AHEAD 0
 #endif
-template <typename T, bool LDSC, bool LOCKED = false, bool BODIES = false>
+template <typename T, bool LOCKED = false, bool BODIES = false>
 __global__ void __launch_bounds__(256) aba_kernel(Args<T> A)
 {
-   extern __shared__ double lds_raw[];
    const DevModel &m = A.m;
    const T *CB = (const T *)m.consts;
-   if constexpr (LDSC)
-   {
-      T *C = (T *)lds_raw;
-      stage_consts<T>(m, C);
-      CB = C;
-   }
    const ciptr meta = as_const(m.meta), dof_map = as_const(m.dof_map), cfg_map = as_const(m.cfg_map);
    const long lane = (long)blockIdx.x * blockDim.x + threadIdx.x;
    const long nlanes = (long)gridDim.x * blockDim.x;
@@ -1035,7 +994,7 @@ __global__ void __launch_bounds__(256) aba_kernel(Args<T> A)
          const int parent = mi[MI_PARENT], type_rt = mi[MI_TYPE], flags = mi[MI_FLAGS];
          auto body = [&](auto kind) { // one dispatch on the joint kind per body, straight-line code per kind (mh_dfs_kernels.h)
          const int type = kind;
-         const CRef<T, LDSC> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          if (!MH_SWEEP_AHEAD)
             pre1(j);
          const T q_in = nq_, v_in = nv_;
@@ -1117,7 +1076,7 @@ __global__ void __launch_bounds__(256) aba_kernel(Args<T> A)
          const int parent = mi[MI_PARENT], type_rt = mi[MI_TYPE], flags = mi[MI_FLAGS];
          auto body = [&](auto kind) { // one dispatch on the joint kind per body, straight-line code per kind (mh_dfs_kernels.h)
          const int type = kind;
-         const CRef<T, LDSC> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          ABI<T> IA = abi_from_rigid(load_inertia<T>(c));
          if (!MH_SWEEP_AHEAD)
             pre2(j);
@@ -1315,7 +1274,7 @@ __global__ void __launch_bounds__(256) aba_kernel(Args<T> A)
          const int parent = mi[MI_PARENT], type_rt = mi[MI_TYPE], flags = mi[MI_FLAGS];
          auto body = [&](auto kind) { // one dispatch on the joint kind per body, straight-line code per kind (mh_dfs_kernels.h)
          const int type = kind;
-         const CRef<T, LDSC> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          if (!MH_SWEEP_AHEAD)
             pre3(j);
          const SV<T> cj3 = ncj3, U_in = nU;
@@ -1645,18 +1604,11 @@ MH_DEV RI<T> ws_load_ri(const T *ws, long ws_stride, int s)
 }
 // H is [B][nv][nv] row-major (h_bs = nv*nv, element (r,c) at r*nv + c) and must be zero-filled before the launch:
 // the kernel writes only the entries of related joints (CompositeRigidBodyMassMatrixCalculator.java:298,841-845).
-template <typename T, bool LDSC>
+template <typename T>
 __global__ void __launch_bounds__(256) crba_kernel(Args<T> A)
 {
-   extern __shared__ double lds_raw[];
    const DevModel &m = A.m;
    const T *CB = (const T *)m.consts;
-   if constexpr (LDSC)
-   {
-      T *C = (T *)lds_raw;
-      stage_consts<T>(m, C);
-      CB = C;
-   }
    const ciptr meta = as_const(m.meta), dof_map = as_const(m.dof_map), cfg_map = as_const(m.cfg_map);
    const long lane = (long)blockIdx.x * blockDim.x + threadIdx.x;
    const long nlanes = (long)gridDim.x * blockDim.x;
@@ -1685,7 +1637,7 @@ __global__ void __launch_bounds__(256) crba_kernel(Args<T> A)
       {
          ciptr mi = meta + j * MI_STRIDE;
          const int parent = mi[MI_PARENT], type = mi[MI_TYPE], flags = mi[MI_FLAGS];
-         const CRef<T, LDSC> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          RI<T> Ic = load_inertia<T>(c);
          if (have_carry)
             add(Ic, rcarry);
@@ -1740,7 +1692,7 @@ __global__ void __launch_bounds__(256) crba_kernel(Args<T> A)
                anc = ma[MI_PARENT];
                if (anc >= 0)
                {
-                  Xp = load_xb<T>(CRef<T, LDSC>{CB + prev * MC_STRIDE});
+                  Xp = load_xb<T>(CRef<T>{CB + prev * MC_STRIDE});
                   jp = joint_again<T>(ta, cfg_map, ma[MI_CFG], qrow, A.q_es, ws, ws_stride, ma[MI_SLOT_JP]);
                   tp = ta;
                }
@@ -1824,18 +1776,11 @@ MH_DEV void fb_up(int type, const JX<T> &jx, const XF<T> &Xb, FB<T> &B)
    translate(B, Xb.p);
 }
 
-template <typename T, bool LDSC>
+template <typename T>
 __global__ void __launch_bounds__(256) coriolis_kernel(Args<T> A)
 {
-   extern __shared__ double lds_raw[];
    const DevModel &m = A.m;
    const T *CB = (const T *)m.consts;
-   if constexpr (LDSC)
-   {
-      T *C = (T *)lds_raw;
-      stage_consts<T>(m, C);
-      CB = C;
-   }
    const ciptr meta = as_const(m.meta), dof_map = as_const(m.dof_map), cfg_map = as_const(m.cfg_map);
    const long lane = (long)blockIdx.x * blockDim.x + threadIdx.x;
    const long nlanes = (long)gridDim.x * blockDim.x;
@@ -1862,7 +1807,7 @@ __global__ void __launch_bounds__(256) coriolis_kernel(Args<T> A)
       {
          ciptr mi = meta + j * MI_STRIDE;
          const int parent = mi[MI_PARENT], type = mi[MI_TYPE], flags = mi[MI_FLAGS];
-         const CRef<T, LDSC> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          SV<T> vp{Z, Z};
          if (parent >= 0)
             vp = (flags & MF_PARENT_ADJ) ? v_prev : ws_load6(ws, ws_stride, meta[parent * MI_STRIDE + MI_SLOT_C]);
@@ -1879,7 +1824,7 @@ __global__ void __launch_bounds__(256) coriolis_kernel(Args<T> A)
       {
          ciptr mi = meta + j * MI_STRIDE;
          const int parent = mi[MI_PARENT], type = mi[MI_TYPE], flags = mi[MI_FLAGS];
-         const CRef<T, LDSC> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          const SV<T> vj = ws_load6(ws, ws_stride, mi[MI_SLOT_C]);
          RI<T> Ic = load_inertia<T>(c);
          FB<T> Bc = fb_from_rigid(Ic, vj); // :671-673
@@ -1938,7 +1883,7 @@ __global__ void __launch_bounds__(256) coriolis_kernel(Args<T> A)
                anc = ma[MI_PARENT];
                if (anc >= 0)
                {
-                  Xp = load_xb<T>(CRef<T, LDSC>{CB + prev * MC_STRIDE});
+                  Xp = load_xb<T>(CRef<T>{CB + prev * MC_STRIDE});
                   jp = joint_again<T>(ta, cfg_map, ma[MI_CFG], qrow, A.q_es, ws, ws_stride, ma[MI_SLOT_JP]);
                   tp = ta;
                }
@@ -1997,18 +1942,11 @@ struct CentArgs
    int at_com;
 };
 
-template <typename T, bool LDSC>
+template <typename T>
 __global__ void __launch_bounds__(256) centroidal_kernel(CentArgs<T> A)
 {
-   extern __shared__ double lds_raw[];
    const DevModel &m = A.m;
    const T *CB = (const T *)m.consts;
-   if constexpr (LDSC)
-   {
-      T *C = (T *)lds_raw;
-      stage_consts<T>(m, C);
-      CB = C;
-   }
    const ciptr meta = as_const(m.meta), dof_map = as_const(m.dof_map), cfg_map = as_const(m.cfg_map);
    const long lane = (long)blockIdx.x * blockDim.x + threadIdx.x;
    const long nlanes = (long)gridDim.x * blockDim.x;
@@ -2037,7 +1975,7 @@ __global__ void __launch_bounds__(256) centroidal_kernel(CentArgs<T> A)
       {
          ciptr mi = meta + j * MI_STRIDE;
          const int parent = mi[MI_PARENT], type = mi[MI_TYPE], flags = mi[MI_FLAGS];
-         const CRef<T, LDSC> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          const JX<T> jx = joint_from_q<T>(type, cfg_map, mi[MI_CFG], qrow, A.q_es, ws, ws_stride, mi[MI_SLOT_JP], true);
          if (!with_b)
             continue;
@@ -2071,7 +2009,7 @@ __global__ void __launch_bounds__(256) centroidal_kernel(CentArgs<T> A)
       {
          ciptr mi = meta + j * MI_STRIDE;
          const int parent = mi[MI_PARENT], type = mi[MI_TYPE], flags = mi[MI_FLAGS];
-         const CRef<T, LDSC> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          RI<T> Ic = load_inertia<T>(c);
          SV<T> f{Z, Z};
          if (with_b)
@@ -2102,7 +2040,7 @@ __global__ void __launch_bounds__(256) centroidal_kernel(CentArgs<T> A)
                   break;
                ciptr ma = meta + anc * MI_STRIDE;
                tp = ma[MI_TYPE];
-               Xp = load_xb<T>(CRef<T, LDSC>{CB + anc * MC_STRIDE});
+               Xp = load_xb<T>(CRef<T>{CB + anc * MC_STRIDE});
                jp = joint_again<T>(tp, cfg_map, ma[MI_CFG], qrow, A.q_es, ws, ws_stride, ma[MI_SLOT_JP]);
                prev = anc;
                anc = ma[MI_PARENT];
@@ -2226,7 +2164,7 @@ MH_DEV XF<T> body_pose_in_root(const DevModel &m, ciptr meta, ciptr cfg_map, con
    if (e < 0)
       return X;
    {
-      const CRef<T, false> c{CB + e * MC_STRIDE};
+      const CRef<T> c{CB + e * MC_STRIDE};
       X.R = M3<T>{c[MC_RF + 0], c[MC_RF + 1], c[MC_RF + 2], c[MC_RF + 3], c[MC_RF + 4], c[MC_RF + 5], c[MC_RF + 6], c[MC_RF + 7], c[MC_RF + 8]};
       X.p = V3<T>{c[MC_PF + 0], c[MC_PF + 1], c[MC_PF + 2]};
    }
@@ -2234,7 +2172,7 @@ MH_DEV XF<T> body_pose_in_root(const DevModel &m, ciptr meta, ciptr cfg_map, con
    {
       ciptr mi = meta + j * MI_STRIDE;
       const int type = mi[MI_TYPE];
-      const CRef<T, false> c{CB + j * MC_STRIDE};
+      const CRef<T> c{CB + j * MC_STRIDE};
       const JX<T> jx = joint_from_q<T>(type, cfg_map, mi[MI_CFG], qrow, q_es, (T *)nullptr, 0, 0, false);
       XF<T> XJ;
       if (general_x(type))
@@ -2314,18 +2252,11 @@ __global__ void __launch_bounds__(256) relative_acceleration_kernel(RelArgs<T> A
 // moment m c instead (what an identification wants).
 // Y is [B][nv][10 n]: A.out, A.f_bs = nv * 10 n, A.f_es = 1 (MH_LAYOUT_SOA: [nv][10 n][B], f_bs = 1, f_es = B); the block of body `e`
 // (caller's joint order) starts at column 10 e.
-template <typename T, bool LDSC, int MODE>
+template <typename T, int MODE>
 __global__ void __launch_bounds__(256) regressor_kernel(Args<T> A)
 {
-   extern __shared__ double lds_raw[];
    const DevModel &m = A.m;
    const T *CB = (const T *)m.consts;
-   if constexpr (LDSC)
-   {
-      T *C = (T *)lds_raw;
-      stage_consts<T>(m, C);
-      CB = C;
-   }
    const ciptr meta = as_const(m.meta), dof_map = as_const(m.dof_map), cfg_map = as_const(m.cfg_map);
    const long lane = (long)blockIdx.x * blockDim.x + threadIdx.x;
    const long nlanes = (long)gridDim.x * blockDim.x;
@@ -2351,7 +2282,7 @@ __global__ void __launch_bounds__(256) regressor_kernel(Args<T> A)
       {
          ciptr mi = meta + j * MI_STRIDE;
          const int parent = mi[MI_PARENT], type = mi[MI_TYPE], flags = mi[MI_FLAGS];
-         const CRef<T, LDSC> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          // ---- the first pass of the inverse dynamics (InverseDynamicsCalculator.java:873-917), as rnea_kernel runs it
          SV<T> vp, ap;
          if (parent < 0)
@@ -2438,7 +2369,7 @@ __global__ void __launch_bounds__(256) regressor_kernel(Args<T> A)
             {
                ciptr mu = meta + up * MI_STRIDE;
                tn = mu[MI_TYPE];
-               Xn = load_xb<T>(CRef<T, LDSC>{CB + up * MC_STRIDE});
+               Xn = load_xb<T>(CRef<T>{CB + up * MC_STRIDE});
                jn = joint_again<T>(tn, cfg_map, mu[MI_CFG], qrow, A.q_es, ws, ws_stride, mu[MI_SLOT_JP]);
             }
             for (int r = 0; r < nd; r++)

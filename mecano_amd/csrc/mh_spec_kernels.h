@@ -899,7 +899,7 @@ MH_DEV void spec_body_outputs(const CX &cx, const SV<T> &acc, const SV<T> &twist
 {
    if constexpr (CX::bodies)
    {
-      const CRef<T, false> c{cx.C + J * MC_STRIDE};
+      const CRef<T> c{cx.C + J * MC_STRIDE};
       const int ext = cx.meta[J * MI_STRIDE + MI_EXT];
       if (cx.bacc)
          store_body_motion<T>(c, cx.bacc, cx.f_es, ext, acc);
@@ -958,7 +958,7 @@ struct RneaSub
       MH_BODY_FENCE();
       constexpr int TYPE = TP::type[J];
       constexpr int DO = Tree<TP>::dof_ofs(J), CO = Tree<TP>::cfg_ofs(J);
-      const CRef<T, false> c{cx.C + J * MC_STRIDE};
+      const CRef<T> c{cx.C + J * MC_STRIDE};
       // (cos, sin) formed in front of the walk: RneaPreStore (slots 0, 1), or -- fused forward dynamics, the bodies of a limb -- the slots the
       // inertia walk of the same wave reads them from (7, 8; rnea_pre_pass)
       constexpr bool PRE3 = CX::csmode == 3 && MH_ZVF_PRE && TYPE == JT_REVOLUTE && Split<TP>::usable() && !Split<TP>::is_trunk(J);
@@ -1007,7 +1007,7 @@ struct RneaSub
       // SGPR file and turns every use into a v_readlane); the pointer is laundered so that the reload is not merged away
       const T *c2p = cx.C + J * MC_STRIDE;
       asm volatile("" : "+s"(c2p));
-      const SV<T> up = force_up(TYPE, jx, load_xb_j<TP, J, T>(CRef<T, false>{c2p}), f);
+      const SV<T> up = force_up(TYPE, jx, load_xb_j<TP, J, T>(CRef<T>{c2p}), f);
       MH_BODY_FENCE();
       return up;
    }
@@ -1046,7 +1046,7 @@ MH_DEV void trunk_va(const CX &cx, SV<T> &v, SV<T> &a)
    if constexpr (TP::parent[J] >= 0)
       trunk_va<TP, TP::parent[J], T, CX, FK, OWN>(cx, vp, ap);
    MH_BODY_FENCE();
-   const CRef<T, false> c{cx.C + J * MC_STRIDE};
+   const CRef<T> c{cx.C + J * MC_STRIDE};
    constexpr bool PRE = CX::rnea_pre && TYPE == JT_REVOLUTE;
    JQ<T> jq;
    if constexpr (!PRE)
@@ -1128,7 +1128,7 @@ struct RneaTrunkUp
          spec_write<TYPE, DO, CX, T>(cx, f);
       SV<T> up = f;
       if constexpr (TP::parent[J] >= 0)
-         up = force_up(TYPE, jx, load_xb_j<TP, J, T>(CRef<T, false>{cx.C + J * MC_STRIDE}), f);
+         up = force_up(TYPE, jx, load_xb_j<TP, J, T>(CRef<T>{cx.C + J * MC_STRIDE}), f);
       MH_BODY_FENCE();
       return up;
    }
@@ -1153,7 +1153,7 @@ MH_DEV SV<T> trunk_v(const CX &cx)
    if constexpr (TP::parent[J] >= 0)
       vp = trunk_v<TP, TP::parent[J], T, CX>(cx);
    MH_BODY_FENCE();
-   const CRef<T, false> c{cx.C + J * MC_STRIDE};
+   const CRef<T> c{cx.C + J * MC_STRIDE};
    const JQ<T> jq = spec_joint_read<TYPE, CO, CX, T>(cx);
    const SV<T> vJ = spec_vec<TYPE, DO, 0, CX, T>(cx, true);
    const XF<T> Xb = load_xb_j<TP, J, T>(c);
@@ -1248,7 +1248,7 @@ struct AbaIn
       constexpr bool HAS_PARENT = TP::parent[J] >= 0;
       constexpr bool LEAF = Tree<TP>::n_children(J) == 0;
       constexpr int DO = Tree<TP>::dof_ofs(J), CO = Tree<TP>::cfg_ofs(J), S0 = Tree<TP>::aba_slot(J);
-      const CRef<T, false> c{cx.C + J * MC_STRIDE};
+      const CRef<T> c{cx.C + J * MC_STRIDE};
       const JQ<T> jq = spec_joint_read<TYPE, CO, CX, T>(cx);
       const SV<T> vJ = spec_vec<TYPE, DO, 0, CX, T>(cx, true);
       const XF<T> Xb0 = load_xb_j<TP, J, T>(c);
@@ -1375,7 +1375,7 @@ struct AbaOut
       constexpr int TYPE = TP::type[J];
       constexpr bool LEAF = Tree<TP>::n_children(J) == 0;
       constexpr int DO = Tree<TP>::dof_ofs(J), CO = Tree<TP>::cfg_ofs(J), S0 = Tree<TP>::aba_slot(J);
-      const CRef<T, false> c{cx.C + J * MC_STRIDE};
+      const CRef<T> c{cx.C + J * MC_STRIDE};
       JX<T> jx;
       JQ<T> jq;
       if constexpr (TYPE == JT_REVOLUTE)
@@ -1601,7 +1601,7 @@ struct CrbaSub
       if constexpr (DC > 0)
       {
          constexpr int CUR = TR::ancestor_at_depth(J, DC), PAR = TR::ancestor_at_depth(J, DC - 1);
-         const CRef<T, false> c{cx.C + CUR * MC_STRIDE};
+         const CRef<T> c{cx.C + CUR * MC_STRIDE};
          F = force_up(TP::type[CUR], path.jx[DC], load_xb_j<TP, CUR, T>(c), F);
          write_ancestor<PAR, COL>(cx, F);
          climb<DC - 1, COL>(cx, path, F);
@@ -1647,7 +1647,7 @@ struct CrbaSub
       if constexpr (!LEAF)
          children<0>(cx, path, acc);
       MH_BODY_FENCE();
-      const CRef<T, false> c{cx.C + J * MC_STRIDE};
+      const CRef<T> c{cx.C + J * MC_STRIDE};
       RI<T> Ic = load_inertia<T>(c);
       if constexpr (!LEAF)
          add(Ic, acc);
@@ -1849,7 +1849,7 @@ struct CorSub
          // the same ancestor it would stay in 24 SGPRs per tree level for the whole subtree -- 2 000 scalar spills on the humanoid
          const T *cp = cx.C + CUR * MC_STRIDE;
          asm volatile("" : "+s"(cp));
-         const XF<T> Xb = load_xb_j<TP, CUR, T>(CRef<T, false>{cp});
+         const XF<T> Xb = load_xb_j<TP, CUR, T>(CRef<T>{cp});
          F1 = force_up(TP::type[CUR], path.jx[DC], Xb, F1);
          F2 = force_up(TP::type[CUR], path.jx[DC], Xb, F2);
          F3 = force_up(TP::type[CUR], path.jx[DC], Xb, F3);
@@ -1890,7 +1890,7 @@ struct CorSub
       MH_BODY_FENCE();
       constexpr int TYPE = TP::type[J], CO = TR::cfg_ofs(J), DO = TR::dof_ofs(J);
       constexpr bool LEAF = TR::n_children(J) == 0;
-      const CRef<T, false> c{cx.C + J * MC_STRIDE};
+      const CRef<T> c{cx.C + J * MC_STRIDE};
       CorPath<T, D + 1> path;
 #pragma unroll
       for (int d = 0; d < D; d++)
@@ -1920,7 +1920,7 @@ struct CorSub
       {
          const T *cp = cx.C + J * MC_STRIDE;
          asm volatile("" : "+s"(cp));
-         const XF<T> Xb = load_xb_j<TP, J, T>(CRef<T, false>{cp});
+         const XF<T> Xb = load_xb_j<TP, J, T>(CRef<T>{cp});
          rigid_up(TYPE, path.jx[D], Xb, out.I); // :651-661
          fb_up(TYPE, path.jx[D], Xb, out.B);    // :675-683
       }
@@ -1984,7 +1984,7 @@ struct CentSub
       constexpr int CUR = TR::ancestor_at_depth(J, DC);
       const T *cp = cx.C + CUR * MC_STRIDE;
       asm volatile("" : "+s"(cp)); // reloaded per step (see CorSub::climb)
-      F = force_up(TP::type[CUR], path.jx[DC], load_xb_j<TP, CUR, T>(CRef<T, false>{cp}), F);
+      F = force_up(TP::type[CUR], path.jx[DC], load_xb_j<TP, CUR, T>(CRef<T>{cp}), F);
       if constexpr (DC > 0)
          return to_root<DC - 1>(cx, path, F);
       else
@@ -2010,7 +2010,7 @@ struct CentSub
       MH_BODY_FENCE();
       constexpr int TYPE = TP::type[J], CO = TR::cfg_ofs(J), DO = TR::dof_ofs(J);
       constexpr bool LEAF = TR::n_children(J) == 0;
-      const CRef<T, false> c{cx.C + J * MC_STRIDE};
+      const CRef<T> c{cx.C + J * MC_STRIDE};
       CrbaPath<T, D + 1> path;
 #pragma unroll
       for (int d = 0; d < D; d++)
@@ -2044,7 +2044,7 @@ struct CentSub
       {
          const T *cp = cx.C + J * MC_STRIDE;
          asm volatile("" : "+s"(cp));
-         const XF<T> Xb = load_xb_j<TP, J, T>(CRef<T, false>{cp});
+         const XF<T> Xb = load_xb_j<TP, J, T>(CRef<T>{cp});
          rigid_up(TYPE, path.jx[D], Xb, out.I);
          out.f = force_up(TYPE, path.jx[D], Xb, out.f);
       }

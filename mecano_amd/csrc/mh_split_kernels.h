@@ -153,7 +153,7 @@ MH_DEV void rnea_split_body(const Args<T> &A, const SplitDev &P, long blk, long 
          const int parent = mi[MI_PARENT], type_rt = mi[MI_TYPE], flags = mi[MI_FLAGS];
          auto kbody = [&](auto kind) {
          const int type = kind;
-         const CRef<T, false> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          SV<T> vp, ap;
          if (parent < 0)
          {
@@ -221,7 +221,7 @@ MH_DEV void rnea_split_body(const Args<T> &A, const SplitDev &P, long blk, long 
          const int parent = mi[MI_PARENT], type_rt = mi[MI_TYPE], flags = mi[MI_FLAGS], xs = mi[MI_HAND];
          auto kbody = [&](auto kind) {
          const int type = kind;
-         const CRef<T, false> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          SV<T> f = st_load6<T>(S, mi[MI_SLOT_F]);
          if (have_carry)
             f = f + carry;
@@ -310,7 +310,7 @@ MH_DEV void aba_split_body(const Args<T> &A, const SplitDev &P, long blk, long n
          const int parent = mi[MI_PARENT], type_rt = mi[MI_TYPE], flags = mi[MI_FLAGS];
          auto kbody = [&](auto kind) {
          const int type = kind;
-         const CRef<T, false> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          SV<T> vp;
          if (parent < 0)
             vp = SV<T>{Z, Z};
@@ -361,7 +361,7 @@ MH_DEV void aba_split_body(const Args<T> &A, const SplitDev &P, long blk, long n
          const int parent = mi[MI_PARENT], type_rt = mi[MI_TYPE], flags = mi[MI_FLAGS], xs = mi[MI_HAND];
          auto kbody = [&](auto kind) {
          const int type = kind;
-         const CRef<T, false> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          ABI<T> IA = abi_from_rigid(load_inertia<T>(c));
          SV<T> pA = st_load6<T>(S, mi[MI_SLOT_F]);
          if (have_carry)
@@ -514,7 +514,7 @@ MH_DEV void aba_split_body(const Args<T> &A, const SplitDev &P, long blk, long n
          const int parent = mi[MI_PARENT], type_rt = mi[MI_TYPE], flags = mi[MI_FLAGS];
          auto kbody = [&](auto kind) {
          const int type = kind;
-         const CRef<T, false> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          SV<T> ap;
          if (parent < 0)
             ap = root_acceleration(A); // :259-264
@@ -665,7 +665,7 @@ __global__ void __launch_bounds__(256) crba_split_kernel(Args<T> A, SplitDev P)
       auto body = [&](int j, int xk0, int xk1) {
          ciptr mi = meta + j * MI_STRIDE;
          const int parent = mi[MI_PARENT], type = mi[MI_TYPE], flags = mi[MI_FLAGS], xs = mi[MI_HAND];
-         const CRef<T, false> c{CB + j * MC_STRIDE};
+         const CRef<T> c{CB + j * MC_STRIDE};
          RI<T> Ic = load_inertia<T>(c);
          if (have_carry)
             add(Ic, rcarry);
@@ -720,7 +720,7 @@ __global__ void __launch_bounds__(256) crba_split_kernel(Args<T> A, SplitDev P)
                anc = ma[MI_PARENT];
                if (anc >= 0)
                {
-                  Xp = load_xb<T>(CRef<T, false>{CB + prev * MC_STRIDE});
+                  Xp = load_xb<T>(CRef<T>{CB + prev * MC_STRIDE});
                   jp = sw_joint_again<T>(S, ta, cfg_map, ma[MI_CFG], qrow, A.q_es, ma[MI_SLOT_JP]);
                   tp = ta;
                }

@@ -421,7 +421,7 @@ struct ZvIn
       ZV_STAMP_BODY(J, 0);
       const T *cp = cx.C + J * MC_STRIDE;
       asm volatile("" : "+s"(cp)); // the constants are read where they are used, never kept across a subtree
-      const CRef<T, false> c{cp};
+      const CRef<T> c{cp};
       // (cos, sin) already in the body's slots: limbs (ZvPre ran, zv_limbs_in_of); CSMODE 2: the bodies of a staged sub-trunk too (ZvPreTrunk); CSMODE 3: every body (left there by the inverse dynamics of the same workgroup)
       constexpr bool PRE = TYPE == JT_REVOLUTE && ((!Split<TP>::is_trunk(J) && (MODE == 0 || MODE == 3)) || ((CX::csmode == 2 || (CX::csmode == 0 && MH_ZV_PRE_WAVE)) && Split<TP>::staged() && Split<TP>::is_trunk(J) && MODE == 1) || (CX::csmode == 3 && Split<TP>::is_trunk(J)));
       JQ<T> jq;
@@ -532,7 +532,7 @@ struct ZvFold
       MH_BODY_FENCE();
       const T *cp = cx.C + J * MC_STRIDE;
       asm volatile("" : "+s"(cp));
-      const CRef<T, false> c{cp};
+      const CRef<T> c{cp};
       SV<T> up{Z, Z};
       if constexpr (TYPE == JT_REVOLUTE || TYPE == JT_PRISMATIC)
       {
@@ -618,7 +618,7 @@ struct ZvOut
       constexpr int RS = Tree<TP>::zv_result_slot(J, CX::SPolicy::shared(J));
       const T *cp = cx.C + J * MC_STRIDE;
       asm volatile("" : "+s"(cp));
-      const CRef<T, false> c{cp};
+      const CRef<T> c{cp};
       const V3<T> Z{T(0), T(0), T(0)};
       SV<T> a{Z, Z};
       if constexpr (HAS_PARENT)
@@ -848,7 +848,7 @@ struct ZvOutW
       constexpr bool WRITES = ZvWalk<TP>::writer(J) == W;
       const T *cp = cx.C + J * MC_STRIDE;
       asm volatile("" : "+s"(cp));
-      const CRef<T, false> c{cp};
+      const CRef<T> c{cp};
       const V3<T> Z{T(0), T(0), T(0)};
       SV<T> a{Z, Z};
       if constexpr (HAS_PARENT)
@@ -2121,7 +2121,7 @@ MH_DEV SV<T> zvf_delta_trunk_a(const CX &cx)
    else
    {
       const SV<T> ap = zvf_delta_trunk_a<TP, P, T, CX>(cx);
-      const CRef<T, false> c{cx.C + J * MC_STRIDE};
+      const CRef<T> c{cx.C + J * MC_STRIDE};
       return motion_down(TYPE, zvf_delta_joint<TP, J, T, CX>(cx), load_xb_j<TP, J, T>(c), ap) + aJ;
    }
 }
@@ -2154,7 +2154,7 @@ struct ZvfDelta
       constexpr bool HAS_PARENT = TP::parent[J] >= 0;
       const T *cp = cx.C + J * MC_STRIDE;
       asm volatile("" : "+s"(cp));
-      const CRef<T, false> c{cp};
+      const CRef<T> c{cp};
       const SV<T> aJ = spec_vec<TYPE, Tree<TP>::dof_ofs(J), 1, CX, T>(cx, true);
       SV<T> a = aJ;
       if constexpr (HAS_PARENT)
@@ -2178,7 +2178,7 @@ struct ZvfDelta
       { // (the pose is read again rather than kept across the subtree: see RneaSub)
          const T *c2p = cx.C + J * MC_STRIDE;
          asm volatile("" : "+s"(c2p));
-         up = force_up(TYPE, zvf_delta_joint<TP, J, T, CX>(cx), load_xb_j<TP, J, T>(CRef<T, false>{c2p}), f);
+         up = force_up(TYPE, zvf_delta_joint<TP, J, T, CX>(cx), load_xb_j<TP, J, T>(CRef<T>{c2p}), f);
       }
       MH_BODY_FENCE();
       return up;

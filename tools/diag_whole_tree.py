@@ -25,7 +25,7 @@ else:
     dev = lambda x: torch.tensor(np.ascontiguousarray(x), device="cuda", dtype=torch.float64)
 
     def model(**env):
-        keys = ("MH_SPEC_DIR", "MH_SPEC_SELFCHECK", "MH_SPEC_SPLIT", "MH_SPEC_IO", "MH_SPEC_ST", "MH_DISABLE_SPEC", "MH_DISABLE_FUSED")
+        keys = ("MH_SPEC_DIR", "MH_SPEC_SELFCHECK", "MH_SPEC_SPLIT", "MH_SPEC_IO", "MH_SPEC_ST", "MH_DISABLE_SPEC")
         for k in keys:
             os.environ.pop(k, None)
         for k, v in env.items():
@@ -43,7 +43,7 @@ else:
             want = ref.aba(q, qdv, tau, g)
             for io in (0, 1):
                 for st in (0, 1):
-                    hm = model(MH_SPEC_DIR=out_dir, MH_SPEC_SELFCHECK=0, MH_SPEC_SPLIT=0, MH_SPEC_IO=io, MH_SPEC_ST=st, MH_DISABLE_FUSED=1)
+                    hm = model(MH_SPEC_DIR=out_dir, MH_SPEC_SELFCHECK=0, MH_SPEC_SPLIT=0, MH_SPEC_IO=io, MH_SPEC_ST=st)
                     for layout, name in ((_lib.LAYOUT_AOS, "AoS"), (_lib.LAYOUT_SOA, "SoA")):
                         if layout == _lib.LAYOUT_SOA:
                             got = hm.aba(q.t().contiguous(), qdv.t().contiguous(), tau.t().contiguous(), g, layout=layout).t()
