@@ -433,6 +433,70 @@ mh_status check_common(mh_model_t &model, int64_t B, const mh_options *opts)
       return fail(MH_ERR_INVALID_ARGUMENT, "model lives on device %d but the calling thread's device is %d", model->device, cur);
    return MH_OK;
 }
+// The options of a compute call (the defaults where opts_in is NULL), checked by check_common -- which switches `model` to their context
+mh_status begin_call(mh_model_t &model, int64_t B, const mh_options *opts_in, mh_options &opts)
+{
+   if (opts_in)
+      opts = *opts_in;
+   else
+      mh_options_default(&opts);
+   return check_common(model, B, &opts);
+}
+
+// groups of 64 configurations: one wave, or one workgroup of four waves, each
+long groups_of(int64_t B) { return (B + 63) / 64; }
+
+// (batch stride, element stride) of a matrix with rows of n entries in the call's layout
+void set_strides(long &bs, long &es, bool soa, int64_t B, long n) { bs = soa ? 1 : n, es = soa ? B : 1; }
+
+// The kernel arguments every call fills alike: the model, the batch, the strides of state (q, v) and wrench-sized (f) rows.  With the
+// gravity argument also the root acceleration and the Coriolis / acceleration switches.  The caller sets the pointers and any stride
+// that differs.
+template <typename T>
+mh::Args<T> make_args(const mh_model *m, int64_t B, const mh_options &o)
+{
+   mh::Args<T> A{};
+   A.m = dev_model<T>(m);
+   A.B = B;
+   const bool soa = o.layout == MH_LAYOUT_SOA;
+   set_strides(A.q_bs, A.q_es, soa, B, m->nq);
+   set_strides(A.v_bs, A.v_es, soa, B, m->nv);
+   set_strides(A.f_bs, A.f_es, soa, B, (long)m->n * 6);
+   return A;
+}
+template <typename T>
+mh::Args<T> make_args(const mh_model *m, int64_t B, const mh_options &o, const double *gravity)
+{
+   mh::Args<T> A = make_args<T>(m, B, o);
+   set_root_acceleration(A, o, gravity);
+   A.coriolis = o.consider_coriolis, A.accel = o.consider_accelerations;
+   return A;
+}
+
+// A code object's launcher returns 0 when it launched, hipErrorNotSupported when the plan is not in the object (the caller goes on to
+// its next plan) and anything else on failure.  True: the call is over, with status st.
+bool spec_done(int rc, const char *what, mh_status &st)
+{
+   if (rc == (int)hipErrorNotSupported)
+      return false;
+   st = rc == 0 ? MH_OK : fail(MH_ERR_HIP, "%s: %s", what, hipGetErrorString((hipError_t)rc));
+   return true;
+}
+
+// a kernel that takes more than 64 KB of dynamic LDS needs its limit raised, once per kernel and model
+mh_status raise_lds_limit(mh_model *model, const void *kern, size_t lds)
+{
+   if (lds > 64 * 1024 && model->lds_attr[kern] < lds)
+   {
+      HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      model->lds_attr[kern] = lds;
+   }
+   return MH_OK;
+}
+
+// Big AoS batches of wide matrices go through transposed scratch copies (launch<T>; MH_GENERIC_TRANSPOSE forces the choice)
+bool auto_transpose(const mh_model *m, int64_t B) { return B >= 8192 && m->nq + m->nv >= 64; }
+bool transposes(const mh_model *m, int64_t B) { return m->use_transpose >= 0 ? m->use_transpose != 0 : auto_transpose(m, B); }
 
 // tree-split kernels: 4 waves per 64 configurations; worth it while the batch cannot give every SIMD a wave of its own otherwise
 // flags for the tree-split kernels: identity maps; rows staged in LDS when the layout is AoS, the maps are dense and it fits
@@ -452,7 +516,7 @@ bool split_ok(const mh_model *m, int algo, int64_t B, bool soa)
    if (m->use_split == 1 || algo == 1 || algo == 0)
       return true; // ABA: the split form needs fewer registers; RNEA: two waves per SIMD and a trunk pass that is a fold of parked
                    // wrenches -- both measured faster than the whole-tree kernels at every batch size and in both layouts
-   const long groups = (B + 63) / 64;
+   const long groups = groups_of(B);
    const long waves = groups * 4 * (algo == 2 ? 2 : 1);
    return waves <= (long)m->cu_count * 4 * kFusedFactor; // fused: while the batch cannot give every SIMD a wave of its own
 }
@@ -468,7 +532,7 @@ bool zv_ok(const mh_model *m, int64_t B, bool soa, int jobs)
    if (soa || !m->dense_maps || m->force_io == 0 || m->n_locked > 0)
       return false;
    const long lds = m->spec.zv_lds_bytes(m->nq, m->nv);
-   return lds > 0 && lds <= 160 * 1024 && (m->use_zv == 2 || (B + 63) / 64 * jobs <= (long)m->cu_count);
+   return lds > 0 && lds <= 160 * 1024 && (m->use_zv == 2 || groups_of(B) * jobs <= (long)m->cu_count);
 }
 // A wait of a bias-split launch that ran into its wall-clock limit (the producer workgroup never published): the kernel wrote NaN rows
 // for that group and set the model's (context's) error word in mapped host memory.  It is a failure of an ASYNCHRONOUS call, so it is
@@ -503,7 +567,7 @@ mh_status check_all_error_words()
 bool zv_self_signalling(const mh_model *m) { return m->ident_maps && m->spec.zv_self_signal && m->spec.zv_self_signal() != 0; }
 mh_status zv_prepare(mh_model *m, int64_t B, hipStream_t stream)
 {
-   const size_t groups = (size_t)((B + 63) / 64);
+   const size_t groups = (size_t)groups_of(B);
    mh_status st = ensure_bytes(m->zv_tau, groups * 64 * m->nv * sizeof(double)); // (whole groups: the two-stage hand-off keeps a matrix [nv][64] per group)
    if (st != MH_OK)
       return st;
@@ -534,10 +598,11 @@ mh_status zv_prepare(mh_model *m, int64_t B, hipStream_t stream)
    }
    return MH_OK;
 }
-// jobs = 2: A.in3b = tau, A.outb = qdd.  jobs = 3: additionally A.in3 = qdd, A.out = tau.  Returns hipErrorNotSupported (as int) in *rc
-// when the code object lacks the plan.
-mh_status zv_launch(mh_model *m, mh::Args<double> &A, int jobs, hipStream_t stream, int *rc)
+// jobs = 2: A.in3b = tau, A.outb = qdd.  jobs = 3: additionally A.in3 = qdd, A.out = tau.  done: the call is over (spec_done); false when
+// the code object lacks the plan.
+mh_status zv_launch(mh_model *m, mh::Args<double> &A, int jobs, hipStream_t stream, bool &done)
 {
+   done = false;
    mh_status st = zv_prepare(m, A.B, stream);
    if (st != MH_OK)
       return st;
@@ -559,11 +624,10 @@ mh_status zv_launch(mh_model *m, mh::Args<double> &A, int jobs, hipStream_t stre
    }
    const int epoch = ++m->zv_epoch;
    int flags = SPEC_IO_LDS | (m->ident_maps ? SPEC_IDENT : 0);
-   *rc = m->spec.launch_zv(flags, &A, self_signal ? m->zv_cols.ptr : m->zv_tau.ptr, (int *)m->zv_flags.ptr, m->zv_error_dev, epoch, jobs, m->zv_same_l2,
-                           m->zv_wait_ticks, (void *)stream);
-   if (*rc != 0 && *rc != (int)hipErrorNotSupported)
-      return fail(MH_ERR_HIP, "bias-split kernel launch failed: %s", hipGetErrorString((hipError_t)*rc));
-   return MH_OK;
+   done = spec_done(m->spec.launch_zv(flags, &A, self_signal ? m->zv_cols.ptr : m->zv_tau.ptr, (int *)m->zv_flags.ptr, m->zv_error_dev, epoch, jobs,
+                                      m->zv_same_l2, m->zv_wait_ticks, (void *)stream),
+                    "bias-split kernel launch failed", st);
+   return st;
 }
 
 // Forward dynamics of device-filling batches as two launches at two workgroups per CU (mh_zv_kernels.h, spec_zvb_*): the same calls the
@@ -576,7 +640,7 @@ bool zvb_ok(const mh_model *m, int64_t B, bool soa)
       return false;
    if (soa || !m->dense_maps || m->force_io == 0 || m->n_locked > 0)
       return false;
-   return m->use_zvb == 2 || (B + 63) / 64 >= 2 * (long)m->cu_count;
+   return m->use_zvb == 2 || groups_of(B) >= 2 * (long)m->cu_count;
 }
 // ... and as ONE launch where the code object has the fused kernel (joints below the root all revolute / fixed, identity index maps)
 bool zvf_ok(const mh_model *m, int64_t B, bool soa)
@@ -587,7 +651,7 @@ bool zvf_ok(const mh_model *m, int64_t B, bool soa)
       return false;
    // measured (humanoid, one MI355X, profiles/r04_zvf_vs_others.txt): 20.5 us against the one-job kernel's 20.3 at 16 384 (one group per CU:
    // a tie), 27.0 against 36.4 at 24 576, 28.4 against 37.8 at 32 768, 195.9 against 250.5 at 262 144
-   return m->use_zvf == 2 || (B + 63) / 64 > (long)m->cu_count;
+   return m->use_zvf == 2 || groups_of(B) > (long)m->cu_count;
 }
 // Inverse dynamics of device-filling batches in a persistent loop that requests the next group's rows behind the trunk pass
 // (spec_zvb_bias_kernel<.., BIAS = false>): AoS matrices, dense index maps; from three groups of 64 configurations per CU upwards, where
@@ -598,22 +662,22 @@ bool rnea_ahead_ok(const mh_model *m, int64_t B, bool soa)
       return false;
    if (soa || !m->dense_maps || m->force_io == 0)
       return false;
-   return m->use_rnea_ahead == 2 || (B + 63) / 64 > 2 * (long)m->cu_count;
+   return m->use_rnea_ahead == 2 || groups_of(B) > 2 * (long)m->cu_count;
 }
-mh_status zvb_launch(mh_model *m, mh::Args<double> &A, hipStream_t stream, int *rc)
+mh_status zvb_launch(mh_model *m, mh::Args<double> &A, hipStream_t stream, bool &done)
 {
-   const size_t padded = (size_t)((A.B + 63) / 64 * 64);
+   done = false;
+   const size_t padded = (size_t)(groups_of(A.B) * 64);
    mh_status st = ensure_bytes(m->zv_tau, (size_t)A.B * m->nv * sizeof(double));
    if (st == MH_OK)
       st = ensure_bytes(m->zvb_cs, std::max<size_t>(1, (size_t)m->spec.zvb_cs_rows()) * padded * sizeof(double));
    if (st != MH_OK)
       return st;
    const int flags = SPEC_IO_LDS | (m->ident_maps ? SPEC_IDENT : 0);
-   const long groups = std::min<long>((A.B + 63) / 64, (long)m->cu_count * 2);
-   *rc = m->spec.launch_zvb(flags, &A, m->zv_tau.ptr, m->zvb_cs.ptr, (long)padded, (int)groups, m->zvb_which, (void *)stream);
-   if (*rc != 0 && *rc != (int)hipErrorNotSupported)
-      return fail(MH_ERR_HIP, "two-launch forward dynamics failed to launch: %s", hipGetErrorString((hipError_t)*rc));
-   return MH_OK;
+   const long groups = std::min<long>(groups_of(A.B), (long)m->cu_count * 2);
+   done = spec_done(m->spec.launch_zvb(flags, &A, m->zv_tau.ptr, m->zvb_cs.ptr, (long)padded, (int)groups, m->zvb_which, (void *)stream),
+                    "two-launch forward dynamics failed to launch", st);
+   return st;
 }
 
 enum Algo
@@ -1003,24 +1067,32 @@ void split_rt_plan(mh_model *m)
    if (!S.usable)
       split_rt_free(m);
 }
+// Workgroups of a run-time tree-split launch: single calls put `wgs` on every CU at most; the pair call (launch_split_rt with pair) one per
+// algorithm and group of 64 configurations, taken while they fit the CUs.  Each has a workspace block of its own.
+int split_rt_grid(const mh_model *m, int64_t B, int wgs) { return (int)std::max<long>(1, std::min<long>(groups_of(B), (long)m->cu_count * wgs)); }
+size_t split_rt_ws_bytes(const mh_model *m, long grid, size_t elem) { return (size_t)m->split_rt.slots * (size_t)grid * 64 * elem; }
+// pair: both algorithms of mh_rnea_aba_f64 in ONE launch (mh::pair_split_kernel), for a model without a code object at small batches:
+// A.in3 = qdd, A.out = tau, A.in3b = tau, A.outb = qdd.
 template <typename T>
-mh_status launch_split_rt(Algo algo, mh_model *model, int64_t B, mh::Args<T> &A, hipStream_t stream)
+mh_status launch_split_rt(Algo algo, mh_model *model, int64_t B, mh::Args<T> &A, hipStream_t stream, bool pair = false)
 {
    const mh_model::SplitRt &S = model->split_rt;
-   const long groups = (B + 63) / 64;
+   const long groups = groups_of(B);
    // workgroups per CU: the fp64 ABA holds ~300 registers (one wave per SIMD), the others fit two workgroups (measured on the humanoid at
    // B = 32768, two groups per CU: RNEA 47 us with two resident workgroups against 66 looping one; round 2, DESIGN_HISTORY.md)
-   const int wgs = (algo == ALGO_ABA && sizeof(T) == 8) ? 1 : 2;
-   const int grid = (int)std::max<long>(1, std::min<long>(groups, (long)model->cu_count * wgs));
+   const int grid = pair ? (int)(2 * groups) : split_rt_grid(model, B, (algo == ALGO_ABA && sizeof(T) == 8) ? 1 : 2);
    // Which record set: everything in LDS when the block fits (no branches); else a share in LDS once the blocks of the workgroups of an
    // XCD outgrow its L2 (measured on the fp64 humanoid: 44 us all-global vs 47 with a share at B = 4096, 71 vs 50 at 8192); else all global.
+   // The pair call keys on its groups: it then takes the record set (hence the kernel instantiation) of the single calls of its batch, and
+   // the two agree bit for bit with it (its grid never exceeds the CUs).
+   const long key = pair ? groups : grid;
    int k = sizeof(T) == 4 ? 0 : 1;
-   if (S.lds_slots[k] < S.slots && (size_t)S.slots * 64 * sizeof(T) * ((size_t)grid / 8 + 1) <= (size_t)3 << 20)
+   if (S.lds_slots[k] < S.slots && (size_t)S.slots * 64 * sizeof(T) * ((size_t)key / 8 + 1) <= (size_t)3 << 20)
       k = 2;
    if (grid > model->cu_count && (size_t)std::min(S.slots, S.lds_slots[k] + mh::SPLIT_LDS_MARGIN) * 64 * sizeof(T) > 80 * 1024)
       k = 2; // two workgroups per CU: an LDS share above half the CU's would serialise them
    const int mode = S.lds_slots[k] >= S.slots ? 0 : (S.lds_slots[k] == 0 ? 1 : 2);
-   mh_status st = ensure_bytes(model->ws, (size_t)S.slots * (size_t)grid * 64 * sizeof(T));
+   mh_status st = ensure_bytes(model->ws, split_rt_ws_bytes(model, grid, sizeof(T)));
    if (st != MH_OK)
       return st;
    A.ws = (T *)model->ws.ptr;
@@ -1030,57 +1102,17 @@ mh_status launch_split_rt(Algo algo, mh_model *model, int64_t B, mh::Args<T> &A,
    for (int w = 0; w < mh::SPLIT_WAVES; w++)
       P.n_seg[w] = S.n_seg[w];
    const size_t lds = mode == 1 ? 0 : (size_t)std::min(S.slots, S.lds_slots[k] + mh::SPLIT_LDS_MARGIN) * 64 * sizeof(T);
-   const void *kern = nullptr;
 #define MH_SPLIT_KERN(NAME) (mode == 0 ? (const void *)&mh::NAME<T, 0> : (mode == 1 ? (const void *)&mh::NAME<T, 1> : (const void *)&mh::NAME<T, 2>))
-   kern = algo == ALGO_RNEA ? MH_SPLIT_KERN(rnea_split_kernel) : (algo == ALGO_ABA ? MH_SPLIT_KERN(aba_split_kernel) : MH_SPLIT_KERN(crba_split_kernel));
+   const void *kern = algo == ALGO_RNEA ? MH_SPLIT_KERN(rnea_split_kernel) : (algo == ALGO_ABA ? MH_SPLIT_KERN(aba_split_kernel) : MH_SPLIT_KERN(crba_split_kernel));
    if constexpr (sizeof(T) == 8)
-      if (algo == ALGO_ABA)
-      { // the machine code the pair call runs (mh::pair_split_kernel): the two calls then agree bit for bit
-         P.roles = 2;
+      if (pair || algo == ALGO_ABA)
+      { // the single forward dynamics runs the pair call's machine code with one role: the two calls then agree bit for bit
+         P.roles = pair ? 0 : 2;
          kern = MH_SPLIT_KERN(pair_split_kernel);
       }
 #undef MH_SPLIT_KERN
-   if (lds > 64 * 1024 && model->lds_attr[kern] < lds)
-   {
-      HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      model->lds_attr[kern] = lds;
-   }
-   void *args[] = {(void *)&A, (void *)&P};
-   HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(256), args, lds, stream));
-   return MH_OK;
-}
-
-// The pair call of a model without a code object at small batches: both algorithms in ONE launch of the run-time tree split
-// (mh::pair_split_kernel): A.in3 = qdd, A.out = tau, A.in3b = tau, A.outb = qdd.  2 * groups workgroups, one per CU.
-mh_status launch_split_rt_pair(mh_model *model, int64_t B, mh::Args<double> &A, hipStream_t stream)
-{
-   using T = double;
-   const mh_model::SplitRt &S = model->split_rt;
-   const long groups = (B + 63) / 64;
-   const int grid = (int)(2 * groups);
-   // the record set (hence the kernel instantiation) the single calls of this batch take (launch_split_rt): the pair call and the two
-   // single calls then run the same machine code and agree bit for bit
-   int k = 1;
-   if (S.lds_slots[k] < S.slots && (size_t)S.slots * 64 * sizeof(T) * ((size_t)groups / 8 + 1) <= (size_t)3 << 20)
-      k = 2;
-   const int mode = S.lds_slots[k] >= S.slots ? 0 : (S.lds_slots[k] == 0 ? 1 : 2);
-   mh_status st = ensure_bytes(model->ws, (size_t)S.slots * (size_t)grid * 64 * sizeof(T));
-   if (st != MH_OK)
+   if ((st = raise_lds_limit(model, kern, lds)) != MH_OK)
       return st;
-   A.ws = (T *)model->ws.ptr;
-   mh::SplitDev P{};
-   P.meta = S.d_meta[k], P.trunk = S.d_trunk, P.seg = S.d_seg, P.xl_ofs = S.d_xl_ofs, P.xl = S.d_xl[k];
-   P.n_trunk = S.n_trunk, P.slots = S.slots;
-   for (int w = 0; w < mh::SPLIT_WAVES; w++)
-      P.n_seg[w] = S.n_seg[w];
-   const size_t lds = mode == 1 ? 0 : (size_t)std::min(S.slots, S.lds_slots[k] + mh::SPLIT_LDS_MARGIN) * 64 * sizeof(T);
-   const void *kern = mode == 0 ? (const void *)&mh::pair_split_kernel<T, 0>
-                                : (mode == 1 ? (const void *)&mh::pair_split_kernel<T, 1> : (const void *)&mh::pair_split_kernel<T, 2>);
-   if (lds > 64 * 1024 && model->lds_attr[kern] < lds)
-   {
-      HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      model->lds_attr[kern] = lds;
-   }
    void *args[] = {(void *)&A, (void *)&P};
    HIP_TRY(hipLaunchKernel(kern, dim3(grid), dim3(256), args, lds, stream));
    return MH_OK;
@@ -1094,7 +1126,7 @@ struct DfsChoice
 DfsChoice dfs_choose(const mh_model *model, Algo algo, size_t elem, int64_t B, bool win, bool pair = false)
 {
    DfsChoice c{};
-   const long waves = (B + 63) / 64;
+   const long waves = groups_of(B);
    c.b_win = win ? 3L * mh::ROW_WIN * mh::ROW_PITCH * (long)elem : 0;
    c.slot_bytes = 64 * (long)elem;
    const long cus = model->cu_count;
@@ -1156,7 +1188,7 @@ struct DfsSetup
 template <typename T>
 mh_status dfs_setup(Algo algo, mh_model *model, int64_t B, bool aos, bool pair, DfsSetup &S)
 {
-   const long waves = (B + 63) / 64;
+   const long waves = groups_of(B);
    const bool win = !pair && dfs_windows(model, algo, sizeof(T), aos);
    const DfsChoice ch = dfs_choose(model, algo, sizeof(T), B, win, pair);
    const long b_win = ch.b_win, slot_bytes = ch.slot_bytes, hand = ch.hand, budget = ch.budget, cus = model->cu_count;
@@ -1211,11 +1243,8 @@ mh_status dfs_setup(Algo algo, mh_model *model, int64_t B, bool aos, bool pair, 
       kern = mode == 0 ? (const void *)&mh::aba_dfs_kernel<T, true, false, 0> : (const void *)&mh::aba_dfs_kernel<T, true, false, 2>;
    else
       kern = mode == 0 ? (const void *)&mh::aba_dfs_kernel<T, false, false, 0> : (mode == 1 ? (const void *)&mh::aba_dfs_kernel<T, false, false, 1> : (const void *)&mh::aba_dfs_kernel<T, false, false, 2>);
-   if (lds > 64 * 1024 && model->lds_attr[kern] < (size_t)lds)
-   {
-      HIP_TRY(hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      model->lds_attr[kern] = (size_t)lds;
-   }
+   if ((st = raise_lds_limit(model, kern, (size_t)lds)) != MH_OK)
+      return st;
    S.plan = plan, S.kern = kern, S.lds = lds, S.gslots = gslots, S.grid = grid, S.win = win;
    return MH_OK;
 }
@@ -1241,25 +1270,44 @@ mh_status launch_dfs(Algo algo, mh_model *model, int64_t B, mh::Args<T> &A, hipS
    return MH_OK;
 }
 
+// What a call of launch<T> may ask for beyond one algorithm's plain output
+template <typename T>
+struct LaunchExtras
+{
+   const T *locked_in = nullptr; // forward dynamics with acceleration-source joints: their given accelerations ...
+   T *locked_out = nullptr;      // ... and the efforts of all joints (may be NULL)
+   T *body_acc = nullptr, *body_twist = nullptr; // per-body outputs (with bodies; either may be NULL)
+   bool bodies = false;
+   double dt = 0.0;                              // a simulation step of forward dynamics (mh_aba_integrate_f64): where a kernel can ride it
+   T *q_next = nullptr, *qd_next = nullptr;      // along it writes the new state and sets *stepped
+   bool *stepped = nullptr;
+   T *joint_wrench = nullptr;                    // inverse dynamics with bodies: the wrench every joint transmits
+};
+// the simulation step riding in a forward-dynamics launch, and taking it off again when that plan is not in the code object
+template <typename T>
+void set_step(mh::Args<T> &A, const LaunchExtras<T> &x)
+{
+   A.dt = (T)x.dt, A.q_next = x.q_next, A.qd_next = x.qd_next;
+}
+template <typename T>
+void clear_step(mh::Args<T> &A)
+{
+   A.dt = T(0), A.q_next = nullptr, A.qd_next = nullptr;
+}
+
 template <typename T>
 mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd, const T *in3, const double gravity[3], const T *fext,
-                 const mh_options *opts_in, T *out, const T *locked_in = nullptr, T *locked_out = nullptr, T *body_acc = nullptr,
-                 T *body_twist = nullptr, bool bodies = false, double step_dt = 0.0, T *q_next = nullptr, T *qd_next = nullptr,
-                 bool *stepped = nullptr, T *joint_wrench = nullptr)
+                 const mh_options *opts_in, T *out, const LaunchExtras<T> &x = LaunchExtras<T>())
 {
    mh_options opts;
-   if (opts_in)
-      opts = *opts_in;
-   else
-      mh_options_default(&opts);
-   mh_status st = check_common(model, B, &opts);
+   mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
       return st;
    if (B == 0)
       return MH_OK; // an empty batch has nothing to read or write: NULL pointers are fine
    if (!q || !out || (algo != ALGO_CRBA && (!qd || !in3 || (!gravity && !opts.use_root_acceleration))))
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
-   if (algo == ALGO_ABA && model->n_locked > 0 && !locked_in)
+   if (algo == ALGO_ABA && model->n_locked > 0 && !x.locked_in)
       return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: forward dynamics needs their accelerations, use mh_aba_locked_f64",
                   model->n_locked);
    // the sweep kernels' per-body workspace (plain RNEA / ABA calls run on the depth-first kernels, which size their own)
@@ -1267,7 +1315,7 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
    // scratch (512 registers + 320 B against 310 and none) -- measured slower at every batch size on every 25..30-body model (humanoid
    // 112 vs 128 us at B = 4096, 1.04 vs 1.30 ms at 262144; profiles/r02_dfs_kernels_rates.txt).  In fp32 it fits and wins (config 5).
    const bool dfs_aba = sizeof(T) == 4 || model->dfs_place >= 0 || model->dfs_aba64;
-   const bool dfs = model->use_dfs && algo != ALGO_CRBA && !bodies && !(algo == ALGO_ABA && (model->n_locked > 0 || !dfs_aba));
+   const bool dfs = model->use_dfs && algo != ALGO_CRBA && !x.bodies && !(algo == ALGO_ABA && (model->n_locked > 0 || !dfs_aba));
    if (!dfs)
    {
       st = ensure_workspace(model, B, sizeof(T));
@@ -1277,40 +1325,29 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
    const Launch L = plan_launch(model, B);
    hipStream_t stream = (hipStream_t)opts.stream;
 
-   mh::Args<T> A{};
-   A.m = dev_model<T>(model);
-   A.B = B;
+   mh::Args<T> A = make_args<T>(model, B, opts, gravity);
    A.q = q, A.qd = qd, A.in3 = in3, A.fext = fext, A.out = out;
-   A.in3b = nullptr, A.outb = nullptr;
-   A.body_acc = body_acc, A.body_twist = body_twist, A.joint_wrench = joint_wrench;
-   A.dt = T(0), A.q_next = nullptr, A.qd_next = nullptr;
+   A.body_acc = x.body_acc, A.body_twist = x.body_twist, A.joint_wrench = x.joint_wrench;
    A.ws = (T *)model->ws.ptr;
    A.ws_stride = L.lanes;
    const bool soa = opts.layout == MH_LAYOUT_SOA;
-   A.q_bs = soa ? 1 : model->nq, A.q_es = soa ? B : 1;
-   A.v_bs = soa ? 1 : model->nv, A.v_es = soa ? B : 1;
-   A.f_bs = soa ? 1 : (long)model->n * 6, A.f_es = soa ? B : 1;
-   set_root_acceleration(A, opts, gravity);
-   A.coriolis = opts.consider_coriolis, A.accel = opts.consider_accelerations;
 
-   if (bodies && algo != ALGO_CRBA)
+   if (x.bodies && algo != ALGO_CRBA)
    { // per-body outputs: run-time-topology kernels (the model's joint source modes must all be effort sources)
       if (model->n_locked > 0 && algo == ALGO_ABA)
          return fail(MH_ERR_INVALID_ARGUMENT, "per-body outputs of forward dynamics are not available while joints are acceleration sources");
-      if (sizeof(T) == 8 && !joint_wrench && split_ok(model, algo == ALGO_RNEA ? 0 : 1, B, soa))
+      if (sizeof(T) == 8 && !x.joint_wrench && split_ok(model, algo == ALGO_RNEA ? 0 : 1, B, soa))
       { // the tree-split kernels write them too (identity maps, rows staged in LDS); other plans: the run-time-topology kernels below
          const int sf = split_flags(model, algo == ALGO_RNEA ? 0 : 1, soa);
          if ((sf & SPEC_IDENT) && (sf & SPEC_IO_LDS))
          {
-            const long groups = std::min<long>((B + 63) / 64, (long)model->cu_count * 2);
-            const int rc = model->spec.launch_split(algo == ALGO_RNEA ? 0 : 1, sf | SPEC_BODIES, &A, (int)groups, (void *)stream);
-            if (rc == 0)
-               return MH_OK;
-            if (rc != (int)hipErrorNotSupported)
-               return fail(MH_ERR_HIP, "tree-split kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+            const long groups = std::min<long>(groups_of(B), (long)model->cu_count * 2);
+            if (spec_done(model->spec.launch_split(algo == ALGO_RNEA ? 0 : 1, sf | SPEC_BODIES, &A, (int)groups, (void *)stream),
+                          "tree-split kernel launch failed", st))
+               return st;
          }
       }
-      if (model->split_rt.usable && model->n_locked == 0 && (model->use_split_rt == 1 || (B + 63) / 64 <= (long)model->cu_count * 2))
+      if (model->split_rt.usable && model->n_locked == 0 && (model->use_split_rt == 1 || groups_of(B) <= (long)model->cu_count * 2))
          return launch_split_rt<T>(algo, model, B, A, stream); // small batches: the run-time tree split writes the per-body outputs too
       if (algo == ALGO_RNEA)
          hipLaunchKernelGGL((mh::rnea_kernel<T, true>), dim3(L.grid), dim3(L.block), 0, stream, A);
@@ -1321,7 +1358,7 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
    }
    if (algo == ALGO_ABA && model->n_locked > 0)
    { // acceleration-source joints: run-time flags per joint, generic kernel only
-      A.in3b = locked_in, A.outb = locked_out;
+      A.in3b = x.locked_in, A.outb = x.locked_out;
       hipLaunchKernelGGL((mh::aba_kernel<T, true>), dim3(L.grid), dim3(L.block), 0, stream, A);
       HIP_TRY(hipGetLastError());
       return MH_OK;
@@ -1330,61 +1367,52 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
    {
       // (a simulation step rides in the inertia job where the index maps are the identity: the two-stage form of the hand-off integrates the
       // rows it holds and writes the new state too -- 17.5 against 20.1 us per step at B = 4096, profiles/r04_step_rates.txt)
-      if (algo == ALGO_ABA && (!q_next || (model->ident_maps && model->use_zv_step)) && zv_ok(model, B, soa, 2))
+      if (algo == ALGO_ABA && (!x.q_next || (model->ident_maps && model->use_zv_step)) && zv_ok(model, B, soa, 2))
       { // forward dynamics as two jobs side by side: bias efforts | articulated inertias, then the bias fold (mh_zv_kernels.h)
          if (const mh_status se = zv_check_error(model); se != MH_OK)
             return se;
          A.in3b = in3, A.outb = out;
-         if (q_next)
-            A.dt = (T)step_dt, A.q_next = q_next, A.qd_next = qd_next;
-         int rc = 0;
-         if (const mh_status sz = zv_launch(model, A, 2, stream, &rc); sz != MH_OK)
-            return sz;
-         if (rc == 0)
+         if (x.q_next)
+            set_step(A, x);
+         bool done = false;
+         if ((st = zv_launch(model, A, 2, stream, done)) != MH_OK || done)
          {
-            if (q_next && stepped)
-               *stepped = true;
-            return MH_OK;
+            if (st == MH_OK && x.q_next && x.stepped)
+               *x.stepped = true;
+            return st;
          }
          A.in3b = nullptr, A.outb = nullptr; // not in this code object: the plans below
-         A.dt = T(0), A.q_next = nullptr, A.qd_next = nullptr;
+         clear_step(A);
       }
-      if (algo == ALGO_ABA && (!q_next || model->use_zv_step) && zvf_ok(model, B, soa))
+      if (algo == ALGO_ABA && (!x.q_next || model->use_zv_step) && zvf_ok(model, B, soa))
       { // device-filling batches: bias efforts, articulated inertias, fold and outward sweep of a group of 64 configurations by ONE workgroup
         // (a simulation step rides along: 32.3 against 42.4 us per step at 32 768, 226.5 against 286.7 at 262 144 -- profiles/r04_step_rates.txt)
-         const long groups = std::min<long>((B + 63) / 64, (long)model->cu_count * 2);
-         if (q_next)
-            A.dt = (T)step_dt, A.q_next = q_next, A.qd_next = qd_next;
-         const int rc = model->spec.launch_zvf(SPEC_IO_LDS | SPEC_IDENT, &A, (int)groups, (void *)stream);
-         if (rc == 0)
+         const long groups = std::min<long>(groups_of(B), (long)model->cu_count * 2);
+         if (x.q_next)
+            set_step(A, x);
+         if (spec_done(model->spec.launch_zvf(SPEC_IO_LDS | SPEC_IDENT, &A, (int)groups, (void *)stream), "fused forward dynamics failed to launch", st))
          {
-            if (q_next && stepped)
-               *stepped = true;
-            return MH_OK;
+            if (st == MH_OK && x.q_next && x.stepped)
+               *x.stepped = true;
+            return st;
          }
-         if (rc != (int)hipErrorNotSupported)
-            return fail(MH_ERR_HIP, "fused forward dynamics failed to launch: %s", hipGetErrorString((hipError_t)rc));
-         A.dt = T(0), A.q_next = nullptr, A.qd_next = nullptr;
+         clear_step(A);
       }
-      if (algo == ALGO_ABA && !q_next && zvb_ok(model, B, soa))
+      if (algo == ALGO_ABA && !x.q_next && zvb_ok(model, B, soa))
       { // ... or as two launches: bias rows and (cos, sin) pairs by one, articulated inertias + fold + outward sweep by the next
-         int rc = 0;
-         if (const mh_status sz = zvb_launch(model, A, stream, &rc); sz != MH_OK)
-            return sz;
-         if (rc == 0)
-            return MH_OK;
+         bool done = false;
+         if ((st = zvb_launch(model, A, stream, done)) != MH_OK || done)
+            return st;
       }
    }
    if constexpr (sizeof(T) == 8)
    {
       if (algo == ALGO_RNEA && rnea_ahead_ok(model, B, soa))
       {
-         const long groups = std::min<long>((B + 63) / 64, (long)model->cu_count * 2);
-         const int rc = model->spec.launch_rnea_ahead(SPEC_IO_LDS | (model->ident_maps ? SPEC_IDENT : 0), &A, (int)groups, (void *)stream);
-         if (rc == 0)
-            return MH_OK;
-         if (rc != (int)hipErrorNotSupported)
-            return fail(MH_ERR_HIP, "inverse dynamics (rows requested ahead) failed to launch: %s", hipGetErrorString((hipError_t)rc));
+         const long groups = std::min<long>(groups_of(B), (long)model->cu_count * 2);
+         if (spec_done(model->spec.launch_rnea_ahead(SPEC_IO_LDS | (model->ident_maps ? SPEC_IDENT : 0), &A, (int)groups, (void *)stream),
+                       "inverse dynamics (rows requested ahead) failed to launch", st))
+            return st;
       }
    }
    if (algo != ALGO_CRBA && sizeof(T) == 8 && split_ok(model, algo == ALGO_RNEA ? 0 : 1, B, soa))
@@ -1392,25 +1420,22 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
       int sf = split_flags(model, algo == ALGO_RNEA ? 0 : 1, soa);
       // device-filling RNEA batches without LDS rows (SoA): the build with a 168-register budget keeps three workgroups per CU busy
       // (124 -> 112 us at B = 262144); smaller batches are faster on the plain build
-      const bool occ3 = algo == ALGO_RNEA && !(sf & SPEC_IO_LDS) && (sf & SPEC_IDENT) && (B + 63) / 64 > (long)model->cu_count * 2;
+      const bool occ3 = algo == ALGO_RNEA && !(sf & SPEC_IO_LDS) && (sf & SPEC_IDENT) && groups_of(B) > (long)model->cu_count * 2;
       if (occ3)
          sf |= SPEC_OCC3;
-      const long groups = std::min<long>((B + 63) / 64, (long)model->cu_count * (occ3 ? 3 : 2));
-      if (algo == ALGO_ABA && q_next && (sf & SPEC_IDENT) && (sf & SPEC_IO_LDS))
+      const long groups = std::min<long>(groups_of(B), (long)model->cu_count * (occ3 ? 3 : 2));
+      if (algo == ALGO_ABA && x.q_next && (sf & SPEC_IDENT) && (sf & SPEC_IO_LDS))
       { // fused simulation step: the kernel integrates the rows it holds in LDS and writes the new state too
-         A.dt = (T)step_dt, A.q_next = q_next, A.qd_next = qd_next;
-         if (stepped)
-            *stepped = true;
+         set_step(A, x);
+         if (x.stepped)
+            *x.stepped = true;
       }
-      const int rc = model->spec.launch_split(algo == ALGO_RNEA ? 0 : 1, sf, &A, (int)groups, (void *)stream);
-      if (rc == 0)
-         return MH_OK;
-      if (rc != (int)hipErrorNotSupported)
-         return fail(MH_ERR_HIP, "tree-split kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+      if (spec_done(model->spec.launch_split(algo == ALGO_RNEA ? 0 : 1, sf, &A, (int)groups, (void *)stream), "tree-split kernel launch failed", st))
+         return st;
       // a code object built without this plan (mh_build_code_object in its fast mode): the run-time-topology kernels serve the call
-      A.dt = T(0), A.q_next = nullptr, A.qd_next = nullptr;
-      if (stepped)
-         *stepped = false;
+      clear_step(A);
+      if (x.stepped)
+         *x.stepped = false;
    }
    if (model->spec.launch && algo != ALGO_CRBA && model->use_spec && sizeof(T) == 8)
    {
@@ -1418,7 +1443,7 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
       // inward -> outward hand-over lives in LDS while the batch is small enough that one wave per CU is all the device
       // would get anyway, otherwise in the global workspace.
       const int a = algo == ALGO_RNEA ? 0 : 1;
-      const long waves = (B + 63) / 64;
+      const long waves = groups_of(B);
       const long LDS_MAX = 160 * 1024;
       int flags = model->ident_maps ? SPEC_IDENT : 0;
       bool io = !soa && model->dense_maps && model->spec.supports(a, SPEC_IO_LDS) && model->spec.lds_bytes(a, SPEC_IO_LDS, model->nq, model->nv) <= LDS_MAX;
@@ -1449,17 +1474,14 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
          A.ws = (T *)model->ws.ptr;
          A.ws_stride = (long)grid * 64;
       }
-      const int rc = model->spec.launch(a, flags, &A, grid, (void *)stream);
-      if (rc == 0)
-         return MH_OK;
-      if (rc != (int)hipErrorNotSupported)
-         return fail(MH_ERR_HIP, "specialised kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+      if (spec_done(model->spec.launch(a, flags, &A, grid, (void *)stream), "specialised kernel launch failed", st))
+         return st;
       A.ws = (T *)model->ws.ptr, A.ws_stride = L.lanes; // (a fast build without the whole-tree kernels: on to the run-time-topology kernels)
       } // else: this (algorithm, memory plan) is not in the code object -- the run-time-topology kernels below serve the call
    }
    // Small batches of a model whose tree branches: the tree split over the four waves of a workgroup (mh_split_kernels.h)
-   if (model->split_rt.usable && algo != ALGO_CRBA && model->n_locked == 0 && !locked_in
-       && (model->use_split_rt == 1 || (B + 63) / 64 <= (long)model->cu_count * 2)) // measured: profiles/r02_split_rt_sweep.txt
+   if (model->split_rt.usable && algo != ALGO_CRBA && model->n_locked == 0 && !x.locked_in
+       && (model->use_split_rt == 1 || groups_of(B) <= (long)model->cu_count * 2)) // measured: profiles/r02_split_rt_sweep.txt
       return launch_split_rt<T>(algo, model, B, A, stream);
    // Run-time-topology RNEA / ABA on AoS matrices: for big batches of wide matrices go through transposed scratch copies
    // (mh::transpose_kernel).  External wrenches keep their own strides.  The depth-first RNEA reads AoS rows through LDS windows instead
@@ -1467,7 +1489,7 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
    T *t_out = nullptr;
    if (algo != ALGO_CRBA && !soa)
    {
-      bool want = model->use_transpose >= 0 ? model->use_transpose != 0 : (B >= 8192 && model->nq + model->nv >= 64);
+      bool want = transposes(model, B);
       if (dfs && want)
          want = algo == ALGO_ABA || !model->ident_maps;
       if (want)
@@ -1519,25 +1541,20 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
                if (const char *e = getenv("MH_CRBA_LPG"))
                   lpg = std::max(1, std::min(64, atoi(e)));
                const long ng = (B + lpg - 1) / lpg;
-               const int rc = model->spec.launch_crba_split(&A, (int)std::min<long>(ng, (long)model->cu_count * 2), lpg, (void *)stream);
-               if (rc == 0)
-                  return MH_OK;
-               if (rc != (int)hipErrorNotSupported)
-                  return fail(MH_ERR_HIP, "tree-split CRBA launch failed: %s", hipGetErrorString((hipError_t)rc));
+               if (spec_done(model->spec.launch_crba_split(&A, (int)std::min<long>(ng, (long)model->cu_count * 2), lpg, (void *)stream),
+                             "tree-split CRBA launch failed", st))
+                  return st;
             }
             const bool packed = model->spec.crba_packed(sflags) != 0;
             if (!packed)
                HIP_TRY(hipMemsetAsync(out, 0, hbytes, stream)); // direct-store kernel writes related entries only
-            const int grid = packed ? (int)std::min<long>((B + 63) / 64, (long)model->cu_count) : L.grid;
-            const int rc = model->spec.launch_crba(sflags, &A, grid, (void *)stream);
-            if (rc == 0)
-               return MH_OK;
-            if (rc != (int)hipErrorNotSupported)
-               return fail(MH_ERR_HIP, "specialised CRBA launch failed: %s", hipGetErrorString((hipError_t)rc));
+            const int grid = packed ? (int)std::min<long>(groups_of(B), (long)model->cu_count) : L.grid;
+            if (spec_done(model->spec.launch_crba(sflags, &A, grid, (void *)stream), "specialised CRBA launch failed", st))
+               return st;
             // not in this code object (fast build): the run-time-topology kernels below
          }
          HIP_TRY(hipMemsetAsync(out, 0, hbytes, stream));
-         if (model->split_rt.usable && (model->use_split_rt == 1 || (B + 63) / 64 <= (long)model->cu_count * 2))
+         if (model->split_rt.usable && (model->use_split_rt == 1 || groups_of(B) <= (long)model->cu_count * 2))
             return launch_split_rt<T>(algo, model, B, A, stream); // small batches: the tree split over four waves (mh_split_kernels.h)
          {
             const int parts = regressor_parts(model, L);
@@ -1555,6 +1572,69 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
    }
    HIP_TRY(hipGetLastError());
    return MH_OK;
+}
+
+// Two calls side by side: the second on the model's own stream, forked from and joined back into the caller's with events, on a
+// workspace of its own -- every launch path sizes and reads model->ws, and model->tr (swap_tr) when it goes through transposed copies
+// of the state matrices; then the first on the caller's stream.  Each call is given the options it is to run with.
+template <class F1, class F2>
+mh_status side_by_side(mh_model *model, const mh_options &opts, bool swap_tr, F1 first, F2 second)
+{
+   hipStream_t s = (hipStream_t)opts.stream;
+   if (!model->pair_stream)
+   {
+      HIP_TRY(hipStreamCreateWithFlags(&model->pair_stream, hipStreamNonBlocking));
+      HIP_TRY(hipEventCreateWithFlags(&model->pair_fork, hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(&model->pair_join, hipEventDisableTiming));
+   }
+   HIP_TRY(hipEventRecord(model->pair_fork, s));
+   HIP_TRY(hipStreamWaitEvent(model->pair_stream, model->pair_fork, 0));
+   mh_options ob = opts;
+   ob.stream = (void *)model->pair_stream;
+   std::swap(model->ws, model->ws_pair);
+   if (swap_tr)
+      std::swap(model->tr, model->tr_pair);
+   const mh_status rb = second(&ob);
+   std::swap(model->ws, model->ws_pair);
+   if (swap_tr)
+      std::swap(model->tr, model->tr_pair);
+   const mh_status ra = first(&opts);
+   HIP_TRY(hipEventRecord(model->pair_join, model->pair_stream)); // join even after an error: the caller's stream must not run ahead
+   HIP_TRY(hipStreamWaitEvent(s, model->pair_join, 0));
+   return rb != MH_OK ? rb : ra;
+}
+template <typename T>
+LaunchExtras<T> body_outputs(T *body_acc, T *body_twist)
+{
+   LaunchExtras<T> x;
+   x.body_acc = body_acc, x.body_twist = body_twist, x.bodies = true;
+   return x;
+}
+LaunchExtras<double> joint_wrenches(double *joint_wrench)
+{
+   LaunchExtras<double> x;
+   x.bodies = true, x.joint_wrench = joint_wrench;
+   return x;
+}
+// Forward dynamics with acceleration-source joints (mh_aba_locked_*): tau_out gets the efforts of all joints
+template <typename T>
+mh_status aba_locked(mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const T *qdd_in, const double gravity[3], const T *f_ext,
+                     const mh_options *opts, T *qdd_out, T *tau_out)
+{
+   if (!model)
+      return fail(MH_ERR_INVALID_ARGUMENT, "model is NULL");
+   if (model->n_locked == 0)
+   { // nothing is locked: the ordinary forward dynamics, efforts copied through
+      mh_status st = launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out);
+      if (st == MH_OK && tau_out && tau_out != tau && B > 0)
+         HIP_TRY(hipMemcpyAsync(tau_out, tau, (size_t)B * model->nv * sizeof(T), hipMemcpyDeviceToDevice, opts ? (hipStream_t)opts->stream : nullptr));
+      return st;
+   }
+   if (B > 0 && !qdd_in)
+      return fail(MH_ERR_INVALID_ARGUMENT, "qdd_in is NULL but %d joint(s) are acceleration sources", model->n_locked);
+   LaunchExtras<T> x;
+   x.locked_in = qdd_in, x.locked_out = tau_out;
+   return launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, x);
 }
 
 // Host-pointer front end (what a JNI / Panama shim with heap or off-heap arrays calls).  The batch is cut into chunks of rows that travel
@@ -1587,11 +1667,7 @@ mh_status launch_host(int kind, mh_model_t model, int64_t B, const T *q, const T
                       const T *fext, const mh_options *opts_in, T *out, T *out2)
 {
    mh_options opts;
-   if (opts_in)
-      opts = *opts_in;
-   else
-      mh_options_default(&opts);
-   mh_status st = check_common(model, B, &opts);
+   mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
       return st;
    if (B == 0)
@@ -1878,11 +1954,7 @@ template <typename T>
 mh_status coriolis_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const mh_options *opts_in, T *H_out, T *C_out)
 {
    mh_options opts;
-   if (opts_in)
-      opts = *opts_in;
-   else
-      mh_options_default(&opts);
-   mh_status st = check_common(model, B, &opts);
+   mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
       return st;
    if (B == 0)
@@ -1895,16 +1967,11 @@ mh_status coriolis_impl(mh_model_t model, int64_t B, const T *q, const T *qd, co
    if (st != MH_OK)
       return st;
    hipStream_t stream = (hipStream_t)opts.stream;
-   mh::Args<T> A{};
-   A.m = dev_model<T>(model);
-   A.B = B;
+   mh::Args<T> A = make_args<T>(model, B, opts);
    A.q = q, A.qd = qd, A.out = H_out, A.outb = C_out;
    A.ws = (T *)model->ws.ptr;
    A.ws_stride = L.lanes;
-   const bool soa = opts.layout == MH_LAYOUT_SOA;
-   A.q_bs = soa ? 1 : model->nq, A.q_es = soa ? B : 1;
-   A.v_bs = soa ? 1 : model->nv, A.v_es = soa ? B : 1;
-   A.f_bs = soa ? 1 : (long)model->nv * model->nv, A.f_es = soa ? B : 1; // strides of H and C
+   set_strides(A.f_bs, A.f_es, opts.layout == MH_LAYOUT_SOA, B, (long)model->nv * model->nv); // strides of H and C
    const size_t hbytes = (size_t)B * model->nv * model->nv * sizeof(T);
    HIP_TRY(hipMemsetAsync(H_out, 0, hbytes, stream)); // the kernel writes the entries of related joints only (:298-300)
    HIP_TRY(hipMemsetAsync(C_out, 0, hbytes, stream));
@@ -1912,17 +1979,14 @@ mh_status coriolis_impl(mh_model_t model, int64_t B, const T *q, const T *qd, co
    {
       if (model->spec.launch_coriolis && model->use_spec)
       { // topology-specialised recursion: ancestors' transforms and velocities in registers, no workspace
-         const long waves = (B + 63) / 64;
-         const int grid = (int)std::max<long>(1, std::min(waves, (long)model->cu_count * 4));
+         const int grid = (int)std::max<long>(1, std::min(groups_of(B), (long)model->cu_count * 4));
          Launch G = L;
          G.grid = grid; // small batches: several waves per group of configurations, each writing every parts-th body's columns
          const int rc = model->spec.launch_coriolis_parts
                            ? model->spec.launch_coriolis_parts(model->ident_maps ? SPEC_IDENT : 0, &A, grid, regressor_parts(model, G), (void *)stream)
                            : model->spec.launch_coriolis(model->ident_maps ? SPEC_IDENT : 0, &A, grid, (void *)stream);
-         if (rc == 0)
-            return MH_OK;
-         if (rc != (int)hipErrorNotSupported)
-            return fail(MH_ERR_HIP, "specialised Coriolis kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+         if (spec_done(rc, "specialised Coriolis kernel launch failed", st))
+            return st;
       }
    }
    hipLaunchKernelGGL((mh::coriolis_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, stream, A);
@@ -1935,11 +1999,7 @@ mh_status regressor_impl(mh_model_t model, int64_t B, const T *q, const T *qd, c
                          int32_t first_moment_columns, T *Y_out)
 {
    mh_options opts;
-   if (opts_in)
-      opts = *opts_in;
-   else
-      mh_options_default(&opts);
-   mh_status st = check_common(model, B, &opts);
+   mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
       return st;
    if (B == 0)
@@ -1952,19 +2012,12 @@ mh_status regressor_impl(mh_model_t model, int64_t B, const T *q, const T *qd, c
    if (st != MH_OK)
       return st;
    hipStream_t stream = (hipStream_t)opts.stream;
-   mh::Args<T> A{};
-   A.m = dev_model<T>(model);
-   A.B = B;
+   mh::Args<T> A = make_args<T>(model, B, opts, gravity);
    A.q = q, A.qd = qd, A.in3 = qdd, A.out = Y_out;
    A.ws = (T *)model->ws.ptr;
    A.ws_stride = L.lanes;
-   const bool soa = opts.layout == MH_LAYOUT_SOA;
-   A.q_bs = soa ? 1 : model->nq, A.q_es = soa ? B : 1;
-   A.v_bs = soa ? 1 : model->nv, A.v_es = soa ? B : 1;
    const long ysize = (long)model->nv * model->n * 10;
-   A.f_bs = soa ? 1 : ysize, A.f_es = soa ? B : 1; // strides of Y
-   set_root_acceleration(A, opts, gravity);
-   A.coriolis = opts.consider_coriolis, A.accel = opts.consider_accelerations;
+   set_strides(A.f_bs, A.f_es, opts.layout == MH_LAYOUT_SOA, B, ysize); // strides of Y
    // entries of joints that do not support a body are zero, and so are the reference's centre-of-mass columns (mh_kernels.h)
    HIP_TRY(hipMemsetAsync(Y_out, 0, (size_t)B * ysize * sizeof(T), stream));
    // the centre-of-mass columns: d tau / d (m c) on request; else the reference's -- zero, or e x a once the twist is switched off
@@ -1983,11 +2036,7 @@ mh_status centroidal_impl(mh_model_t model, int64_t B, const T *q, const T *qd, 
                           T *A_out, T *b_out, T *com_out)
 {
    mh_options opts;
-   if (opts_in)
-      opts = *opts_in;
-   else
-      mh_options_default(&opts);
-   mh_status st = check_common(model, B, &opts);
+   mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
       return st;
    if (frame_mode != MH_CENTROIDAL_FRAME_FIXED && frame_mode != MH_CENTROIDAL_FRAME_AT_COM)
@@ -2009,11 +2058,11 @@ mh_status centroidal_impl(mh_model_t model, int64_t B, const T *q, const T *qd, 
    A.ws = (T *)model->ws.ptr;
    A.ws_stride = L.lanes;
    const bool soa = opts.layout == MH_LAYOUT_SOA;
-   A.q_bs = soa ? 1 : model->nq, A.q_es = soa ? B : 1;
-   A.v_bs = soa ? 1 : model->nv, A.v_es = soa ? B : 1;
-   A.a_bs = soa ? 1 : 6L * model->nv, A.a_es = soa ? B : 1;
-   A.b_bs = soa ? 1 : 6, A.b_es = soa ? B : 1;
-   A.c_bs = soa ? 1 : 3, A.c_es = soa ? B : 1;
+   set_strides(A.q_bs, A.q_es, soa, B, model->nq);
+   set_strides(A.v_bs, A.v_es, soa, B, model->nv);
+   set_strides(A.a_bs, A.a_es, soa, B, 6L * model->nv);
+   set_strides(A.b_bs, A.b_es, soa, B, 6);
+   set_strides(A.c_bs, A.c_es, soa, B, 3);
    for (int k = 0; k < 9; k++)
       A.fR[k] = frame ? (T)frame[k] : (T)(k % 4 == 0 ? 1 : 0);
    for (int k = 0; k < 3; k++)
@@ -2024,17 +2073,14 @@ mh_status centroidal_impl(mh_model_t model, int64_t B, const T *q, const T *qd, 
    {
       if (model->spec.launch_centroidal && model->use_spec)
       {
-         const long waves = (B + 63) / 64;
-         const int grid = (int)std::max<long>(1, std::min(waves, (long)model->cu_count * 4));
+         const int grid = (int)std::max<long>(1, std::min(groups_of(B), (long)model->cu_count * 4));
          Launch G = L;
          G.grid = grid;
          const int rc = model->spec.launch_centroidal_parts
                            ? model->spec.launch_centroidal_parts(model->ident_maps ? SPEC_IDENT : 0, &A, grid, regressor_parts(model, G), (void *)stream)
                            : model->spec.launch_centroidal(model->ident_maps ? SPEC_IDENT : 0, &A, grid, (void *)stream);
-         if (rc == 0)
-            return MH_OK;
-         if (rc != (int)hipErrorNotSupported)
-            return fail(MH_ERR_HIP, "specialised centroidal kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
+         if (spec_done(rc, "specialised centroidal kernel launch failed", st))
+            return st;
       }
    }
    hipLaunchKernelGGL((mh::centroidal_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, stream, A);
@@ -2046,11 +2092,7 @@ mh_status integrate_impl(mh_model_t model, int64_t B, double dt, const T *q, con
                                 T *qd_out, T *qdd_out)
 {
    mh_options opts;
-   if (opts_in)
-      opts = *opts_in;
-   else
-      mh_options_default(&opts);
-   mh_status st = check_common(model, B, &opts);
+   mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
       return st;
    if (B == 0)
@@ -2064,8 +2106,8 @@ mh_status integrate_impl(mh_model_t model, int64_t B, double dt, const T *q, con
    A.B = B, A.dt = (T)dt;
    A.q = q, A.qd = qd, A.qdd = qdd, A.q_out = q_out, A.qd_out = qd_out, A.qdd_out = qdd_out;
    const bool soa = opts.layout == MH_LAYOUT_SOA;
-   A.q_bs = soa ? 1 : model->nq, A.q_es = soa ? B : 1;
-   A.v_bs = soa ? 1 : model->nv, A.v_es = soa ? B : 1;
+   set_strides(A.q_bs, A.q_es, soa, B, model->nq);
+   set_strides(A.v_bs, A.v_es, soa, B, model->nv);
    const int block = 256;
    if (soa)
    {
@@ -2977,8 +3019,8 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       if (st != MH_OK)
          return st;
    }
-   const bool transposes = m->use_transpose >= 0 ? m->use_transpose != 0 : (max_batch >= 8192 && m->nq + m->nv >= 64);
-   if (transposes)
+   const bool transposed = transposes(m, max_batch);
+   if (transposed)
       st = ensure_bytes(m->tr, (size_t)max_batch * ((size_t)m->nq + 3 * (size_t)m->nv) * sizeof(double));
    if (st != MH_OK)
       return st;
@@ -2990,7 +3032,7 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
    size_t dfs_bytes = 0;
    if (m->use_dfs)
    {
-      const long cus = m->cu_count, classes = ((max_batch + 63) / 64 + cus - 1) / cus;
+      const long cus = m->cu_count, classes = (groups_of(max_batch) + cus - 1) / cus;
       for (long wpc = classes; wpc >= 1; wpc--)
       {
          const int64_t B = std::min<int64_t>(max_batch, (int64_t)wpc * cus * 64);
@@ -3004,16 +3046,16 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
                if ((st = dfs_setup<float>(algo, m, B, aos != 0, false, S)) != MH_OK)
                   return st;
             }
-            if (B >= 8192 && m->use_dfs_pair && m->nq + m->nv >= 64 && (st = dfs_setup<float>(ALGO_ABA, m, B, aos != 0, true, S)) != MH_OK)
+            if (m->use_dfs_pair && auto_transpose(m, B) && (st = dfs_setup<float>(ALGO_ABA, m, B, aos != 0, true, S)) != MH_OK)
                return st;
          }
       }
    }
    if (m->split_rt.usable) // the run-time tree split: one workspace block per workgroup
-      dfs_bytes = std::max(dfs_bytes, (size_t)m->split_rt.slots * (size_t)std::max<long>(1, std::min<long>((max_batch + 63) / 64, 2L * m->cu_count)) * 64 * sizeof(double));
+      dfs_bytes = std::max(dfs_bytes, split_rt_ws_bytes(m, split_rt_grid(m, max_batch, 2), sizeof(double)));
    if (dfs_bytes > 0)
       st = ensure_bytes(m->ws, dfs_bytes);
-   if (st == MH_OK && (max_batch + 63) / 64 <= (long)m->cu_count)
+   if (st == MH_OK && groups_of(max_batch) <= (long)m->cu_count)
       st = ensure_bytes(m->ws_pair, m->ws.bytes);
    // round 3's plans: the bias-split launches (their scratch for the largest batch they serve: two jobs on every group of 64 within the
    // CUs), the one-launch pair of the run-time tree split (twice the workgroups of a single call), the shared transposed copies of
@@ -3028,11 +3070,11 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
    { // the two-launch forward dynamics of device-filling batches (models without the fused kernel): bias rows and (cos, sin) pairs
       st = ensure_bytes(m->zv_tau, (size_t)max_batch * m->nv * sizeof(double));
       if (st == MH_OK)
-         st = ensure_bytes(m->zvb_cs, std::max<size_t>(1, (size_t)m->spec.zvb_cs_rows()) * (size_t)((max_batch + 63) / 64 * 64) * sizeof(double));
+         st = ensure_bytes(m->zvb_cs, std::max<size_t>(1, (size_t)m->spec.zvb_cs_rows()) * (size_t)(groups_of(max_batch) * 64) * sizeof(double));
    }
-   if (st == MH_OK && m->split_rt.usable)
-      st = ensure_bytes(m->ws, (size_t)m->split_rt.slots * (size_t)std::min<long>(2 * ((max_batch + 63) / 64), (long)m->cu_count) * 64 * sizeof(double));
-   if (st == MH_OK && transposes && m->use_dfs)
+   if (st == MH_OK && m->split_rt.usable) // the pair call's grid
+      st = ensure_bytes(m->ws, split_rt_ws_bytes(m, std::min<long>(2 * groups_of(max_batch), (long)m->cu_count), sizeof(double)));
+   if (st == MH_OK && transposed && m->use_dfs)
       st = ensure_bytes(m->tr_pair, (size_t)max_batch * ((size_t)m->nq + 5 * (size_t)m->nv) * sizeof(float));
    return st;
 }
@@ -3093,8 +3135,9 @@ mh_status mh_aba_integrate_f64(mh_model_t model, int64_t B, double dt, const dou
    if (nan_bits(dt))
       return fail(MH_ERR_INVALID_ARGUMENT, "dt is NaN");
    bool stepped = false;
-   mh_status st = launch<double>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, nullptr, nullptr, nullptr, nullptr, false, dt, q_next,
-                                 qd_next, &stepped);
+   LaunchExtras<double> x;
+   x.dt = dt, x.q_next = q_next, x.qd_next = qd_next, x.stepped = &stepped;
+   mh_status st = launch<double>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, x);
    if (st != MH_OK || stepped || B == 0)
       return st;
    return mh_integrate_f64(model, B, dt, q, qd, qdd_out, opts, q_next, qd_next, nullptr);
@@ -3107,20 +3150,19 @@ mh_status mh_integrate_f32(mh_model_t model, int64_t B, double dt, const float *
 mh_status mh_rnea_bodies_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double gravity[3],
                              const double *f_ext, const mh_options *opts, double *tau_out, double *body_acc_out, double *body_twist_out)
 {
-   return launch<double>(ALGO_RNEA, model, B, q, qd, qdd, gravity, f_ext, opts, tau_out, nullptr, nullptr, body_acc_out, body_twist_out, true);
+   return launch<double>(ALGO_RNEA, model, B, q, qd, qdd, gravity, f_ext, opts, tau_out, body_outputs<double>(body_acc_out, body_twist_out));
 }
 mh_status mh_aba_bodies_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
                             const double *f_ext, const mh_options *opts, double *qdd_out, double *body_acc_out, double *body_twist_out)
 {
-   return launch<double>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, nullptr, nullptr, body_acc_out, body_twist_out, true);
+   return launch<double>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, body_outputs<double>(body_acc_out, body_twist_out));
 }
 mh_status mh_rnea_joint_wrenches_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double gravity[3],
                                      const double *f_ext, const mh_options *opts, double *tau_out, double *joint_wrench_out)
 {
    if (B > 0 && !joint_wrench_out)
       return fail(MH_ERR_INVALID_ARGUMENT, "joint_wrench_out is NULL");
-   return launch<double>(ALGO_RNEA, model, B, q, qd, qdd, gravity, f_ext, opts, tau_out, nullptr, nullptr, nullptr, nullptr, true, 0.0, nullptr, nullptr,
-                         nullptr, joint_wrench_out);
+   return launch<double>(ALGO_RNEA, model, B, q, qd, qdd, gravity, f_ext, opts, tau_out, joint_wrenches(joint_wrench_out));
 }
 mh_status mh_aba_joint_wrenches_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
                                     const double *f_ext, const mh_options *opts, double *qdd_out, double *joint_wrench_out)
@@ -3129,15 +3171,10 @@ mh_status mh_aba_joint_wrenches_f64(mh_model_t model, int64_t B, const double *q
       return fail(MH_ERR_INVALID_ARGUMENT, "joint_wrench_out is NULL");
    // the scratch below belongs to the CONTEXT of the call: resolve it before anything mutable is touched (launch() does so for itself only)
    mh_options o;
-   if (opts)
-      o = *opts;
-   else
-      mh_options_default(&o);
-   opts = &o;
-   mh_status st = check_common(model, B, opts);
+   mh_status st = begin_call(model, B, opts, o);
    if (st != MH_OK)
       return st;
-   st = launch<double>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out);
+   st = launch<double>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &o, qdd_out);
    if (st != MH_OK || B == 0)
       return st;
    // ForwardDynamicsCalculator.getJointWrench (ForwardDynamicsCalculator.java:1330-1363) is a Newton-Euler sweep over the accelerations
@@ -3146,19 +3183,14 @@ mh_status mh_aba_joint_wrenches_f64(mh_model_t model, int64_t B, const double *q
    st = ensure_bytes(model->aux, (size_t)B * model->nv * sizeof(double));
    if (st != MH_OK)
       return st;
-   return launch<double>(ALGO_RNEA, model, B, q, qd, qdd_out, gravity, f_ext, opts, (double *)model->aux.ptr, nullptr, nullptr, nullptr, nullptr, true,
-                         0.0, nullptr, nullptr, nullptr, joint_wrench_out);
+   return launch<double>(ALGO_RNEA, model, B, q, qd, qdd_out, gravity, f_ext, &o, (double *)model->aux.ptr, joint_wrenches(joint_wrench_out));
 }
 mh_status mh_relative_acceleration_f64(mh_model_t model, int64_t B, const double *q, const double *body_acc, const double *body_twist,
                                        const double gravity[3], int32_t n_pairs, const int32_t *base_joints, const int32_t *body_joints,
                                        const mh_options *opts_in, double *out)
 {
    mh_options opts;
-   if (opts_in)
-      opts = *opts_in;
-   else
-      mh_options_default(&opts);
-   mh_status st = check_common(model, B, &opts);
+   mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
       return st;
    if (n_pairs < 0)
@@ -3187,9 +3219,9 @@ mh_status mh_relative_acceleration_f64(mh_model_t model, int64_t B, const double
    A.q = q, A.body_acc = body_acc, A.body_twist = opts.consider_coriolis ? body_twist : nullptr, A.out = out;
    A.pairs = (const int *)model->pairs.ptr, A.n_pairs = n_pairs;
    const bool soa = opts.layout == MH_LAYOUT_SOA;
-   A.q_bs = soa ? 1 : model->nq, A.q_es = soa ? B : 1;
-   A.f_bs = soa ? 1 : (long)model->n * 6, A.f_es = soa ? B : 1;
-   A.o_bs = soa ? 1 : (long)n_pairs * 6, A.o_es = soa ? B : 1;
+   set_strides(A.q_bs, A.q_es, soa, B, model->nq);
+   set_strides(A.f_bs, A.f_es, soa, B, (long)model->n * 6);
+   set_strides(A.o_bs, A.o_es, soa, B, (long)n_pairs * 6);
    set_root_acceleration(A, opts, gravity);
    if (opts.consider_coriolis && !body_twist)
       return fail(MH_ERR_INVALID_ARGUMENT, "body_twist is NULL but velocities are considered (opts->consider_coriolis)");
@@ -3232,18 +3264,7 @@ int32_t mh_model_n_acceleration_sources(mh_model_t model) { return model ? model
 mh_status mh_aba_locked_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double *qdd_in,
                             const double gravity[3], const double *f_ext, const mh_options *opts, double *qdd_out, double *tau_out)
 {
-   if (!model)
-      return fail(MH_ERR_INVALID_ARGUMENT, "model is NULL");
-   if (model->n_locked == 0)
-   { // nothing is locked: the ordinary forward dynamics, efforts copied through
-      mh_status st = launch<double>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out);
-      if (st == MH_OK && tau_out && tau_out != tau && B > 0)
-         HIP_TRY(hipMemcpyAsync(tau_out, tau, (size_t)B * model->nv * sizeof(double), hipMemcpyDeviceToDevice, opts ? (hipStream_t)opts->stream : nullptr));
-      return st;
-   }
-   if (B > 0 && !qdd_in)
-      return fail(MH_ERR_INVALID_ARGUMENT, "qdd_in is NULL but %d joint(s) are acceleration sources", model->n_locked);
-   return launch<double>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, qdd_in, tau_out);
+   return aba_locked<double>(model, B, q, qd, tau, qdd_in, gravity, f_ext, opts, qdd_out, tau_out);
 }
 // The pair calls run their two algorithms side by side (or phase by phase in one workgroup): an output that overlaps an input of the OTHER
 // algorithm would be read half-written.  (mh_rnea_* then mh_aba_* is the call sequence for in-place use.)
@@ -3261,11 +3282,7 @@ mh_status mh_rnea_aba_f64(mh_model_t model, int64_t B, const double *q, const do
                           const double gravity[3], const double *f_ext, const mh_options *opts_in, double *tau_out, double *qdd_out)
 {
    mh_options opts;
-   if (opts_in)
-      opts = *opts_in;
-   else
-      mh_options_default(&opts);
-   mh_status st = check_common(model, B, &opts);
+   mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
       return st;
    if (B == 0)
@@ -3274,7 +3291,7 @@ mh_status mh_rnea_aba_f64(mh_model_t model, int64_t B, const double *q, const do
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
    if (pair_outputs_overlap(q, qd, qdd, tau, tau_out, qdd_out, (size_t)B * model->nq * sizeof(double), (size_t)B * model->nv * sizeof(double)))
       return fail(MH_ERR_INVALID_ARGUMENT, "mh_rnea_aba_f64: tau_out / qdd_out must not overlap q, qd, qdd, tau or each other (the two algorithms run concurrently)");
-   const long waves = (B + 63) / 64;
+   const long waves = groups_of(B);
    const bool fusable = model->n_locked == 0 && model->spec.launch_fused && model->use_spec && model->dense_maps && opts.layout == MH_LAYOUT_AOS
                         && opts.consider_coriolis && opts.consider_accelerations && 2 * waves <= (long)model->cu_count * kFusedFactor
                         && model->spec.fused_lds_bytes(model->nq, model->nv) <= 160 * 1024
@@ -3291,43 +3308,19 @@ mh_status mh_rnea_aba_f64(mh_model_t model, int64_t B, const double *q, const do
       const bool no_spec = !model->use_spec || !model->spec.launch_split || !model->spec.split_usable || !model->spec.split_usable();
       if (no_spec && model->split_rt.usable && model->n_locked == 0 && model->use_split_rt != 0 && 2 * waves <= (long)model->cu_count)
       {
-         mh::Args<double> P{};
-         P.m = dev_model<double>(model);
-         P.B = B;
+         mh::Args<double> P = make_args<double>(model, B, opts, gravity);
          P.q = q, P.qd = qd, P.in3 = qdd, P.fext = f_ext, P.out = tau_out;
          P.in3b = tau, P.outb = qdd_out;
-         const bool soa = opts.layout == MH_LAYOUT_SOA;
-         P.q_bs = soa ? 1 : model->nq, P.q_es = soa ? B : 1;
-         P.v_bs = soa ? 1 : model->nv, P.v_es = soa ? B : 1;
-         P.f_bs = soa ? 1 : (long)model->n * 6, P.f_es = soa ? B : 1;
-         set_root_acceleration(P, opts, gravity);
-         P.coriolis = opts.consider_coriolis, P.accel = opts.consider_accelerations;
-         return launch_split_rt_pair(model, B, P, s);
+         return launch_split_rt<double>(ALGO_ABA, model, B, P, s, true);
       }
       if (waves > (long)model->cu_count) // measured: pays up to one wave per CU (profiles/r02_generic_pair_side_by_side.txt)
       {
          mh_status r = mh_rnea_f64(model, B, q, qd, qdd, gravity, f_ext, &opts, tau_out);
          return r != MH_OK ? r : mh_aba_f64(model, B, q, qd, tau, gravity, f_ext, &opts, qdd_out);
       }
-      if (!model->pair_stream)
-      {
-         HIP_TRY(hipStreamCreateWithFlags(&model->pair_stream, hipStreamNonBlocking));
-         HIP_TRY(hipEventCreateWithFlags(&model->pair_fork, hipEventDisableTiming));
-         HIP_TRY(hipEventCreateWithFlags(&model->pair_join, hipEventDisableTiming));
-      }
-      HIP_TRY(hipEventRecord(model->pair_fork, s));
-      HIP_TRY(hipStreamWaitEvent(model->pair_stream, model->pair_fork, 0));
-      mh_options ob = opts;
-      ob.stream = (void *)model->pair_stream;
-      std::swap(model->ws, model->ws_pair); // every launch path sizes and reads model->ws ...
-      std::swap(model->tr, model->tr_pair); // ... and model->tr when it goes through transposed copies of the state matrices
-      const mh_status rb = mh_aba_f64(model, B, q, qd, tau, gravity, f_ext, &ob, qdd_out);
-      std::swap(model->ws, model->ws_pair);
-      std::swap(model->tr, model->tr_pair);
-      const mh_status ra = mh_rnea_f64(model, B, q, qd, qdd, gravity, f_ext, &opts, tau_out);
-      HIP_TRY(hipEventRecord(model->pair_join, model->pair_stream)); // join even after an error: the caller's stream must not run ahead
-      HIP_TRY(hipStreamWaitEvent(s, model->pair_join, 0));
-      return rb != MH_OK ? rb : ra;
+      return side_by_side(
+         model, opts, true, [&](const mh_options *o) { return mh_rnea_f64(model, B, q, qd, qdd, gravity, f_ext, o, tau_out); },
+         [&](const mh_options *o) { return mh_aba_f64(model, B, q, qd, tau, gravity, f_ext, o, qdd_out); });
    };
    // Device-filling batches: the fused forward-dynamics kernel computes tau too (its inverse-dynamics phase has h, one more walk without
    // velocities adds M(q) qdd of the caller's accelerations: mh_zv_kernels.h, ZvfDelta) -- one launch instead of the inverse dynamics'
@@ -3335,72 +3328,44 @@ mh_status mh_rnea_aba_f64(mh_model_t model, int64_t B, const double *q, const do
    if (model->n_locked == 0 && model->use_spec && model->use_zvf_pair && opts.layout == MH_LAYOUT_AOS && opts.consider_coriolis && opts.consider_accelerations
        && zvf_ok(model, B, false) && model->spec.zvf_pair_usable && model->spec.zvf_pair_usable())
    {
-      mh::Args<double> Z{};
-      Z.m = dev_model<double>(model);
-      Z.B = B;
+      mh::Args<double> Z = make_args<double>(model, B, opts, gravity); // (AoS, both terms considered)
       Z.q = q, Z.qd = qd, Z.in3 = tau, Z.fext = f_ext, Z.out = qdd_out;
       Z.in3b = qdd, Z.outb = tau_out;
-      Z.q_bs = model->nq, Z.q_es = 1, Z.v_bs = model->nv, Z.v_es = 1, Z.f_bs = (long)model->n * 6, Z.f_es = 1;
-      set_root_acceleration(Z, opts, gravity);
-      Z.coriolis = 1, Z.accel = 1;
-      const long groups = std::min<long>((B + 63) / 64, (long)model->cu_count * 2);
-      const int rcz = model->spec.launch_zvf(SPEC_IO_LDS | SPEC_IDENT, &Z, (int)groups, opts.stream);
-      if (rcz == 0)
-         return MH_OK;
-      if (rcz != (int)hipErrorNotSupported)
-         return fail(MH_ERR_HIP, "fused forward + inverse dynamics failed to launch: %s", hipGetErrorString((hipError_t)rcz));
+      const long groups = std::min<long>(waves, (long)model->cu_count * 2);
+      if (spec_done(model->spec.launch_zvf(SPEC_IO_LDS | SPEC_IDENT, &Z, (int)groups, opts.stream), "fused forward + inverse dynamics failed to launch", st))
+         return st;
    }
    if (!fusable)
       return two_calls();
-   mh::Args<double> A{};
-   A.m = dev_model<double>(model);
-   A.B = B;
+   mh::Args<double> A = make_args<double>(model, B, opts, gravity); // (AoS, both terms considered)
    A.q = q, A.qd = qd, A.in3 = qdd, A.fext = f_ext, A.out = tau_out;
    A.in3b = tau, A.outb = qdd_out;
-   A.body_acc = nullptr, A.body_twist = nullptr;
-   A.dt = 0.0, A.q_next = nullptr, A.qd_next = nullptr;
-   A.ws = nullptr, A.ws_stride = 0;
-   A.q_bs = model->nq, A.q_es = 1, A.v_bs = model->nv, A.v_es = 1, A.f_bs = (long)model->n * 6, A.f_es = 1;
-   set_root_acceleration(A, opts, gravity);
-   A.coriolis = 1, A.accel = 1;
    if (zv_ok(model, B, false, 3))
    { // three jobs in one launch: bias efforts | articulated inertias + bias fold | the inverse dynamics output (mh_zv_kernels.h)
-      if (const mh_status se = zv_check_error(model); se != MH_OK)
-         return se;
-      int rc3 = 0;
-      if (const mh_status sz = zv_launch(model, A, 3, (hipStream_t)opts.stream, &rc3); sz != MH_OK)
-         return sz;
-      if (rc3 == 0)
-         return MH_OK;
+      if ((st = zv_check_error(model)) != MH_OK)
+         return st;
+      bool done = false;
+      if ((st = zv_launch(model, A, 3, (hipStream_t)opts.stream, done)) != MH_OK || done)
+         return st;
    }
    if (split_ok(model, 2, B, false))
    {
-      const int rc2 = model->spec.launch_split(2, split_flags(model, 2, false), &A, (int)waves, opts.stream);
-      if (rc2 == 0)
-         return MH_OK;
-      if (rc2 != (int)hipErrorNotSupported)
-         return fail(MH_ERR_HIP, "fused tree-split kernel launch failed: %s", hipGetErrorString((hipError_t)rc2));
+      if (spec_done(model->spec.launch_split(2, split_flags(model, 2, false), &A, (int)waves, opts.stream), "fused tree-split kernel launch failed", st))
+         return st;
       return two_calls(); // not in this code object (fast build)
    }
    if (!model->spec.supports(1, SPEC_ST_LDS | (model->ident_maps ? SPEC_IDENT : 0)))
    // no whole-tree ABA in this code object (trees with a tree-split form) and the tree-split launch was ruled out: two calls
       return two_calls();
-   const int rc = model->spec.launch_fused(model->ident_maps ? SPEC_IDENT : 0, &A, (int)waves, opts.stream);
-   if (rc == (int)hipErrorNotSupported)
-      return two_calls();
-   if (rc != 0)
-      return fail(MH_ERR_HIP, "fused kernel launch failed: %s", hipGetErrorString((hipError_t)rc));
-   return MH_OK;
+   if (spec_done(model->spec.launch_fused(model->ident_maps ? SPEC_IDENT : 0, &A, (int)waves, opts.stream), "fused kernel launch failed", st))
+      return st;
+   return two_calls();
 }
 mh_status mh_rnea_crba_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double gravity[3],
                            const double *f_ext, const mh_options *opts_in, double *tau_out, double *H_out)
 {
    mh_options opts;
-   if (opts_in)
-      opts = *opts_in;
-   else
-      mh_options_default(&opts);
-   mh_status st = check_common(model, B, &opts);
+   mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
       return st;
    if (B == 0)
@@ -3408,22 +3373,16 @@ mh_status mh_rnea_crba_f64(mh_model_t model, int64_t B, const double *q, const d
    if (!q || !qd || !qdd || (!gravity && !opts.use_root_acceleration) || !tau_out || !H_out)
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
    hipStream_t s = (hipStream_t)opts.stream;
-   const long groups = (B + 63) / 64;
+   const long groups = groups_of(B);
    // one launch: tree-split RNEA groups and tree-split CRBA groups side by side (code object with identity maps, AoS, no switches, no
    // external wrenches through this path; batches that leave room for both on the device)
    if (model->spec.launch_rnea_crba && model->use_spec && model->ident_maps && model->dense_maps && opts.layout == MH_LAYOUT_AOS
        && opts.consider_coriolis && opts.consider_accelerations && model->use_split != 0 && model->spec.split_usable && model->spec.split_usable()
        && model->spec.crba_split_usable && model->spec.crba_split_usable() && groups <= (long)model->cu_count * 2)
    {
-      mh::Args<double> A{};
-      A.m = dev_model<double>(model);
-      A.B = B;
+      mh::Args<double> A = make_args<double>(model, B, opts, gravity); // (AoS, both terms considered)
       A.q = q, A.qd = qd, A.in3 = qdd, A.fext = f_ext, A.out = tau_out;
-      A.in3b = nullptr, A.outb = H_out;
-      A.ws = nullptr, A.ws_stride = 0;
-      A.q_bs = model->nq, A.q_es = 1, A.v_bs = model->nv, A.v_es = 1, A.f_bs = (long)model->n * 6, A.f_es = 1;
-      set_root_acceleration(A, opts, gravity);
-      A.coriolis = 1, A.accel = 1;
+      A.outb = H_out;
       // thin CRBA workgroups: its write-out is bound by the stores in flight per CU.  Every workgroup must be resident at once (the RNEA
       // groups would otherwise queue behind the CRBA's): one per CU, two where the thinner image leaves LDS for it (202 registers: two
       // waves per SIMD)
@@ -3445,11 +3404,8 @@ mh_status mh_rnea_crba_f64(mh_model_t model, int64_t B, const double *q, const d
             lpg = (int)fit;
       }
       const long ng = std::min<long>((B + lpg - 1) / lpg, (long)model->cu_count * 2);
-      const int rc = model->spec.launch_rnea_crba(&A, (int)groups, (int)ng, lpg, (void *)s);
-      if (rc == 0)
-         return MH_OK;
-      if (rc != (int)hipErrorNotSupported)
-         return fail(MH_ERR_HIP, "fused RNEA + CRBA launch failed: %s", hipGetErrorString((hipError_t)rc));
+      if (spec_done(model->spec.launch_rnea_crba(&A, (int)groups, (int)ng, lpg, (void *)s), "fused RNEA + CRBA launch failed", st))
+         return st;
    }
    // two launches; side by side while the batch leaves most of the device idle (the CRBA on the model's own stream; it needs no workspace
    // of the RNEA's kind when a code object serves it, and gets its own otherwise)
@@ -3458,23 +3414,9 @@ mh_status mh_rnea_crba_f64(mh_model_t model, int64_t B, const double *q, const d
       st = mh_rnea_f64(model, B, q, qd, qdd, gravity, f_ext, &opts, tau_out);
       return st != MH_OK ? st : mh_crba_f64(model, B, q, &opts, H_out);
    }
-   if (!model->pair_stream)
-   {
-      HIP_TRY(hipStreamCreateWithFlags(&model->pair_stream, hipStreamNonBlocking));
-      HIP_TRY(hipEventCreateWithFlags(&model->pair_fork, hipEventDisableTiming));
-      HIP_TRY(hipEventCreateWithFlags(&model->pair_join, hipEventDisableTiming));
-   }
-   HIP_TRY(hipEventRecord(model->pair_fork, s));
-   HIP_TRY(hipStreamWaitEvent(model->pair_stream, model->pair_fork, 0));
-   mh_options ob = opts;
-   ob.stream = (void *)model->pair_stream;
-   std::swap(model->ws, model->ws_pair);
-   const mh_status rb = mh_crba_f64(model, B, q, &ob, H_out);
-   std::swap(model->ws, model->ws_pair);
-   const mh_status ra = mh_rnea_f64(model, B, q, qd, qdd, gravity, f_ext, &opts, tau_out);
-   HIP_TRY(hipEventRecord(model->pair_join, model->pair_stream));
-   HIP_TRY(hipStreamWaitEvent(s, model->pair_join, 0));
-   return rb != MH_OK ? rb : ra;
+   return side_by_side(
+      model, opts, false, [&](const mh_options *o) { return mh_rnea_f64(model, B, q, qd, qdd, gravity, f_ext, o, tau_out); },
+      [&](const mh_options *o) { return mh_crba_f64(model, B, q, o, H_out); });
 }
 mh_status mh_rnea_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const double gravity[3],
                       const float *f_ext, const mh_options *opts, float *tau_out)
@@ -3498,17 +3440,15 @@ mh_status mh_crba_f32(mh_model_t model, int64_t B, const float *q, const mh_opti
 mh_status mh_rnea_aba_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const float *tau,
                           const double gravity[3], const float *f_ext, const mh_options *opts_in, float *tau_out, float *qdd_out)
 {
-   mh_options opts;
-   if (opts_in)
-      opts = *opts_in;
-   else
-      mh_options_default(&opts);
    if (model && B > 0 && q && qd && qdd && tau && tau_out && qdd_out
        && pair_outputs_overlap(q, qd, qdd, tau, tau_out, qdd_out, (size_t)B * model->nq * sizeof(float), (size_t)B * model->nv * sizeof(float)))
       return fail(MH_ERR_INVALID_ARGUMENT, "mh_rnea_aba_f32: tau_out / qdd_out must not overlap q, qd, qdd, tau or each other (the two algorithms run concurrently)");
-   const bool big = model && B >= 8192 && q && qd && qdd && tau && tau_out && qdd_out && !f_ext && model->use_dfs && model->n_locked == 0
-                    && model->use_transpose < 0 && model->nq + model->nv >= 64 && opts.consider_coriolis
-                    && opts.consider_accelerations;
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts); // (the two single calls below check again, on the context's copy)
+   if (st != MH_OK)
+      return st;
+   const bool big = q && qd && qdd && tau && tau_out && qdd_out && !f_ext && model->use_dfs && model->n_locked == 0 && model->use_transpose < 0
+                    && auto_transpose(model, B) && opts.consider_coriolis && opts.consider_accelerations;
    const bool shared = big && opts.layout == MH_LAYOUT_AOS;
    // ONE walk for both (round 5; mh_dfs_kernels.h: aba_dfs_kernel<.., PAIR>) unless a run-time tree split or a code object serves the model
    // (small / specialised models hardly get here: 8192 configurations of >= 64 state entries); MH_DFS_PAIR=0 keeps the two launches
@@ -3518,44 +3458,34 @@ mh_status mh_rnea_aba_f32(mh_model_t model, int64_t B, const float *q, const flo
    bool rounds_favour_two = false;
    if (big)
    {
-      const long wpc = ((B + 63) / 64 + model->cu_count - 1) / model->cu_count, r8 = (wpc + 7) / 8, r12 = (wpc + 11) / 12;
+      const long wpc = (groups_of(B) + model->cu_count - 1) / model->cu_count, r8 = (wpc + 7) / 8, r12 = (wpc + 11) / 12;
       const long two = (r12 * 132 < r8 * 100 ? r12 * 132 : r8 * 100) * 125; // (x 1e4)
       rounds_favour_two = two < r8 * 10000;
    }
    const bool fused = big && model->use_dfs_pair && !rounds_favour_two && !(model->spec.handle && model->use_spec)
-                      && !(model->split_rt.usable && (model->use_split_rt == 1 || (B + 63) / 64 <= (long)model->cu_count * 2));
-   auto fused_walk = [&](mh_model *mdl, const float *sq, const float *sqd, const float *sqdd, const float *stau, float *o1, float *o2) -> mh_status {
-      mh::Args<float> A{};
-      A.m = dev_model<float>(mdl);
-      A.B = B;
+                      && !(model->split_rt.usable && (model->use_split_rt == 1 || groups_of(B) <= (long)model->cu_count * 2));
+   // the walk on SoA rows (the caller's, or the transposed copies): both terms considered
+   auto fused_walk = [&](const float *sq, const float *sqd, const float *sqdd, const float *stau, float *o1, float *o2) -> mh_status {
+      mh_options so = opts;
+      so.layout = MH_LAYOUT_SOA;
+      mh::Args<float> A = make_args<float>(model, B, so, gravity);
       A.q = sq, A.qd = sqd, A.in3 = sqdd, A.out = o1, A.in3b = stau, A.outb = o2;
-      A.fext = nullptr, A.body_acc = nullptr, A.body_twist = nullptr, A.joint_wrench = nullptr;
-      A.dt = 0.0f, A.q_next = nullptr, A.qd_next = nullptr;
-      A.q_bs = 1, A.q_es = B, A.v_bs = 1, A.v_es = B, A.f_bs = 1, A.f_es = B;
-      set_root_acceleration(A, opts, gravity);
-      A.coriolis = 1, A.accel = 1;
-      const mh_status r = launch_dfs<float>(ALGO_ABA, mdl, B, A, (hipStream_t)opts.stream, true);
+      const mh_status r = launch_dfs<float>(ALGO_ABA, model, B, A, (hipStream_t)opts.stream, true);
       if (r == MH_OK)
          HIP_TRY(hipGetLastError());
       return r;
    };
    if (fused && opts.layout == MH_LAYOUT_SOA)
    { // SoA matrices: the walk reads and writes the caller's buffers
-      mh_status st = check_common(model, B, &opts);
-      if (st != MH_OK)
-         return st;
       if (!gravity && !opts.use_root_acceleration)
          return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
-      return fused_walk(model, q, qd, qdd, tau, tau_out, qdd_out);
+      return fused_walk(q, qd, qdd, tau, tau_out, qdd_out);
    }
    if (!shared)
    {
       const mh_status r = mh_rnea_f32(model, B, q, qd, qdd, gravity, f_ext, &opts, tau_out);
       return r != MH_OK ? r : mh_aba_f32(model, B, q, qd, tau, gravity, f_ext, &opts, qdd_out);
    }
-   mh_status st = check_common(model, B, &opts);
-   if (st != MH_OK)
-      return st;
    if (!gravity && !opts.use_root_acceleration)
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
    const size_t nq = model->nq, nv = model->nv, Bz = (size_t)B;
@@ -3573,7 +3503,7 @@ mh_status mh_rnea_aba_f32(mh_model_t model, int64_t B, const float *q, const flo
    mh_options so = opts;
    so.layout = MH_LAYOUT_SOA;
    if (fused)
-      st = fused_walk(model, t_q, t_qd, t_qdd, t_tau, t_o1, t_o2);
+      st = fused_walk(t_q, t_qd, t_qdd, t_tau, t_o1, t_o2);
    else
    {
       st = launch<float>(ALGO_RNEA, model, B, t_q, t_qd, t_qdd, gravity, nullptr, &so, t_o1);
@@ -3620,28 +3550,17 @@ mh_status mh_crba_f32_host(mh_model_t model, int64_t B, const float *q, const mh
 mh_status mh_rnea_bodies_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const double gravity[3],
                              const float *f_ext, const mh_options *opts, float *tau_out, float *body_acc_out, float *body_twist_out)
 {
-   return launch<float>(ALGO_RNEA, model, B, q, qd, qdd, gravity, f_ext, opts, tau_out, nullptr, nullptr, body_acc_out, body_twist_out, true);
+   return launch<float>(ALGO_RNEA, model, B, q, qd, qdd, gravity, f_ext, opts, tau_out, body_outputs<float>(body_acc_out, body_twist_out));
 }
 mh_status mh_aba_bodies_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const double gravity[3],
                             const float *f_ext, const mh_options *opts, float *qdd_out, float *body_acc_out, float *body_twist_out)
 {
-   return launch<float>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, nullptr, nullptr, body_acc_out, body_twist_out, true);
+   return launch<float>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, body_outputs<float>(body_acc_out, body_twist_out));
 }
 mh_status mh_aba_locked_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const float *qdd_in,
                             const double gravity[3], const float *f_ext, const mh_options *opts, float *qdd_out, float *tau_out)
 {
-   if (!model)
-      return fail(MH_ERR_INVALID_ARGUMENT, "model is NULL");
-   if (model->n_locked == 0)
-   {
-      mh_status st = launch<float>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out);
-      if (st == MH_OK && tau_out && tau_out != tau && B > 0)
-         HIP_TRY(hipMemcpyAsync(tau_out, tau, (size_t)B * model->nv * sizeof(float), hipMemcpyDeviceToDevice, opts ? (hipStream_t)opts->stream : nullptr));
-      return st;
-   }
-   if (B > 0 && !qdd_in)
-      return fail(MH_ERR_INVALID_ARGUMENT, "qdd_in is NULL but %d joint(s) are acceleration sources", model->n_locked);
-   return launch<float>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, qdd_in, tau_out);
+   return aba_locked<float>(model, B, q, qd, tau, qdd_in, gravity, f_ext, opts, qdd_out, tau_out);
 }
 // ---- device memory for hosts without a HIP binding of their own (a Java shim keeps simulation state resident between steps with these)
 mh_status mh_device_alloc(size_t bytes, void **ptr_out)
@@ -3718,11 +3637,7 @@ mh_status mh_crba_coriolis_f64_host(mh_model_t model, int64_t B, const double *q
                                     double *C_out)
 {
    mh_options opts;
-   if (opts_in)
-      opts = *opts_in;
-   else
-      mh_options_default(&opts);
-   mh_status st = check_common(model, B, &opts);
+   mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
       return st;
    if (B == 0)
@@ -3749,11 +3664,7 @@ mh_status mh_centroidal_f64_host(mh_model_t model, int64_t B, const double *q, c
                                  const mh_options *opts_in, double *A_out, double *b_out, double *com_out)
 {
    mh_options opts;
-   if (opts_in)
-      opts = *opts_in;
-   else
-      mh_options_default(&opts);
-   mh_status st = check_common(model, B, &opts);
+   mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
       return st;
    if (B == 0)
