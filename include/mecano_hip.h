@@ -421,6 +421,28 @@ mh_status mh_centroidal_f32(mh_model_t model, int64_t B, const float *q, const f
                             const mh_options *opts, float *A_out, float *b_out, float *com_out);
 
 /*
+ * ---- gravity efforts and their gradient (MultiBodyGravityGradientCalculator.getTauMatrix / getTauGradientMatrix,
+ *      algorithms/MultiBodyGravityGradientCalculator.java:397-672) ----
+ * tau_out [B][nv]: the joint efforts that hold the system against gravity and the external wrenches -- mh_rnea_* with both switches off,
+ * same gravity, same f_ext.  grad_out [B][nv][nv] row-major (MH_LAYOUT_SOA: [nv*nv][B], as H_out of mh_crba_*): entry [i][j] is
+ * d tau_i / d q_j, so that tau(q + dq) = tau(q) + grad(q) dq.  dq lives in velocity space: it is the step
+ * MultiBodySystemStateIntegrator.integrateFromVelocity applies (for a SixDoF, planar or spherical joint a twist increment in the frame
+ * after the joint, not a quaternion delta).  Every external wrench is held constant IN THE WORLD while the configuration varies.
+ * Entries of joints neither of which is an ancestor of the other are zero; the kernel writes the whole matrix, zeros included, so
+ * grad_out need not be cleared.  The gravity part is symmetric between DoFs of different joints; the external part goes to the
+ * [descendant][ancestor] entry only, and with opposite signs to the two entries of a pair of DoFs of one multi-DoF joint.
+ * gravity[3] is a HOST pointer, the vector g in the root body frame (not NULL).  f_ext as for mh_rnea_* (may be NULL).  Either output may
+ * be NULL, not both (MH_ERR_INVALID_ARGUMENT).  opts->consider_coriolis, opts->consider_accelerations, opts->use_root_acceleration and
+ * opts->root_acceleration are ignored: the calculator has no velocities, no accelerations and no moving base.  Ignored subtrees are
+ * lumped by the host as for every other call (mh_model_desc).  Device pointers, asynchronous on opts->stream; run-time-topology kernel
+ * for every model; after mh_reserve the call allocates nothing.
+ */
+mh_status mh_gravity_gradient_f64(mh_model_t model, int64_t B, const double *q, const double gravity[3], const double *f_ext,
+                                  const mh_options *opts, double *tau_out, double *grad_out);
+mh_status mh_gravity_gradient_f32(mh_model_t model, int64_t B, const float *q, const double gravity[3], const float *f_ext,
+                                  const mh_options *opts, float *tau_out, float *grad_out);
+
+/*
  * ---- state integration (MultiBodySystemStateIntegrator.doubleIntegrateFromAcceleration, tools/MultiBodySystemStateIntegrator.java:365-441,
  *      503-575, 710-733): the step downstream of forward dynamics, so that a simulation loop never leaves the device ----
  * One explicit constant-acceleration step of size dt for every joint of every configuration: 1-DoF q' = q + dt qd + dt^2/2 qdd,

@@ -115,6 +115,13 @@ public final class MecanoHipNative
    /** (model, B, q, body_acc, body_twist|NULL, gravity, n_pairs, base_joints (host int[]), body_joints (host int[]), opts, out) */
    static final MethodHandle RELATIVE_ACCELERATION = handle("mh_relative_acceleration_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                                                    JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * MultiBodyGravityGradientCalculator.getTauMatrix / getTauGradientMatrix for B configurations: (model, B, q, gravity[3] (host),
+    * f_ext|NULL, opts|NULL, tau_out|NULL, grad_out|NULL), grad_out [B][nv][nv] row-major; not both outputs NULL.
+    */
+   static final MethodHandle GRAVITY_GRADIENT = handle("mh_gravity_gradient_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 (float matrices on the device) */
+   static final MethodHandle GRAVITY_GRADIENT_F32 = handle("mh_gravity_gradient_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
    /** (model, B, dt, q, qd, qdd, opts, q_out, qd_out, qdd_out|NULL) */
    static final MethodHandle INTEGRATE = handle("mh_integrate_f64", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                            ADDRESS));

@@ -5,6 +5,7 @@
 * ``CompositeRigidBodyMassMatrixCalculator`` algorithms/CompositeRigidBodyMassMatrixCalculator.java:157-233, 286-303, 344-348
 * ``JointTorqueRegressorCalculator``         algorithms/JointTorqueRegressorCalculator.java:101-133, 173-190, 360-502 (a caller of the first)
 * ``MultiBodyResponseCalculator``            algorithms/MultiBodyResponseCalculator.java:120-140, 288-935 (a caller of the second)
+* ``MultiBodyGravityGradientCalculator``     algorithms/MultiBodyGravityGradientCalculator.java:141-351, 397-672
 
 Differences a user of the reference must know (all forced by batching, none changes results):
 
@@ -708,6 +709,67 @@ class CompositeRigidBodyMassMatrixCalculator(_Base):
         """origin of a centre-of-mass centroidal frame in its parent frame (algorithms/CenterOfMassCalculator.java:70-91)"""
         self._centroidal()
         return self._com
+
+
+class MultiBodyGravityGradientCalculator(_Base):
+    """algorithms/MultiBodyGravityGradientCalculator.java: the joint efforts that hold the system against gravity and external wrenches
+    (getTauMatrix, :319-323) and their gradient with respect to the configuration (getTauGradientMatrix, :347-351), batched:
+    tau(q + dq) = tau(q) + grad(q) dq with dq in velocity space and every external wrench held constant in the world.
+
+    Batched: ``compute(q)`` with q [B, nq] on the device; the getters then return [B, nv] and [B, nv, nv].  The reference's own face:
+    set the joints' configuration, ``reset()``, and the getters evaluate that ONE configuration (nv x 1 and nv x nv numpy matrices).
+    Ignored subtrees are always lumped into the body they hang from, as the reference does (updateIgnoredSubtreeInertia, :262-290)."""
+
+    def __init__(self, input):
+        super().__init__(input, considerIgnoredSubtreesInertia=True)
+        self._tau = self._grad = None
+        self._dirty = True
+
+    def setGravitionalAcceleration(self, *gravity):
+        """The reference's spelling and overloads (:141-208): a 3-tuple in the inertial frame, ``(gz)`` or ``(gx, gy, gz)``."""
+        self.setGravitationalAcceleration(*gravity)
+        if self._gravity.size != 3:
+            raise ValueError("gravity is a scalar (z) or three components")
+        self.reset()
+
+    def setExternalWrench(self, rigidBody, externalWrench):
+        super().setExternalWrench(rigidBody, externalWrench)
+        self.reset()
+
+    def setExternalWrenchesToZero(self):
+        super().setExternalWrenchesToZero()
+        self.reset()
+
+    def reset(self):
+        """:253-256: the outputs are evaluated again the next time a getter is called."""
+        self._dirty = True
+
+    def compute(self, q):
+        """(tau [B, nv], grad [B, nv, nv]) of B configurations; external wrenches as set with setExternalWrenches."""
+        self._tau, self._grad = self.model.gravity_gradient(q, self._gravity, self._f_ext, self.layout)
+        self._dirty = False
+        return self._tau, self._grad
+
+    def _update(self):
+        if not self._dirty:
+            return
+        import torch
+        from .multibody import JointStateType
+        nv = self.model.nv
+        q = torch.tensor(self._extract(JointStateType.CONFIGURATION, self.model.nq), device="cuda")
+        f = self._single_f_ext()
+        f = None if f is None else torch.tensor(f, device="cuda")
+        tau, grad = self.model.gravity_gradient(q, self._gravity, f, _lib.LAYOUT_AOS)
+        self._tau, self._grad = tau.cpu().numpy().reshape(nv, 1), grad.cpu().numpy().reshape(nv, nv)
+        self._dirty = False
+
+    def getTauMatrix(self):
+        self._update()
+        return self._tau
+
+    def getTauGradientMatrix(self):
+        self._update()
+        return self._grad
 
 
 class MultiBodySystemStateIntegrator:

@@ -7,6 +7,7 @@
 #include "../../include/mecano_hip.h"
 #include "mh_dfs_kernels.h"
 #include "mh_split_kernels.h"
+#include "mh_gravity_kernels.h"
 
 #include <dlfcn.h>
 #include <spawn.h>
@@ -257,6 +258,12 @@ struct mh_model
    int n_nonadjacent = 0; // bodies whose parent is not the body before them in engine order (branch points of the tree)
    double *d_consts64 = nullptr;
    float *d_consts32 = nullptr;
+   // mh_gravity_gradient_*: subtree masses (engine order) and, per body, the matrix columns of unrelated joints (mh_gravity_kernels.h)
+   std::vector<double> sub_mass;
+   std::vector<int> grav_zero_ofs, grav_zero_cols;
+   double *d_sub_mass64 = nullptr;
+   float *d_sub_mass32 = nullptr;
+   int *d_grav_zero_ofs = nullptr, *d_grav_zero_cols = nullptr;
    Workspace ws;
    // staging buffers of the *_host entry points
    Workspace stage;
@@ -2087,6 +2094,43 @@ mh_status centroidal_impl(mh_model_t model, int64_t B, const T *q, const T *qd, 
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
+// Gravity efforts and their gradient (MultiBodyGravityGradientCalculator): run-time-topology kernel, which writes every entry of its
+// outputs -- no memset in front of it
+template <typename T>
+mh_status gravity_gradient_impl(mh_model_t model, int64_t B, const T *q, const double *gravity, const T *f_ext, const mh_options *opts_in, T *tau_out,
+                                T *grad_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   if (!gravity)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL");
+   if (!tau_out && !grad_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "tau_out and grad_out are both NULL");
+   if (B == 0)
+      return MH_OK;
+   if (!q)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL configuration pointer");
+   const Launch L = plan_launch(model, B);
+   const int parts = regressor_parts(model, L);
+   st = ensure_parts_workspace(model, L, parts, sizeof(T));
+   if (st != MH_OK)
+      return st;
+   mh::GravArgs<T> G{};
+   mh::Args<T> &A = G.a;
+   A = make_args<T>(model, B, opts);
+   A.q = q, A.fext = f_ext, A.out = tau_out, A.outb = grad_out;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = L.lanes;
+   A.gx = (T)gravity[0], A.gy = (T)gravity[1], A.gz = (T)gravity[2]; // the vector itself: opts->root_acceleration plays no part
+   set_strides(G.g_bs, G.g_es, opts.layout == MH_LAYOUT_SOA, B, (long)model->nv * model->nv);
+   G.sub_mass = sizeof(T) == 8 ? (const T *)model->d_sub_mass64 : (const T *)model->d_sub_mass32;
+   G.zero_ofs = model->d_grav_zero_ofs, G.zero_cols = model->d_grav_zero_cols;
+   hipLaunchKernelGGL((mh::gravity_gradient_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
 template <typename T>
 mh_status integrate_impl(mh_model_t model, int64_t B, double dt, const T *q, const T *qd, const T *qdd, const mh_options *opts_in, T *q_out,
                                 T *qd_out, T *qdd_out)
@@ -2421,6 +2465,45 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
    }
    m->n_slots = std::max(slots, 1);
 
+   // ---- gravity gradient (mh_gravity_kernels.h): the subtree masses do not depend on q; the zero pattern of its matrix is the topology's
+   {
+      m->sub_mass.assign(n, 0.0);
+      for (int e = n - 1; e >= 0; e--)
+      {
+         m->sub_mass[e] += m->consts[(size_t)e * mh::MC_STRIDE + mh::MC_M];
+         if (P.eparent[e] >= 0)
+            m->sub_mass[P.eparent[e]] += m->sub_mass[e];
+      }
+      std::vector<char> owned(d->nv, 0);
+      for (int k = 0; k < edofo[n]; k++)
+         owned[m->dof_map[k]] = 1;
+      std::vector<char> related((size_t)n * n, 0); // related[a * n + b]: a == b or one is an ancestor of the other
+      for (int e = 0; e < n; e++)
+         for (int a = e; a >= 0; a = P.eparent[a])
+            related[(size_t)e * n + a] = related[(size_t)a * n + e] = 1;
+      m->grav_zero_ofs.assign(n + 2, 0);
+      for (int e = 0; e < n; e++)
+      {
+         if (edofo[e + 1] > edofo[e]) // (a joint without DoFs has no rows)
+         {
+            for (int b = 0; b < n; b++)
+               if (!related[(size_t)e * n + b])
+                  for (int k = edofo[b]; k < edofo[b + 1]; k++)
+                     m->grav_zero_cols.push_back(m->dof_map[k]);
+            for (int r = 0; r < d->nv; r++)
+               if (!owned[r])
+                  m->grav_zero_cols.push_back(r);
+         }
+         m->grav_zero_ofs[e + 1] = (int)m->grav_zero_cols.size();
+      }
+      for (int r = 0; r < d->nv; r++)
+         if (!owned[r])
+            m->grav_zero_cols.push_back(r);
+      m->grav_zero_ofs[n + 1] = (int)m->grav_zero_cols.size();
+      if (m->grav_zero_cols.empty())
+         m->grav_zero_cols.push_back(0);
+   }
+
    // ---- depth-first kernels: children counts, stack-frame / hand-over offsets, event program (mh_dfs_kernels.h)
    {
       std::vector<int> nch(n, 0), ofs_r(n, 0), ofs_a(n, 0), ofs_p(n, 0);
@@ -2545,6 +2628,7 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
    m->device = dev;
    m->topo_key = P.key;
    std::vector<float> c32(m->consts.begin(), m->consts.end());
+   std::vector<float> sm32(m->sub_mass.begin(), m->sub_mass.end());
    auto up = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
       hipError_t r = hipMalloc(dst, bytes);
       if (r != hipSuccess)
@@ -2565,6 +2649,14 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
       e = up((void **)&m->d_consts64, m->consts.data(), m->consts.size() * sizeof(double));
    if (e == hipSuccess)
       e = up((void **)&m->d_consts32, c32.data(), c32.size() * sizeof(float));
+   if (e == hipSuccess)
+      e = up((void **)&m->d_sub_mass64, m->sub_mass.data(), m->sub_mass.size() * sizeof(double));
+   if (e == hipSuccess)
+      e = up((void **)&m->d_sub_mass32, sm32.data(), sm32.size() * sizeof(float));
+   if (e == hipSuccess)
+      e = up((void **)&m->d_grav_zero_ofs, m->grav_zero_ofs.data(), m->grav_zero_ofs.size() * sizeof(int));
+   if (e == hipSuccess)
+      e = up((void **)&m->d_grav_zero_cols, m->grav_zero_cols.data(), m->grav_zero_cols.size() * sizeof(int));
    if (e != hipSuccess)
    {
       mh_model_destroy(m);
@@ -2728,6 +2820,10 @@ static void release_model(mh_model *m)
    (void)hipFree(m->d_prog_seq);
    (void)hipFree(m->d_consts64);
    (void)hipFree(m->d_consts32);
+   (void)hipFree(m->d_sub_mass64);
+   (void)hipFree(m->d_sub_mass32);
+   (void)hipFree(m->d_grav_zero_ofs);
+   (void)hipFree(m->d_grav_zero_cols);
    free_scratch(m);
    if (m->spec.handle)
       dlclose(m->spec.handle);
@@ -3120,6 +3216,16 @@ mh_status mh_centroidal_f32(mh_model_t model, int64_t B, const float *q, const f
                             const mh_options *opts, float *A_out, float *b_out, float *com_out)
 {
    return centroidal_impl<float>(model, B, q, qd, frame, frame_mode, opts, A_out, b_out, com_out);
+}
+mh_status mh_gravity_gradient_f64(mh_model_t model, int64_t B, const double *q, const double gravity[3], const double *f_ext,
+                                  const mh_options *opts, double *tau_out, double *grad_out)
+{
+   return gravity_gradient_impl<double>(model, B, q, gravity, f_ext, opts, tau_out, grad_out);
+}
+mh_status mh_gravity_gradient_f32(mh_model_t model, int64_t B, const float *q, const double gravity[3], const float *f_ext, const mh_options *opts,
+                                  float *tau_out, float *grad_out)
+{
+   return gravity_gradient_impl<float>(model, B, q, gravity, f_ext, opts, tau_out, grad_out);
 }
 mh_status mh_integrate_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *qdd, const mh_options *opts,
                            double *q_out, double *qd_out, double *qdd_out)

@@ -515,6 +515,41 @@ class HipModel:
                                                                   C.data_ptr()))
         return H, C
 
+    def gravity_gradient(self, q, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Joint efforts that hold the system against gravity and the external wrenches, and their gradient with respect to the
+        configuration (MultiBodyGravityGradientCalculator.getTauMatrix / getTauGradientMatrix, MultiBodyGravityGradientCalculator.java:
+        319-351): (tau [B, nv], grad [B, nv, nv]) with tau(q + dq) = tau(q) + grad(q) dq, dq in velocity space, the wrenches held constant
+        in the world.  Device tensors (fp64 / fp32); SoA: tau [nv, B], grad [nv * nv, B].  ``gravity`` is the 3-vector g.  ``out``: a
+        (tau, grad) pair of tensors to write into; either may be None (that output is then not computed), not both."""
+        import torch
+        B, dt, sfx, stream = self._device_inputs([q], layout)
+        a = [float(v) for v in np.asarray(gravity, dtype=np.float64).reshape(-1)]
+        if len(a) != 3:
+            raise _lib.MecanoHipError(2, f"gravity must have 3 entries, got {len(a)}")
+        if f_ext is not None and (not self._is_torch(f_ext) or not f_ext.is_cuda or f_ext.dtype != dt or not f_ext.is_contiguous()):
+            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+        self._check_f_ext(f_ext, B, layout)
+        aos = layout == _lib.LAYOUT_AOS
+        shapes = ((B, self.nv) if aos else (self.nv, B), (B, self.nv, self.nv) if aos else (self.nv * self.nv, B))
+        if out is None:
+            out = tuple(torch.empty(s, dtype=dt, device=q.device) for s in shapes)
+        tau, grad = out
+        if tau is None and grad is None:
+            raise _lib.MecanoHipError(1, "both outputs are None")
+        for t, s, name in ((tau, shapes[0], "tau"), (grad, shapes[1], "grad")):
+            if t is None:
+                continue
+            if not self._is_torch(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+            if tuple(t.shape) != s:
+                raise _lib.MecanoHipError(2, f"{name} output has shape {tuple(t.shape)}, expected {s}")
+        opts = self._options(layout, stream=stream)
+        _lib.check(getattr(_lib.load(), f"mh_gravity_gradient_{sfx}")(self._h, B, q.data_ptr(), (ctypes.c_double * 3)(*a),
+                                                                     None if f_ext is None else f_ext.data_ptr(), ctypes.byref(opts),
+                                                                     None if tau is None else tau.data_ptr(),
+                                                                     None if grad is None else grad.data_ptr()))
+        return tau, grad
+
     def regressor(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), layout=_lib.LAYOUT_AOS, consider_coriolis=True, consider_accelerations=True,
                   first_moment_columns=False):
         """Joint torque regressor (JointTorqueRegressorCalculator.compute, JointTorqueRegressorCalculator.java:173-190): Y [B, nv, 10 n_joints]
