@@ -443,6 +443,37 @@ mh_status mh_gravity_gradient_f32(mh_model_t model, int64_t B, const float *q, c
                                   const mh_options *opts, float *tau_out, float *grad_out);
 
 /*
+ * ---- inverse apparent inertia of bodies (MultiBodyResponseCalculator.computeRigidBodyApparentSpatialInertiaInverse /
+ *      computeRigidBodyApparentLinearInertiaInverse, applyRigidBodyWrench + getAccelerationChangeProvider,
+ *      algorithms/MultiBodyResponseCalculator.java:288-500, 608-627, 859-862, 1191-1338) ----
+ * How target body b accelerates when a wrench acts on target body a, for n_targets bodies at once: the 6 x 6 blocks of W = J H^-1 J^T,
+ * from the articulated-body recursion itself (neither J nor H is formed), at zero velocity.
+ * target_joints (HOST, [n_targets]): positions in the model's joint list; the target is that joint's successor body, as in f_ext and
+ * body_acc_out.  Duplicates are allowed (two contact points on one body, with different poses).
+ * target_poses (HOST, [n_targets][12], R row-major 9 + p 3, or NULL = identity): the reference's inertiaFrame as a constant pose relative
+ * to the target's body-fixed frame (the frame body_acc_out of mh_aba_bodies_* is expressed in).  The wrench (moment, force) acts at and
+ * is expressed in that frame; the response is the change of the spatial acceleration (angular, linear) of that frame's origin, expressed
+ * in it.  The change of frame is the plain motion / force transform (no velocities, hence no Coriolis terms).  R must be a rotation to 1e-9.
+ * blocks = MH_APPARENT_BLOCKS_DIAGONAL: W_out [B][n_targets][6][6] (MH_LAYOUT_SOA: [n_targets * 36][B]), block k = response of target k to a
+ * wrench on itself; its lower-right 3 x 3 is the inverse apparent linear inertia.
+ * blocks = MH_APPARENT_BLOCKS_COUPLED: W_out [B][6 K][6 K] row-major, K = n_targets (MH_LAYOUT_SOA: [(6 K)^2][B]), block (b, a) = response of
+ * target b to a unit wrench on target a.  Its diagonal blocks carry the bits of the DIAGONAL call; W is symmetric up to rounding (every
+ * block is computed, none mirrored).
+ * The model's joint source modes hold, as in mh_aba_locked_*: an MH_ACCELERATION_SOURCE joint keeps a zero change of acceleration and hands
+ * the articulated inertia of its subtree to its parent undiminished.  Every entry of W_out is written (no memset needed), nothing outside
+ * it.  W_out must not overlap q.  MH_ERR_INVALID_ARGUMENT: NULL q / W_out / target_joints, n_targets outside 1 ... MH_MAX_APPARENT_TARGETS,
+ * a joint index out of range, an unknown blocks value, a pose that is no rotation, W_out overlapping q.  B = 0 returns MH_OK and touches
+ * nothing.  Device pointers, asynchronous on opts->stream; run-time-topology kernel for every model; targets and poses travel as kernel
+ * arguments: nothing is uploaded, and after mh_reserve the call allocates nothing.
+ */
+enum { MH_APPARENT_BLOCKS_DIAGONAL = 0, MH_APPARENT_BLOCKS_COUPLED = 1 };
+#define MH_MAX_APPARENT_TARGETS 16
+mh_status mh_apparent_inertia_inverse_f64(mh_model_t model, int64_t B, const double *q, int32_t n_targets, const int32_t *target_joints,
+                                          const double *target_poses, int32_t blocks, const mh_options *opts, double *W_out);
+mh_status mh_apparent_inertia_inverse_f32(mh_model_t model, int64_t B, const float *q, int32_t n_targets, const int32_t *target_joints,
+                                          const double *target_poses, int32_t blocks, const mh_options *opts, float *W_out);
+
+/*
  * ---- state integration (MultiBodySystemStateIntegrator.doubleIntegrateFromAcceleration, tools/MultiBodySystemStateIntegrator.java:365-441,
  *      503-575, 710-733): the step downstream of forward dynamics, so that a simulation loop never leaves the device ----
  * One explicit constant-acceleration step of size dt for every joint of every configuration: 1-DoF q' = q + dt qd + dt^2/2 qdd,

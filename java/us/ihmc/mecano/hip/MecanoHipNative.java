@@ -122,6 +122,19 @@ public final class MecanoHipNative
    static final MethodHandle GRAVITY_GRADIENT = handle("mh_gravity_gradient_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
    /** the same in fp32 (float matrices on the device) */
    static final MethodHandle GRAVITY_GRADIENT_F32 = handle("mh_gravity_gradient_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** mh_apparent_inertia_inverse_*: the targets' own 6 x 6 blocks, or the coupled 6K x 6K matrix; at most this many targets per call */
+   static final int APPARENT_BLOCKS_DIAGONAL = 0, APPARENT_BLOCKS_COUPLED = 1;
+   static final int MAX_APPARENT_TARGETS = 16;
+   /**
+    * MultiBodyResponseCalculator.computeRigidBodyApparentSpatialInertiaInverse / applyRigidBodyWrench + getAccelerationChangeProvider for
+    * B configurations and up to 16 target bodies, one launch: (model, B, q, n_targets, target_joints (host int[]), target_poses (host
+    * double[n_targets][12])|NULL, blocks, opts|NULL, W_out), W_out [B][n_targets][6][6] or [B][6 n_targets][6 n_targets] row-major.
+    */
+   static final MethodHandle APPARENT_INERTIA_INVERSE = handle("mh_apparent_inertia_inverse_f64", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
+                                                                                                           JAVA_INT, ADDRESS, ADDRESS));
+   /** the same in fp32 (float q / W_out on the device; the poses stay double) */
+   static final MethodHandle APPARENT_INERTIA_INVERSE_F32 = handle("mh_apparent_inertia_inverse_f32", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
+                                                                                                               JAVA_INT, ADDRESS, ADDRESS));
    /** (model, B, dt, q, qd, qdd, opts, q_out, qd_out, qdd_out|NULL) */
    static final MethodHandle INTEGRATE = handle("mh_integrate_f64", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                            ADDRESS));

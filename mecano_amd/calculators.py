@@ -589,32 +589,35 @@ class MultiBodyResponseCalculator:
     getJointTwistChange = getJointAccelerationChange  # :915-932
 
     # ---- apparent inertias (:288-600): columns = responses to unit disturbances
-    def computeRigidBodyApparentSpatialInertiaInverse(self, target):
-        """:288-330 with inertiaFrame = the target's body-fixed frame: [B, 6, 6], change of the body's spatial acceleration per unit
-        wrench on it (symmetric); ``None`` for a body this calculator does not consider."""
-        k = self._body_pos.get(id(target))
-        if k is None:
+    def _apparent(self, targets, inertiaFrames, coupled):
+        ks = [self._body_pos.get(id(t)) for t in targets]
+        if any(k is None for k in ks):
             return None
-        B = self._batch()
-        saved = (self._wrenches, self._efforts)
-        out = self._zeros(B, 6, 6)
-        for c in range(6):
-            self._clear()
-            w = self._zeros(B, 6)
-            w[:, c] = 1.0
-            self.applyRigidBodyWrench(target, w)
-            self._propagate()
-            if self._provider.body_acc is None:
-                raise ValueError("apparent inertias need every joint to be an effort source")
-            out[:, :, c] = self._provider.body_acc[:, k, :]
-        self._clear()
-        self._wrenches, self._efforts = saved
-        return out
+        self._batch()
+        poses = None
+        if inertiaFrames is not None:
+            ident = np.array([1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0])
+            poses = np.stack([ident if f is None else np.asarray(f, dtype=np.float64).reshape(12) for f in inertiaFrames])
+        return self.model.apparent_inertia_inverse(self._q, ks, poses, coupled, _lib.LAYOUT_AOS)
 
-    def computeRigidBodyApparentLinearInertiaInverse(self, target):
-        """:449-500 with inertiaFrame = the target's body-fixed frame: [B, 3, 3], linear acceleration of the frame origin per unit force"""
-        M = self.computeRigidBodyApparentSpatialInertiaInverse(target)
+    def computeRigidBodyApparentSpatialInertiaInverse(self, target, inertiaFrame=None):
+        """:288-440: [B, 6, 6], change of the spatial acceleration of ``inertiaFrame`` per unit wrench acting at and expressed in it
+        (symmetric); ``None`` for a body this calculator does not consider.  ``inertiaFrame``: a pose of 12 numbers (R row-major, p)
+        relative to the target's body-fixed frame, None = that frame itself.  One launch of mh_apparent_inertia_inverse_*;
+        acceleration-source joints keep a zero change (:1230-1238, 1275-1281)."""
+        W = self._apparent([target], None if inertiaFrame is None else [inertiaFrame], False)
+        return None if W is None else W[:, 0]
+
+    def computeRigidBodyApparentLinearInertiaInverse(self, target, inertiaFrame=None):
+        """:449-500: [B, 3, 3], linear acceleration of the origin of ``inertiaFrame`` per unit force at it"""
+        M = self.computeRigidBodyApparentSpatialInertiaInverse(target, inertiaFrame)
         return None if M is None else M[:, 3:, 3:]
+
+    def computeApparentInertiaInverse(self, targets, inertiaFrames=None):
+        """The coupled inverse apparent inertia of K bodies (applyRigidBodyWrench(a) + getAccelerationChangeProvider().getAccelerationOfBody(b)
+        for every pair, :608-627, 859-862): [B, 6K, 6K], block (b, a) = change of the spatial acceleration of target b's frame per unit
+        wrench on target a's; one launch.  ``inertiaFrames``: one pose (or None) per target; ``None`` if a body is not considered."""
+        return self._apparent(list(targets), inertiaFrames, True)
 
     def computeJointApparentInertiaInverse(self, target):
         """:512-590: [B, dofs, dofs] (1-DoF joints: [B, 1, 1]), change of the joint's accelerations per unit effort"""

@@ -8,6 +8,7 @@
 #include "mh_dfs_kernels.h"
 #include "mh_split_kernels.h"
 #include "mh_gravity_kernels.h"
+#include "mh_response_kernels.h"
 
 #include <dlfcn.h>
 #include <spawn.h>
@@ -264,6 +265,11 @@ struct mh_model
    double *d_sub_mass64 = nullptr;
    float *d_sub_mass32 = nullptr;
    int *d_grav_zero_ofs = nullptr, *d_grav_zero_cols = nullptr;
+   // mh_apparent_inertia_inverse_*: Euler tour of the tree and the slots of the six-column accelerations (mh_response_kernels.h), and
+   // the workspace slots per lane of that kernel: the model's, 36 per body with a child that does not directly follow it, 6 per DoF
+   std::vector<int> resp_info;
+   int *d_resp_info = nullptr;
+   int resp_slots = 0, resp_a_base = 0, resp_u_base = 0;
    Workspace ws;
    // staging buffers of the *_host entry points
    Workspace stage;
@@ -2131,6 +2137,95 @@ mh_status gravity_gradient_impl(mh_model_t model, int64_t B, const T *q, const d
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
+// Inverse apparent inertia of K target bodies (MultiBodyResponseCalculator): run-time-topology kernel, which writes every entry of W --
+// no memset in front of it.  Targets and their frames travel as kernel arguments; which bodies the sweeps visit is decided on the device
+// from the model's Euler tour, so the call uploads nothing and allocates nothing beyond the workspace mh_reserve covers.
+static int response_parts(const mh_model *model, const Launch &L, int n_targets)
+{
+   return (int)std::max<long>(1, std::min<long>(n_targets, (long)model->cu_count * 4 / L.grid));
+}
+template <typename T>
+mh_status apparent_inertia_impl(mh_model_t model, int64_t B, const T *q, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
+                                int32_t blocks, const mh_options *opts_in, T *W_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   if (n_targets < 1 || n_targets > MH_MAX_APPARENT_TARGETS)
+      return fail(MH_ERR_INVALID_ARGUMENT, "n_targets = %d is outside 1 ... %d", n_targets, MH_MAX_APPARENT_TARGETS);
+   if (blocks != MH_APPARENT_BLOCKS_DIAGONAL && blocks != MH_APPARENT_BLOCKS_COUPLED)
+      return fail(MH_ERR_INVALID_ARGUMENT, "unknown blocks value %d", blocks);
+   if (!target_joints)
+      return fail(MH_ERR_INVALID_ARGUMENT, "target_joints is NULL");
+   mh::RespArgs<T> G{};
+   for (int k = 0; k < n_targets; k++)
+   {
+      const int i = target_joints[k];
+      if (i < 0 || i >= model->n)
+         return fail(MH_ERR_INVALID_ARGUMENT, "target %d names joint %d (the model has %d joints)", k, i, model->n);
+      const int e = model->engine_of[i];
+      G.tgt[k] = e;
+      // the target frame in the canonical after-joint frame: (body-fixed -> canonical) o (target frame -> body-fixed)
+      const double *c = &model->consts[(size_t)e * mh::MC_STRIDE];
+      const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+      const double *X = target_poses ? target_poses + 12 * k : ident;
+      double det = X[0] * (X[4] * X[8] - X[5] * X[7]) - X[1] * (X[3] * X[8] - X[5] * X[6]) + X[2] * (X[3] * X[7] - X[4] * X[6]);
+      double worst = std::fabs(det - 1.0);
+      for (int r = 0; r < 3; r++)
+         for (int s = 0; s < 3; s++)
+         {
+            double g = 0.0;
+            for (int t = 0; t < 3; t++)
+               g += X[3 * t + r] * X[3 * t + s];
+            worst = std::max(worst, std::fabs(g - (r == s ? 1.0 : 0.0)));
+         }
+      if (!(worst <= 1.0e-9)) // (a NaN fails too)
+         return fail(MH_ERR_INVALID_ARGUMENT, "target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", k, worst);
+      for (int r = 0; r < 3; r++)
+      {
+         double p = c[mh::MC_PF + r];
+         for (int t = 0; t < 3; t++)
+            p += c[mh::MC_RF + 3 * r + t] * X[9 + t];
+         G.pose[k][9 + r] = (T)p;
+         for (int s = 0; s < 3; s++)
+         {
+            double v = 0.0;
+            for (int t = 0; t < 3; t++)
+               v += c[mh::MC_RF + 3 * r + t] * X[3 * t + s];
+            G.pose[k][3 * r + s] = (T)v;
+         }
+      }
+   }
+   if (B == 0)
+      return MH_OK;
+   if (!q || !W_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL configuration / output pointer");
+   const bool coupled = blocks == MH_APPARENT_BLOCKS_COUPLED;
+   const long wsize = coupled ? 36L * n_targets * n_targets : 36L * n_targets;
+   {
+      const char *q0 = (const char *)q, *w0 = (const char *)W_out;
+      if (q0 < w0 + (size_t)B * wsize * sizeof(T) && w0 < q0 + (size_t)B * model->nq * sizeof(T))
+         return fail(MH_ERR_INVALID_ARGUMENT, "W_out overlaps q");
+   }
+   const Launch L = plan_launch(model, B);
+   const int parts = response_parts(model, L, n_targets);
+   st = ensure_bytes(model->ws, (size_t)model->resp_slots * (size_t)L.lanes * (size_t)parts * sizeof(T));
+   if (st != MH_OK)
+      return st;
+   mh::Args<T> &A = G.a;
+   A = make_args<T>(model, B, opts);
+   A.q = q, A.out = W_out;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = L.lanes;
+   set_strides(G.w_bs, G.w_es, opts.layout == MH_LAYOUT_SOA, B, wsize);
+   G.info = model->d_resp_info;
+   G.slots = model->resp_slots, G.a_base = model->resp_a_base, G.u_base = model->resp_u_base;
+   G.n_targets = n_targets, G.coupled = coupled;
+   hipLaunchKernelGGL((mh::apparent_inertia_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
 template <typename T>
 mh_status integrate_impl(mh_model_t model, int64_t B, double dt, const T *q, const T *qd, const T *qdd, const mh_options *opts_in, T *q_out,
                                 T *qd_out, T *qdd_out)
@@ -2504,6 +2599,42 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
          m->grav_zero_cols.push_back(0);
    }
 
+   // ---- apparent inertia inverses (mh_response_kernels.h): which body lies under which is the topology's
+   {
+      std::vector<std::vector<int>> kids(n);
+      std::vector<int> roots;
+      for (int e = 0; e < n; e++)
+         (P.eparent[e] >= 0 ? kids[P.eparent[e]] : roots).push_back(e);
+      m->resp_info.assign((size_t)n * mh::RI_STRIDE, 0);
+      int clock = 0, n_a = 0;
+      std::vector<std::pair<int, size_t>> stack; // (body, next child)
+      for (int r : roots)
+      {
+         stack.push_back({r, 0});
+         m->resp_info[(size_t)r * mh::RI_STRIDE + mh::RI_TIN] = clock++;
+         while (!stack.empty())
+         {
+            auto &[e, next] = stack.back();
+            if (next < kids[e].size())
+            {
+               const int ch = kids[e][next++];
+               m->resp_info[(size_t)ch * mh::RI_STRIDE + mh::RI_TIN] = clock++;
+               stack.push_back({ch, 0});
+            }
+            else
+            {
+               m->resp_info[(size_t)e * mh::RI_STRIDE + mh::RI_TOUT] = clock++;
+               stack.pop_back();
+            }
+         }
+      }
+      for (int e = 0; e < n; e++)
+         m->resp_info[(size_t)e * mh::RI_STRIDE + mh::RI_SLOT_A] = (m->meta[(size_t)e * mh::MI_STRIDE + mh::MI_FLAGS] & mh::MF_STORE_VA) ? 36 * n_a++ : -1;
+      m->resp_a_base = m->n_slots;
+      m->resp_u_base = m->resp_a_base + 36 * n_a;
+      m->resp_slots = m->resp_u_base + 6 * edofo[n];
+   }
+
    // ---- depth-first kernels: children counts, stack-frame / hand-over offsets, event program (mh_dfs_kernels.h)
    {
       std::vector<int> nch(n, 0), ofs_r(n, 0), ofs_a(n, 0), ofs_p(n, 0);
@@ -2657,6 +2788,8 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
       e = up((void **)&m->d_grav_zero_ofs, m->grav_zero_ofs.data(), m->grav_zero_ofs.size() * sizeof(int));
    if (e == hipSuccess)
       e = up((void **)&m->d_grav_zero_cols, m->grav_zero_cols.data(), m->grav_zero_cols.size() * sizeof(int));
+   if (e == hipSuccess)
+      e = up((void **)&m->d_resp_info, m->resp_info.data(), m->resp_info.size() * sizeof(int));
    if (e != hipSuccess)
    {
       mh_model_destroy(m);
@@ -2824,6 +2957,7 @@ static void release_model(mh_model *m)
    (void)hipFree(m->d_sub_mass32);
    (void)hipFree(m->d_grav_zero_ofs);
    (void)hipFree(m->d_grav_zero_cols);
+   (void)hipFree(m->d_resp_info);
    free_scratch(m);
    if (m->spec.handle)
       dlclose(m->spec.handle);
@@ -3105,6 +3239,12 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       st = ensure_bytes(m->ws, (size_t)m->n_slots * (size_t)L.lanes * regressor_parts(m, L) * sizeof(double));
       if (st != MH_OK)
          return st;
+      // mh_apparent_inertia_inverse_*: its own slots behind the model's, one block per wave, up to one wave per target
+      // (grid * parts is not monotonic in the batch: the bound over every batch up to max_batch)
+      const long resp_waves = std::max<long>(L.grid, std::min<long>((long)MH_MAX_APPARENT_TARGETS * L.grid, (long)m->cu_count * 4));
+      st = ensure_bytes(m->ws, (size_t)m->resp_slots * (size_t)resp_waves * 64 * sizeof(double));
+      if (st != MH_OK)
+         return st;
    }
    // the whole-tree specialised ABA keeps its hand-over store in the same workspace (more slots than the run-time-topology plan of a
    // chain), and big AoS batches of wide matrices go through transposed scratch copies: reserve both, so that compute calls allocate nothing
@@ -3226,6 +3366,16 @@ mh_status mh_gravity_gradient_f32(mh_model_t model, int64_t B, const float *q, c
                                   float *tau_out, float *grad_out)
 {
    return gravity_gradient_impl<float>(model, B, q, gravity, f_ext, opts, tau_out, grad_out);
+}
+mh_status mh_apparent_inertia_inverse_f64(mh_model_t model, int64_t B, const double *q, int32_t n_targets, const int32_t *target_joints,
+                                          const double *target_poses, int32_t blocks, const mh_options *opts, double *W_out)
+{
+   return apparent_inertia_impl<double>(model, B, q, n_targets, target_joints, target_poses, blocks, opts, W_out);
+}
+mh_status mh_apparent_inertia_inverse_f32(mh_model_t model, int64_t B, const float *q, int32_t n_targets, const int32_t *target_joints,
+                                          const double *target_poses, int32_t blocks, const mh_options *opts, float *W_out)
+{
+   return apparent_inertia_impl<float>(model, B, q, n_targets, target_joints, target_poses, blocks, opts, W_out);
 }
 mh_status mh_integrate_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *qdd, const mh_options *opts,
                            double *q_out, double *qd_out, double *qdd_out)

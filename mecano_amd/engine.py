@@ -550,6 +550,43 @@ class HipModel:
                                                                      None if grad is None else grad.data_ptr()))
         return tau, grad
 
+    def apparent_inertia_inverse(self, q, targets, poses=None, coupled=False, layout=_lib.LAYOUT_AOS, out=None):
+        """Inverse apparent inertia of the successor bodies of the joints ``targets`` (positions in the joint list, 1 to 16, duplicates
+        allowed): how target b accelerates per unit wrench on target a (MultiBodyResponseCalculator.
+        computeRigidBodyApparentSpatialInertiaInverse, applyRigidBodyWrench + getAccelerationChangeProvider,
+        MultiBodyResponseCalculator.java:288-440, 608-627, 859-862), one launch.  ``poses`` [K, 12] (R row-major, p) or None: the frame of
+        every target relative to its body-fixed frame, in which the wrench acts and the response is expressed.  ``coupled=False``:
+        [B, K, 6, 6], the targets' own blocks; ``coupled=True``: [B, 6K, 6K], block (b, a) = response of b to a wrench on a.  SoA:
+        [K * 36, B] / [(6K)^2, B].  The model's joint source modes hold.  numpy in -> numpy out (fp64); device tensors (fp64 / fp32)
+        stay on the device, and ``out`` is a device tensor to write into."""
+        import torch
+        if not self._is_torch(q):
+            W = self.apparent_inertia_inverse(torch.tensor(_np(q, np.float64), device="cuda"), targets, poses, coupled, layout)
+            return W.cpu().numpy()
+        B, dt, sfx, stream = self._device_inputs([q], layout)
+        tgt = np.ascontiguousarray(np.asarray(targets, dtype=np.int32).reshape(-1))
+        K = int(tgt.shape[0])
+        if poses is not None:
+            poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1))
+            if poses.shape[0] != 12 * K:
+                raise _lib.MecanoHipError(2, f"poses must hold 12 numbers per target ({12 * K}), got {poses.shape[0]}")
+        size = 36 * K * K if coupled else 36 * K
+        aos_shape = (B, 6 * K, 6 * K) if coupled else (B, K, 6, 6)
+        shape = aos_shape if layout == _lib.LAYOUT_AOS else (size, B)
+        if out is None:
+            out = torch.empty(shape, dtype=dt, device=q.device)
+        else:
+            if not self._is_torch(out) or not out.is_cuda or out.dtype != dt or not out.is_contiguous():
+                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+            if tuple(out.shape) != shape:
+                raise _lib.MecanoHipError(2, f"W output has shape {tuple(out.shape)}, expected {shape}")
+        opts = self._options(layout, stream=stream)
+        _lib.check(getattr(_lib.load(), f"mh_apparent_inertia_inverse_{sfx}")(
+            self._h, B, q.data_ptr(), K, tgt.ctypes.data, None if poses is None else poses.ctypes.data,
+            _lib.APPARENT_BLOCKS_COUPLED if coupled else _lib.APPARENT_BLOCKS_DIAGONAL,
+            ctypes.byref(opts), out.data_ptr()))
+        return out
+
     def regressor(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), layout=_lib.LAYOUT_AOS, consider_coriolis=True, consider_accelerations=True,
                   first_moment_columns=False):
         """Joint torque regressor (JointTorqueRegressorCalculator.compute, JointTorqueRegressorCalculator.java:173-190): Y [B, nv, 10 n_joints]
