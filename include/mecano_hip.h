@@ -474,6 +474,32 @@ mh_status mh_apparent_inertia_inverse_f32(mh_model_t model, int64_t B, const flo
                                           const double *target_poses, int32_t blocks, const mh_options *opts, float *W_out);
 
 /*
+ * ---- inverse of the joint-space inertia matrix (columns of H^-1: MultiBodyResponseCalculator.applyJointWrench and the recursion behind
+ *      it, algorithms/MultiBodyResponseCalculator.java:685-735, 1206-1338; a joint's diagonal block is
+ *      computeJointApparentInertiaInverse, :512-590) ----
+ * H^-1 of every configuration, or some of its columns, from the articulated-body recursion: H is not formed and nothing dense is
+ * factorised.  It is d qdd / d tau of the forward dynamics.
+ * columns (HOST) = NULL: all nv columns, n_columns is ignored; Hinv_out [B][nv][nv] row-major (MH_LAYOUT_SOA: [nv * nv][B]), laid out and
+ * indexed like H_out of mh_crba_* (the model's DoF index map).
+ * columns given: 1 ... MH_MAX_INVERSE_COLUMNS DoF indices in that same index space, duplicates allowed; Hinv_out [B][nv][n_columns]
+ * (MH_LAYOUT_SOA: [nv * n_columns][B]), column k = H^-1 e_columns[k].  A listed column carries the bits of that column of the full call.
+ * Column c is what mh_aba_* returns for qd = 0, gravity = 0, no external wrenches and tau = e_c.  The model's joint source modes hold as
+ * in mh_aba_locked_* with qdd_in = 0: rows and columns of the DoFs of an MH_ACCELERATION_SOURCE joint are zero, the rest is the inverse of
+ * H restricted to the DoFs of the effort-source joints.  Rows and columns of DoF indices no joint owns are zero.  H^-1 is symmetric up
+ * to rounding (every entry is computed, none mirrored).
+ * Every entry of Hinv_out is written (no memset needed), nothing outside it.  Hinv_out must not overlap q.  MH_ERR_INVALID_ARGUMENT: NULL
+ * q / Hinv_out, with columns given n_columns outside 1 ... MH_MAX_INVERSE_COLUMNS or an index outside 0 ... nv - 1, Hinv_out overlapping
+ * q.  B = 0 returns MH_OK and touches nothing, as does a model with nv = 0.  opts->consider_coriolis, consider_accelerations and the root
+ * acceleration play no part.  Device pointers, asynchronous on opts->stream; run-time-topology kernel for every model; the columns travel
+ * as kernel arguments: nothing is uploaded, and after mh_reserve the call allocates nothing.
+ */
+#define MH_MAX_INVERSE_COLUMNS 64
+mh_status mh_mass_matrix_inverse_f64(mh_model_t model, int64_t B, const double *q, int32_t n_columns, const int32_t *columns,
+                                     const mh_options *opts, double *Hinv_out);
+mh_status mh_mass_matrix_inverse_f32(mh_model_t model, int64_t B, const float *q, int32_t n_columns, const int32_t *columns,
+                                     const mh_options *opts, float *Hinv_out);
+
+/*
  * ---- state integration (MultiBodySystemStateIntegrator.doubleIntegrateFromAcceleration, tools/MultiBodySystemStateIntegrator.java:365-441,
  *      503-575, 710-733): the step downstream of forward dynamics, so that a simulation loop never leaves the device ----
  * One explicit constant-acceleration step of size dt for every joint of every configuration: 1-DoF q' = q + dt qd + dt^2/2 qdd,

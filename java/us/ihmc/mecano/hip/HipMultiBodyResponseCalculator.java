@@ -9,7 +9,9 @@ import us.ihmc.mecano.multiBodySystem.interfaces.JointReadOnly;
 import us.ihmc.mecano.multiBodySystem.interfaces.MultiBodySystemReadOnly;
 import us.ihmc.mecano.multiBodySystem.interfaces.RigidBodyReadOnly;
 
+import static java.lang.foreign.ValueLayout.ADDRESS;
 import static java.lang.foreign.ValueLayout.JAVA_DOUBLE;
+import static java.lang.foreign.ValueLayout.JAVA_INT;
 
 /**
  * Batched drop-in for MultiBodyResponseCalculator (java:120-140, 224-250, 288-935): the change in joint and body accelerations (for
@@ -189,6 +191,68 @@ public class HipMultiBodyResponseCalculator implements AutoCloseable
       testWrenches = savedWrenches;
       testEfforts = savedEfforts;
       upToDate = false;
+      return out;
+   }
+
+   /**
+    * computeJointApparentInertiaInverse(target, ...) (java:512-590): B x (dofs * dofs), row b = the dofs x dofs matrix (row-major) that maps
+    * an effort at the joint to the change of its accelerations -- the joint's diagonal block of the inverse of the mass matrix; zeros for an
+    * acceleration-source joint.  One launch of mh_mass_matrix_inverse_f64 for the joint's columns; null for a joint that is not considered.
+    * The disturbances applied so far are kept.
+    */
+   public DMatrixRMaj computeJointApparentInertiaInverse(JointReadOnly target)
+   {
+      if (model.indexOf(target) < 0)
+         return null;
+      int[] rows = forwardDynamicsCalculator.getInput().getJointMatrixIndexProvider().getJointDoFIndices(target);
+      DMatrixRMaj columns = inverseColumns(rows);
+      int B = batch.batchSize, dofs = rows.length;
+      DMatrixRMaj out = new DMatrixRMaj(B, dofs * dofs);
+      for (int b = 0; b < B; b++)
+         for (int r = 0; r < dofs; r++)
+            for (int c = 0; c < dofs; c++)
+               out.set(b, r * dofs + c, columns.get(b, rows[r] * dofs + c));
+      return out;
+   }
+
+   /**
+    * The inverse of the joint-space inertia matrix: B x (nv * nv), row b = H^-1 of configuration b (row-major, indexed like the mass
+    * matrix).  The reference has no such method: it is applyJointWrench with a unit effort at one DoF (java:685-735), the propagation
+    * (java:1206-1338) and the joint acceleration changes (java:887-904), for every DoF in turn.  One launch.
+    */
+   public DMatrixRMaj computeJointSpaceInertiaInverse()
+   {
+      return inverseColumns(null);
+   }
+
+   /** B x (nv * n): the listed columns of the inverse of the mass matrix (null: all nv), one launch of mh_mass_matrix_inverse_f64 */
+   private DMatrixRMaj inverseColumns(int[] columns)
+   {
+      int B = batch.batchSize, n = columns == null ? model.nv : columns.length;
+      DMatrixRMaj out = new DMatrixRMaj(B, model.nv * n);
+      if (out.getNumElements() == 0)
+         return out;
+      try (Arena arena = Arena.ofConfined())
+      {
+         MemorySegment result = arena.allocate(ADDRESS);
+         MecanoHipNative.invoke(() -> (int) MecanoHipNative.DEVICE_ALLOC.invokeExact((long) out.getNumElements() * Double.BYTES, result));
+         MemorySegment device = result.get(ADDRESS, 0);
+         try
+         {
+            MemorySegment list = columns == null ? MemorySegment.NULL : arena.allocateFrom(JAVA_INT, columns);
+            MemorySegment options = MecanoHipNative.options(arena, true, true);
+            MecanoHipNative.invoke(() -> (int) MecanoHipNative.MASS_MATRIX_INVERSE.invokeExact(model.handle, (long) B, batch.q, n, list, options, device));
+            long count = out.getNumElements();
+            MemorySegment host = arena.allocate(JAVA_DOUBLE, count);
+            MecanoHipNative.invoke(() -> (int) MecanoHipNative.COPY_TO_HOST.invokeExact(host, device, count * Double.BYTES, MemorySegment.NULL));
+            MecanoHipNative.invoke(() -> (int) MecanoHipNative.STREAM_SYNCHRONIZE.invokeExact(MemorySegment.NULL));
+            MemorySegment.copy(host, JAVA_DOUBLE, 0, out.data, 0, (int) count);
+         }
+         finally
+         {
+            MecanoHipNative.invoke(() -> (int) MecanoHipNative.DEVICE_FREE.invokeExact(device));
+         }
+      }
       return out;
    }
 

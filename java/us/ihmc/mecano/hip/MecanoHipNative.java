@@ -135,6 +135,16 @@ public final class MecanoHipNative
    /** the same in fp32 (float q / W_out on the device; the poses stay double) */
    static final MethodHandle APPARENT_INERTIA_INVERSE_F32 = handle("mh_apparent_inertia_inverse_f32", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
                                                                                                                JAVA_INT, ADDRESS, ADDRESS));
+   /** mh_mass_matrix_inverse_*: at most this many listed columns per call */
+   static final int MAX_INVERSE_COLUMNS = 64;
+   /**
+    * The inverse of the joint-space inertia matrix, or some of its columns, for B configurations, one launch: (model, B, q, n_columns,
+    * columns (host int[])|NULL = all nv, opts|NULL, Hinv_out), Hinv_out [B][nv][nv] or [B][nv][n_columns] row-major, indexed like the mass
+    * matrix.  MultiBodyResponseCalculator.computeJointApparentInertiaInverse is the joint's diagonal block.
+    */
+   static final MethodHandle MASS_MATRIX_INVERSE = handle("mh_mass_matrix_inverse_f64", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 (float q / Hinv_out on the device) */
+   static final MethodHandle MASS_MATRIX_INVERSE_F32 = handle("mh_mass_matrix_inverse_f32", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
    /** (model, B, dt, q, qd, qdd, opts, q_out, qd_out, qdd_out|NULL) */
    static final MethodHandle INTEGRATE = handle("mh_integrate_f64", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                            ADDRESS));

@@ -620,22 +620,23 @@ class MultiBodyResponseCalculator:
         return self._apparent(list(targets), inertiaFrames, True)
 
     def computeJointApparentInertiaInverse(self, target):
-        """:512-590: [B, dofs, dofs] (1-DoF joints: [B, 1, 1]), change of the joint's accelerations per unit effort"""
+        """:512-590: [B, dofs, dofs] (1-DoF joints: [B, 1, 1]), change of the joint's accelerations per unit effort: the joint's diagonal
+        block of H^-1.  One launch of mh_mass_matrix_inverse_* for the columns of the joint's DoFs, then its rows; an
+        acceleration-source joint gets zeros (:1230-1238, 1275-1281).  Efforts and wrenches applied before stay as they are."""
         if self._joint_pos.get(id(target)) is None:
             return None
-        B = self._batch()
+        self._batch()
         rows = list(self.input.getJointMatrixIndexProvider().getJointDoFIndices(target))
-        saved = (self._wrenches, self._efforts)
-        out = self._zeros(B, len(rows), len(rows))
-        for c in range(len(rows)):
-            self._clear()
-            e = self._zeros(B, len(rows))
-            e[:, c] = 1.0
-            self.applyJointWrench(target, e)
-            out[:, :, c] = self._propagate()[:, rows]
-        self._clear()
-        self._wrenches, self._efforts = saved
-        return out
+        return self.model.mass_matrix_inverse(self._q, rows, _lib.LAYOUT_AOS)[:, rows]
+
+    def computeJointSpaceInertiaInverse(self):
+        """[B, nv, nv]: H^-1, the change of every joint acceleration per unit effort at every DoF, indexed like the mass matrix; one
+        launch of mh_mass_matrix_inverse_*.  The reference has no such method: it is applyJointWrench with a unit effort at one DoF
+        (:685-735) followed by propagateImpulse's climb and descent (:1206-1252, 1301-1338) and getJointAccelerationChange of every joint
+        (:887-904), for every DoF in turn -- computeJointApparentInertiaInverse (:512-590) without the restriction to the joint's own
+        rows.  Rows and columns of acceleration-source joints are zero."""
+        self._batch()
+        return self.model.mass_matrix_inverse(self._q, None, _lib.LAYOUT_AOS)
 
 
 class CompositeRigidBodyMassMatrixCalculator(_Base):

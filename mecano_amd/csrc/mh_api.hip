@@ -9,6 +9,7 @@
 #include "mh_split_kernels.h"
 #include "mh_gravity_kernels.h"
 #include "mh_response_kernels.h"
+#include "mh_minv_kernels.h"
 
 #include <dlfcn.h>
 #include <spawn.h>
@@ -270,6 +271,10 @@ struct mh_model
    std::vector<int> resp_info;
    int *d_resp_info = nullptr;
    int resp_slots = 0, resp_a_base = 0, resp_u_base = 0;
+   // mh_mass_matrix_inverse_*: per DoF index of the model's index map, 8 * engine index of the joint that owns it + its place among the
+   // joint's DoFs (-1: no joint); the kernel (mh_minv_kernels.h) works in the workspace slots of the apparent-inertia kernel
+   std::vector<int> minv_owner;
+   int *d_minv_owner = nullptr;
    Workspace ws;
    // staging buffers of the *_host entry points
    Workspace stage;
@@ -2226,6 +2231,61 @@ mh_status apparent_inertia_impl(mh_model_t model, int64_t B, const T *q, int32_t
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
+// Inverse of the joint-space inertia matrix, all columns or a list of them: run-time-topology kernel, which writes every entry of its
+// output -- no memset in front of it.  The listed columns travel as kernel arguments (resolved here to joint and place); the call
+// uploads nothing and allocates nothing beyond the workspace mh_reserve covers.
+static int minv_groups(int n_columns) { return (n_columns + mh::MINV_GROUP - 1) / mh::MINV_GROUP; }
+template <typename T>
+mh_status mass_matrix_inverse_impl(mh_model_t model, int64_t B, const T *q, int32_t n_columns, const int32_t *columns, const mh_options *opts_in,
+                                   T *Hinv_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   mh::MinvArgs<T> G{};
+   if (columns)
+   {
+      if (n_columns < 1 || n_columns > MH_MAX_INVERSE_COLUMNS)
+         return fail(MH_ERR_INVALID_ARGUMENT, "n_columns = %d is outside 1 ... %d", n_columns, MH_MAX_INVERSE_COLUMNS);
+      for (int k = 0; k < n_columns; k++)
+      {
+         if (columns[k] < 0 || columns[k] >= model->nv)
+            return fail(MH_ERR_INVALID_ARGUMENT, "column %d names DoF index %d (nv = %d)", k, columns[k], model->nv);
+         G.col[k] = model->minv_owner[columns[k]];
+      }
+   }
+   else
+      n_columns = model->nv;
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!q || !Hinv_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL configuration / output pointer");
+   const long hsize = (long)model->nv * n_columns;
+   {
+      const char *q0 = (const char *)q, *h0 = (const char *)Hinv_out;
+      if (q0 < h0 + (size_t)B * hsize * sizeof(T) && h0 < q0 + (size_t)B * model->nq * sizeof(T))
+         return fail(MH_ERR_INVALID_ARGUMENT, "Hinv_out overlaps q");
+   }
+   const Launch L = plan_launch(model, B);
+   const int parts = response_parts(model, L, minv_groups(n_columns));
+   st = ensure_bytes(model->ws, (size_t)model->resp_slots * (size_t)L.lanes * (size_t)parts * sizeof(T));
+   if (st != MH_OK)
+      return st;
+   mh::Args<T> &A = G.a;
+   A = make_args<T>(model, B, opts);
+   A.q = q, A.out = Hinv_out;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = L.lanes;
+   set_strides(G.h_bs, G.h_es, opts.layout == MH_LAYOUT_SOA, B, hsize);
+   G.info = model->d_resp_info, G.owner = model->d_minv_owner;
+   G.zero_ofs = model->d_grav_zero_ofs, G.zero_cols = model->d_grav_zero_cols;
+   G.slots = model->resp_slots, G.a_base = model->resp_a_base, G.u_base = model->resp_u_base;
+   G.n_columns = n_columns, G.listed = columns != nullptr;
+   hipLaunchKernelGGL((mh::mass_matrix_inverse_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
 template <typename T>
 mh_status integrate_impl(mh_model_t model, int64_t B, double dt, const T *q, const T *qd, const T *qdd, const mh_options *opts_in, T *q_out,
                                 T *qd_out, T *qdd_out)
@@ -2634,6 +2694,11 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
       m->resp_u_base = m->resp_a_base + 36 * n_a;
       m->resp_slots = m->resp_u_base + 6 * edofo[n];
    }
+   // ---- inverse of the joint-space inertia matrix (mh_minv_kernels.h): which joint owns which DoF index
+   m->minv_owner.assign((size_t)std::max(1, d->nv), -1);
+   for (int e = 0; e < n; e++)
+      for (int k = edofo[e]; k < edofo[e + 1]; k++)
+         m->minv_owner[m->dof_map[k]] = 8 * e + (k - edofo[e]);
 
    // ---- depth-first kernels: children counts, stack-frame / hand-over offsets, event program (mh_dfs_kernels.h)
    {
@@ -2790,6 +2855,8 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
       e = up((void **)&m->d_grav_zero_cols, m->grav_zero_cols.data(), m->grav_zero_cols.size() * sizeof(int));
    if (e == hipSuccess)
       e = up((void **)&m->d_resp_info, m->resp_info.data(), m->resp_info.size() * sizeof(int));
+   if (e == hipSuccess)
+      e = up((void **)&m->d_minv_owner, m->minv_owner.data(), m->minv_owner.size() * sizeof(int));
    if (e != hipSuccess)
    {
       mh_model_destroy(m);
@@ -2958,6 +3025,7 @@ static void release_model(mh_model *m)
    (void)hipFree(m->d_grav_zero_ofs);
    (void)hipFree(m->d_grav_zero_cols);
    (void)hipFree(m->d_resp_info);
+   (void)hipFree(m->d_minv_owner);
    free_scratch(m);
    if (m->spec.handle)
       dlclose(m->spec.handle);
@@ -3240,8 +3308,10 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       if (st != MH_OK)
          return st;
       // mh_apparent_inertia_inverse_*: its own slots behind the model's, one block per wave, up to one wave per target
-      // (grid * parts is not monotonic in the batch: the bound over every batch up to max_batch)
-      const long resp_waves = std::max<long>(L.grid, std::min<long>((long)MH_MAX_APPARENT_TARGETS * L.grid, (long)m->cu_count * 4));
+      // (grid * parts is not monotonic in the batch: the bound over every batch up to max_batch); mh_mass_matrix_inverse_* works in
+      // the same slots with up to one wave per group of six columns
+      const long resp_parts = std::max<long>(MH_MAX_APPARENT_TARGETS, minv_groups(std::max<int>(m->nv, MH_MAX_INVERSE_COLUMNS)));
+      const long resp_waves = std::max<long>(L.grid, std::min<long>(resp_parts * L.grid, (long)m->cu_count * 4));
       st = ensure_bytes(m->ws, (size_t)m->resp_slots * (size_t)resp_waves * 64 * sizeof(double));
       if (st != MH_OK)
          return st;
@@ -3376,6 +3446,16 @@ mh_status mh_apparent_inertia_inverse_f32(mh_model_t model, int64_t B, const flo
                                           const double *target_poses, int32_t blocks, const mh_options *opts, float *W_out)
 {
    return apparent_inertia_impl<float>(model, B, q, n_targets, target_joints, target_poses, blocks, opts, W_out);
+}
+mh_status mh_mass_matrix_inverse_f64(mh_model_t model, int64_t B, const double *q, int32_t n_columns, const int32_t *columns,
+                                     const mh_options *opts, double *Hinv_out)
+{
+   return mass_matrix_inverse_impl<double>(model, B, q, n_columns, columns, opts, Hinv_out);
+}
+mh_status mh_mass_matrix_inverse_f32(mh_model_t model, int64_t B, const float *q, int32_t n_columns, const int32_t *columns,
+                                     const mh_options *opts, float *Hinv_out)
+{
+   return mass_matrix_inverse_impl<float>(model, B, q, n_columns, columns, opts, Hinv_out);
 }
 mh_status mh_integrate_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *qdd, const mh_options *opts,
                            double *q_out, double *qd_out, double *qdd_out)

@@ -587,6 +587,32 @@ class HipModel:
             ctypes.byref(opts), out.data_ptr()))
         return out
 
+    def mass_matrix_inverse(self, q, columns=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Inverse of the joint-space inertia matrix, H^-1 = d qdd / d tau, from the articulated-body recursion in one launch
+        (MultiBodyResponseCalculator.applyJointWrench and its recursion, MultiBodyResponseCalculator.java:685-735, 1206-1338; H is not
+        formed).  ``columns=None``: [B, nv, nv], indexed like ``crba``'s H.  ``columns``: 1 to 64 DoF indices of that index space,
+        duplicates allowed: [B, nv, K], column k = H^-1 e_columns[k], with the bits of that column of the full call.  SoA: [nv * nv, B] /
+        [nv * K, B].  The model's joint source modes hold: rows and columns of acceleration-source joints are zero.  numpy in -> numpy
+        out (fp64); device tensors (fp64 / fp32) stay on the device, and ``out`` is a device tensor to write into."""
+        import torch
+        if not self._is_torch(q):
+            return self.mass_matrix_inverse(torch.tensor(_np(q, np.float64), device="cuda"), columns, layout).cpu().numpy()
+        B, dt, sfx, stream = self._device_inputs([q], layout)
+        cols = None if columns is None else np.ascontiguousarray(np.asarray(columns, dtype=np.int32).reshape(-1))
+        K = self.nv if cols is None else int(cols.shape[0])
+        shape = (B, self.nv, K) if layout == _lib.LAYOUT_AOS else (self.nv * K, B)
+        if out is None:
+            out = torch.empty(shape, dtype=dt, device=q.device)
+        else:
+            if not self._is_torch(out) or not out.is_cuda or out.dtype != dt or not out.is_contiguous():
+                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+            if tuple(out.shape) != shape:
+                raise _lib.MecanoHipError(2, f"Hinv output has shape {tuple(out.shape)}, expected {shape}")
+        opts = self._options(layout, stream=stream)
+        _lib.check(getattr(_lib.load(), f"mh_mass_matrix_inverse_{sfx}")(
+            self._h, B, q.data_ptr(), K, None if cols is None else cols.ctypes.data, ctypes.byref(opts), out.data_ptr()))
+        return out
+
     def regressor(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), layout=_lib.LAYOUT_AOS, consider_coriolis=True, consider_accelerations=True,
                   first_moment_columns=False):
         """Joint torque regressor (JointTorqueRegressorCalculator.compute, JointTorqueRegressorCalculator.java:173-190): Y [B, nv, 10 n_joints]

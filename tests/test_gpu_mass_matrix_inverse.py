@@ -1,0 +1,381 @@
+"""mh_mass_matrix_inverse_f64 / _f32 on the device against the CPU checker (tests/mass_matrix_inverse_check.py, pinned by
+tests/test_mass_matrix_inverse_cpu.py), through the C-ABI (HipModel.mass_matrix_inverse is the ctypes call) and the calculator mirror."""
+import ctypes
+
+import numpy as np
+import pytest
+
+import apparent_inertia_check as ac
+import mass_matrix_inverse_check as mc
+from helpers import DistinctRows, check_cover, close, f32_aba_forward_factor, group_cover, poisoned, record_parity
+from test_apparent_inertia_cpu import CASES, WELL_CONDITIONED, make_case, states, system_of
+
+pytestmark = pytest.mark.gpu
+
+AOS, SOA = 0, 1
+INVALID = 1  # MH_ERR_INVALID_ARGUMENT
+
+
+@pytest.fixture(scope="module")
+def torch_cuda(hip_lib):
+    import torch
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    return torch
+
+
+def dev(torch, x, dtype=None):
+    return torch.tensor(np.ascontiguousarray(x), device="cuda", dtype=dtype or torch.float64)
+
+
+def model_of(desc, locked):
+    from mecano_amd.engine import HipModel
+    hm = HipModel(desc)
+    if locked is not None:
+        hm.set_joint_source_modes(locked)
+    return hm
+
+
+def run(torch, hm, q, columns, layout, dtype=None):
+    """Device call on a host array laid out as the call wants it; returns AoS-shaped fp64 numpy [B, nv, K]."""
+    dq = dev(torch, q, dtype)
+    if layout == SOA:
+        dq = dq.t().contiguous()
+    Hinv = hm.mass_matrix_inverse(dq, columns, layout)
+    torch.cuda.synchronize()
+    B, K = q.shape[0], hm.nv if columns is None else len(columns)
+    if layout == SOA:
+        Hinv = Hinv.t()
+    return Hinv.cpu().numpy().astype(np.float64).reshape(B, hm.nv, K)
+
+
+@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("layout", [AOS, SOA])
+def test_fp64_matches_checker(torch_cuda, case, layout):
+    """Every family, both layouts, the full matrix and a column list (a strict subset of a multi-DoF joint's DoFs, a duplicate); 70
+    configurations: one full group of 64 and a ragged one, the column groups split over several waves per group of configurations."""
+    from oracle.cpu_oracle import OracleModel
+    sys_, desc, locked = make_case(case)
+    hm, om, B = model_of(desc, locked), OracleModel(desc), 70
+    q = states(sys_, B)
+    bounds = ac.bound_of(om, q, desc.n_joints, case in WELL_CONDITIONED)
+    full = mc.mass_matrix_inverse(om, q, None, locked)
+    cols = mc.column_list(desc)
+    ac.close_rows(run(torch_cuda, hm, q, None, layout), full, bounds, label=f"{case} full")
+    ac.close_rows(run(torch_cuda, hm, q, cols, layout), full[:, :, cols], bounds, label=f"{case} columns")
+    if locked is not None:
+        held, _ = mc.locked_dofs(desc, locked)
+        got = run(torch_cuda, hm, q, None, layout)
+        assert held and not got[:, held, :].any() and not got[:, :, held].any()
+
+
+@pytest.mark.parametrize("case", ["arm7", "humanoid30", "tree128"])
+def test_fp32_matches_fp64_checker(torch_cuda, case):
+    """fp32 against the fp64 checker on the fp32-rounded configurations, per configuration within f32_aba_forward_factor(n) cond_inf(H)
+    2^-24 max(1, |ref|_inf): the bound the apparent-inertia tests fixed for the same recursion.  No configuration is left out, whatever
+    its cond_inf(H); achieved / bound is recorded."""
+    from oracle.cpu_oracle import OracleModel
+    torch = torch_cuda
+    sys_, desc, _ = make_case(case)
+    hm, om, B = model_of(desc, None), OracleModel(desc), 70
+    q = states(sys_, B).astype(np.float32)
+    q64 = q.astype(np.float64)
+    conds = ac.mass_matrix_conds(om, q64)
+    factor = f32_aba_forward_factor(desc.n_joints)
+    ref = mc.mass_matrix_inverse(om, q64)
+    cols = mc.column_list(desc)
+    scale = np.maximum(1.0, np.abs(ref).reshape(B, -1).max(axis=1))
+    for layout in (AOS, SOA):
+        for what, columns, r in (("full", None, ref), ("columns", cols, ref[:, :, cols])):
+            Hinv = run(torch, hm, q, columns, layout, torch.float32)
+            assert not np.isnan(Hinv).any()
+            rel = np.abs(Hinv - r).reshape(B, -1).max(axis=1) / scale
+            ratio = float((rel / (conds * 2.0 ** -24)).max())
+            print(f"{case} fp32 {what} layout {layout}: err / (cond u) = {ratio:.3e}, factor {factor:.3e}, achieved / bound = {ratio / factor:.3e}, "
+                  f"largest cond_inf(H) u = {conds.max() * 2.0 ** -24:.3e}")
+            record_parity(ratio, factor, f"fp32 {case} {what} layout {layout} err / (cond_inf(H) u)")
+            assert ratio <= factor
+
+
+@pytest.mark.parametrize("case", ["humanoid30", "mixed_tree", "locked2"])
+def test_listed_columns_carry_the_bits_of_the_full_call(torch_cuda, case):
+    """Whatever its place in the list and its companions, fp64 and fp32, both layouts; and the matrix is symmetric to the bound (every
+    entry is computed, none mirrored)."""
+    from oracle.cpu_oracle import OracleModel
+    torch = torch_cuda
+    sys_, desc, locked = make_case(case)
+    hm, om, B = model_of(desc, locked), OracleModel(desc), 200
+    q = states(sys_, B)
+    cols = mc.column_list(desc)
+    lists = (cols, cols[::-1], [cols[0]], [int(c) for c in np.random.default_rng(3).integers(0, desc.nv, 64)])
+    for dtype in (torch.float64, torch.float32):
+        for layout in (AOS, SOA):
+            full = run(torch, hm, q, None, layout, dtype)
+            for columns in lists:
+                assert np.array_equal(run(torch, hm, q, columns, layout, dtype), full[:, :, columns])
+    full = run(torch, hm, q, None, AOS)
+    ac.close_rows(full, full.transpose(0, 2, 1), ac.bound_of(om, q, desc.n_joints, case in WELL_CONDITIONED), label=f"{case} symmetry")
+
+
+def test_custom_index_provider_and_listing_order(torch_cuda):
+    """Rows and columns follow the model's DoF index map; a model listed in another joint order gives the same matrix."""
+    from mecano_amd import random_tools as rt
+    from mecano_amd.multibody import ModelDesc
+    from oracle.cpu_oracle import OracleModel
+    torch = torch_cuda
+    rng = np.random.default_rng(31)
+    sys_ = system_of(rt.nextJointTree(rng, 12, ("revolute", "prismatic")))
+    d = sys_.toModelDesc()
+    n, B = d.n_joints, 70
+    q = states(sys_, B)
+    om = OracleModel(d)
+    bounds = ac.bound_of(om, q, n, False)
+    ref = mc.mass_matrix_inverse(om, q)
+    base = run(torch, model_of(d, None), q, None, AOS)
+    ac.close_rows(base, ref, bounds, label="default map")
+    # joint k now owns matrix row perm[k] (and configuration entry perm[k])
+    perm = rng.permutation(d.nv).astype(np.int32)
+    d1 = sys_.toModelDesc()
+    d1.dof_indices, d1.cfg_indices = perm.copy(), perm.copy()
+    q1 = np.zeros_like(q)
+    q1[:, perm] = q
+    got = run(torch, model_of(d1, None), q1, None, AOS)
+    assert np.array_equal(got[np.ix_(range(B), perm, perm)], base)
+    ac.close_rows(got, mc.mass_matrix_inverse(OracleModel(d1), q1), bounds, label="permuted map")
+    cols = [int(perm[3]), int(perm[0]), int(perm[3])]
+    assert np.array_equal(run(torch, model_of(d1, None), q1, cols, SOA), got[:, :, cols])
+    # another listing order of the joints, same rows
+    order = rng.permutation(n)
+    inv = np.argsort(order)
+    r = lambda a, w: np.asarray(a).reshape(n, w)[order].reshape(-1)
+    parent = np.array([(-1 if d.parent[o] < 0 else inv[d.parent[o]]) for o in order], dtype=np.int32)
+    d2 = ModelDesc(n, d.nq, d.nv, parent, np.asarray(d.joint_type)[order], r(d.axis, 3), r(d.X_before, 12), r(d.X_com, 12), r(d.inertia_J, 9),
+                   np.asarray(d.inertia_mass)[order], r(d.inertia_com, 3), np.asarray(d.dof_indices)[order], np.asarray(d.cfg_indices)[order])
+    ac.close_rows(run(torch, model_of(d2, None), q, None, AOS), ref, bounds, label="another listing order")
+
+
+def test_joint_source_modes_set_after_creation_and_back(torch_cuda):
+    from oracle.cpu_oracle import OracleModel
+    torch = torch_cuda
+    sys_, desc, locked = make_case("locked2")
+    hm, om, B = model_of(desc, None), OracleModel(desc), 70
+    q = states(sys_, B)
+    bounds = ac.bound_of(om, q, desc.n_joints, True)
+    first = run(torch, hm, q, None, AOS)
+    ac.close_rows(first, mc.mass_matrix_inverse(om, q), bounds, label="all effort sources")
+    hm.set_joint_source_modes(locked)
+    got = run(torch, hm, q, None, AOS)
+    ac.close_rows(got, mc.mass_matrix_inverse(om, q, None, locked), bounds, label="two acceleration sources")
+    assert np.abs(got - first).max() > 1.0e-3
+    hm.set_joint_source_modes(np.zeros(desc.n_joints, dtype=np.int32))
+    assert np.array_equal(run(torch, hm, q, None, AOS), first)
+
+
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("listed", [False, True])
+def test_device_filling_batch_covers_every_row_group(torch_cuda, layout, listed):
+    """More than twice the waves the grid holds (8 per CU), plus a ragged last group: every lane loops over several groups of 64
+    (gridDim.y = 1).  B distinct rows, a poisoned output with a guard row behind it, every row group checked, every entry written."""
+    from oracle.cpu_oracle import OracleModel
+    torch = torch_cuda
+    cus = int(torch.cuda.get_device_properties(0).multi_processor_count)
+    sys_, desc, _ = make_case("arm7")
+    hm, om = model_of(desc, None), OracleModel(desc)
+    B, grid = 2 * 8 * cus * 64 + 64 + 37, 8 * cus
+    rows = DistinctRows(sys_, 256, seed=29)
+    q = rows.device(torch, B)[0]
+    idx = group_cover(B, grid)
+    cols = [5, 0, 3, 5, 6, 1, 2, 4] if listed else None
+    K = len(cols) if listed else desc.nv
+    if layout == AOS:
+        H, guard = poisoned(torch, B, (desc.nv, K), torch.float64)
+        hm.mass_matrix_inverse(q, cols, AOS, out=H)
+        H_rows = H
+    else:
+        H_t, guard = poisoned(torch, desc.nv * K, (B,), torch.float64)
+        hm.mass_matrix_inverse(q.t().contiguous(), cols, SOA, out=H_t)
+        H_rows = H_t.t()
+    torch.cuda.synchronize()
+    ref = mc.mass_matrix_inverse(om, rows.rows(idx)[0], cols)
+    check_cover(H_rows, guard, idx, ref.reshape(len(idx), -1), 1.0e-10, label="Hinv")
+
+
+def test_small_ragged_batches_and_guards(torch_cuda):
+    """B not a multiple of 64, down to one configuration: several waves share a group of configurations (gridDim.y > 1), each with its
+    groups of columns; the guard row stays untouched and no NaN is left."""
+    from oracle.cpu_oracle import OracleModel
+    torch = torch_cuda
+    sys_, desc, _ = make_case("mixed_tree")
+    hm, om = model_of(desc, None), OracleModel(desc)
+    cols = mc.column_list(desc)
+    for B in (1, 63, 64 * 3 + 1, 4096):
+        q = states(sys_, B)
+        bounds = ac.bound_of(om, q, desc.n_joints, False)
+        ref = mc.mass_matrix_inverse(om, q)
+        for columns, r in ((None, ref), (cols, ref[:, :, cols])):
+            H, guard = poisoned(torch, B, r.shape[1:], torch.float64)
+            hm.mass_matrix_inverse(dev(torch, q), columns, AOS, out=H)
+            torch.cuda.synchronize()
+            assert torch.isnan(guard).all() and not torch.isnan(H).any()
+            ac.close_rows(H.cpu().numpy(), r, bounds, label=f"B={B} {'full' if columns is None else 'columns'}")
+
+
+def test_one_dof_and_numpy_round_trip(torch_cuda):
+    """nv = 1: one revolute joint, H^-1 = 1 / (inertia about the axis); numpy in -> numpy out."""
+    from mecano_amd import random_tools as rt
+    from oracle.cpu_oracle import OracleModel
+    sys_ = system_of(rt.nextJointChain(np.random.default_rng(2), 1, ("revolute",)))
+    desc = sys_.toModelDesc()
+    hm, om = model_of(desc, None), OracleModel(desc)
+    q = states(sys_, 5)
+    got = hm.mass_matrix_inverse(q)
+    assert isinstance(got, np.ndarray) and got.shape == (5, 1, 1)
+    close(got, 1.0 / om.crba(q), 1.0e-12)
+    assert np.array_equal(hm.mass_matrix_inverse(q, [0, 0]), np.concatenate([got, got], axis=2))
+
+
+def test_context_two_streams_out_reuse_and_graph(torch_cuda):
+    """A context other than the default one on a stream of its own gives the default context's bits, a second stream too; `out=` is
+    written in place and may be used again; after reserve() the first call is captured into a graph (it allocates and uploads nothing:
+    one kernel node) and the replay equals the eager call."""
+    torch = torch_cuda
+    sys_, desc, _ = make_case("humanoid30")
+    hm, B = model_of(desc, None), 1000
+    q = dev(torch, states(sys_, B))
+    cols = mc.column_list(desc)
+    for columns in (None, cols):
+        ref = hm.mass_matrix_inverse(q, columns)
+        torch.cuda.synchronize()
+        view = hm.context()
+        view.reserve(B)
+        out = torch.empty_like(ref)
+        s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(s2):
+            graph = torch.cuda.CUDAGraph()
+            out.zero_()
+            torch.cuda.synchronize()
+            with torch.cuda.graph(graph, stream=s2):  # the context's first call
+                view.mass_matrix_inverse(q, columns, out=out)
+        torch.cuda.synchronize()
+        assert not out.any()  # captured, not executed
+        graph.replay()
+        torch.cuda.synchronize()
+        assert torch.equal(out, ref)
+        out.zero_()
+        with torch.cuda.stream(s1):
+            assert view.mass_matrix_inverse(q, columns, out=out) is out
+            view.check(s1.cuda_stream)
+            assert torch.equal(out, ref)
+            out.zero_()
+        torch.cuda.synchronize()
+        with torch.cuda.stream(s2):
+            view.mass_matrix_inverse(q, columns, out=out)
+            view.check(s2.cuda_stream)
+            assert torch.equal(out, ref)
+        torch.cuda.synchronize()
+        view.close()
+
+
+def test_refusals_leave_the_output_untouched(torch_cuda):
+    from mecano_amd import _lib
+    torch = torch_cuda
+    sys_, desc, _ = make_case("arm7")
+    hm, B = model_of(desc, None), 10
+    lib = _lib.load()
+    q = dev(torch, states(sys_, B))
+    H, guard = poisoned(torch, B, (7, 7), torch.float64)
+    opts = hm._options(AOS, stream=torch.cuda.current_stream().cuda_stream)
+    good = np.array([2, 6, 2], dtype=np.int32)
+    beyond = np.array([2, 7], dtype=np.int32)
+    negative = np.array([-1, 2], dtype=np.int32)
+    many = np.zeros(65, dtype=np.int32)
+
+    def call(fn=lib.mh_mass_matrix_inverse_f64, B=B, q=q.data_ptr(), n=0, c=None, out=H.data_ptr()):
+        st = fn(hm._h, B, q, n, c, ctypes.byref(opts), out)
+        torch.cuda.synchronize()
+        return st
+
+    refusals = {"NULL q": dict(q=None), "NULL Hinv_out": dict(out=None), "no columns": dict(n=0, c=good.ctypes.data),
+                "too many columns": dict(n=65, c=many.ctypes.data), "index beyond nv": dict(n=2, c=beyond.ctypes.data),
+                "negative index": dict(n=2, c=negative.ctypes.data), "Hinv_out overlaps q": dict(out=q.data_ptr())}
+    for fn in (lib.mh_mass_matrix_inverse_f64, lib.mh_mass_matrix_inverse_f32):
+        for what, kw in refusals.items():
+            assert call(fn=fn, **kw) == INVALID, what
+            assert lib.mh_last_error(), what
+            assert torch.isnan(H).all() and torch.isnan(guard).all(), what
+    q_before = q.clone()
+    assert call(B=0) == 0 and call(B=0, q=None, out=None) == 0 and call(B=0, n=3, c=good.ctypes.data) == 0
+    assert torch.isnan(H).all() and torch.equal(q, q_before)
+    assert call(n=-5) == 0  # n_columns is ignored without a list
+    assert not torch.isnan(H).any() and torch.isnan(guard).all()
+    assert call(n=64, c=many.ctypes.data, out=torch.empty((B, 7, 64), dtype=torch.float64, device="cuda").data_ptr()) == 0
+    with pytest.raises(_lib.MecanoHipError):
+        hm.mass_matrix_inverse(q, out=q)  # aliasing: refused by shape here, by the overlap check in the library above
+    with pytest.raises(_lib.MecanoHipError):
+        hm.mass_matrix_inverse(q, [1, 2], out=torch.empty((B, 7, 3), dtype=torch.float64, device="cuda"))
+    with pytest.raises(ValueError):
+        hm.mass_matrix_inverse(q, out=torch.empty((B, 7, 7), dtype=torch.float32, device="cuda"))
+
+
+@pytest.mark.parametrize("with_locked", [False, True])
+def test_mirror_blocks_are_blocks_of_the_full_inverse(torch_cuda, with_locked):
+    """computeJointApparentInertiaInverse of a 1-DoF, a spherical and the floating joint equals the joint's block of
+    computeJointSpaceInertiaInverse(), with and without acceleration-source joints; and equals the route the mirror took before: one
+    forward-dynamics call per DoF of the joint, with a unit effort."""
+    from mecano_amd import random_tools as rt
+    from mecano_amd.calculators import ForwardDynamicsCalculator, MultiBodyResponseCalculator
+    from oracle.cpu_oracle import OracleModel
+    torch = torch_cuda
+    picked = {}
+    for seed in range(40):  # a mixed tree that has all three kinds of joint
+        sys_ = system_of(rt.nextJointTree(np.random.default_rng(100 + seed), 14, ("revolute", "prismatic", "sixdof", "spherical")))
+        desc = sys_.toModelDesc()
+        kinds = [int(t) for t in desc.joint_type]
+        picked = {"one": next((j for j, t in enumerate(kinds) if t in (0, 1)), None), "spherical": next((j for j, t in enumerate(kinds) if t == 5), None),
+                  "floating": next((j for j, t in enumerate(kinds) if t == 2), None)}
+        if all(v is not None for v in picked.values()):
+            break
+    assert all(v is not None for v in picked.values())
+    om, B = OracleModel(desc), 70
+    q = states(sys_, B)
+    fd = ForwardDynamicsCalculator(sys_)
+    locked = None
+    if with_locked:  # the spherical joint itself and one other joint
+        locked = np.zeros(desc.n_joints, dtype=np.int32)
+        locked[picked["spherical"]] = 1
+        locked[next(j for j in range(desc.n_joints) if j not in picked.values() and desc.joint_type[j] != 3)] = 1
+        fd.setJointSourceModes([int(v) for v in locked])
+    calc = MultiBodyResponseCalculator(fd)
+    calc.reset(dev(torch, q))
+    full = calc.computeJointSpaceInertiaInverse()
+    torch.cuda.synchronize()
+    bounds = ac.bound_of(om, q, desc.n_joints, False)
+    ref = mc.mass_matrix_inverse(om, q, None, locked)
+    ac.close_rows(full.cpu().numpy(), ref, bounds, label="full inverse")
+    joints = sys_.getJointsToConsider()
+    provider = sys_.getJointMatrixIndexProvider()
+    z = torch.zeros((B, desc.nv), dtype=torch.float64, device="cuda")
+    for name, j in picked.items():
+        rows = list(provider.getJointDoFIndices(joints[j]))
+        block = calc.computeJointApparentInertiaInverse(joints[j])
+        torch.cuda.synchronize()
+        assert tuple(block.shape) == (B, len(rows), len(rows))
+        assert torch.equal(block, full[:, rows][:, :, rows]), name
+        if with_locked and name == "spherical":
+            assert not block.any()
+        old = torch.empty_like(block)
+        for c, row in enumerate(rows):
+            e = z.clone()
+            e[:, row] = 1.0
+            if with_locked:
+                qdd = calc.model.aba_locked(dev(torch, q), z, e, z, (0.0, 0.0, 0.0))[0]
+            else:
+                qdd = calc.model.aba(dev(torch, q), z, e, (0.0, 0.0, 0.0))
+            old[:, :, c] = qdd[:, rows]
+        torch.cuda.synchronize()
+        ac.close_rows(block.cpu().numpy(), old.cpu().numpy(), bounds, label=f"{name} joint against forward dynamics")
+    calc.reset(q)  # numpy in -> numpy out
+    assert isinstance(calc.computeJointSpaceInertiaInverse(), np.ndarray)
+    from mecano_amd.multibody import RigidBody
+    stranger = rt.nextJointChain(np.random.default_rng(1), 1, ("revolute",))[0]
+    assert calc.computeJointApparentInertiaInverse(stranger) is None
