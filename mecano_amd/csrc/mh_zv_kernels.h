@@ -152,9 +152,23 @@ __device__ unsigned long long zv_probe_body[4096 * 32 * 4];
 #else
 #define ZV_STAMP_BODY(body, ph)
 #endif
+// ... or, -DMH_ZV_PROBE_TAIL instead of -DMH_ZV_PROBE_BODY, inside the bias fold and the outward sweep: 0 children folded, 1 handed up,
+// 2 outward step entered, 3 acceleration formed; a trunk body's outward stamps by the wave that writes its accelerations
+#ifdef MH_ZV_PROBE_TAIL
+#define ZV_STAMP_TAIL(body, ph)                                                                                                            \
+   do                                                                                                                                      \
+   {                                                                                                                                       \
+      const unsigned long long t_ = __builtin_amdgcn_s_memrealtime();                                                                      \
+      if ((threadIdx.x & 63) == 0 && cx.own < 4096 && ((body) != 0 || cx.wave == 0))                                                      \
+         zv_probe_body[(cx.own * 32 + (body)) * 4 + (ph)] = t_;                                                                            \
+   } while (0)
+#else
+#define ZV_STAMP_TAIL(body, ph)
+#endif
 #else
 #define ZV_STAMP(job, ph)
 #define ZV_STAMP_BODY(body, ph)
+#define ZV_STAMP_TAIL(body, ph)
 #endif
 // A workgroup barrier that orders LDS traffic only.  __syncthreads() carries a workgroup-scope release fence, which on gfx950 waits for
 // EVERY outstanding vector-memory operation of the wave (s_waitcnt vmcnt(0)): loads requested ahead of time would be waited for at the
@@ -530,6 +544,7 @@ struct ZvFold
       if constexpr (!LEAF)
          children<0>(cx, pA);
       MH_BODY_FENCE();
+      ZV_STAMP_TAIL(J, 0);
       const T *cp = cx.C + J * MC_STRIDE;
       asm volatile("" : "+s"(cp));
       const CRef<T> c{cp};
@@ -583,6 +598,7 @@ struct ZvFold
          up = force_up(TYPE, jx, load_xb_j<TP, J, T>(c), pA);
       }
       MH_BODY_FENCE();
+      ZV_STAMP_TAIL(J, 1);
       return up;
    }
 };
@@ -616,6 +632,7 @@ struct ZvOut
       constexpr bool LEAF = Tree<TP>::n_children(J) == 0;
       constexpr int DO = Tree<TP>::dof_ofs(J), CO = Tree<TP>::cfg_ofs(J);
       constexpr int RS = Tree<TP>::zv_result_slot(J, CX::SPolicy::shared(J));
+      ZV_STAMP_TAIL(J, 2);
       const T *cp = cx.C + J * MC_STRIDE;
       asm volatile("" : "+s"(cp));
       const CRef<T> c{cp};
@@ -652,6 +669,7 @@ struct ZvOut
          a = x;
       }
       MH_BODY_FENCE();
+      ZV_STAMP_TAIL(J, 3);
       if constexpr (!LEAF)
          children<0>(cx, a);
    }
@@ -792,7 +810,28 @@ MH_DEV void zv_limbs_fold(const CX &cx)
 
 // ---- which trunk bodies a wave has to walk in the outward sweep: those above a limb it owns (it needs their accelerations), plus the
 //      ones it WRITES the accelerations of -- for every trunk body the lowest-numbered wave that walks it anyway
-template <class TP>
+// A context may RELAY (ZvRelayCtx; the two-stage inertia job): a wave that owns a late limb (a leg: six steps that wait for nobody) does
+// not walk a sub-trunk for the early limbs it also owns (the neck beside the leg).  It walks the late limb first and takes the outward
+// acceleration of the early limb's parent from the limb's own exchange record, where a wave without a late limb that walks that trunk
+// body anyway (poster) has left it.  Slot map of limb k's record while a relay is under way (21 slots; the bias fold has its wrench in
+// 0-5, a sub-trunk's in 6-11): 12-17 the parent's acceleration (angular, linear), 18 the lane's flag (0: not there yet), 19-20 unused.
+// The owner clears the flag behind the barrier in front of the fold; the poster writes behind the fold's last barrier.
+template <class CXB>
+struct ZvRelayCtx : CXB
+{
+   static constexpr bool relay = true;
+};
+template <class CX, class = void>
+struct zv_relay
+{
+   static constexpr bool value = false;
+};
+template <class CX>
+struct zv_relay<CX, std::enable_if_t<CX::relay>>
+{
+   static constexpr bool value = true;
+};
+template <class TP, bool RELAY = false>
 struct ZvWalk
 {
    using S = Split<TP>;
@@ -803,10 +842,28 @@ struct ZvWalk
             return true;
       return false;
    }
+   static constexpr bool owns_late(int W)
+   {
+      for (int k = 0; k < S::n_limbs(); k++)
+         if (S::owner(k) == W && S::is_late(k))
+            return true;
+      return false;
+   }
+   // the wave that leaves the acceleration of limb k's parent for k's owner (-1: nobody, k is walked to as ever)
+   static constexpr int poster(int k)
+   {
+      if (!RELAY || !S::staged() || S::is_late(k) || !owns_late(S::owner(k)) || TP::parent[S::limb_root(k)] == S::root())
+         return -1;
+      for (int w = 0; w < 4; w++)
+         if (!owns_late(w) && ZvWalk<TP, false>::needs(w, TP::parent[S::limb_root(k)]))
+            return w;
+      return -1;
+   }
+   static constexpr bool relayed(int k) { return poster(k) >= 0; }
    static constexpr bool needs(int W, int J)
    {
       for (int k = 0; k < S::n_limbs(); k++)
-         if (S::owner(k) == W && below(S::limb_root(k), J))
+         if (S::owner(k) == W && below(S::limb_root(k), J) && !relayed(k))
             return true;
       return false;
    }
@@ -818,10 +875,40 @@ struct ZvWalk
       return 0;
    }
 };
+constexpr int ZV_RELAY_A = 12, ZV_RELAY_FLAG = 18; // (slots of the limb's exchange record, see above)
+// poster: the acceleration of trunk body J, for every relayed limb hanging off it that wave W posts for
+template <class TP, int J, int W, int K, typename T, class CX>
+MH_DEV void zv_relay_post(const CX &cx, const SV<T> &a)
+{
+   using S = Split<TP>;
+   if constexpr (K < S::n_limbs())
+   {
+      if constexpr (TP::parent[S::limb_root(K)] == J && ZvWalk<TP, true>::poster(K) == W)
+      {
+         x_put6<K, ZV_XW, ZV_RELAY_A, CX, T>(cx, a);
+         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); // the six values are in LDS before the flag is
+         __hip_atomic_store(cx.xbase + (K * ZV_XW + ZV_RELAY_FLAG) * 64, T(1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+      zv_relay_post<TP, J, W, K + 1, T, CX>(cx, a);
+   }
+}
+// owner, behind the barrier in front of the fold: the flags of its relayed limbs down
+template <class TP, int W, int K, typename T, class CX>
+MH_DEV void zv_relay_clear(const CX &cx)
+{
+   using S = Split<TP>;
+   if constexpr (K < S::n_limbs())
+   {
+      if constexpr (S::owner(K) == W && ZvWalk<TP, true>::relayed(K))
+         x_put<K, ZV_XW, ZV_RELAY_FLAG, CX, T>(cx, T(0));
+      zv_relay_clear<TP, W, K + 1, T, CX>(cx);
+   }
+}
 // outward sweep of wave W over the trunk (MODE 1 of ZvOut with the subtrees pruned in which W owns nothing), then W's limbs
 template <class TP, int J, int W, typename T, class CX>
 struct ZvOutW
 {
+   using WK = ZvWalk<TP, zv_relay<CX>::value>;
    template <int K>
    static MH_DEV void children(const CX &cx, const SV<T> &a)
    {
@@ -830,10 +917,10 @@ struct ZvOutW
          constexpr int C = Tree<TP>::child(J, K);
          if constexpr (!Split<TP>::is_trunk(C))
          {
-            if constexpr (Split<TP>::owner(Split<TP>::limb_index(C)) == W)
+            if constexpr (Split<TP>::owner(Split<TP>::limb_index(C)) == W && !WK::relayed(Split<TP>::limb_index(C)))
                ZvOut<TP, C, T, CX, 0>::run(cx, a);
          }
-         else if constexpr (ZvWalk<TP>::needs(W, C))
+         else if constexpr (WK::needs(W, C))
             ZvOutW<TP, C, W, T, CX>::run(cx, a);
          children<K + 1>(cx, a);
       }
@@ -845,7 +932,9 @@ struct ZvOutW
       constexpr bool HAS_PARENT = TP::parent[J] >= 0;
       constexpr int DO = Tree<TP>::dof_ofs(J), CO = Tree<TP>::cfg_ofs(J);
       constexpr int RS = Tree<TP>::zv_result_slot(J, CX::SPolicy::shared(J));
-      constexpr bool WRITES = ZvWalk<TP>::writer(J) == W;
+      constexpr bool WRITES = WK::writer(J) == W;
+      if constexpr (WRITES)
+         ZV_STAMP_TAIL(J, 2);
       const T *cp = cx.C + J * MC_STRIDE;
       asm volatile("" : "+s"(cp));
       const CRef<T> c{cp};
@@ -882,6 +971,10 @@ struct ZvOutW
          a = x;
       }
       MH_BODY_FENCE();
+      if constexpr (WRITES)
+         ZV_STAMP_TAIL(J, 3);
+      if constexpr (zv_relay<CX>::value)
+         zv_relay_post<TP, J, W, 0, T, CX>(cx, a);
       children<0>(cx, a);
    }
 };
@@ -892,9 +985,28 @@ MH_DEV void zv_roots_out_wave(const CX &cx)
    {
       const V3<T> Z{T(0), T(0), T(0)};
       constexpr int R = Tree<TP>::child(-1, K);
-      if constexpr (ZvWalk<TP>::needs(W, R) || ZvWalk<TP>::writer(R) == W)
+      using WK = ZvWalk<TP, zv_relay<CX>::value>;
+      if constexpr (WK::needs(W, R) || WK::writer(R) == W)
          ZvOutW<TP, R, W, T, CX>::run(cx, SV<T>{Z, Z});
       zv_roots_out_wave<TP, W, T, CX, K + 1>(cx);
+   }
+}
+// owner: its relayed limbs, behind everything else it walks -- by then the parent's acceleration has long been posted
+template <class TP, int W, int K, typename T, class CX>
+MH_DEV void zv_relay_out(const CX &cx)
+{
+   using S = Split<TP>;
+   if constexpr (K < S::n_limbs())
+   {
+      if constexpr (S::owner(K) == W && ZvWalk<TP, true>::relayed(K))
+      {
+         const lds_ptr<T> flag = cx.xbase + (K * ZV_XW + ZV_RELAY_FLAG) * 64;
+         while (__builtin_amdgcn_ballot_w64(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) == T(0)) != 0)
+            __builtin_amdgcn_s_sleep(1);
+         asm volatile("" ::: "memory");
+         ZvOut<TP, S::limb_root(K), T, CX, 0>::run(cx, x_get6<K, ZV_XW, ZV_RELAY_A, CX, T>(cx));
+      }
+      zv_relay_out<TP, W, K + 1, T, CX>(cx);
    }
 }
 // limbs of wave W in the bias fold: LATE = -1 all, 0 / 1 the early / late ones of a staged trunk
@@ -950,6 +1062,8 @@ MH_DEV void zv_fold_out(const CX &cx, const HOOK &hook = HOOK())
 #ifdef MH_ZV_PROBE
             const long k = (long)cx.own; // (the group, for the stamps: zv_aba_group leaves it there in probe builds)
 #endif
+            if constexpr (zv_relay<CX>::value)
+               zv_relay_clear<TP, W, 0, T, CX>(cx);
             zv_limbs_fold_sel<TP, W, 0, 0, T, CX>(cx);
             hook.after_early();
             ZV_STAMP(1, 7);
@@ -980,6 +1094,8 @@ MH_DEV void zv_fold_out(const CX &cx, const HOOK &hook = HOOK())
          hook.before_out();
          asm volatile("" ::: "memory");
          zv_roots_out_wave<TP, W, T, CX>(cx);
+         if constexpr (zv_relay<CX>::value)
+            zv_relay_out<TP, W, 0, T, CX>(cx);
       }
       else
          zv_fold_out<TP, W + 1, T, CX, HOOK>(cx, hook);
@@ -1674,7 +1790,7 @@ template <class TP, typename T, bool STEP>
 MH_DEV void zv_aba_group2(const Args<T> &A, long k, lds_ptr<T> lds, const T *taup, const ZvSync &sy)
 {
    using S = Split<TP>;
-   using CX = Ctx<T, true, true, ZvStore<TP>, false, 0>;
+   using CX = ZvRelayCtx<Ctx<T, true, true, ZvStore<TP>, false, 0>>; // (the outward sweep relays: ZvWalk)
    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
    const int lane = threadIdx.x & 63;
    constexpr int nq = Tree<TP>::total_cfgs(), nv = Tree<TP>::total_dofs(); // (dense index maps: the model's nq, nv -- known without the kernel-argument segment)
