@@ -500,6 +500,40 @@ mh_status mh_mass_matrix_inverse_f32(mh_model_t model, int64_t B, const float *q
                                      const mh_options *opts, float *Hinv_out);
 
 /*
+ * ---- first-order derivatives of the inverse and the forward dynamics at a moving state (no calculator of the reference: its
+ *      MultiBodyGravityGradientCalculator is the qd = 0, qdd = 0 special case, which mh_rnea_derivatives_* reproduces) ----
+ * mh_rnea_derivatives_*: tau_out [B][nv] (may be NULL) = mh_rnea_* of the same inputs; dtau_dq_out and dtau_dqd_out [B][nv][nv] row-major
+ * (MH_LAYOUT_SOA: [nv * nv][B], laid out and indexed like grad_out of mh_gravity_gradient_*): entry [i][j] is d tau_i / d q_j, respectively
+ * d tau_i / d qd_j.  Either matrix may be NULL, not both (MH_ERR_INVALID_ARGUMENT).  dq is a velocity-space step, exactly as in
+ * mh_gravity_gradient_*: the step mh_integrate_* applies (for a SixDoF, planar or spherical joint a twist increment in the frame after the
+ * joint); the COMPONENTS of qd and qdd are held fixed while q moves, and every external wrench is held constant IN THE WORLD.
+ * opts->consider_coriolis = 0 evaluates at qd = 0 (qd may then be NULL) and writes d tau / d qd as zeros; opts->consider_accelerations = 0
+ * evaluates at qdd = 0 (qdd may then be NULL).  opts->use_root_acceleration / root_acceleration are honoured as in mh_rnea_* (gravity may
+ * then be NULL).  The model's joint source modes play no part.  Every entry of both matrices is written, zeros of unrelated joints
+ * included (no memset needed), nothing outside the outputs.  The outputs must not overlap the inputs or each other
+ * (MH_ERR_INVALID_ARGUMENT).  B = 0 or nv = 0 returns MH_OK and touches nothing.  Analytic, O(n depth) per configuration: one launch of a
+ * run-time-topology kernel for every model.  Device pointers, asynchronous on opts->stream, contexts honoured; after mh_reserve the call
+ * allocates nothing.
+ * mh_aba_derivatives_*: with qdd = mh_aba_*(q, qd, tau), dqdd_dq_out = -H^-1 d tau / d q and dqdd_dqd_out = -H^-1 d tau / d qd at that qdd
+ * (same layout, same meaning of dq; at least one of the two, MH_ERR_INVALID_ARGUMENT otherwise), and d qdd / d tau = H^-1.  qdd_out [B][nv]
+ * and Hinv_out [B][nv][nv] may be NULL: they then go to scratch of the context, which mh_reserve / mh_context_reserve set aside while it
+ * stays within 4 GiB (a larger need is met at the first such call).  Launches composed on opts->stream: forward dynamics (whichever plan
+ * mh_aba_* takes), the kernel above, the full mh_mass_matrix_inverse_*, and a product kernel that replaces each matrix D by -H^-1 D in
+ * place, column by column (H^-1 is read as its transpose: symmetric up to rounding).  nv <= 4096.  A model with MH_ACCELERATION_SOURCE
+ * joints is refused (MH_ERR_INVALID_ARGUMENT), as by mh_aba_*.  The outputs must not overlap the inputs or each other.
+ */
+mh_status mh_rnea_derivatives_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double gravity[3],
+                                  const double *f_ext, const mh_options *opts, double *tau_out, double *dtau_dq_out, double *dtau_dqd_out);
+mh_status mh_rnea_derivatives_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const double gravity[3],
+                                  const float *f_ext, const mh_options *opts, float *tau_out, float *dtau_dq_out, float *dtau_dqd_out);
+mh_status mh_aba_derivatives_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
+                                 const double *f_ext, const mh_options *opts, double *qdd_out, double *dqdd_dq_out, double *dqdd_dqd_out,
+                                 double *Hinv_out);
+mh_status mh_aba_derivatives_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const double gravity[3],
+                                 const float *f_ext, const mh_options *opts, float *qdd_out, float *dqdd_dq_out, float *dqdd_dqd_out,
+                                 float *Hinv_out);
+
+/*
  * ---- state integration (MultiBodySystemStateIntegrator.doubleIntegrateFromAcceleration, tools/MultiBodySystemStateIntegrator.java:365-441,
  *      503-575, 710-733): the step downstream of forward dynamics, so that a simulation loop never leaves the device ----
  * One explicit constant-acceleration step of size dt for every joint of every configuration: 1-DoF q' = q + dt qd + dt^2/2 qdd,

@@ -122,6 +122,24 @@ public final class MecanoHipNative
    static final MethodHandle GRAVITY_GRADIENT = handle("mh_gravity_gradient_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
    /** the same in fp32 (float matrices on the device) */
    static final MethodHandle GRAVITY_GRADIENT_F32 = handle("mh_gravity_gradient_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * Derivatives of the inverse dynamics at a moving state for B states: (model, B, q, qd, qdd, gravity[3] (host), f_ext|NULL, opts|NULL,
+    * tau_out|NULL, dtau_dq_out|NULL, dtau_dqd_out|NULL), matrices [B][nv][nv] row-major; not both matrices NULL.
+    */
+   static final MethodHandle RNEA_DERIVATIVES = handle("mh_rnea_derivatives_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                         ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 (float matrices on the device) */
+   static final MethodHandle RNEA_DERIVATIVES_F32 = handle("mh_rnea_derivatives_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                             ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * Derivatives of the forward dynamics: (model, B, q, qd, tau, gravity[3] (host), f_ext|NULL, opts|NULL, qdd_out|NULL, dqdd_dq_out|NULL,
+    * dqdd_dqd_out|NULL, Hinv_out|NULL), matrices [B][nv][nv] row-major; not both derivative matrices NULL.
+    */
+   static final MethodHandle ABA_DERIVATIVES = handle("mh_aba_derivatives_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                       ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle ABA_DERIVATIVES_F32 = handle("mh_aba_derivatives_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                           ADDRESS, ADDRESS, ADDRESS, ADDRESS));
    /** mh_apparent_inertia_inverse_*: the targets' own 6 x 6 blocks, or the coupled 6K x 6K matrix; at most this many targets per call */
    static final int APPARENT_BLOCKS_DIAGONAL = 0, APPARENT_BLOCKS_COUPLED = 1;
    static final int MAX_APPARENT_TARGETS = 16;

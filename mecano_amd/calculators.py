@@ -227,6 +227,12 @@ class InverseDynamicsCalculator(_Base):
     def getJointTauMatrix(self):
         return self._tau
 
+    def getJointTauGradients(self, q, qd, qdd):
+        """No counterpart in the reference: (tau, d tau / d q, d tau / d qd) of B states, [B, nv] and [B, nv, nv], from one analytic
+        launch (``HipModel.rnea_derivatives``), with this calculator's gravity or root acceleration, external wrenches and switches.  dq
+        is a velocity-space step, as in MultiBodyGravityGradientCalculator, which this reproduces at qd = 0, qdd = 0."""
+        return self.model.rnea_derivatives(q, qd, qdd, self._gravity, self._f_ext, self.layout, self._coriolis, self._accel)
+
     def getComputedJointWrench(self, joint):
         """InverseDynamicsCalculator.java:578-585: [B, 6] (moment, force) in the frame after the joint, ``None`` for a joint this
         calculator does not consider; needs ``compute(..., wrenches=True)``."""
@@ -427,6 +433,12 @@ class ForwardDynamicsCalculator(_Base):
 
     def getJointAccelerationMatrix(self):
         return self._qdd
+
+    def getJointAccelerationGradients(self, q, qd, tau):
+        """No counterpart in the reference: (qdd, d qdd / d q, d qdd / d qd, H^-1 = d qdd / d tau) of B states, [B, nv] and [B, nv, nv]
+        (``HipModel.aba_derivatives``), with this calculator's gravity or root acceleration and external wrenches.  Every joint must be
+        an effort source."""
+        return self.model.aba_derivatives(q, qd, tau, self._gravity, self._f_ext, self.layout)
 
     def getComputedJointAcceleration(self, joint):
         """``getComputedJointAcceleration(joint)`` (:600-610): N x 1 after a one-configuration compute, None for a joint that is not considered."""

@@ -10,6 +10,7 @@
 #include "mh_gravity_kernels.h"
 #include "mh_response_kernels.h"
 #include "mh_minv_kernels.h"
+#include "mh_rnea_deriv_kernels.h"
 
 #include <dlfcn.h>
 #include <spawn.h>
@@ -275,6 +276,12 @@ struct mh_model
    // joint's DoFs (-1: no joint); the kernel (mh_minv_kernels.h) works in the workspace slots of the apparent-inertia kernel
    std::vector<int> minv_owner;
    int *d_minv_owner = nullptr;
+   // mh_rnea_derivatives_* / mh_aba_derivatives_*: first workspace slot of every body in that kernel's own plan (mh_rnea_deriv_kernels.h)
+   // and its slots per lane; scratch of the forward form (Hinv and qdd the caller did not ask for)
+   std::vector<int> deriv_slot;
+   int *d_deriv_slot = nullptr;
+   int deriv_slots = 0;
+   Workspace deriv;
    Workspace ws;
    // staging buffers of the *_host entry points
    Workspace stage;
@@ -2286,6 +2293,144 @@ mh_status mass_matrix_inverse_impl(mh_model_t model, int64_t B, const T *q, int3
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
+// Derivatives of the inverse dynamics with respect to q and qd (mh_rnea_deriv_kernels.h): run-time-topology kernel, which writes every
+// entry of its outputs -- no memset in front of it -- in a slot plan of its own (more per body than the model's common plan holds)
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+   const char *a0 = (const char *)a, *b0 = (const char *)b;
+   return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
+}
+static size_t deriv_ws_bytes(const mh_model *m, const Launch &L, int parts, size_t elem)
+{
+   return (size_t)m->deriv_slots * (size_t)L.lanes * (size_t)parts * elem;
+}
+// the scratch mh_reserve sets aside for the forward form (Hinv and qdd the caller does not ask for) stays within this; a larger need is
+// met at the first such call
+constexpr size_t kDerivReserveCap = (size_t)4 << 30;
+static size_t deriv_scratch_bytes(const mh_model *m, int64_t B, size_t elem) { return (size_t)B * ((size_t)m->nv * m->nv + (size_t)m->nv) * elem; }
+template <typename T>
+mh_status rnea_derivatives_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const double *gravity, const T *f_ext,
+                                const mh_options *opts_in, T *tau_out, T *dq_out, T *dqd_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   if (!gravity && !opts.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (!dq_out && !dqd_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "dtau_dq_out and dtau_dqd_out are both NULL");
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!q || (opts.consider_coriolis && !qd) || (opts.consider_accelerations && !qdd))
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state pointer (qd may be NULL with consider_coriolis = 0, qdd with consider_accelerations = 0)");
+   {
+      const size_t nq = (size_t)B * model->nq * sizeof(T), nvb = (size_t)B * model->nv * sizeof(T), nm = nvb * model->nv,
+                   nf = (size_t)B * model->n * 6 * sizeof(T);
+      const void *in[4] = {q, opts.consider_coriolis ? qd : nullptr, opts.consider_accelerations ? qdd : nullptr, f_ext};
+      const size_t in_bytes[4] = {nq, nvb, nvb, nf};
+      const void *out[3] = {tau_out, dq_out, dqd_out};
+      const size_t out_bytes[3] = {nvb, nm, nm};
+      for (int o = 0; o < 3; o++)
+      {
+         for (int i = 0; i < 4; i++)
+            if (ranges_overlap(out[o], out_bytes[o], in[i], in_bytes[i]))
+               return fail(MH_ERR_INVALID_ARGUMENT, "an output overlaps an input");
+         for (int p = o + 1; p < 3; p++)
+            if (ranges_overlap(out[o], out_bytes[o], out[p], out_bytes[p]))
+               return fail(MH_ERR_INVALID_ARGUMENT, "two outputs overlap");
+      }
+   }
+   const Launch L = plan_launch(model, B);
+   const int parts = regressor_parts(model, L);
+   st = ensure_bytes(model->ws, deriv_ws_bytes(model, L, parts, sizeof(T)));
+   if (st != MH_OK)
+      return st;
+   mh::DerivArgs<T> G{};
+   mh::Args<T> &A = G.a;
+   A = make_args<T>(model, B, opts, gravity);
+   A.q = q, A.qd = qd, A.in3 = qdd, A.fext = f_ext, A.out = tau_out;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = L.lanes;
+   G.dq = dq_out, G.dqd = dqd_out;
+   set_strides(G.g_bs, G.g_es, opts.layout == MH_LAYOUT_SOA, B, (long)model->nv * model->nv);
+   G.slot = model->d_deriv_slot, G.slots = model->deriv_slots;
+   G.zero_ofs = model->d_grav_zero_ofs, G.zero_cols = model->d_grav_zero_cols;
+   hipLaunchKernelGGL((mh::rnea_derivatives_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
+// Derivatives of the forward dynamics: launches composed on the caller's stream -- forward dynamics (whichever plan mh_aba_* takes), the
+// inverse-dynamics derivatives at that qdd straight into the caller's matrices, the full inverse mass matrix, and D <- -Hinv D in place.
+template <typename T>
+mh_status aba_derivatives_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const double *gravity, const T *f_ext,
+                                      const mh_options *opts_in, T *qdd_out, T *dq_out, T *dqd_out, T *Hinv_out)
+{
+   // the scratch below belongs to the CONTEXT of the call: resolve it before anything mutable is touched
+   mh_options o;
+   mh_status st = begin_call(model, B, opts_in, o);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: the derivatives of the forward dynamics take none", model->n_locked);
+   if (!gravity && !o.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (!dq_out && !dqd_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "dqdd_dq_out and dqdd_dqd_out are both NULL");
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!q || !qd || !tau)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state pointer");
+   if (model->nv > mh::NEG_SOLVE_LDS_ENTRIES) // one column of a matrix has to fit the product kernel's LDS buffer
+      return fail(MH_ERR_INVALID_ARGUMENT, "nv = %d is beyond the %d DoFs the product kernel takes", model->nv, mh::NEG_SOLVE_LDS_ENTRIES);
+   const size_t nvb = (size_t)B * model->nv * sizeof(T), nm = nvb * model->nv;
+   {
+      const void *in[4] = {q, qd, tau, f_ext};
+      const size_t in_bytes[4] = {(size_t)B * model->nq * sizeof(T), nvb, nvb, (size_t)B * model->n * 6 * sizeof(T)};
+      const void *out[4] = {qdd_out, dq_out, dqd_out, Hinv_out};
+      const size_t out_bytes[4] = {nvb, nm, nm, nm};
+      for (int a = 0; a < 4; a++)
+      {
+         for (int i = 0; i < 4; i++)
+            if (ranges_overlap(out[a], out_bytes[a], in[i], in_bytes[i]))
+               return fail(MH_ERR_INVALID_ARGUMENT, "an output overlaps an input");
+         for (int b = a + 1; b < 4; b++)
+            if (ranges_overlap(out[a], out_bytes[a], out[b], out_bytes[b]))
+               return fail(MH_ERR_INVALID_ARGUMENT, "two outputs overlap");
+      }
+   }
+   T *qdd = qdd_out, *Hinv = Hinv_out;
+   if (!qdd || !Hinv)
+   {
+      st = ensure_bytes(model->deriv, deriv_scratch_bytes(model, B, sizeof(T)));
+      if (st != MH_OK)
+         return st;
+      if (!Hinv)
+         Hinv = (T *)model->deriv.ptr;
+      if (!qdd)
+         qdd = (T *)model->deriv.ptr + (size_t)B * model->nv * model->nv;
+   }
+   st = launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &o, qdd);
+   if (st != MH_OK)
+      return st;
+   mh_options od = o; // the inverse dynamics at the state forward dynamics saw: both switches on
+   od.consider_coriolis = 1, od.consider_accelerations = 1;
+   st = rnea_derivatives_impl<T>(model, B, q, qd, qdd, gravity, f_ext, &od, nullptr, dq_out, dqd_out);
+   if (st != MH_OK)
+      return st;
+   st = mass_matrix_inverse_impl<T>(model, B, q, 0, nullptr, &o, Hinv);
+   if (st != MH_OK)
+      return st;
+   mh::NegSolveArgs<T> N{};
+   N.Hinv = Hinv, N.D0 = dq_out ? dq_out : dqd_out, N.D1 = dq_out ? dqd_out : nullptr;
+   N.B = B, N.nv = model->nv;
+   set_strides(N.bs, N.es, o.layout == MH_LAYOUT_SOA, B, (long)model->nv * model->nv);
+   N.kc = std::max(1, std::min(model->nv, mh::NEG_SOLVE_LDS_ENTRIES / model->nv));
+   const int grid = (int)std::min<int64_t>(B, (int64_t)model->cu_count * 32);
+   hipLaunchKernelGGL((mh::neg_hinv_product_kernel<T>), dim3(grid), dim3(256), 0, (hipStream_t)o.stream, N);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
 template <typename T>
 mh_status integrate_impl(mh_model_t model, int64_t B, double dt, const T *q, const T *qd, const T *qdd, const mh_options *opts_in, T *q_out,
                                 T *qd_out, T *qdd_out)
@@ -2700,6 +2845,16 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
       for (int k = edofo[e]; k < edofo[e + 1]; k++)
          m->minv_owner[m->dof_map[k]] = 8 * e + (k - edofo[e]);
 
+   // ---- derivatives of the inverse dynamics (mh_rnea_deriv_kernels.h): that kernel's own slot plan
+   m->deriv_slot.assign((size_t)std::max(1, n), 0);
+   m->deriv_slots = 0;
+   for (int e = 0; e < n; e++)
+   {
+      m->deriv_slot[e] = m->deriv_slots;
+      m->deriv_slots += (m->meta[(size_t)e * mh::MI_STRIDE + mh::MI_FLAGS] & mh::MF_STORE_VA) ? mh::DS_BRANCH : mh::DS_BODY;
+   }
+   m->deriv_slots = std::max(m->deriv_slots, 1);
+
    // ---- depth-first kernels: children counts, stack-frame / hand-over offsets, event program (mh_dfs_kernels.h)
    {
       std::vector<int> nch(n, 0), ofs_r(n, 0), ofs_a(n, 0), ofs_p(n, 0);
@@ -2857,6 +3012,8 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
       e = up((void **)&m->d_resp_info, m->resp_info.data(), m->resp_info.size() * sizeof(int));
    if (e == hipSuccess)
       e = up((void **)&m->d_minv_owner, m->minv_owner.data(), m->minv_owner.size() * sizeof(int));
+   if (e == hipSuccess)
+      e = up((void **)&m->d_deriv_slot, m->deriv_slot.data(), m->deriv_slot.size() * sizeof(int));
    if (e != hipSuccess)
    {
       mh_model_destroy(m);
@@ -2995,11 +3152,12 @@ static void free_scratch(mh_model *m)
    (void)hipFree(m->tr.ptr);
    (void)hipFree(m->aux.ptr);
    (void)hipFree(m->pairs.ptr);
+   (void)hipFree(m->deriv.ptr);
 }
 // a fresh set of the above for a copy of a handle
 static void reset_scratch(mh_model *m)
 {
-   m->ws = m->stage = m->ws_pair = m->zv_tau = m->zv_cols = m->zv_flags = m->zvb_cs = m->tr = m->tr_pair = m->aux = m->pairs = Workspace{};
+   m->ws = m->stage = m->ws_pair = m->zv_tau = m->zv_cols = m->zv_flags = m->zvb_cs = m->tr = m->tr_pair = m->aux = m->pairs = m->deriv = Workspace{};
    m->hs_in = m->hs_run = m->hs_out = nullptr;
    for (int k = 0; k < 3; k++)
       m->ev_in[k] = m->ev_run[k] = m->ev_out[k] = nullptr;
@@ -3023,6 +3181,7 @@ static void release_model(mh_model *m)
    (void)hipFree(m->d_sub_mass64);
    (void)hipFree(m->d_sub_mass32);
    (void)hipFree(m->d_grav_zero_ofs);
+   (void)hipFree(m->d_deriv_slot);
    (void)hipFree(m->d_grav_zero_cols);
    (void)hipFree(m->d_resp_info);
    (void)hipFree(m->d_minv_owner);
@@ -3313,6 +3472,14 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       const long resp_parts = std::max<long>(MH_MAX_APPARENT_TARGETS, minv_groups(std::max<int>(m->nv, MH_MAX_INVERSE_COLUMNS)));
       const long resp_waves = std::max<long>(L.grid, std::min<long>(resp_parts * L.grid, (long)m->cu_count * 4));
       st = ensure_bytes(m->ws, (size_t)m->resp_slots * (size_t)resp_waves * 64 * sizeof(double));
+      if (st != MH_OK)
+         return st;
+      // mh_rnea_derivatives_* / mh_aba_derivatives_*: the kernel's own slot plan, parts as the regressor's (grid * parts is bounded as
+      // above), and the scratch of the forward form
+      const long deriv_waves = std::max<long>(L.grid, std::min<long>(8L * L.grid, (long)m->cu_count * 4));
+      st = ensure_bytes(m->ws, (size_t)m->deriv_slots * (size_t)deriv_waves * 64 * sizeof(double));
+      if (st == MH_OK && m->nv > 0 && deriv_scratch_bytes(m, max_batch, sizeof(double)) <= kDerivReserveCap)
+         st = ensure_bytes(m->deriv, deriv_scratch_bytes(m, max_batch, sizeof(double)));
       if (st != MH_OK)
          return st;
    }
@@ -3899,6 +4066,28 @@ mh_status mh_aba_locked_f32(mh_model_t model, int64_t B, const float *q, const f
    return aba_locked<float>(model, B, q, qd, tau, qdd_in, gravity, f_ext, opts, qdd_out, tau_out);
 }
 // ---- device memory for hosts without a HIP binding of their own (a Java shim keeps simulation state resident between steps with these)
+mh_status mh_rnea_derivatives_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double gravity[3],
+                                  const double *f_ext, const mh_options *opts, double *tau_out, double *dtau_dq_out, double *dtau_dqd_out)
+{
+   return rnea_derivatives_impl<double>(model, B, q, qd, qdd, gravity, f_ext, opts, tau_out, dtau_dq_out, dtau_dqd_out);
+}
+mh_status mh_rnea_derivatives_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const double gravity[3],
+                                  const float *f_ext, const mh_options *opts, float *tau_out, float *dtau_dq_out, float *dtau_dqd_out)
+{
+   return rnea_derivatives_impl<float>(model, B, q, qd, qdd, gravity, f_ext, opts, tau_out, dtau_dq_out, dtau_dqd_out);
+}
+mh_status mh_aba_derivatives_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
+                                 const double *f_ext, const mh_options *opts, double *qdd_out, double *dqdd_dq_out, double *dqdd_dqd_out,
+                                 double *Hinv_out)
+{
+   return aba_derivatives_impl<double>(model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, dqdd_dq_out, dqdd_dqd_out, Hinv_out);
+}
+mh_status mh_aba_derivatives_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const double gravity[3],
+                                 const float *f_ext, const mh_options *opts, float *qdd_out, float *dqdd_dq_out, float *dqdd_dqd_out,
+                                 float *Hinv_out)
+{
+   return aba_derivatives_impl<float>(model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, dqdd_dq_out, dqdd_dqd_out, Hinv_out);
+}
 mh_status mh_device_alloc(size_t bytes, void **ptr_out)
 {
    if (!ptr_out)

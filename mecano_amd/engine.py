@@ -613,6 +613,71 @@ class HipModel:
             self._h, B, q.data_ptr(), K, None if cols is None else cols.ctypes.data, ctypes.byref(opts), out.data_ptr()))
         return out
 
+    def _derivative_outputs(self, q, B, dt, layout, out, names):
+        """The outputs of the two derivative calls: a vector [B, nv], then nv x nv matrices; ``out`` a tuple with None for what is not
+        wanted, or None for all of them."""
+        import torch
+        aos = layout == _lib.LAYOUT_AOS
+        vec, mat = (B, self.nv) if aos else (self.nv, B), (B, self.nv, self.nv) if aos else (self.nv * self.nv, B)
+        shapes = (vec,) + (mat,) * (len(names) - 1)
+        if out is None:
+            return tuple(torch.empty(s, dtype=dt, device=q.device) for s in shapes)
+        if len(out) != len(names):
+            raise _lib.MecanoHipError(2, f"out must hold {len(names)} entries ({', '.join(names)})")
+        for t, s, name in zip(out, shapes, names):
+            if t is None:
+                continue
+            if not self._is_torch(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+            if tuple(t.shape) != s:
+                raise _lib.MecanoHipError(2, f"{name} output has shape {tuple(t.shape)}, expected {s}")
+        return tuple(out)
+
+    def rnea_derivatives(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, consider_coriolis=True,
+                         consider_accelerations=True, out=None):
+        """Inverse dynamics and its first-order derivatives at a moving state, one analytic launch: (tau [B, nv], dtau_dq [B, nv, nv],
+        dtau_dqd [B, nv, nv]), entry [i][j] = d tau_i / d q_j resp. d tau_i / d qd_j.  dq is a velocity-space step (what ``integrate``
+        applies), the components of qd and qdd are held fixed, the wrenches are held constant in the world.  Device tensors (fp64 /
+        fp32); SoA: [nv, B] and [nv * nv, B].  ``gravity``: the 3-vector g or a 6-D root acceleration, as for ``rnea``.  ``qdd`` may be
+        None with ``consider_accelerations=False``, ``qd`` with ``consider_coriolis=False``.  ``out``: a (tau, dtau_dq, dtau_dqd) tuple to
+        write into; any may be None (not computed), not both matrices."""
+        given = [t for t in (q, qd if consider_coriolis else None, qdd if consider_accelerations else None) if t is not None]
+        B, dt, sfx, stream = self._device_inputs(given, layout)
+        if (consider_coriolis and qd is None) or (consider_accelerations and qdd is None):
+            raise _lib.MecanoHipError(1, "qd / qdd may be None only with their switch off")
+        if f_ext is not None and (not self._is_torch(f_ext) or not f_ext.is_cuda or f_ext.dtype != dt or not f_ext.is_contiguous()):
+            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+        self._check_f_ext(f_ext, B, layout)
+        tau, dq, dqd = self._derivative_outputs(q, B, dt, layout, out, ("tau", "dtau_dq", "dtau_dqd"))
+        if dq is None and dqd is None:
+            raise _lib.MecanoHipError(1, "both matrices are None")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, consider_coriolis, consider_accelerations, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_rnea_derivatives_{sfx}")(
+            self._h, B, q.data_ptr(), ptr(qd) if consider_coriolis else None, ptr(qdd) if consider_accelerations else None, g, ptr(f_ext),
+            ctypes.byref(opts), ptr(tau), ptr(dq), ptr(dqd)))
+        return tau, dq, dqd
+
+    def aba_derivatives(self, q, qd, tau, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Forward dynamics and its first-order derivatives: (qdd [B, nv], dqdd_dq, dqdd_dqd, Hinv [B, nv, nv]) with dqdd_dq = -H^-1
+        d tau / d q and dqdd_dqd = -H^-1 d tau / d qd at qdd = aba(q, qd, tau), and d qdd / d tau = H^-1.  Steps, layouts and ``gravity`` as
+        for ``rnea_derivatives``.  ``out``: a (qdd, dqdd_dq, dqdd_dqd, Hinv) tuple to write into; any may be None (qdd and Hinv then go to
+        scratch of the model), not both derivative matrices.  A model with acceleration-source joints is refused."""
+        B, dt, sfx, stream = self._device_inputs([q, qd, tau], layout)
+        if f_ext is not None and (not self._is_torch(f_ext) or not f_ext.is_cuda or f_ext.dtype != dt or not f_ext.is_contiguous()):
+            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+        self._check_f_ext(f_ext, B, layout)
+        qdd, dq, dqd, Hinv = self._derivative_outputs(q, B, dt, layout, out, ("qdd", "dqdd_dq", "dqdd_dqd", "Hinv"))
+        if dq is None and dqd is None:
+            raise _lib.MecanoHipError(1, "both derivative matrices are None")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, True, True, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_aba_derivatives_{sfx}")(
+            self._h, B, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), g, ptr(f_ext), ctypes.byref(opts), ptr(qdd), ptr(dq), ptr(dqd), ptr(Hinv)))
+        return qdd, dq, dqd, Hinv
+
     def regressor(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), layout=_lib.LAYOUT_AOS, consider_coriolis=True, consider_accelerations=True,
                   first_moment_columns=False):
         """Joint torque regressor (JointTorqueRegressorCalculator.compute, JointTorqueRegressorCalculator.java:173-190): Y [B, nv, 10 n_joints]
