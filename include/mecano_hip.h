@@ -534,6 +534,34 @@ mh_status mh_aba_derivatives_f32(mh_model_t model, int64_t B, const float *q, co
                                  float *Hinv_out);
 
 /*
+ * ---- inverse and forward dynamics with per-configuration inertial parameters: B different robots of one topology and geometry
+ *      (domain randomisation, identification by simulation error, payload sweeps; no calculator of the reference evaluates a batch) ----
+ * pi (DEVICE) is [B][n_joints][10], MH_LAYOUT_SOA: [10 n_joints][B] (opts->layout, as for every other matrix of the call).  The ten
+ * numbers of joint j's successor body, j in mh_model_desc order, are (mass, com_x, com_y, com_z, Jxx, Jxy, Jxz, Jyy, Jyz, Jzz):
+ * inertia_mass, inertia_com and the symmetric part of inertia_J with their mh_model_desc meaning (J about the origin of the body-fixed
+ * frame, in its axes) -- the parameter order of mh_regressor_*.  Fixed joints have a block too (their successor carries inertia); a body
+ * that had an ignored subtree lumped into it by the host is parametrised by its lumped values.  The call replaces what the description
+ * gave for inertia and nothing else: topology, joint frames, axes and index maps stay the model's.
+ * mh_model_inertial_parameters: the model's own values in this layout, pi_out (HOST) [n_joints][10]; the matching call with them in
+ * every row reproduces mh_rnea_* / mh_aba_* (to rounding: the device applies the host's map from the ten numbers to its inertia record).
+ * Gravity, f_ext, opts->root_acceleration, the two switches of mh_rnea_*, stream and context behave as in mh_rnea_* / mh_aba_*; while any
+ * joint is MH_ACCELERATION_SOURCE, mh_aba_parameters_* returns MH_ERR_INVALID_ARGUMENT as mh_aba_* does.  pi = NULL is
+ * MH_ERR_INVALID_ARGUMENT.  A pi that is no physical inertia is not diagnosed: like the reference's unguarded 1/D it shows as inf / nan
+ * in that row only, and the call returns MH_OK.  The output may alias an input, as in the single calls.  Run-time-topology kernels for
+ * every model (mh_params_kernels.h); device pointers, asynchronous on opts->stream; after mh_reserve and one first call the entry points
+ * only enqueue work (graph-capturable).
+ */
+mh_status mh_model_inertial_parameters(mh_model_t model, double *pi_out);
+mh_status mh_rnea_parameters_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double *pi,
+                                 const double gravity[3], const double *f_ext, const mh_options *opts, double *tau_out);
+mh_status mh_rnea_parameters_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const float *pi,
+                                 const double gravity[3], const float *f_ext, const mh_options *opts, float *tau_out);
+mh_status mh_aba_parameters_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double *pi,
+                                const double gravity[3], const double *f_ext, const mh_options *opts, double *qdd_out);
+mh_status mh_aba_parameters_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const float *pi,
+                                const double gravity[3], const float *f_ext, const mh_options *opts, float *qdd_out);
+
+/*
  * ---- state integration (MultiBodySystemStateIntegrator.doubleIntegrateFromAcceleration, tools/MultiBodySystemStateIntegrator.java:365-441,
  *      503-575, 710-733): the step downstream of forward dynamics, so that a simulation loop never leaves the device ----
  * One explicit constant-acceleration step of size dt for every joint of every configuration: 1-DoF q' = q + dt qd + dt^2/2 qdd,

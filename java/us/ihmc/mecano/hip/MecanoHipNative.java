@@ -140,6 +140,23 @@ public final class MecanoHipNative
    /** the same in fp32 */
    static final MethodHandle ABA_DERIVATIVES_F32 = handle("mh_aba_derivatives_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                                            ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** The model's own inertial parameters: (model, pi_out (host double[n_joints][10])), the layout of a row of pi below. */
+   static final MethodHandle MODEL_INERTIAL_PARAMETERS = handle("mh_model_inertial_parameters", status(ADDRESS, ADDRESS));
+   /**
+    * Inverse dynamics with per-configuration inertial parameters: (model, B, q, qd, qdd, pi, gravity[3] (host), f_ext|NULL, opts|NULL,
+    * tau_out), pi [B][n_joints][10] on the device: (mass, com, Jxx, Jxy, Jxz, Jyy, Jyz, Jzz) per joint in description order.
+    */
+   static final MethodHandle RNEA_PARAMETERS = handle("mh_rnea_parameters_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                       ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle RNEA_PARAMETERS_F32 = handle("mh_rnea_parameters_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                           ADDRESS, ADDRESS));
+   /** Forward dynamics with per-configuration inertial parameters: (model, B, q, qd, tau, pi, gravity[3] (host), f_ext|NULL, opts|NULL, qdd_out). */
+   static final MethodHandle ABA_PARAMETERS = handle("mh_aba_parameters_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                     ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle ABA_PARAMETERS_F32 = handle("mh_aba_parameters_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                         ADDRESS, ADDRESS));
    /** mh_apparent_inertia_inverse_*: the targets' own 6 x 6 blocks, or the coupled 6K x 6K matrix; at most this many targets per call */
    static final int APPARENT_BLOCKS_DIAGONAL = 0, APPARENT_BLOCKS_COUPLED = 1;
    static final int MAX_APPARENT_TARGETS = 16;

@@ -11,6 +11,7 @@
 #include "mh_response_kernels.h"
 #include "mh_minv_kernels.h"
 #include "mh_rnea_deriv_kernels.h"
+#include "mh_params_kernels.h"
 
 #include <dlfcn.h>
 #include <spawn.h>
@@ -282,6 +283,9 @@ struct mh_model
    int *d_deriv_slot = nullptr;
    int deriv_slots = 0;
    Workspace deriv;
+   // mh_model_inertial_parameters / mh_rnea_parameters_* / mh_aba_parameters_*: the description's ten inertial numbers per joint, in
+   // mh_model_desc order (host only: the kernels of mh_params_kernels.h take them per configuration from the call)
+   std::vector<double> inertial_parameters;
    Workspace ws;
    // staging buffers of the *_host entry points
    Workspace stage;
@@ -2293,6 +2297,63 @@ mh_status mass_matrix_inverse_impl(mh_model_t model, int64_t B, const T *q, int3
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
+// Inverse / forward dynamics with the inertial parameters of every configuration in the batch (mh_params_kernels.h): run-time-topology
+// kernels in the model's own workspace plan.  AoS: pi is read in place (the kernel stages it through LDS); big batches of wide state
+// matrices go through the transposed scratch copies of launch<T>, as the fixed-parameter run-time-topology calls do.
+template <typename T>
+mh_status parameters_impl(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd, const T *in3, const T *pi, const double *gravity,
+                          const T *f_ext, const mh_options *opts_in, T *out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   if (algo == ALGO_ABA && model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: forward dynamics with inertial parameters takes none", model->n_locked);
+   if (!pi)
+      return fail(MH_ERR_INVALID_ARGUMENT, "pi is NULL");
+   if (B == 0)
+      return MH_OK;
+   if (!q || !qd || !in3 || !out || (!gravity && !opts.use_root_acceleration))
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
+   st = ensure_workspace(model, B, sizeof(T));
+   if (st != MH_OK)
+      return st;
+   const Launch L = plan_launch(model, B);
+   hipStream_t stream = (hipStream_t)opts.stream;
+   const bool soa = opts.layout == MH_LAYOUT_SOA;
+   mh::ParamArgs<T> G{};
+   mh::Args<T> &A = G.a;
+   A = make_args<T>(model, B, opts, gravity);
+   A.q = q, A.qd = qd, A.in3 = in3, A.fext = f_ext, A.out = out;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = L.lanes;
+   G.pi = pi;
+   set_strides(G.p_bs, G.p_es, soa, B, (long)model->n * mh::PARAMS_PER_BODY);
+   T *t_out = nullptr;
+   if (!soa && transposes(model, B))
+   {
+      const size_t nq = model->nq, nv = model->nv;
+      st = ensure_bytes(model->tr, (size_t)B * (nq + 3 * nv) * sizeof(T));
+      if (st != MH_OK)
+         return st;
+      T *t_q = (T *)model->tr.ptr, *t_qd = t_q + (size_t)B * nq, *t_in3 = t_qd + (size_t)B * nv;
+      t_out = t_in3 + (size_t)B * nv;
+      mh::transpose_rows<T>(q, t_q, (long)B, (long)nq, true, stream);
+      mh::transpose_rows<T>(qd, t_qd, (long)B, (long)nv, true, stream);
+      mh::transpose_rows<T>(in3, t_in3, (long)B, (long)nv, true, stream);
+      A.q = t_q, A.qd = t_qd, A.in3 = t_in3, A.out = t_out;
+      A.q_bs = 1, A.q_es = B, A.v_bs = 1, A.v_es = B;
+   }
+   if (algo == ALGO_RNEA)
+      hipLaunchKernelGGL((mh::rnea_parameters_kernel<T>), dim3(L.grid), dim3(L.block), 0, stream, G);
+   else
+      hipLaunchKernelGGL((mh::aba_parameters_kernel<T>), dim3(L.grid), dim3(L.block), 0, stream, G);
+   if (t_out)
+      mh::transpose_rows<T>((const T *)t_out, out, (long)B, (long)model->nv, false, stream);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
 // Derivatives of the inverse dynamics with respect to q and qd (mh_rnea_deriv_kernels.h): run-time-topology kernel, which writes every
 // entry of its outputs -- no memset in front of it -- in a slot plan of its own (more per body than the model's common plan holds)
 static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
@@ -2760,10 +2821,21 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
       c[mh::MC_M] = mass;
       for (int k = 0; k < 3; k++)
          c[mh::MC_H + k] = h0[k] + mass * pf[k];
+      // (mh_params_kernels.h, inertia_from_parameters: the same map on the device, per configuration)
       c[mh::MC_I + 0] = I[0], c[mh::MC_I + 1] = 0.5 * (I[1] + I[3]), c[mh::MC_I + 2] = 0.5 * (I[2] + I[6]);
       c[mh::MC_I + 3] = I[4], c[mh::MC_I + 4] = 0.5 * (I[5] + I[7]), c[mh::MC_I + 5] = I[8];
    }
    m->n_slots = std::max(slots, 1);
+   m->inertial_parameters.resize((size_t)n * mh::PARAMS_PER_BODY);
+   for (int i = 0; i < n; i++)
+   {
+      double *p = &m->inertial_parameters[(size_t)i * mh::PARAMS_PER_BODY];
+      const double *J = d->inertia_J + 9 * i;
+      p[0] = d->inertia_mass[i];
+      for (int k = 0; k < 3; k++)
+         p[1 + k] = d->inertia_com[3 * i + k];
+      p[4] = J[0], p[5] = 0.5 * (J[1] + J[3]), p[6] = 0.5 * (J[2] + J[6]), p[7] = J[4], p[8] = 0.5 * (J[5] + J[7]), p[9] = J[8];
+   }
 
    // ---- gravity gradient (mh_gravity_kernels.h): the subtree masses do not depend on q; the zero pattern of its matrix is the topology's
    {
@@ -3301,6 +3373,15 @@ mh_status mh_topology_key(const mh_model_desc *desc, char key_out[17], int32_t *
 int32_t mh_model_nq(mh_model_t m) { return m ? m->nq : -1; }
 int32_t mh_model_nv(mh_model_t m) { return m ? m->nv : -1; }
 int32_t mh_model_n_joints(mh_model_t m) { return m ? m->n : -1; }
+mh_status mh_model_inertial_parameters(mh_model_t model, double *pi_out)
+{
+   if (!model)
+      return fail(MH_ERR_INVALID_ARGUMENT, "model is NULL");
+   if (!pi_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "pi_out is NULL");
+   std::copy(model->inertial_parameters.begin(), model->inertial_parameters.end(), pi_out);
+   return MH_OK;
+}
 const char *mh_model_kernel_variant(mh_model_t m) { return m ? m->variant.c_str() : ""; }
 uint32_t mh_model_warnings(mh_model_t m) { return m ? m->warnings : 0u; }
 const char *mh_model_warning_text(mh_model_t m) { return m ? m->warning_text.c_str() : ""; }
@@ -3458,7 +3539,7 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
    mh_status st = check_common(m, max_batch, nullptr);
    if (st != MH_OK)
       return st;
-   st = ensure_workspace(m, max_batch, sizeof(double));
+   st = ensure_workspace(m, max_batch, sizeof(double)); // (mh_rnea_parameters_* / mh_aba_parameters_* work in this plan too)
    if (st != MH_OK)
       return st;
    { // mh_regressor_*: one workspace block per wave, several waves per group of configurations on small batches
@@ -4087,6 +4168,26 @@ mh_status mh_aba_derivatives_f32(mh_model_t model, int64_t B, const float *q, co
                                  float *Hinv_out)
 {
    return aba_derivatives_impl<float>(model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, dqdd_dq_out, dqdd_dqd_out, Hinv_out);
+}
+mh_status mh_rnea_parameters_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double *pi,
+                                 const double gravity[3], const double *f_ext, const mh_options *opts, double *tau_out)
+{
+   return parameters_impl<double>(ALGO_RNEA, model, B, q, qd, qdd, pi, gravity, f_ext, opts, tau_out);
+}
+mh_status mh_rnea_parameters_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const float *pi,
+                                 const double gravity[3], const float *f_ext, const mh_options *opts, float *tau_out)
+{
+   return parameters_impl<float>(ALGO_RNEA, model, B, q, qd, qdd, pi, gravity, f_ext, opts, tau_out);
+}
+mh_status mh_aba_parameters_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double *pi,
+                                const double gravity[3], const double *f_ext, const mh_options *opts, double *qdd_out)
+{
+   return parameters_impl<double>(ALGO_ABA, model, B, q, qd, tau, pi, gravity, f_ext, opts, qdd_out);
+}
+mh_status mh_aba_parameters_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const float *pi,
+                                const double gravity[3], const float *f_ext, const mh_options *opts, float *qdd_out)
+{
+   return parameters_impl<float>(ALGO_ABA, model, B, q, qd, tau, pi, gravity, f_ext, opts, qdd_out);
 }
 mh_status mh_device_alloc(size_t bytes, void **ptr_out)
 {

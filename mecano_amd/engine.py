@@ -678,6 +678,65 @@ class HipModel:
             self._h, B, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), g, ptr(f_ext), ctypes.byref(opts), ptr(qdd), ptr(dq), ptr(dqd), ptr(Hinv)))
         return qdd, dq, dqd, Hinv
 
+    def inertial_parameters(self) -> np.ndarray:
+        """The model's own inertial parameters, [n_joints, 10]: (mass, com_x, com_y, com_z, Jxx, Jxy, Jxz, Jyy, Jyz, Jzz) of joint j's
+        successor body in the description's order -- ``inertia_mass``, ``inertia_com`` and the symmetric part of ``inertia_J``, the order
+        of ``regressor`` and of ``OracleModel.parameter_vector``.  A row of ``pi`` for ``rnea_parameters`` / ``aba_parameters`` is this
+        array flattened: perturb it instead of reconstructing it."""
+        out = np.empty((self.n_joints, 10), dtype=np.float64)
+        _lib.check(_lib.load().mh_model_inertial_parameters(self._h, out.ctypes.data))
+        return out
+
+    def _parameters_call(self, kind, q, qd, x3, pi, gravity, f_ext, layout, consider_coriolis, consider_accelerations, out):
+        import torch
+        if not self._is_torch(q):  # numpy in -> numpy out (float32 arrays go to the fp32 kernels)
+            ndt = np.float32 if getattr(q, "dtype", None) == np.float32 else np.float64
+            dev = lambda x: None if x is None else torch.tensor(_np(x, ndt), device="cuda")
+            res = self._parameters_call(kind, dev(q), dev(qd), dev(x3), dev(pi), gravity, dev(f_ext), layout, consider_coriolis,
+                                        consider_accelerations, None).cpu().numpy()
+            if out is not None:
+                out[...] = res
+                return out
+            return res
+        B, dt, sfx, stream = self._device_inputs([q, qd, x3], layout)
+        aos = layout == _lib.LAYOUT_AOS
+        for t in (pi, f_ext):
+            if t is not None and (not self._is_torch(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
+                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+        if pi is None:
+            raise _lib.MecanoHipError(1, "pi is None")
+        want = ((B, self.n_joints, 10), (B, self.n_joints * 10)) if aos else ((self.n_joints * 10, B),)
+        if tuple(pi.shape) not in want:
+            raise _lib.MecanoHipError(2, f"inertial parameters have shape {tuple(pi.shape)}, expected {want[0]}")
+        self._check_f_ext(f_ext, B, layout)
+        if out is None:
+            out = torch.empty_like(qd)
+        else:
+            if not self._is_torch(out) or not out.is_cuda or out.dtype != dt or not out.is_contiguous():
+                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+            if tuple(out.shape) != tuple(qd.shape):
+                raise _lib.MecanoHipError(2, f"output has shape {tuple(out.shape)}, expected {tuple(qd.shape)}")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, consider_coriolis, consider_accelerations, stream, root_acceleration=ra)
+        _lib.check(getattr(_lib.load(), f"mh_{kind}_parameters_{sfx}")(
+            self._h, B, q.data_ptr(), qd.data_ptr(), x3.data_ptr(), pi.data_ptr(), g, None if f_ext is None else f_ext.data_ptr(),
+            ctypes.byref(opts), out.data_ptr()))
+        return out
+
+    def rnea_parameters(self, q, qd, qdd, pi, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, consider_coriolis=True,
+                        consider_accelerations=True, out=None):
+        """Inverse dynamics of B different robots of this model's topology and geometry: row r is evaluated with the inertial parameters
+        ``pi[r]`` ([B, n_joints, 10]; SoA: [10 n_joints, B]; the ten numbers and their order as in ``inertial_parameters``).  Everything
+        else as for ``rnea``.  Device tensors (fp64 / fp32) stay on the device, ``out`` is a device tensor to write into; numpy in ->
+        numpy out."""
+        return self._parameters_call("rnea", q, qd, qdd, pi, gravity, f_ext, layout, consider_coriolis, consider_accelerations, out)
+
+    def aba_parameters(self, q, qd, tau, pi, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Forward dynamics of B different robots: row r with the inertial parameters ``pi[r]``, laid out as for ``rnea_parameters``;
+        everything else as for ``aba``.  A ``pi`` that is no physical inertia is not diagnosed: it shows as inf / nan in that row only.
+        A model with acceleration-source joints is refused."""
+        return self._parameters_call("aba", q, qd, tau, pi, gravity, f_ext, layout, True, True, out)
+
     def regressor(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), layout=_lib.LAYOUT_AOS, consider_coriolis=True, consider_accelerations=True,
                   first_moment_columns=False):
         """Joint torque regressor (JointTorqueRegressorCalculator.compute, JointTorqueRegressorCalculator.java:173-190): Y [B, nv, 10 n_joints]
