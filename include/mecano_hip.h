@@ -269,6 +269,14 @@ mh_status mh_reserve(mh_model_t model, int64_t max_batch);
  * f_ext is NULL or a device pointer [B][n_joints][6] (AoS) / [n_joints*6][B] (SoA) holding, for the
  * successor body of each listed joint, the external wrench (moment, force) in its body-fixed frame.
  * Calls are asynchronous on opts->stream.
+ *
+ * Aliasing.  "Alias" means the same pointer and the same shape; any other overlap of two arguments is a partial overlap.  The rules hold
+ * for the f64 and the f32 form of a call alike; they are checked on the host after the NULL checks, before anything is launched or
+ * allocated, and a refused call (MH_ERR_INVALID_ARGUMENT, mh_last_error names the two arguments that overlap) leaves its outputs untouched.
+ * mh_rnea_*, mh_aba_*: the output may be exactly one of the call's input state matrices -- qd, the third input (qdd or tau), or q where
+ * nq == nv, every joint with degrees of freedom is revolute and its entry of q is its entry of qd (a kernel reads a revolute angle once;
+ * prismatic and planar coordinates are read again after the joint's output has been stored).  The aliased call gives the bits of the
+ * out-of-place call.  The output never overlaps f_ext; a partial overlap with any input is refused.
  */
 mh_status mh_rnea_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd,
                       const double gravity[3], const double *f_ext, const mh_options *opts, double *tau_out);
@@ -291,6 +299,8 @@ mh_status mh_rnea_aba_f64(mh_model_t model, int64_t B, const double *q, const do
  * (what a whole-body controller evaluates per tick: algorithms/InverseDynamicsCalculator.java:496-501,
  * algorithms/CompositeRigidBodyMassMatrixCalculator.java:344-348): tau_out [B][nv], H_out [B][nv][nv].  With a code object the two run
  * side by side in ONE launch; otherwise as two launches, concurrently on small batches.  Same arguments as mh_rnea_f64 / mh_crba_f64.
+ * Aliasing: tau_out may be qd or qdd.  The mass matrix reads q while the inverse dynamics writes tau_out, so tau_out overlapping q is
+ * refused (also where nq == nv), as is H_out overlapping any input or tau_out (MH_ERR_INVALID_ARGUMENT).
  */
 mh_status mh_rnea_crba_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double gravity[3],
                            const double *f_ext, const mh_options *opts, double *tau_out, double *H_out);
@@ -316,7 +326,9 @@ int32_t mh_model_n_acceleration_sources(mh_model_t model);
  * :1237-1253, 1284-1297, 1315-1363).  tau [B][nv] is read at the DoFs of the effort-source joints, qdd_in [B][nv] at the DoFs of
  * the acceleration-source joints (it may be NULL when there are none).  qdd_out receives every joint's acceleration (the given
  * ones copied through); tau_out, when not NULL, every joint's effort (the given ones copied through, the efforts that realise the
- * prescribed accelerations computed).  In-place use (qdd_out == qdd_in, tau_out == tau) is allowed.
+ * prescribed accelerations computed).  Aliasing: qdd_out is qdd_in or disjoint from every input (q, qd, tau, qdd_in, f_ext); tau_out is
+ * tau or disjoint from every input; qdd_out and tau_out are disjoint from each other.  Everything else is refused
+ * (MH_ERR_INVALID_ARGUMENT) -- qdd_out == tau among it: the kernel stores a joint's acceleration and then copies its effort through.
  */
 mh_status mh_aba_locked_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double *qdd_in,
                             const double gravity[3], const double *f_ext, const mh_options *opts, double *qdd_out, double *tau_out);
@@ -329,6 +341,8 @@ mh_status mh_aba_locked_f64(mh_model_t model, int64_t B, const double *q, const 
  * out like f_ext; either may be NULL.  As in the reference the acceleration carries the root acceleration -g, and the RNEA switches
  * apply (consider_coriolis = 0: velocity terms dropped and twists reported as zero).  Models with a tree-split code object, identity
  * index maps and AoS matrices run variants of the tree-split kernels that write them as well; every other case the run-time-topology kernels.
+ * Aliasing: tau_out / qdd_out as in mh_rnea_* / mh_aba_*; body_acc_out and body_twist_out must be disjoint from every input, from
+ * tau_out / qdd_out and from each other (MH_ERR_INVALID_ARGUMENT otherwise).
  */
 mh_status mh_rnea_bodies_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double gravity[3],
                              const double *f_ext, const mh_options *opts, double *tau_out, double *body_acc_out, double *body_twist_out);
@@ -342,6 +356,9 @@ mh_status mh_aba_bodies_f64(mh_model_t model, int64_t B, const double *q, const 
  * before projection onto the motion subspace, expressed in the joint's frame after the joint: joint_wrench_out [B][n_joints][6], laid
  * out like f_ext.  tau = S^T wrench.  The forward-dynamics form evaluates, like the reference, a Newton-Euler sweep over the accelerations
  * it has just computed (a second launch on the same stream); it needs every joint to be an effort source.  Run-time-topology kernels.
+ * Aliasing: tau_out of mh_rnea_joint_wrenches_f64 as in mh_rnea_*.  qdd_out of mh_aba_joint_wrenches_f64 may be tau and no other input:
+ * the second launch reads q, qd and f_ext again, beside the accelerations.  joint_wrench_out must be disjoint from every input and from
+ * tau_out / qdd_out.  MH_ERR_INVALID_ARGUMENT otherwise.
  */
 mh_status mh_rnea_joint_wrenches_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double gravity[3],
                                      const double *f_ext, const mh_options *opts, double *tau_out, double *joint_wrench_out);
@@ -547,7 +564,8 @@ mh_status mh_aba_derivatives_f32(mh_model_t model, int64_t B, const float *q, co
  * Gravity, f_ext, opts->root_acceleration, the two switches of mh_rnea_*, stream and context behave as in mh_rnea_* / mh_aba_*; while any
  * joint is MH_ACCELERATION_SOURCE, mh_aba_parameters_* returns MH_ERR_INVALID_ARGUMENT as mh_aba_* does.  pi = NULL is
  * MH_ERR_INVALID_ARGUMENT.  A pi that is no physical inertia is not diagnosed: like the reference's unguarded 1/D it shows as inf / nan
- * in that row only, and the call returns MH_OK.  The output may alias an input, as in the single calls.  Run-time-topology kernels for
+ * in that row only, and the call returns MH_OK.  Aliasing as in mh_rnea_* / mh_aba_*: the output may be qd, the third input, or q under
+ * the conditions given there; it never overlaps f_ext or pi, and a partial overlap is refused.  Run-time-topology kernels for
  * every model (mh_params_kernels.h); device pointers, asynchronous on opts->stream; after mh_reserve and one first call the entry points
  * only enqueue work (graph-capturable).
  */
@@ -567,7 +585,9 @@ mh_status mh_aba_parameters_f32(mh_model_t model, int64_t B, const float *q, con
  * One explicit constant-acceleration step of size dt for every joint of every configuration: 1-DoF q' = q + dt qd + dt^2/2 qdd,
  * qd' = qd + dt qdd; 6-DoF joints integrate the pose with the rotation vector dt w + dt^2/2 dw appended to the quaternion and
  * re-express twist and acceleration in the new frame after the joint, exactly as the reference does.  q_out [B][nq], qd_out [B][nv]
- * and (optional, may be NULL) qdd_out [B][nv] may alias the inputs (in-place step).  Entries no considered joint owns are not written.
+ * and (optional, may be NULL) qdd_out [B][nv] may be their own inputs (in-place step: q_out == q, qd_out == qd, qdd_out == qdd); any other
+ * overlap of an output with an input or with another output is refused (MH_ERR_INVALID_ARGUMENT).  Entries no considered joint owns are
+ * not written.
  * Device pointers, asynchronous on opts->stream; opts->layout as for the other calls.
  */
 mh_status mh_integrate_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *qdd,
@@ -577,8 +597,9 @@ mh_status mh_integrate_f64(mh_model_t model, int64_t B, double dt, const double 
  * integrate(q, qd, qdd_out).  Same results as mh_aba_f64 followed by mh_integrate_f64 (ForwardDynamicsCalculator.compute +
  * MultiBodySystemStateIntegrator.doubleIntegrateFromAcceleration; the loop of MultiBodySystemStateIntegratorTest.java:245-250).  Models
  * with a tree-split code object, identity index maps and AoS matrices run it as ONE launch (the new state is formed from the rows the
- * forward-dynamics kernel already holds in LDS); every other case issues the two launches.  q_next / qd_next may alias q / qd;
- * qdd_out is the forward-dynamics result (not re-expressed by the step).
+ * forward-dynamics kernel already holds in LDS); every other case issues the two launches.  Aliasing: q_next may be q and qd_next may be
+ * qd; qdd_out must be disjoint from every input and from q_next and qd_next (the step reads it again); any other overlap is refused
+ * (MH_ERR_INVALID_ARGUMENT).  qdd_out is the forward-dynamics result (not re-expressed by the step).
  */
 mh_status mh_aba_integrate_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *tau,
                                const double gravity[3], const double *f_ext, const mh_options *opts, double *qdd_out, double *q_next,

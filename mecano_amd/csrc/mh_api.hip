@@ -345,6 +345,10 @@ struct mh_model
    int dense_maps = 0;      // nq / nv equal the joints' totals (no unused matrix rows): rows can be staged as dense blocks
    int force_io = -1, force_st = -1; // MH_SPEC_IO / MH_SPEC_ST = 0 | 1 override the heuristics (measurements)
    int n_locked = 0;        // joints in MH_ACCELERATION_SOURCE mode (mh_model_set_joint_source_modes)
+   // an output of nv columns may be q itself: nq == nv, every joint with DoFs is revolute, and its row of q is its row of qd.  A kernel
+   // reads a revolute joint's angle once (cos, sin live on in registers or workspace) and writes only that joint's entry of the output;
+   // prismatic and planar coordinates are read from q again after the joint's output has been stored (joint_again, mh_kernels.h)
+   int q_may_be_out = 0;
 };
 
 struct mh_context
@@ -474,6 +478,52 @@ mh_status begin_call(mh_model_t &model, int64_t B, const mh_options *opts_in, mh
 
 // groups of 64 configurations: one wave, or one workgroup of four waves, each
 long groups_of(int64_t B) { return (B + 63) / 64; }
+
+// ---- the aliasing contract of the compute calls (include/mecano_hip.h, "Aliasing").  Host-side pointer comparisons, made after the NULL
+// checks and before anything is launched or allocated: a refused call leaves its outputs untouched.
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
+{
+   const char *a0 = (const char *)a, *b0 = (const char *)b;
+   return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
+}
+struct InRange
+{
+   const char *name;
+   const void *p;
+   size_t bytes;
+};
+struct OutRange
+{
+   const char *name;
+   const void *p;
+   size_t bytes;
+   unsigned may_be; // bit i: the output may BE input i -- the same pointer and the same size
+};
+// An output may be at most one of the inputs its mask names; any other overlap with an input, and any overlap of two outputs, is refused.
+// NULL pointers and empty ranges overlap nothing.
+mh_status check_aliasing(const char *call, const InRange *ins, int n_ins, const OutRange *outs, int n_outs)
+{
+   for (int o = 0; o < n_outs; o++)
+   {
+      const char *is = nullptr;
+      for (int i = 0; i < n_ins; i++)
+      {
+         if (!ranges_overlap(outs[o].p, outs[o].bytes, ins[i].p, ins[i].bytes))
+            continue;
+         const bool same = outs[o].p == ins[i].p && outs[o].bytes == ins[i].bytes;
+         if (!same || !((outs[o].may_be >> i) & 1u))
+            return fail(MH_ERR_INVALID_ARGUMENT, "%s: %s must not overlap %s%s", call, outs[o].name, ins[i].name,
+                        same ? "" : ((outs[o].may_be >> i) & 1u) ? " (it may be that matrix itself, not a part of it)" : "");
+         if (is)
+            return fail(MH_ERR_INVALID_ARGUMENT, "%s: %s overlaps both %s and %s (it may be one input, not two)", call, outs[o].name, is, ins[i].name);
+         is = ins[i].name;
+      }
+      for (int p = o + 1; p < n_outs; p++)
+         if (ranges_overlap(outs[o].p, outs[o].bytes, outs[p].p, outs[p].bytes))
+            return fail(MH_ERR_INVALID_ARGUMENT, "%s: the outputs %s and %s overlap", call, outs[o].name, outs[p].name);
+   }
+   return MH_OK;
+}
 
 // (batch stride, element stride) of a matrix with rows of n entries in the call's layout
 void set_strides(long &bs, long &es, bool soa, int64_t B, long n) { bs = soa ? 1 : n, es = soa ? B : 1; }
@@ -1339,6 +1389,15 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
    if (algo == ALGO_ABA && model->n_locked > 0 && !x.locked_in)
       return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: forward dynamics needs their accelerations, use mh_aba_locked_f64",
                   model->n_locked);
+   if (algo != ALGO_CRBA)
+   { // the output may be qd, the third input, or q where nq == nv; the per-body / per-joint outputs are disjoint from everything
+      const size_t bq = (size_t)B * model->nq * sizeof(T), bv = (size_t)B * model->nv * sizeof(T), bf = (size_t)B * model->n * 6 * sizeof(T);
+      const InRange ins[4] = {{"q", q, bq}, {"qd", qd, bv}, {algo == ALGO_RNEA ? "qdd" : "tau", in3, bv}, {"f_ext", fext, bf}};
+      const OutRange outs[4] = {{algo == ALGO_RNEA ? "tau_out" : "qdd_out", out, bv, model->q_may_be_out ? 7u : 6u}, {"body_acc_out", x.body_acc, bf, 0u},
+                                {"body_twist_out", x.body_twist, bf, 0u}, {"joint_wrench_out", x.joint_wrench, bf, 0u}};
+      if ((st = check_aliasing(algo == ALGO_RNEA ? "inverse dynamics" : "forward dynamics", ins, 4, outs, 4)) != MH_OK)
+         return st;
+   }
    // the sweep kernels' per-body workspace (plain RNEA / ABA calls run on the depth-first kernels, which size their own)
    // fp64 ABA stays on the sweep kernel: the depth-first walk fuses passes one and two, which in fp64 costs the whole register file plus
    // scratch (512 registers + 320 B against 310 and none) -- measured slower at every batch size on every 25..30-body model (humanoid
@@ -1650,20 +1709,34 @@ template <typename T>
 mh_status aba_locked(mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const T *qdd_in, const double gravity[3], const T *f_ext,
                      const mh_options *opts, T *qdd_out, T *tau_out)
 {
-   if (!model)
-      return fail(MH_ERR_INVALID_ARGUMENT, "model is NULL");
+   // the call's own validation first (launch<T> repeats it on the context's copy), then the aliasing rule, then any launch
+   mh_options o;
+   mh_status st0 = begin_call(model, B, opts, o);
+   if (st0 != MH_OK)
+      return st0;
+   if (B > 0 && (!q || !qd || !tau || !qdd_out || (!gravity && !o.use_root_acceleration)))
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
+   if (B > 0)
+   { // qdd_out is qdd_in or apart from every input, tau_out is tau or apart from every input: the outward pass stores a joint's acceleration
+     // and then copies its effort through, so qdd_out == tau would hand accelerations to tau_out
+      const size_t bq = (size_t)B * model->nq * sizeof(T), bv = (size_t)B * model->nv * sizeof(T), bf = (size_t)B * model->n * 6 * sizeof(T);
+      const InRange ins[5] = {{"q", q, bq}, {"qd", qd, bv}, {"tau", tau, bv}, {"qdd_in", qdd_in, bv}, {"f_ext", f_ext, bf}};
+      const OutRange outs[2] = {{"qdd_out", qdd_out, bv, 1u << 3}, {"tau_out", tau_out, bv, 1u << 2}};
+      if (const mh_status sa = check_aliasing("mh_aba_locked", ins, 5, outs, 2); sa != MH_OK)
+         return sa;
+   }
    if (model->n_locked == 0)
    { // nothing is locked: the ordinary forward dynamics, efforts copied through
-      mh_status st = launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out);
+      mh_status st = launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &o, qdd_out);
       if (st == MH_OK && tau_out && tau_out != tau && B > 0)
-         HIP_TRY(hipMemcpyAsync(tau_out, tau, (size_t)B * model->nv * sizeof(T), hipMemcpyDeviceToDevice, opts ? (hipStream_t)opts->stream : nullptr));
+         HIP_TRY(hipMemcpyAsync(tau_out, tau, (size_t)B * model->nv * sizeof(T), hipMemcpyDeviceToDevice, (hipStream_t)o.stream));
       return st;
    }
    if (B > 0 && !qdd_in)
       return fail(MH_ERR_INVALID_ARGUMENT, "qdd_in is NULL but %d joint(s) are acceleration sources", model->n_locked);
    LaunchExtras<T> x;
    x.locked_in = qdd_in, x.locked_out = tau_out;
-   return launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, x);
+   return launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &o, qdd_out, x);
 }
 
 // Host-pointer front end (what a JNI / Panama shim with heap or off-heap arrays calls).  The batch is cut into chunks of rows that travel
@@ -2316,6 +2389,14 @@ mh_status parameters_impl(Algo algo, mh_model_t model, int64_t B, const T *q, co
       return MH_OK;
    if (!q || !qd || !in3 || !out || (!gravity && !opts.use_root_acceleration))
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
+   {
+      const size_t bq = (size_t)B * model->nq * sizeof(T), bv = (size_t)B * model->nv * sizeof(T), bj = (size_t)B * model->n * sizeof(T);
+      const InRange ins[5] = {{"q", q, bq}, {"qd", qd, bv}, {algo == ALGO_RNEA ? "qdd" : "tau", in3, bv}, {"f_ext", f_ext, 6 * bj},
+                              {"pi", pi, mh::PARAMS_PER_BODY * bj}};
+      const OutRange o1 = {algo == ALGO_RNEA ? "tau_out" : "qdd_out", out, bv, model->q_may_be_out ? 7u : 6u};
+      if ((st = check_aliasing(algo == ALGO_RNEA ? "mh_rnea_parameters" : "mh_aba_parameters", ins, 5, &o1, 1)) != MH_OK)
+         return st;
+   }
    st = ensure_workspace(model, B, sizeof(T));
    if (st != MH_OK)
       return st;
@@ -2356,11 +2437,6 @@ mh_status parameters_impl(Algo algo, mh_model_t model, int64_t B, const T *q, co
 }
 // Derivatives of the inverse dynamics with respect to q and qd (mh_rnea_deriv_kernels.h): run-time-topology kernel, which writes every
 // entry of its outputs -- no memset in front of it -- in a slot plan of its own (more per body than the model's common plan holds)
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb)
-{
-   const char *a0 = (const char *)a, *b0 = (const char *)b;
-   return a && b && na && nb && a0 < b0 + nb && b0 < a0 + na;
-}
 static size_t deriv_ws_bytes(const mh_model *m, const Launch &L, int parts, size_t elem)
 {
    return (size_t)m->deriv_slots * (size_t)L.lanes * (size_t)parts * elem;
@@ -2506,6 +2582,13 @@ mh_status integrate_impl(mh_model_t model, int64_t B, double dt, const T *q, con
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
    if (nan_bits(dt))
       return fail(MH_ERR_INVALID_ARGUMENT, "dt is NaN");
+   { // the in-place step: every output may be its own input, nothing else
+      const size_t bq = (size_t)B * model->nq * sizeof(T), bv = (size_t)B * model->nv * sizeof(T);
+      const InRange ins[3] = {{"q", q, bq}, {"qd", qd, bv}, {"qdd", qdd, bv}};
+      const OutRange outs[3] = {{"q_out", q_out, bq, 1u}, {"qd_out", qd_out, bv, 2u}, {"qdd_out", qdd_out, bv, 4u}};
+      if ((st = check_aliasing("mh_integrate", ins, 3, outs, 3)) != MH_OK)
+         return st;
+   }
    mh::IntArgs<T> A;
    A.m = dev_model<T>(model);
    A.B = B, A.dt = (T)dt;
@@ -2722,6 +2805,10 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
       m->ident_maps = m->dof_map[k] == k;
    for (int k = 0; m->ident_maps && k < ecfgo[n]; k++)
       m->ident_maps = m->cfg_map[k] == k;
+   m->q_may_be_out = d->nq == d->nv;
+   for (int i = 0; m->q_may_be_out && i < n; i++)
+      if (dofo[i + 1] > dofo[i])
+         m->q_may_be_out = d->joint_type[i] == MH_JOINT_REVOLUTE && d->cfg_indices[cfgo[i]] == d->dof_indices[dofo[i]];
    if (m->dof_map.empty())
       m->dof_map.push_back(0);
    if (m->cfg_map.empty())
@@ -3711,13 +3798,26 @@ mh_status mh_integrate_f64(mh_model_t model, int64_t B, double dt, const double 
    return integrate_impl<double>(model, B, dt, q, qd, qdd, opts, q_out, qd_out, qdd_out);
 }
 mh_status mh_aba_integrate_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *tau,
-                               const double gravity[3], const double *f_ext, const mh_options *opts, double *qdd_out, double *q_next,
+                               const double gravity[3], const double *f_ext, const mh_options *opts_in, double *qdd_out, double *q_next,
                                double *qd_next)
 {
-   if (B > 0 && (!q_next || !qd_next))
+   mh_options o;
+   mh_status st0 = begin_call(model, B, opts_in, o);
+   if (st0 != MH_OK)
+      return st0;
+   if (B > 0 && (!q || !qd || !tau || !qdd_out || !q_next || !qd_next || (!gravity && !o.use_root_acceleration)))
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
    if (nan_bits(dt))
       return fail(MH_ERR_INVALID_ARGUMENT, "dt is NaN");
+   const mh_options *opts = &o;
+   if (B > 0)
+   { // the new state may replace the old one; qdd_out is read again by the step, after the new state of other rows may have been written
+      const size_t bq = (size_t)B * model->nq * sizeof(double), bv = (size_t)B * model->nv * sizeof(double);
+      const InRange ins[4] = {{"q", q, bq}, {"qd", qd, bv}, {"tau", tau, bv}, {"f_ext", f_ext, (size_t)B * model->n * 6 * sizeof(double)}};
+      const OutRange outs[3] = {{"qdd_out", qdd_out, bv, 0u}, {"q_next", q_next, bq, 1u}, {"qd_next", qd_next, bv, 2u}};
+      if (const mh_status sa = check_aliasing("mh_aba_integrate_f64", ins, 4, outs, 3); sa != MH_OK)
+         return sa;
+   }
    bool stepped = false;
    LaunchExtras<double> x;
    x.dt = dt, x.q_next = q_next, x.qd_next = qd_next, x.stepped = &stepped;
@@ -3758,6 +3858,15 @@ mh_status mh_aba_joint_wrenches_f64(mh_model_t model, int64_t B, const double *q
    mh_status st = begin_call(model, B, opts, o);
    if (st != MH_OK)
       return st;
+   if (B > 0)
+   { // before the first launch: the second one reads q, qd, f_ext and qdd_out again while it writes the wrenches
+      const size_t bv = (size_t)B * model->nv * sizeof(double), bf = (size_t)B * model->n * 6 * sizeof(double);
+      const InRange ins[4] = {{"q", q, (size_t)B * model->nq * sizeof(double)}, {"qd", qd, bv}, {"tau", tau, bv}, {"f_ext", f_ext, bf}};
+      // (so qdd_out may be tau, which the second launch does not read, and nothing else)
+      const OutRange outs[2] = {{"qdd_out", qdd_out, bv, 4u}, {"joint_wrench_out", joint_wrench_out, bf, 0u}};
+      if ((st = check_aliasing("mh_aba_joint_wrenches_f64", ins, 4, outs, 2)) != MH_OK)
+         return st;
+   }
    st = launch<double>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &o, qdd_out);
    if (st != MH_OK || B == 0)
       return st;
@@ -3956,6 +4065,14 @@ mh_status mh_rnea_crba_f64(mh_model_t model, int64_t B, const double *q, const d
       return MH_OK;
    if (!q || !qd || !qdd || (!gravity && !opts.use_root_acceleration) || !tau_out || !H_out)
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
+   { // the mass matrix reads q while the inverse dynamics writes tau_out: tau_out may be qd or qdd, never q; H_out is apart from everything
+      const size_t bv = (size_t)B * model->nv * sizeof(double);
+      const InRange ins[4] = {{"q", q, (size_t)B * model->nq * sizeof(double)}, {"qd", qd, bv}, {"qdd", qdd, bv},
+                              {"f_ext", f_ext, (size_t)B * model->n * 6 * sizeof(double)}};
+      const OutRange outs[2] = {{"tau_out", tau_out, bv, 6u}, {"H_out", H_out, bv * model->nv, 0u}};
+      if ((st = check_aliasing("mh_rnea_crba_f64", ins, 4, outs, 2)) != MH_OK)
+         return st;
+   }
    hipStream_t s = (hipStream_t)opts.stream;
    const long groups = groups_of(B);
    // one launch: tree-split RNEA groups and tree-split CRBA groups side by side (code object with identity maps, AoS, no switches, no

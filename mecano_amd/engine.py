@@ -217,7 +217,7 @@ class HipModel:
 
     def aba_locked(self, q, qd, tau, qdd_in, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS):
         """Forward dynamics with acceleration-source joints: returns (qdd, tau) of all DoFs (fp64).  numpy inputs are moved to
-        the current HIP device and the results back."""
+        the current HIP device and the results back.  (The C call takes qdd_out == qdd_in and tau_out == tau, no other overlap.)"""
         import torch
         lib = _lib.load()
         host = not self._is_torch(q)
@@ -322,7 +322,8 @@ class HipModel:
 
     def integrate(self, dt, q, qd, qdd, layout=_lib.LAYOUT_AOS, out=None, return_acceleration=False):
         """One step of MultiBodySystemStateIntegrator.doubleIntegrateFromAcceleration on device tensors (fp64 / fp32).  ``out`` =
-        (q_out, qd_out[, qdd_out]) may name the inputs themselves for an in-place step; by default new tensors are returned."""
+        (q_out, qd_out[, qdd_out]) may name the inputs themselves for an in-place step (each output its own input; any other overlap is
+        refused); by default new tensors are returned."""
         import torch
         lib = _lib.load()
         dt_ = q.dtype
@@ -347,7 +348,7 @@ class HipModel:
 
     def step(self, dt, q, qd, tau, gravity=(0.0, 0.0, -9.81), f_ext=None, inplace=False):
         """One simulation step (forward dynamics + state integration, mh_aba_integrate_f64): returns (q_next, qd_next, qdd).  AoS fp64
-        device tensors; ``inplace=True`` overwrites q and qd."""
+        device tensors; ``inplace=True`` overwrites q and qd (q_next == q, qd_next == qd; qdd is always a tensor of its own)."""
         import torch
         lib = _lib.load()
         for t in (q, qd, tau) + ((f_ext,) if f_ext is not None else ()):
@@ -727,13 +728,13 @@ class HipModel:
                         consider_accelerations=True, out=None):
         """Inverse dynamics of B different robots of this model's topology and geometry: row r is evaluated with the inertial parameters
         ``pi[r]`` ([B, n_joints, 10]; SoA: [10 n_joints, B]; the ten numbers and their order as in ``inertial_parameters``).  Everything
-        else as for ``rnea``.  Device tensors (fp64 / fp32) stay on the device, ``out`` is a device tensor to write into; numpy in ->
-        numpy out."""
+        else as for ``rnea``.  Device tensors (fp64 / fp32) stay on the device, ``out`` is a device tensor to write into -- it may be qd or
+        qdd themselves (include/mecano_hip.h, "Aliasing"), any other overlap with an input is refused; numpy in -> numpy out."""
         return self._parameters_call("rnea", q, qd, qdd, pi, gravity, f_ext, layout, consider_coriolis, consider_accelerations, out)
 
     def aba_parameters(self, q, qd, tau, pi, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
         """Forward dynamics of B different robots: row r with the inertial parameters ``pi[r]``, laid out as for ``rnea_parameters``;
-        everything else as for ``aba``.  A ``pi`` that is no physical inertia is not diagnosed: it shows as inf / nan in that row only.
+        everything else as for ``aba`` (``out`` may be qd or tau themselves, no other overlap).  A ``pi`` that is no physical inertia is not diagnosed: it shows as inf / nan in that row only.
         A model with acceleration-source joints is refused."""
         return self._parameters_call("aba", q, qd, tau, pi, gravity, f_ext, layout, True, True, out)
 

@@ -403,7 +403,14 @@ def test_pair_call_refuses_outputs_that_overlap_its_inputs(torch_cuda):
             with pytest.raises(_lib.MecanoHipError) as e:
                 hm.bind_rnea_aba(q, qd, qdd, tau, bad[0], bad[1], G)()
             assert "overlap" in str(e.value)
-        # in place, one after the other
-        t_ref = hm.rnea(q, qd, qdd, G)
+        # in place, one after the other: mh_rnea_* with tau_out == qdd, then mh_aba_* with qdd_out == tau, on copies
+        lib, sfx = _lib.load(), "f64" if dt == torch.float64 else "f32"
+        g, _ = hm._root(G)
+        opts = hm._options(_lib.LAYOUT_AOS, stream=torch.cuda.current_stream().cuda_stream)
+        t_ref, a_ref = qdd.clone(), tau.clone()
+        _lib.check(getattr(lib, f"mh_rnea_{sfx}")(hm._h, 256, q.data_ptr(), qd.data_ptr(), t_ref.data_ptr(), g, None, ctypes.byref(opts), t_ref.data_ptr()))
+        _lib.check(getattr(lib, f"mh_aba_{sfx}")(hm._h, 256, q.data_ptr(), qd.data_ptr(), a_ref.data_ptr(), g, None, ctypes.byref(opts), a_ref.data_ptr()))
+        torch.cuda.synchronize()
         assert torch.equal(t_ref, o1) or (t_ref - o1).abs().max().item() <= 1e-4
+        assert torch.equal(a_ref, o2) or (a_ref - o2).abs().max().item() <= 1e-4
 
