@@ -551,6 +551,48 @@ mh_status mh_aba_derivatives_f32(mh_model_t model, int64_t B, const float *q, co
                                  float *Hinv_out);
 
 /*
+ * ---- the chart of the velocity-space derivatives, and the linearisation of the simulation step ----
+ * mh_configuration_add_*: q_out [B][nq] = q (+) dq, dq [B][nv]: the pure configuration step every gradient above is defined in --
+ * MultiBodySystemStateIntegrator.integrateFromVelocity with dt = 1 and twist dq (tools/MultiBodySystemStateIntegrator.java:164-243), per
+ * joint: 1-DoF q + dq; SixDoF Q' = Q exp(dth), p' = p + R(Q) dp with the INITIAL orientation; spherical the rotational half; planar the same
+ * rule in the XZ plane; fixed joints have nothing to update.  (mh_integrate_* with qd = dq is NOT this step: its double integrator adds a
+ * w x v term.)  Entries of q_out no joint owns are not written.  q_out may be q itself; any other overlap is refused.
+ * mh_configuration_difference_*: the dq_out [B][nv] with q0 (+) dq_out = q1: rotations as the rotation vector of Q0^-1 Q1 in its shortest
+ * form (|dth| <= pi; both quaternions are normalised on input), dp = R(Q0)^T (p1 - p0), a planar pitch as the plain difference (not
+ * wrapped).  DoF entries no joint owns are written as 0.  dq_out overlaps neither input.
+ * Both: device pointers, asynchronous on opts->stream, opts->layout, index maps and contexts honoured; one elementwise
+ * run-time-topology kernel, nothing allocated (graph-capturable); B = 0 returns MH_OK and touches nothing.
+ * mh_aba_integrate_derivatives_*: the discrete pair (A, B) of the step mh_aba_integrate_f64 takes -- mh_aba_* followed by mh_integrate_*
+ * with step dt --, x' = step(x, u), dx' = A dx + B du with x = (q, qd), dx = (dq, dqd) in R^(2 nv) and u = tau.  dq is a velocity-space
+ * step in the (+) above and dq' the velocity-space step of q_next, q_next(x (+) dx) (-) q_next(x); dqd and dqd' are plain component
+ * increments (for a SixDoF joint qd_next is expressed in the NEW frame after the joint, as mh_integrate_* returns it); external wrenches
+ * are held fixed IN THE WORLD, as in mh_aba_derivatives_*.  A_out [B][2 nv][2 nv] row-major, rows and columns over dq in the model's DoF
+ * index space, then dqd; B_out [B][2 nv][nv]; MH_LAYOUT_SOA: [(2 nv)^2][B] and [2 nv nv][B].  Either matrix may be NULL, not both;
+ * qdd_out may be NULL; q_next and qd_next may be NULL only together, and given they are what mh_integrate_* gives for the call's qdd (one
+ * more launch of the integrator kernel).  Rows and columns of DoF indices no joint owns are zero; every entry of both matrices is
+ * written (no memset needed), nothing outside the outputs.  The outputs overlap neither the inputs nor each other -- q_next == q and
+ * qd_next == qd included: the matrices are formed from the old state.  dt may be 0 (A = identity on owned DoFs, B = 0, exactly) or
+ * negative; a dt that is not finite is MH_ERR_INVALID_ARGUMENT, as are MH_ACCELERATION_SOURCE joints in the model.  B = 0 or nv = 0
+ * returns MH_OK and touches nothing.  opts->use_root_acceleration is honoured.  Launches composed on opts->stream: mh_aba_derivatives_*
+ * with d qdd / d q, d qdd / d qd and H^-1 in scratch of the context (set aside by mh_reserve / mh_context_reserve while all of it stays
+ * within 4 GiB; a larger need is met at the first call), and one assembly kernel that reads each element of the three once and writes
+ * each element of A and B once, rows contiguous across lanes in both layouts.  After reserve and one first call the entry point only
+ * enqueues work.
+ */
+mh_status mh_configuration_add_f64(mh_model_t model, int64_t B, const double *q, const double *dq, const mh_options *opts, double *q_out);
+mh_status mh_configuration_add_f32(mh_model_t model, int64_t B, const float *q, const float *dq, const mh_options *opts, float *q_out);
+mh_status mh_configuration_difference_f64(mh_model_t model, int64_t B, const double *q0, const double *q1, const mh_options *opts,
+                                          double *dq_out);
+mh_status mh_configuration_difference_f32(mh_model_t model, int64_t B, const float *q0, const float *q1, const mh_options *opts,
+                                          float *dq_out);
+mh_status mh_aba_integrate_derivatives_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *tau,
+                                           const double gravity[3], const double *f_ext, const mh_options *opts, double *qdd_out,
+                                           double *q_next, double *qd_next, double *A_out, double *B_out);
+mh_status mh_aba_integrate_derivatives_f32(mh_model_t model, int64_t B, double dt, const float *q, const float *qd, const float *tau,
+                                           const double gravity[3], const float *f_ext, const mh_options *opts, float *qdd_out,
+                                           float *q_next, float *qd_next, float *A_out, float *B_out);
+
+/*
  * ---- inverse and forward dynamics with per-configuration inertial parameters: B different robots of one topology and geometry
  *      (domain randomisation, identification by simulation error, payload sweeps; no calculator of the reference evaluates a batch) ----
  * pi (DEVICE) is [B][n_joints][10], MH_LAYOUT_SOA: [10 n_joints][B] (opts->layout, as for every other matrix of the call).  The ten

@@ -140,6 +140,23 @@ public final class MecanoHipNative
    /** the same in fp32 */
    static final MethodHandle ABA_DERIVATIVES_F32 = handle("mh_aba_derivatives_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                                            ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** q_out = q (+) dq, the pure configuration step of the velocity-space derivatives: (model, B, q, dq, opts|NULL, q_out); q_out may be q. */
+   static final MethodHandle CONFIGURATION_ADD = handle("mh_configuration_add_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle CONFIGURATION_ADD_F32 = handle("mh_configuration_add_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** The dq_out with q0 (+) dq_out = q1: (model, B, q0, q1, opts|NULL, dq_out). */
+   static final MethodHandle CONFIGURATION_DIFFERENCE = handle("mh_configuration_difference_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle CONFIGURATION_DIFFERENCE_F32 = handle("mh_configuration_difference_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * Linearisation of the simulation step: (model, B, dt, q, qd, tau, gravity[3] (host), f_ext|NULL, opts|NULL, qdd_out|NULL, q_next|NULL,
+    * qd_next|NULL, A_out|NULL, B_out|NULL), A [B][2 nv][2 nv], B [B][2 nv][nv] row-major; not both matrices NULL, q_next and qd_next together.
+    */
+   static final MethodHandle ABA_INTEGRATE_DERIVATIVES = handle("mh_aba_integrate_derivatives_f64", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                                           ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle ABA_INTEGRATE_DERIVATIVES_F32 = handle("mh_aba_integrate_derivatives_f32", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                                               ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
    /** The model's own inertial parameters: (model, pi_out (host double[n_joints][10])), the layout of a row of pi below. */
    static final MethodHandle MODEL_INERTIAL_PARAMETERS = handle("mh_model_inertial_parameters", status(ADDRESS, ADDRESS));
    /**

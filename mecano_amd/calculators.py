@@ -440,6 +440,12 @@ class ForwardDynamicsCalculator(_Base):
         an effort source."""
         return self.model.aba_derivatives(q, qd, tau, self._gravity, self._f_ext, self.layout)
 
+    def getStepLinearization(self, dt, q, qd, tau):
+        """No counterpart in the reference: (qdd, q_next, qd_next, A, B) of B states, the discrete linearisation dx' = A dx + B dtau of
+        forward dynamics followed by one integrator step of size ``dt`` (``HipModel.step_derivatives``), with this calculator's gravity or
+        root acceleration and external wrenches.  Every joint must be an effort source."""
+        return self.model.step_derivatives(dt, q, qd, tau, self._gravity, self._f_ext, self.layout)
+
     def getComputedJointAcceleration(self, joint):
         """``getComputedJointAcceleration(joint)`` (:600-610): N x 1 after a one-configuration compute, None for a joint that is not considered."""
         if not getattr(self, "_single", False):

@@ -12,6 +12,7 @@
 #include "mh_minv_kernels.h"
 #include "mh_rnea_deriv_kernels.h"
 #include "mh_params_kernels.h"
+#include "mh_step_kernels.h"
 
 #include <dlfcn.h>
 #include <spawn.h>
@@ -94,6 +95,14 @@ M3d frame_with_z(const double k[3])
 // NaN tests on raw 64-bit words that never pass through a `double` value: this translation unit is built with -ffinite-math-only, under
 // which x != x folds to false AND double parameters carry nofpclass(nan), so that even a bit test on a double argument may be folded away
 inline bool nan_word(unsigned long long u) { return (u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull && (u & 0x000fffffffffffffull) != 0; }
+inline bool nonfinite_word(unsigned long long u) { return (u & 0x7ff0000000000000ull) == 0x7ff0000000000000ull; }
+inline bool nonfinite_bits(const double &x)
+{
+   unsigned long long u;
+   std::memcpy(&u, (const void *)&x, sizeof u);
+   asm volatile("" : "+r"(u));
+   return nonfinite_word(u);
+}
 inline bool nan_bits(const double &x)
 {
    unsigned long long u;
@@ -283,6 +292,8 @@ struct mh_model
    int *d_deriv_slot = nullptr;
    int deriv_slots = 0;
    Workspace deriv;
+   // mh_aba_integrate_derivatives_*: d qdd / d q and d qdd / d qd of the call (Hinv and qdd go to `deriv`)
+   Workspace step;
    // mh_model_inertial_parameters / mh_rnea_parameters_* / mh_aba_parameters_*: the description's ten inertial numbers per joint, in
    // mh_model_desc order (host only: the kernels of mh_params_kernels.h take them per configuration from the call)
    std::vector<double> inertial_parameters;
@@ -2445,6 +2456,7 @@ static size_t deriv_ws_bytes(const mh_model *m, const Launch &L, int parts, size
 // met at the first such call
 constexpr size_t kDerivReserveCap = (size_t)4 << 30;
 static size_t deriv_scratch_bytes(const mh_model *m, int64_t B, size_t elem) { return (size_t)B * ((size_t)m->nv * m->nv + (size_t)m->nv) * elem; }
+static size_t step_scratch_bytes(const mh_model *m, int64_t B, size_t elem) { return (size_t)B * 2 * (size_t)m->nv * m->nv * elem; }
 template <typename T>
 mh_status rnea_derivatives_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const double *gravity, const T *f_ext,
                                 const mh_options *opts_in, T *tau_out, T *dq_out, T *dqd_out)
@@ -2610,6 +2622,142 @@ mh_status integrate_impl(mh_model_t model, int64_t B, double dt, const T *q, con
       hipLaunchKernelGGL((mh::integrate_aos_kernel<T>), dim3(grid), dim3(block), ((size_t)model->n * 3 + 2) * sizeof(int), (hipStream_t)opts.stream, A, tile);
    }
    HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
+
+// q (+) dq and q1 (-) q0 (mh_step_kernels.h): one elementwise run-time-topology kernel each, no workspace
+template <typename T>
+mh::ChartArgs<T> chart_args(const mh_model *model, int64_t B, const mh_options &opts)
+{
+   mh::ChartArgs<T> A{};
+   A.m = dev_model<T>(model);
+   A.B = B;
+   A.soa = opts.layout == MH_LAYOUT_SOA;
+   set_strides(A.q_bs, A.q_es, A.soa, B, model->nq);
+   set_strides(A.v_bs, A.v_es, A.soa, B, model->nv);
+   A.unowned = model->d_grav_zero_cols + model->grav_zero_ofs[model->n];
+   A.n_unowned = model->grav_zero_ofs[model->n + 1] - model->grav_zero_ofs[model->n];
+   return A;
+}
+static int chart_grid(const mh_model *model, int64_t B)
+{
+   return (int)std::max<int64_t>(1, std::min<int64_t>((B * std::max(model->n, model->nv) + 255) / 256, (int64_t)model->cu_count * 8));
+}
+template <typename T>
+mh_status configuration_add_impl(mh_model_t model, int64_t B, const T *q, const T *dq, const mh_options *opts_in, T *q_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   if (B == 0)
+      return MH_OK;
+   if (!q || !dq || !q_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
+   {
+      const InRange ins[2] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"dq", dq, (size_t)B * model->nv * sizeof(T)}};
+      const OutRange out = {"q_out", q_out, (size_t)B * model->nq * sizeof(T), 1u};
+      if ((st = check_aliasing("mh_configuration_add", ins, 2, &out, 1)) != MH_OK)
+         return st;
+   }
+   mh::ChartArgs<T> A = chart_args<T>(model, B, opts);
+   A.a = q, A.b = dq, A.out = q_out;
+   hipLaunchKernelGGL((mh::configuration_add_kernel<T>), dim3(chart_grid(model, B)), dim3(256), 0, (hipStream_t)opts.stream, A);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
+template <typename T>
+mh_status configuration_difference_impl(mh_model_t model, int64_t B, const T *q0, const T *q1, const mh_options *opts_in, T *dq_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   if (B == 0)
+      return MH_OK;
+   if (!q0 || !q1 || !dq_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
+   {
+      const size_t bq = (size_t)B * model->nq * sizeof(T);
+      const InRange ins[2] = {{"q0", q0, bq}, {"q1", q1, bq}};
+      const OutRange out = {"dq_out", dq_out, (size_t)B * model->nv * sizeof(T), 0u};
+      if ((st = check_aliasing("mh_configuration_difference", ins, 2, &out, 1)) != MH_OK)
+         return st;
+   }
+   mh::ChartArgs<T> A = chart_args<T>(model, B, opts);
+   A.a = q0, A.b = q1, A.out = dq_out;
+   hipLaunchKernelGGL((mh::configuration_difference_kernel<T>), dim3(chart_grid(model, B)), dim3(256), 0, (hipStream_t)opts.stream, A);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
+// Linearisation of the simulation step: launches composed on the caller's stream -- mh_aba_derivatives_* with both derivative matrices in
+// the context's `step` scratch and H^-1 (and qdd, unless the caller takes it) in its `deriv` scratch, the assembly kernel of
+// mh_step_kernels.h, and the integrator kernel when the new state is asked for.
+template <typename T>
+mh_status step_derivatives_impl(mh_model_t model, int64_t B, const double &dt, const T *q, const T *qd, const T *tau, const double *gravity,
+                                const T *f_ext, const mh_options *opts_in, T *qdd_out, T *q_next, T *qd_next, T *A_out, T *B_out)
+{
+   mh_options o;
+   mh_status st = begin_call(model, B, opts_in, o);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: the linearisation of the step takes none", model->n_locked);
+   if (nonfinite_bits(dt))
+      return fail(MH_ERR_INVALID_ARGUMENT, "dt is not finite");
+   if (!gravity && !o.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (B == 0 || model->nv == 0) // (nothing to write: the pointers of empty matrices may well be NULL)
+      return MH_OK;
+   if (!A_out && !B_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "A_out and B_out are both NULL");
+   if ((q_next == nullptr) != (qd_next == nullptr))
+      return fail(MH_ERR_INVALID_ARGUMENT, "q_next and qd_next may be NULL only together");
+   if (!q || !qd || !tau)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state pointer");
+   if (model->nv > mh::NEG_SOLVE_LDS_ENTRIES)
+      return fail(MH_ERR_INVALID_ARGUMENT, "nv = %d is beyond the %d DoFs mh_aba_derivatives takes", model->nv, mh::NEG_SOLVE_LDS_ENTRIES);
+   const size_t nv = (size_t)model->nv, bv = (size_t)B * nv * sizeof(T), bq = (size_t)B * model->nq * sizeof(T);
+   {
+      const InRange ins[4] = {{"q", q, bq}, {"qd", qd, bv}, {"tau", tau, bv}, {"f_ext", f_ext, (size_t)B * model->n * 6 * sizeof(T)}};
+      const OutRange outs[5] = {{"qdd_out", qdd_out, bv, 0u}, {"q_next", q_next, bq, 0u}, {"qd_next", qd_next, bv, 0u},
+                                {"A_out", A_out, 4 * bv * nv, 0u}, {"B_out", B_out, 2 * bv * nv, 0u}};
+      if ((st = check_aliasing("mh_aba_integrate_derivatives", ins, 4, outs, 5)) != MH_OK)
+         return st;
+   }
+   if ((st = ensure_bytes(model->step, step_scratch_bytes(model, B, sizeof(T)))) != MH_OK)
+      return st;
+   T *Dq = (T *)model->step.ptr, *Dv = Dq + (size_t)B * nv * nv;
+   st = aba_derivatives_impl<T>(model, B, q, qd, tau, gravity, f_ext, &o, qdd_out, Dq, Dv, nullptr);
+   if (st != MH_OK)
+      return st;
+   const bool soa = o.layout == MH_LAYOUT_SOA;
+   hipStream_t stream = (hipStream_t)o.stream;
+   mh::StepArgs<T> S{};
+   S.m = dev_model<T>(model);
+   S.B = B, S.dt = (T)dt;
+   S.qd = qd, S.qdd = qdd_out ? qdd_out : (T *)model->deriv.ptr + (size_t)B * nv * nv;
+   S.Dq = Dq, S.Dv = Dv, S.Hinv = (const T *)model->deriv.ptr;
+   S.A = A_out, S.Bm = B_out;
+   S.unowned = model->d_grav_zero_cols + model->grav_zero_ofs[model->n];
+   S.n_unowned = model->grav_zero_ofs[model->n + 1] - model->grav_zero_ofs[model->n];
+   set_strides(S.v_bs, S.v_es, soa, B, (long)nv);
+   set_strides(S.d_bs, S.d_es, soa, B, (long)(nv * nv));
+   set_strides(S.a_bs, S.a_es, soa, B, (long)(4 * nv * nv));
+   set_strides(S.b_bs, S.b_es, soa, B, (long)(2 * nv * nv));
+   if (soa)
+   {
+      const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((B + 255) / 256, (int64_t)model->cu_count * 8));
+      hipLaunchKernelGGL((mh::step_assemble_soa_kernel<T>), dim3(grid), dim3(256), 0, stream, S);
+   }
+   else
+   {
+      const int grid = (int)std::min<int64_t>(B, (int64_t)model->cu_count * 8);
+      hipLaunchKernelGGL((mh::step_assemble_aos_kernel<T>), dim3(grid), dim3(256), 0, stream, S);
+   }
+   HIP_TRY(hipGetLastError());
+   if (q_next)
+      return integrate_impl<T>(model, B, dt, q, qd, S.qdd, &o, q_next, qd_next, nullptr);
    return MH_OK;
 }
 } // namespace
@@ -3312,11 +3460,12 @@ static void free_scratch(mh_model *m)
    (void)hipFree(m->aux.ptr);
    (void)hipFree(m->pairs.ptr);
    (void)hipFree(m->deriv.ptr);
+   (void)hipFree(m->step.ptr);
 }
 // a fresh set of the above for a copy of a handle
 static void reset_scratch(mh_model *m)
 {
-   m->ws = m->stage = m->ws_pair = m->zv_tau = m->zv_cols = m->zv_flags = m->zvb_cs = m->tr = m->tr_pair = m->aux = m->pairs = m->deriv = Workspace{};
+   m->ws = m->stage = m->ws_pair = m->zv_tau = m->zv_cols = m->zv_flags = m->zvb_cs = m->tr = m->tr_pair = m->aux = m->pairs = m->deriv = m->step = Workspace{};
    m->hs_in = m->hs_run = m->hs_out = nullptr;
    for (int k = 0; k < 3; k++)
       m->ev_in[k] = m->ev_run[k] = m->ev_out[k] = nullptr;
@@ -3648,6 +3797,9 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       st = ensure_bytes(m->ws, (size_t)m->deriv_slots * (size_t)deriv_waves * 64 * sizeof(double));
       if (st == MH_OK && m->nv > 0 && deriv_scratch_bytes(m, max_batch, sizeof(double)) <= kDerivReserveCap)
          st = ensure_bytes(m->deriv, deriv_scratch_bytes(m, max_batch, sizeof(double)));
+      // mh_aba_integrate_derivatives_*: the two derivative matrices beside them, under the same cap
+      if (st == MH_OK && m->nv > 0 && deriv_scratch_bytes(m, max_batch, sizeof(double)) + step_scratch_bytes(m, max_batch, sizeof(double)) <= kDerivReserveCap)
+         st = ensure_bytes(m->step, step_scratch_bytes(m, max_batch, sizeof(double)));
       if (st != MH_OK)
          return st;
    }
@@ -4285,6 +4437,34 @@ mh_status mh_aba_derivatives_f32(mh_model_t model, int64_t B, const float *q, co
                                  float *Hinv_out)
 {
    return aba_derivatives_impl<float>(model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, dqdd_dq_out, dqdd_dqd_out, Hinv_out);
+}
+mh_status mh_configuration_add_f64(mh_model_t model, int64_t B, const double *q, const double *dq, const mh_options *opts, double *q_out)
+{
+   return configuration_add_impl<double>(model, B, q, dq, opts, q_out);
+}
+mh_status mh_configuration_add_f32(mh_model_t model, int64_t B, const float *q, const float *dq, const mh_options *opts, float *q_out)
+{
+   return configuration_add_impl<float>(model, B, q, dq, opts, q_out);
+}
+mh_status mh_configuration_difference_f64(mh_model_t model, int64_t B, const double *q0, const double *q1, const mh_options *opts, double *dq_out)
+{
+   return configuration_difference_impl<double>(model, B, q0, q1, opts, dq_out);
+}
+mh_status mh_configuration_difference_f32(mh_model_t model, int64_t B, const float *q0, const float *q1, const mh_options *opts, float *dq_out)
+{
+   return configuration_difference_impl<float>(model, B, q0, q1, opts, dq_out);
+}
+mh_status mh_aba_integrate_derivatives_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *tau,
+                                           const double gravity[3], const double *f_ext, const mh_options *opts, double *qdd_out,
+                                           double *q_next, double *qd_next, double *A_out, double *B_out)
+{
+   return step_derivatives_impl<double>(model, B, dt, q, qd, tau, gravity, f_ext, opts, qdd_out, q_next, qd_next, A_out, B_out);
+}
+mh_status mh_aba_integrate_derivatives_f32(mh_model_t model, int64_t B, double dt, const float *q, const float *qd, const float *tau,
+                                           const double gravity[3], const float *f_ext, const mh_options *opts, float *qdd_out,
+                                           float *q_next, float *qd_next, float *A_out, float *B_out)
+{
+   return step_derivatives_impl<float>(model, B, dt, q, qd, tau, gravity, f_ext, opts, qdd_out, q_next, qd_next, A_out, B_out);
 }
 mh_status mh_rnea_parameters_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double *pi,
                                  const double gravity[3], const double *f_ext, const mh_options *opts, double *tau_out)

@@ -679,6 +679,73 @@ class HipModel:
             self._h, B, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), g, ptr(f_ext), ctypes.byref(opts), ptr(qdd), ptr(dq), ptr(dqd), ptr(Hinv)))
         return qdd, dq, dqd, Hinv
 
+    def _chart_call(self, name, a, b, b_cols, out_cols, layout, out):
+        import torch
+        B, dt, sfx, stream = self._device_inputs([a], layout)
+        aos = layout == _lib.LAYOUT_AOS
+        shape_of = lambda n: (B, n) if aos else (n, B)
+        if not self._is_torch(b) or not b.is_cuda or b.dtype != dt or not b.is_contiguous():
+            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+        if tuple(b.shape) != shape_of(b_cols):
+            raise _lib.MecanoHipError(2, f"second input has shape {tuple(b.shape)}, expected {shape_of(b_cols)}")
+        if out is None:
+            out = torch.empty(shape_of(out_cols), dtype=dt, device=a.device)
+        else:
+            if not self._is_torch(out) or not out.is_cuda or out.dtype != dt or not out.is_contiguous():
+                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+            if tuple(out.shape) != shape_of(out_cols):
+                raise _lib.MecanoHipError(2, f"output has shape {tuple(out.shape)}, expected {shape_of(out_cols)}")
+        opts = self._options(layout, stream=stream)
+        _lib.check(getattr(_lib.load(), f"{name}_{sfx}")(self._h, B, a.data_ptr(), b.data_ptr(), ctypes.byref(opts), out.data_ptr()))
+        return out
+
+    def configuration_add(self, q, dq, layout=_lib.LAYOUT_AOS, out=None):
+        """q (+) dq, the pure configuration step the velocity-space derivatives are defined in: ``integrateFromVelocity`` with dt = 1 and
+        twist dq [B, nv] (SixDoF: Q exp(dth), p + R(Q) dp).  Not ``integrate`` with qd = dq, whose double integrator adds a w x v term.
+        Device tensors (fp64 / fp32); ``out`` may be q itself.  Entries of q no joint owns are copied only when ``out`` is None."""
+        if out is None:
+            out = q.clone()
+        return self._chart_call("mh_configuration_add", q, dq, self.nv, self.nq, layout, out)
+
+    def configuration_difference(self, q0, q1, layout=_lib.LAYOUT_AOS, out=None):
+        """The dq [B, nv] with q0 (+) dq = q1: rotation vectors in their shortest form, dp = R(Q0)^T (p1 - p0)."""
+        return self._chart_call("mh_configuration_difference", q0, q1, self.nq, self.nv, layout, out)
+
+    def step_derivatives(self, dt, q, qd, tau, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Linearisation of the simulation step ``aba`` then ``integrate`` with step ``dt``: (qdd [B, nv], q_next [B, nq], qd_next [B, nv],
+        A [B, 2nv, 2nv], B [B, 2nv, nv]) with dx' = A dx + B dtau, x = (q, qd); dq and dq' are velocity-space steps in the chart of
+        ``configuration_add`` / ``configuration_difference``, dqd and dqd' component increments, the wrenches held in the world.  SoA:
+        [nv, B], [nq, B], [nv, B], [(2nv)^2, B], [2nv nv, B].  ``out``: a (qdd, q_next, qd_next, A, B) tuple to write into; any may be None
+        (not returned), not both matrices, q_next and qd_next only together.  A model with acceleration-source joints is refused."""
+        import torch
+        B, dtp, sfx, stream = self._device_inputs([q, qd, tau], layout)
+        if f_ext is not None and (not self._is_torch(f_ext) or not f_ext.is_cuda or f_ext.dtype != dtp or not f_ext.is_contiguous()):
+            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+        self._check_f_ext(f_ext, B, layout)
+        aos, nv = layout == _lib.LAYOUT_AOS, self.nv
+        shapes = ((B, nv), (B, self.nq), (B, nv), (B, 2 * nv, 2 * nv), (B, 2 * nv, nv)) if aos else \
+                 ((nv, B), (self.nq, B), (nv, B), (4 * nv * nv, B), (2 * nv * nv, B))
+        names = ("qdd", "q_next", "qd_next", "A", "B")
+        if out is None:
+            out = tuple(torch.empty(s, dtype=dtp, device=q.device) for s in shapes)
+            out = (out[0], q.clone(), qd.clone()) + out[3:]  # entries no joint owns are passed through unchanged
+        else:
+            if len(out) != 5:
+                raise _lib.MecanoHipError(2, f"out must hold 5 entries ({', '.join(names)})")
+            for t, s, name in zip(out, shapes, names):
+                if t is None:
+                    continue
+                if not self._is_torch(t) or not t.is_cuda or t.dtype != dtp or not t.is_contiguous():
+                    raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+                if tuple(t.shape) != s:
+                    raise _lib.MecanoHipError(2, f"{name} output has shape {tuple(t.shape)}, expected {s}")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, True, True, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_aba_integrate_derivatives_{sfx}")(
+            self._h, B, float(dt), q.data_ptr(), qd.data_ptr(), tau.data_ptr(), g, ptr(f_ext), ctypes.byref(opts), *[ptr(t) for t in out]))
+        return tuple(out)
+
     def inertial_parameters(self) -> np.ndarray:
         """The model's own inertial parameters, [n_joints, 10]: (mass, com_x, com_y, com_z, Jxx, Jxy, Jxz, Jyy, Jyz, Jzz) of joint j's
         successor body in the description's order -- ``inertia_mass``, ``inertia_com`` and the symmetric part of ``inertia_J``, the order
