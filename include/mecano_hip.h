@@ -260,7 +260,12 @@ mh_status mh_model_check(mh_model_t model, mh_context_t ctx, void *stream);
  * join with a stream of the model's own: they can be captured in a HIP graph and replayed.  The depth-first frame plans of every batch
  * size up to max_batch (both algorithms, both precisions, both layouts, the fp32 fused pair walk) are uploaded here, not at a call
  * (tests/test_gpu_parity.py::test_entry_points_are_graph_capturable,
- * tests/test_gpu_persistent_loops.py::test_reserve_then_capture_every_batch_class). */
+ * tests/test_gpu_persistent_loops.py::test_reserve_then_capture_every_batch_class).
+ * Memory: beside the workspaces, the scratch matrices of the derivative calls and of the AoS form of mh_body_poses_* /
+ * mh_geometric_jacobian_* are set aside here for every model and every context, used or not, each while it stays within 4 GiB at
+ * max_batch (a larger need is met by the first call that has it).  The kinematics scratch holds the largest target list:
+ * max_batch * max(6 * 16 * (nv + 1), 12 * max(16, n_joints)) doubles -- 23.8 KB per configuration for a 30-DoF model, 97 MB at
+ * max_batch = 4096, 3.1 GB at 131 072; from 180 400 configurations on it is left to the first AoS call. */
 mh_status mh_reserve(mh_model_t model, int64_t max_batch);
 
 /*
@@ -489,6 +494,50 @@ mh_status mh_apparent_inertia_inverse_f64(mh_model_t model, int64_t B, const dou
                                           const double *target_poses, int32_t blocks, const mh_options *opts, double *W_out);
 mh_status mh_apparent_inertia_inverse_f32(mh_model_t model, int64_t B, const float *q, int32_t n_targets, const int32_t *target_joints,
                                           const double *target_poses, int32_t blocks, const mh_options *opts, float *W_out);
+
+/*
+ * ---- body poses and geometric Jacobians (the frame tree's getTransformToDesiredFrame towards the root body frame;
+ *      GeometricJacobianCalculator.setKinematicChain / getJacobianMatrix / getConvectiveTerm,
+ *      algorithms/GeometricJacobianCalculator.java:148-158, 249-279, 316-377, 578-633; the chain is
+ *      MultiBodySystemTools.collectJointPath, tools/MultiBodySystemTools.java:170-207) ----
+ * Conventions of both calls, those of mh_apparent_inertia_inverse_* and mh_relative_acceleration_f64:
+ * target_joints / base_joints (HOST, [n_targets]): positions in the model's joint list; a position names that joint's successor body, -1
+ * names the root body.  Duplicates are allowed.  target_poses (HOST, [n_targets][12], R row-major 9 + p 3, or NULL = identity): a constant
+ * pose of the target frame relative to the target's body-fixed frame (for the root body: relative to the root body frame); R must be a
+ * rotation to 1e-9.  Targets, bases and poses travel as kernel arguments: nothing is uploaded, and after mh_reserve the calls allocate
+ * nothing and can be captured in a graph (AoS outputs of more than 4 GiB at the reserved batch are staged in scratch the first such call
+ * allocates).  B = 0 returns MH_OK and touches nothing.  Every entry of every output is written, zeros included, and nothing outside it.
+ * Outputs must not overlap inputs or each other.  MH_ERR_INVALID_ARGUMENT: such an overlap, NULL q / output / target_joints, n_targets
+ * outside its range, a joint index outside -1 ... n_joints - 1, a pose that is no rotation, conv_out without qd.  Ignored subtrees (they
+ * are not in the joint list), the index maps and MH_LAYOUT_SOA are honoured as everywhere else; quaternions are normalised on input.
+ * Device pointers, asynchronous on opts->stream, contexts honoured; run-time-topology kernels for every model.
+ *
+ * mh_body_poses_*: pose_out [B][n_targets][12] (MH_LAYOUT_SOA: [12 n_targets][B]), R row-major then p: the pose of every target frame in
+ * the root body frame -- the frame `gravity` is expressed in: x_root = R x + p.  target_joints = NULL with n_targets = n_joints (and
+ * target_poses = NULL): the body-fixed frame of every body, in joint order.  Otherwise 1 <= n_targets <= MH_MAX_KINEMATIC_TARGETS.
+ *
+ * mh_geometric_jacobian_*: J_out [B][6 n_targets][nv] row-major (MH_LAYOUT_SOA: [6 n_targets * nv][B]); block k, rows 6 k ... 6 k + 5
+ * (angular, then linear), is the geometric Jacobian of target k:  J qd  is the twist of the target frame relative to the body
+ * base_joints[k] (NULL: the root body for every target), expressed in the target frame.  Columns are indexed like tau.  Columns of joints
+ * off the chain between base and target are zero; joints on the base's side of the common ancestor enter with their unit twists
+ * inverted, as in the reference (:268-271).  With every base at the root the stacked matrix is the J of MH_APPARENT_BLOCKS_COUPLED:
+ * W = J H^-1 J^T.  conv_out [B][n_targets][6] (MH_LAYOUT_SOA: [6 n_targets][B]; may be NULL, needs qd otherwise; qd may be NULL when it
+ * is): the convective term Jdot qd of getConvectiveTerm (:316-377, 629-633), the acceleration of the target relative to the base at zero
+ * joint accelerations in the reference's convention -- what mh_relative_acceleration_f64 returns after an mh_rnea_bodies_f64 call with
+ * qdd = 0, re-expressed in the target pose.  The Jacobian frame is always rigidly attached to the end effector (a constant pose in the
+ * target body): the only case in which the reference's convective term is valid (its warning, :288, :587, :605).
+ */
+#define MH_MAX_KINEMATIC_TARGETS 16
+mh_status mh_body_poses_f64(mh_model_t model, int64_t B, const double *q, int32_t n_targets, const int32_t *target_joints,
+                            const double *target_poses, const mh_options *opts, double *pose_out);
+mh_status mh_body_poses_f32(mh_model_t model, int64_t B, const float *q, int32_t n_targets, const int32_t *target_joints,
+                            const double *target_poses, const mh_options *opts, float *pose_out);
+mh_status mh_geometric_jacobian_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_targets,
+                                    const int32_t *base_joints, const int32_t *target_joints, const double *target_poses,
+                                    const mh_options *opts, double *J_out, double *conv_out);
+mh_status mh_geometric_jacobian_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_targets,
+                                    const int32_t *base_joints, const int32_t *target_joints, const double *target_poses,
+                                    const mh_options *opts, float *J_out, float *conv_out);
 
 /*
  * ---- inverse of the joint-space inertia matrix (columns of H^-1: MultiBodyResponseCalculator.applyJointWrench and the recursion behind

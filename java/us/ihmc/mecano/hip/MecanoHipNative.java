@@ -187,6 +187,26 @@ public final class MecanoHipNative
    /** the same in fp32 (float q / W_out on the device; the poses stay double) */
    static final MethodHandle APPARENT_INERTIA_INVERSE_F32 = handle("mh_apparent_inertia_inverse_f32", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
                                                                                                                JAVA_INT, ADDRESS, ADDRESS));
+   /** mh_body_poses_* / mh_geometric_jacobian_*: at most this many listed targets per call */
+   static final int MAX_KINEMATIC_TARGETS = 16;
+   /**
+    * Poses of frames fixed in bodies, in the root body frame, for B configurations, one launch: (model, B, q, n_targets, target_joints (host
+    * int[], -1 = the root body)|NULL = every body, target_poses (host double[n_targets][12])|NULL, opts|NULL, pose_out), pose_out
+    * [B][n_targets][12], R row-major then p.
+    */
+   static final MethodHandle BODY_POSES = handle("mh_body_poses_f64", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 (float q / pose_out on the device; the poses stay double) */
+   static final MethodHandle BODY_POSES_F32 = handle("mh_body_poses_f32", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * GeometricJacobianCalculator.getJacobianMatrix / getConvectiveTerm for B configurations and up to 16 kinematic chains, one launch:
+    * (model, B, q, qd|NULL, n_targets, base_joints (host int[])|NULL = the root body, target_joints (host int[]), target_poses (host
+    * double[n_targets][12])|NULL, opts|NULL, J_out, conv_out|NULL), J_out [B][6 n_targets][nv] row-major, conv_out [B][n_targets][6].
+    */
+   static final MethodHandle GEOMETRIC_JACOBIAN = handle("mh_geometric_jacobian_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
+                                                                                               ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 (float q / qd / J_out / conv_out on the device; the poses stay double) */
+   static final MethodHandle GEOMETRIC_JACOBIAN_F32 = handle("mh_geometric_jacobian_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
+                                                                                                   ADDRESS, ADDRESS, ADDRESS, ADDRESS));
    /** mh_mass_matrix_inverse_*: at most this many listed columns per call */
    static final int MAX_INVERSE_COLUMNS = 64;
    /**

@@ -6,6 +6,7 @@
 * ``JointTorqueRegressorCalculator``         algorithms/JointTorqueRegressorCalculator.java:101-133, 173-190, 360-502 (a caller of the first)
 * ``MultiBodyResponseCalculator``            algorithms/MultiBodyResponseCalculator.java:120-140, 288-935 (a caller of the second)
 * ``MultiBodyGravityGradientCalculator``     algorithms/MultiBodyGravityGradientCalculator.java:141-351, 397-672
+* ``GeometricJacobianCalculator``            algorithms/GeometricJacobianCalculator.java:103-158, 232-279, 316-377, 440-633
 
 Differences a user of the reference must know (all forced by batching, none changes results):
 
@@ -655,6 +656,139 @@ class MultiBodyResponseCalculator:
         rows.  Rows and columns of acceleration-source joints are zero."""
         self._batch()
         return self.model.mass_matrix_inverse(self._q, None, _lib.LAYOUT_AOS)
+
+
+class GeometricJacobianCalculator:
+    """algorithms/GeometricJacobianCalculator.java:103-158, 232-279, 316-377, 440-633, batched: the geometric Jacobian of the kinematic chain
+    from ``base`` to ``endEffector`` (any two bodies of the system; the chain may cross their common ancestor, :258-277) and its
+    convective term, one launch of mh_geometric_jacobian_* per ``reset``.
+
+    The reference reads q and qd from the joints' frames; here ``reset(q, qd=None)`` sets the B configurations (and velocities, which only
+    the convective term needs).  Matrices come back in the reference's compact layout, [B, 6, chain DoFs] with the columns in
+    base-to-end-effector joint order (:260-277), gathered on the device from the library's 6 x nv block.  The Jacobian frame is the end
+    effector's body-fixed frame or a frame fixed in the end effector, given as a pose of 12 numbers (R row-major, p) relative to it: the
+    only case in which the reference's convective term is valid (its warning, :288, :587, :605); anything else is refused."""
+
+    def __init__(self, input):
+        self.input = _as_system(input)
+        self.model = HipModel(self.input.toModelDesc())
+        self._joints = self.input.getJointsToConsider()
+        self._body_pos = {id(j.getSuccessor()): k for k, j in enumerate(self._joints)}
+        self._body_pos[id(self.input.getRootBody())] = -1
+        self.clear()
+
+    def clear(self):
+        """:112-122"""
+        self.base = self.endEffector = None
+        self._chain, self._cols, self._pose = [], [], None
+        self._q = self._qd = None
+        self._results()
+
+    def _results(self):
+        self._J = self._c = None
+
+    def reset(self, q=None, qd=None):
+        """:127-131; ``q`` [B, nq] and optionally ``qd`` [B, nv]: the states the Jacobian is evaluated at (kept when omitted)."""
+        if q is not None:
+            self._q, self._qd = q, qd
+        self._results()
+
+    def setKinematicChain(self, base, endEffector):
+        """:148-158; the Jacobian frame goes back to the end effector's body-fixed frame."""
+        if id(base) not in self._body_pos or id(endEffector) not in self._body_pos:
+            raise ValueError("base and end effector must be bodies this calculator's system considers")
+        self.base, self.endEffector, self._pose = base, endEffector, None
+        kb, ke = self._body_pos[id(base)], self._body_pos[id(endEffector)]
+        parent = {k: self._body_pos[id(j.getPredecessor())] for k, j in enumerate(self._joints)}
+
+        def climb(k):
+            out = []
+            while k >= 0:
+                out.append(k)
+                k = parent[k]
+            return out
+        up, down = climb(kb), climb(ke)
+        while up and down and up[-1] == down[-1]:  # MultiBodySystemTools.collectJointPath (tools/MultiBodySystemTools.java:170-207)
+            up.pop(), down.pop()
+        self._chain = [self._joints[k] for k in up + down[::-1]]
+        provider = self.input.getJointMatrixIndexProvider()
+        self._cols = [d for j in self._chain for d in provider.getJointDoFIndices(j)]
+        self._results()
+
+    def setJacobianFrame(self, jacobianFrame):
+        """:232-238, for a frame fixed in the end effector only: None (its body-fixed frame) or a pose of 12 numbers relative to it."""
+        if self.endEffector is None:
+            raise RuntimeError("The base and end-effector have to be set first.")
+        if jacobianFrame is not None:
+            try:
+                pose = np.asarray(jacobianFrame, dtype=np.float64).reshape(12)
+            except (TypeError, ValueError):
+                raise ValueError("the Jacobian frame must be fixed in the end effector: None or a pose of 12 numbers (R row-major, p) relative "
+                                 "to its body-fixed frame; the reference's convective term is biased for any other frame") from None
+            jacobianFrame = pose
+        self._pose = jacobianFrame
+        self._results()
+
+    def getBase(self):
+        return self.base
+
+    def getEndEffector(self):
+        return self.endEffector
+
+    def getJointsFromBaseToEndEffector(self):
+        """:567-570"""
+        return list(self._chain)
+
+    def getNumberOfDegreesOfFreedom(self) -> int:
+        """:556-559"""
+        return len(self._cols) if self.endEffector is not None else -1
+
+    def _update(self, convective):
+        if self.base is None or self.endEffector is None:
+            raise RuntimeError("The base and end-effector have to be set first.")  # :254-255
+        if self._q is None:
+            raise ValueError("call reset(q) with the configurations first")
+        if self._J is not None and (self._c is not None or not convective):
+            return
+        if convective and self._qd is None:
+            raise ValueError("the convective term needs the velocities: reset(q, qd)")
+        r = self.model.geometric_jacobian(self._q, [self._body_pos[id(self.endEffector)]], [self._body_pos[id(self.base)]],
+                                          None if self._pose is None else self._pose[None], self._qd if convective else None, convective)
+        J, c = r if convective else (r, None)
+        self._J = J[:, :, self._cols]
+        self._c = None if c is None else c[:, 0]
+
+    def getJacobianMatrix(self):
+        """:578-582: [B, 6, chain DoFs]"""
+        self._update(False)
+        return self._J
+
+    def getConvectiveTermMatrix(self):
+        """:611-615: [B, 6], Jdot qd"""
+        self._update(True)
+        return self._c
+
+    getConvectiveTerm = getConvectiveTermMatrix  # :629-633
+
+    @staticmethod
+    def _times(J, x):
+        if HipModel._is_torch(J):
+            import torch
+            return torch.einsum("bij,bj->bi", J, x if HipModel._is_torch(x) else torch.as_tensor(np.asarray(x), dtype=J.dtype, device=J.device))
+        return np.einsum("bij,bj->bi", J, np.asarray(x, dtype=np.float64))
+
+    def getEndEffectorTwist(self, jointVelocities):
+        """:440-444: [B, 6] = J qd_chain, the twist of the end effector relative to the base in the Jacobian frame"""
+        return self._times(self.getJacobianMatrix(), jointVelocities)
+
+    def getEndEffectorAcceleration(self, jointAccelerations):
+        """:456-461: [B, 6] = J qdd_chain + the convective term"""
+        return self._times(self.getJacobianMatrix(), jointAccelerations) + self.getConvectiveTermMatrix()
+
+    def getJointTorques(self, endEffectorWrench):
+        """:477-484: [B, chain DoFs] = J^T w for a wrench (moment, force) on the end effector expressed in the Jacobian frame"""
+        J = self.getJacobianMatrix()
+        return self._times(J.transpose(1, 2) if HipModel._is_torch(J) else J.transpose(0, 2, 1), endEffectorWrench)
 
 
 class CompositeRigidBodyMassMatrixCalculator(_Base):

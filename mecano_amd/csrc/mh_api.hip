@@ -10,6 +10,7 @@
 #include "mh_gravity_kernels.h"
 #include "mh_response_kernels.h"
 #include "mh_minv_kernels.h"
+#include "mh_kinematics_kernels.h"
 #include "mh_rnea_deriv_kernels.h"
 #include "mh_params_kernels.h"
 #include "mh_step_kernels.h"
@@ -294,6 +295,8 @@ struct mh_model
    Workspace deriv;
    // mh_aba_integrate_derivatives_*: d qdd / d q and d qdd / d qd of the call (Hinv and qdd go to `deriv`)
    Workspace step;
+   // mh_body_poses_* / mh_geometric_jacobian_*: the SoA form of AoS outputs, which a transposition then brings to the caller's rows
+   Workspace kin;
    // mh_model_inertial_parameters / mh_rnea_parameters_* / mh_aba_parameters_*: the description's ten inertial numbers per joint, in
    // mh_model_desc order (host only: the kernels of mh_params_kernels.h take them per configuration from the call)
    std::vector<double> inertial_parameters;
@@ -2326,6 +2329,150 @@ mh_status apparent_inertia_impl(mh_model_t model, int64_t B, const T *q, int32_t
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
+// Poses of frames fixed in bodies and geometric Jacobians between bodies (mh_kinematics_kernels.h): run-time-topology kernels, which write
+// every entry of their outputs -- no memset in front of them.  Targets, bases and frames travel as kernel arguments.  The kernels store
+// SoA (coalesced) always: AoS outputs are produced in scratch of the context and brought to rows by a transposition, so that no lane
+// writes entries 6 K nv elements apart.
+static size_t kin_ws_bytes(const mh_model *m, long waves, size_t elem) { return (size_t)m->n * mh::KIN_SLOTS * (size_t)waves * 64 * elem; }
+static size_t kin_scratch_entries(const mh_model *m, int n_targets, bool jacobian, bool conv)
+{
+   return jacobian ? 6 * (size_t)n_targets * (size_t)m->nv + (conv ? 6 * (size_t)n_targets : 0) : 12 * (size_t)n_targets;
+}
+static double rotation_error(const double *X)
+{
+   const double det = X[0] * (X[4] * X[8] - X[5] * X[7]) - X[1] * (X[3] * X[8] - X[5] * X[6]) + X[2] * (X[3] * X[7] - X[4] * X[6]);
+   double worst = std::fabs(det - 1.0);
+   for (int r = 0; r < 3; r++)
+      for (int s = 0; s < 3; s++)
+      {
+         double g = 0.0;
+         for (int t = 0; t < 3; t++)
+            g += X[3 * t + r] * X[3 * t + s];
+         worst = std::max(worst, std::fabs(g - (r == s ? 1.0 : 0.0)));
+      }
+   return worst; // (NaN where an entry is)
+}
+template <typename T>
+mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int64_t B, const T *q, const T *qd, int32_t n_targets,
+                          const int32_t *base_joints, const int32_t *target_joints, const double *target_poses, const mh_options *opts_in,
+                          T *pose_out, T *J_out, T *conv_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   const bool all_bodies = !jacobian && !target_joints;
+   if (all_bodies)
+   {
+      if (n_targets != model->n)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target_joints is NULL (every body) but n_targets = %d is not the model's %d joints", call, n_targets, model->n);
+      if (target_poses)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target_poses given without target_joints (every body comes with the identity pose)", call);
+   }
+   else
+   {
+      if (!target_joints)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target_joints is NULL", call);
+      if (n_targets < 1 || n_targets > MH_MAX_KINEMATIC_TARGETS)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: n_targets = %d is outside 1 ... %d", call, n_targets, MH_MAX_KINEMATIC_TARGETS);
+   }
+   mh::KinArgs<T> G{};
+   for (int k = 0; k < (all_bodies ? 0 : n_targets); k++)
+   {
+      const int i = target_joints[k], ib = base_joints ? base_joints[k] : -1;
+      if (i < -1 || i >= model->n)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d names joint %d (the model has %d joints; -1 is the root body)", call, k, i, model->n);
+      if (ib < -1 || ib >= model->n)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: base %d names joint %d (the model has %d joints; -1 is the root body)", call, k, ib, model->n);
+      G.tgt[k] = i < 0 ? -1 : model->engine_of[i];
+      G.base[k] = ib < 0 ? -1 : model->engine_of[ib];
+      const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+      const double *X = target_poses ? target_poses + 12 * k : ident;
+      const double worst = rotation_error(X);
+      if (!(worst <= 1.0e-9)) // (a NaN fails too)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", call, k, worst);
+      // the target frame in the canonical after-joint frame: (body-fixed -> canonical) o (target frame -> body-fixed); the root body's
+      // body-fixed frame is the root frame itself
+      const double *c = i < 0 ? ident : &model->consts[(size_t)G.tgt[k] * mh::MC_STRIDE + mh::MC_RF];
+      for (int r = 0; r < 3; r++)
+      {
+         double p = c[9 + r];
+         for (int t = 0; t < 3; t++)
+            p += c[3 * r + t] * X[9 + t];
+         G.pose[k][9 + r] = (T)p;
+         for (int s = 0; s < 3; s++)
+         {
+            double v = 0.0;
+            for (int t = 0; t < 3; t++)
+               v += c[3 * r + t] * X[3 * t + s];
+            G.pose[k][3 * r + s] = (T)v;
+         }
+      }
+   }
+   if (B == 0)
+      return MH_OK;
+   if (!q || (jacobian ? !J_out : !pose_out))
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: NULL configuration / output pointer", call);
+   if (conv_out && !qd)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: the convective term needs qd", call);
+   const size_t n_pose = 12 * (size_t)n_targets, n_J = 6 * (size_t)n_targets * (size_t)model->nv, n_conv = 6 * (size_t)n_targets;
+   {
+      const size_t bq = (size_t)B * model->nq * sizeof(T), bv = (size_t)B * model->nv * sizeof(T);
+      const InRange ins[2] = {{"q", q, bq}, {"qd", jacobian ? qd : nullptr, bv}};
+      const OutRange outs[3] = {{"pose_out", pose_out, (size_t)B * n_pose * sizeof(T), 0u},
+                                {"J_out", J_out, (size_t)B * n_J * sizeof(T), 0u},
+                                {"conv_out", conv_out, (size_t)B * n_conv * sizeof(T), 0u}};
+      if ((st = check_aliasing(call, ins, 2, outs, 3)) != MH_OK)
+         return st;
+   }
+   const Launch L = plan_launch(model, B);
+   const int parts = jacobian ? response_parts(model, L, n_targets) : 1;
+   st = ensure_bytes(model->ws, kin_ws_bytes(model, (long)L.grid * parts, sizeof(T)));
+   if (st != MH_OK)
+      return st;
+   // B = 1: the two layouts are the same memory
+   const bool staged = opts.layout != MH_LAYOUT_SOA && B > 1;
+   T *pose_dst = pose_out, *J_dst = J_out, *conv_dst = conv_out;
+   if (staged)
+   {
+      st = ensure_bytes(model->kin, (size_t)B * kin_scratch_entries(model, n_targets, jacobian, conv_out != nullptr) * sizeof(T));
+      if (st != MH_OK)
+         return st;
+      pose_dst = J_dst = (T *)model->kin.ptr;
+      if (conv_out)
+         conv_dst = J_dst + (size_t)B * n_J;
+   }
+   hipStream_t stream = (hipStream_t)opts.stream;
+   mh::Args<T> &A = G.a;
+   A = make_args<T>(model, B, opts);
+   A.q = q, A.qd = conv_out ? qd : nullptr;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = L.lanes;
+   G.pose_out = pose_dst, G.J = J_dst, G.conv = conv_dst;
+   G.p_bs = G.j_bs = G.c_bs = 1, G.p_es = G.j_es = G.c_es = (long)B;
+   G.info = model->d_resp_info;
+   G.zero_ofs = model->d_grav_zero_ofs, G.zero_cols = model->d_grav_zero_cols;
+   G.n_targets = n_targets, G.all_bodies = all_bodies;
+   if (jacobian)
+      hipLaunchKernelGGL((mh::geometric_jacobian_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, stream, G);
+   else
+      hipLaunchKernelGGL((mh::body_poses_kernel<T>), dim3(L.grid), dim3(L.block), 0, stream, G);
+   HIP_TRY(hipGetLastError());
+   if (staged)
+   {
+      if (!jacobian)
+         mh::transpose_rows<T>(pose_dst, pose_out, (long)B, (long)n_pose, false, stream);
+      else
+      {
+         if (n_J)
+            mh::transpose_rows<T>(J_dst, J_out, (long)B, (long)n_J, false, stream);
+         if (conv_out)
+            mh::transpose_rows<T>(conv_dst, conv_out, (long)B, (long)n_conv, false, stream);
+      }
+      HIP_TRY(hipGetLastError());
+   }
+   return MH_OK;
+}
 // Inverse of the joint-space inertia matrix, all columns or a list of them: run-time-topology kernel, which writes every entry of its
 // output -- no memset in front of it.  The listed columns travel as kernel arguments (resolved here to joint and place); the call
 // uploads nothing and allocates nothing beyond the workspace mh_reserve covers.
@@ -3461,11 +3608,12 @@ static void free_scratch(mh_model *m)
    (void)hipFree(m->pairs.ptr);
    (void)hipFree(m->deriv.ptr);
    (void)hipFree(m->step.ptr);
+   (void)hipFree(m->kin.ptr);
 }
 // a fresh set of the above for a copy of a handle
 static void reset_scratch(mh_model *m)
 {
-   m->ws = m->stage = m->ws_pair = m->zv_tau = m->zv_cols = m->zv_flags = m->zvb_cs = m->tr = m->tr_pair = m->aux = m->pairs = m->deriv = m->step = Workspace{};
+   m->ws = m->stage = m->ws_pair = m->zv_tau = m->zv_cols = m->zv_flags = m->zvb_cs = m->tr = m->tr_pair = m->aux = m->pairs = m->deriv = m->step = m->kin = Workspace{};
    m->hs_in = m->hs_run = m->hs_out = nullptr;
    for (int k = 0; k < 3; k++)
       m->ev_in[k] = m->ev_run[k] = m->ev_out[k] = nullptr;
@@ -3802,6 +3950,17 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
          st = ensure_bytes(m->step, step_scratch_bytes(m, max_batch, sizeof(double)));
       if (st != MH_OK)
          return st;
+      // mh_body_poses_* / mh_geometric_jacobian_*: pose and twist of every body per lane, up to one wave per target (bounded as above),
+      // and the SoA form of their AoS outputs for the largest target list, while it stays within the cap of the scratch above
+      const long kin_waves = std::max<long>(L.grid, std::min<long>((long)MH_MAX_KINEMATIC_TARGETS * L.grid, (long)m->cu_count * 4));
+      st = ensure_bytes(m->ws, kin_ws_bytes(m, kin_waves, sizeof(double)));
+      if (st != MH_OK)
+         return st;
+      const size_t kin_entries = std::max(kin_scratch_entries(m, MH_MAX_KINEMATIC_TARGETS, true, true), kin_scratch_entries(m, std::max(m->n, MH_MAX_KINEMATIC_TARGETS), false, false));
+      if ((size_t)max_batch * kin_entries * sizeof(double) <= kDerivReserveCap)
+         st = ensure_bytes(m->kin, (size_t)max_batch * kin_entries * sizeof(double));
+      if (st != MH_OK)
+         return st;
    }
    // the whole-tree specialised ABA keeps its hand-over store in the same workspace (more slots than the run-time-topology plan of a
    // chain), and big AoS batches of wide matrices go through transposed scratch copies: reserve both, so that compute calls allocate nothing
@@ -3923,6 +4082,28 @@ mh_status mh_gravity_gradient_f32(mh_model_t model, int64_t B, const float *q, c
                                   float *tau_out, float *grad_out)
 {
    return gravity_gradient_impl<float>(model, B, q, gravity, f_ext, opts, tau_out, grad_out);
+}
+mh_status mh_body_poses_f64(mh_model_t model, int64_t B, const double *q, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
+                            const mh_options *opts, double *pose_out)
+{
+   return kinematics_impl<double>("mh_body_poses_f64", false, model, B, q, nullptr, n_targets, nullptr, target_joints, target_poses, opts, pose_out, nullptr, nullptr);
+}
+mh_status mh_body_poses_f32(mh_model_t model, int64_t B, const float *q, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
+                            const mh_options *opts, float *pose_out)
+{
+   return kinematics_impl<float>("mh_body_poses_f32", false, model, B, q, nullptr, n_targets, nullptr, target_joints, target_poses, opts, pose_out, nullptr, nullptr);
+}
+mh_status mh_geometric_jacobian_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_targets, const int32_t *base_joints,
+                                    const int32_t *target_joints, const double *target_poses, const mh_options *opts, double *J_out, double *conv_out)
+{
+   return kinematics_impl<double>("mh_geometric_jacobian_f64", true, model, B, q, qd, n_targets, base_joints, target_joints, target_poses, opts, nullptr, J_out,
+                                  conv_out);
+}
+mh_status mh_geometric_jacobian_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_targets, const int32_t *base_joints,
+                                    const int32_t *target_joints, const double *target_poses, const mh_options *opts, float *J_out, float *conv_out)
+{
+   return kinematics_impl<float>("mh_geometric_jacobian_f32", true, model, B, q, qd, n_targets, base_joints, target_joints, target_poses, opts, nullptr, J_out,
+                                 conv_out);
 }
 mh_status mh_apparent_inertia_inverse_f64(mh_model_t model, int64_t B, const double *q, int32_t n_targets, const int32_t *target_joints,
                                           const double *target_poses, int32_t blocks, const mh_options *opts, double *W_out)

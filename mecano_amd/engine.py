@@ -588,6 +588,81 @@ class HipModel:
             ctypes.byref(opts), out.data_ptr()))
         return out
 
+    # ------------------------------------------------------------------ kinematics: where the bodies are, how they move with the joints
+    @staticmethod
+    def _kinematic_targets(targets, bases, poses):
+        tgt = np.ascontiguousarray(np.asarray(targets, dtype=np.int32).reshape(-1))
+        K = int(tgt.shape[0])
+        if bases is not None:
+            bases = np.ascontiguousarray(np.asarray(bases, dtype=np.int32).reshape(-1))
+            if bases.shape[0] != K:
+                raise _lib.MecanoHipError(2, f"bases must name one body per target ({K}), got {bases.shape[0]}")
+        if poses is not None:
+            poses = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1))
+            if poses.shape[0] != 12 * K:
+                raise _lib.MecanoHipError(2, f"poses must hold 12 numbers per target ({12 * K}), got {poses.shape[0]}")
+        return tgt, K, bases, poses
+
+    def _kinematic_output(self, out, shape, dt, device, name):
+        import torch
+        if out is None:
+            return torch.empty(shape, dtype=dt, device=device)
+        if not self._is_torch(out) or not out.is_cuda or out.dtype != dt or not out.is_contiguous():
+            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+        if tuple(out.shape) != shape:
+            raise _lib.MecanoHipError(2, f"{name} output has shape {tuple(out.shape)}, expected {shape}")
+        return out
+
+    def body_poses(self, q, targets=None, poses=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Poses of frames fixed in bodies, in the root body frame (the frame ``gravity`` is expressed in): [B, K, 12], R row-major then p,
+        x_root = R x + p; SoA: [12 K, B].  ``targets``: 1 to 16 positions in the joint list (the joint's successor body; -1 = the root
+        body; duplicates allowed), each with a constant pose ``poses`` [K, 12] relative to its body-fixed frame (None: identity).
+        ``targets=None``: the body-fixed frame of every body, in joint order (K = n_joints).  numpy in -> numpy out (fp64); device
+        tensors (fp64 / fp32) stay on the device, and ``out`` is a device tensor to write into."""
+        import torch
+        if not self._is_torch(q):
+            return self.body_poses(torch.tensor(_np(q, np.float64), device="cuda"), targets, poses, layout).cpu().numpy()
+        B, dt, sfx, stream = self._device_inputs([q], layout)
+        if targets is None:
+            if poses is not None:
+                raise _lib.MecanoHipError(1, "poses need targets: every body comes with the identity pose")
+            tgt, K = None, self.n_joints
+        else:
+            tgt, K, _, poses = self._kinematic_targets(targets, None, poses)
+        out = self._kinematic_output(out, (B, K, 12) if layout == _lib.LAYOUT_AOS else (12 * K, B), dt, q.device, "pose")
+        opts = self._options(layout, stream=stream)
+        _lib.check(getattr(_lib.load(), f"mh_body_poses_{sfx}")(
+            self._h, B, q.data_ptr(), K, None if tgt is None else tgt.ctypes.data, None if poses is None else poses.ctypes.data,
+            ctypes.byref(opts), out.data_ptr()))
+        return out
+
+    def geometric_jacobian(self, q, targets, bases=None, poses=None, qd=None, convective=False, layout=_lib.LAYOUT_AOS, out=None):
+        """Geometric Jacobians of K target frames (GeometricJacobianCalculator.getJacobianMatrix, GeometricJacobianCalculator.java:249-279,
+        for K kinematic chains in one launch): [B, 6 K, nv], block k = the 6 x nv Jacobian (angular rows, then linear) of target k, with
+        J qd the twist of the target frame relative to the body ``bases[k]`` (None: the root body) expressed in the target frame; columns
+        indexed like tau, zero off the chain.  ``targets`` / ``bases``: positions in the joint list (-1 = the root body), ``poses``
+        [K, 12] the target frames relative to the body-fixed frames (None: identity).  ``convective=True`` (needs ``qd``): returns
+        (J, c) with c [B, K, 6] the convective term Jdot qd (getConvectiveTerm, :316-377).  SoA: [6 K nv, B] and [6 K, B].  numpy in ->
+        numpy out (fp64); device tensors (fp64 / fp32) stay on the device; ``out``: the tensor J, or the pair (J, c), to write into."""
+        import torch
+        if not self._is_torch(q):
+            r = self.geometric_jacobian(torch.tensor(_np(q, np.float64), device="cuda"), targets, bases, poses,
+                                        None if qd is None else torch.tensor(_np(qd, np.float64), device="cuda"), convective, layout)
+            return tuple(t.cpu().numpy() for t in r) if convective else r.cpu().numpy()
+        if convective and qd is None:
+            raise _lib.MecanoHipError(1, "the convective term needs qd")
+        B, dt, sfx, stream = self._device_inputs([q] if qd is None else [q, qd], layout)
+        tgt, K, bases, poses = self._kinematic_targets(targets, bases, poses)
+        aos = layout == _lib.LAYOUT_AOS
+        J_out, c_out = (out if convective else (out, None)) if out is not None else (None, None)
+        J = self._kinematic_output(J_out, (B, 6 * K, self.nv) if aos else (6 * K * self.nv, B), dt, q.device, "J")
+        c = self._kinematic_output(c_out, (B, K, 6) if aos else (6 * K, B), dt, q.device, "convective term") if convective else None
+        opts = self._options(layout, stream=stream)
+        _lib.check(getattr(_lib.load(), f"mh_geometric_jacobian_{sfx}")(
+            self._h, B, q.data_ptr(), None if qd is None else qd.data_ptr(), K, None if bases is None else bases.ctypes.data, tgt.ctypes.data,
+            None if poses is None else poses.ctypes.data, ctypes.byref(opts), J.data_ptr(), None if c is None else c.data_ptr()))
+        return (J, c) if convective else J
+
     def mass_matrix_inverse(self, q, columns=None, layout=_lib.LAYOUT_AOS, out=None):
         """Inverse of the joint-space inertia matrix, H^-1 = d qdd / d tau, from the articulated-body recursion in one launch
         (MultiBodyResponseCalculator.applyJointWrench and its recursion, MultiBodyResponseCalculator.java:685-735, 1206-1338; H is not
