@@ -174,6 +174,71 @@ struct FreshOnCopy : T
       return *this;
    }
 };
+std::mutex g_error_words_mutex;
+std::vector<int *> g_error_words; // every live model's / context's mapped error word (mh_stream_synchronize has no handle to ask)
+
+// Everything compute calls write: owned by a model (its default context) and by every context (mh_context_create).  Declared, defaulted
+// and released HERE only: a member added to this struct is a context's own without another line anywhere.
+struct ContextState
+{
+   Workspace ws;
+   // mh_rnea_aba_f64 without a fused kernel, small batches: the two launches run side by side, the ABA on this stream with its own workspace
+   Workspace ws_pair;
+   hipStream_t pair_stream = nullptr;
+   hipEvent_t pair_fork = nullptr, pair_join = nullptr;
+   // staging buffers of the *_host entry points
+   Workspace stage;
+   // pipelined host path: copy-in / compute / copy-out streams and per-slot events of a ring of three device chunk slots
+   hipStream_t hs_in = nullptr, hs_run = nullptr, hs_out = nullptr;
+   hipEvent_t ev_in[3] = {}, ev_run[3] = {}, ev_out[3] = {};
+   // AoS -> SoA scratch copies of the state matrices for the run-time-topology kernels (big batches of wide matrices); tr_pair: the
+   // copies of the forward dynamics call that runs beside the inverse dynamics call on pair_stream (they would share addresses otherwise)
+   Workspace tr, tr_pair;
+   // scratch of the composite entry points: efforts of the Newton-Euler sweep behind mh_aba_joint_wrenches_f64, pair lists of
+   // mh_relative_acceleration_f64
+   Workspace aux, pairs;
+   FreshOnCopy<std::vector<int>> pairs_host;
+   // mh_rnea_derivatives_* / mh_aba_derivatives_*: scratch of the forward form (Hinv and qdd the caller did not ask for)
+   Workspace deriv;
+   // mh_aba_integrate_derivatives_*: d qdd / d q and d qdd / d qd of the call (Hinv and qdd go to `deriv`)
+   Workspace step;
+   // mh_body_poses_* / mh_geometric_jacobian_*: the SoA form of AoS outputs, which a transposition then brings to the caller's rows
+   Workspace kin;
+   // bias-split forward dynamics (mh_zv_kernels.h): tau - h(q, qd) rows, one flag per 64 configurations (a launch stores its epoch there),
+   // an error word in mapped host memory that a timed-out wait sets (read at the next call of the model)
+   Workspace zv_tau, zv_flags;
+   Workspace zv_cols;     // two-stage hand-off with self-signalling limb columns (identity index maps): [groups][nv][64], holds the sentinel
+                          // between launches (mh_zv_kernels.h: ZV_SENTINEL) -- written by nothing but those launches
+   Workspace zvb_cs;      // two-launch forward dynamics: (cos, sin) of the revolute joints, [2 n_rev][B rounded up to 64]
+   int zv_epoch = 0;
+   int *zv_error_host = nullptr, *zv_error_dev = nullptr;
+   FreshOnCopy<std::map<const void *, size_t>> lds_attr; // dynamic-LDS limit already raised per kernel (the model lives on one device, one host thread at a time)
+};
+void free_scratch(ContextState &c)
+{
+   for (Workspace *w : {&c.ws, &c.ws_pair, &c.stage, &c.tr, &c.tr_pair, &c.aux, &c.pairs, &c.deriv, &c.step, &c.kin, &c.zv_tau, &c.zv_flags, &c.zv_cols, &c.zvb_cs})
+      (void)hipFree(w->ptr);
+   if (c.zv_error_host)
+   {
+      {
+         std::lock_guard<std::mutex> lock(g_error_words_mutex);
+         g_error_words.erase(std::remove(g_error_words.begin(), g_error_words.end(), c.zv_error_host), g_error_words.end());
+      }
+      (void)hipHostFree(c.zv_error_host);
+   }
+   if (c.pair_stream)
+   {
+      (void)hipStreamDestroy(c.pair_stream);
+      (void)hipEventDestroy(c.pair_fork);
+      (void)hipEventDestroy(c.pair_join);
+   }
+   for (hipEvent_t e : {c.ev_in[0], c.ev_in[1], c.ev_in[2], c.ev_run[0], c.ev_run[1], c.ev_run[2], c.ev_out[0], c.ev_out[1], c.ev_out[2]})
+      if (e)
+         (void)hipEventDestroy(e);
+   for (hipStream_t s : {c.hs_in, c.hs_run, c.hs_out})
+      if (s)
+         (void)hipStreamDestroy(s);
+}
 } // namespace
 
 // entry points of a topology-specialised code object (mh_spec.hip), resolved with dlsym
@@ -226,7 +291,7 @@ enum : int
    SPEC_OCC3 = 32
 };
 
-struct mh_model
+struct mh_model : ContextState
 {
    int n = 0, nq = 0, nv = 0, n_slots = 0;
    SpecLib spec;
@@ -244,7 +309,6 @@ struct mh_model
    int pair_stack = 0;    // ... of the fused RNEA + ABA walk (aba_dfs_kernel<.., PAIR>)
    int use_dfs_pair = 1;  // MH_DFS_PAIR=0: mh_rnea_aba_f32 on big batches issues the two depth-first kernels one after the other, as before round 5
    int use_dfs = 1;       // MH_DFS=0: the sweep kernels of mh_kernels.h serve plain RNEA / ABA calls too (A/B measurements)
-   FreshOnCopy<std::map<const void *, size_t>> lds_attr; // dynamic-LDS limit already raised per kernel (the model lives on one device, one host thread at a time)
    double nonleaf_fraction = 1.0; // share of bodies with children: those are the ones that touch the depth stack
    // depth-first kernels: frame homes for a given LDS budget (slots per wave), one copy of the body records per (algorithm, budget) on
    // the device; built on first use (dfs_plan), dropped when the records change (joint source modes)
@@ -261,7 +325,7 @@ struct mh_model
       PlainMutex &operator=(const PlainMutex &) { return *this; }
    } dfs_mutex;
    // mh_context_create: a context is a copy of the model's host-side description that SHARES its device records (parent owns them) and
-   // owns everything compute calls write -- workspace, scratch matrices, staging buffers, streams, hand-off flags, the error word
+   // owns everything compute calls write -- a ContextState of its own
    mh_model *parent = nullptr;
    int n_contexts = 0; // live contexts of this model (guarded by g_context_mutex)
    bool destroy_pending = false; // mh_model_destroy was called while contexts were alive: the last mh_context_destroy releases the model
@@ -288,43 +352,20 @@ struct mh_model
    std::vector<int> minv_owner;
    int *d_minv_owner = nullptr;
    // mh_rnea_derivatives_* / mh_aba_derivatives_*: first workspace slot of every body in that kernel's own plan (mh_rnea_deriv_kernels.h)
-   // and its slots per lane; scratch of the forward form (Hinv and qdd the caller did not ask for)
+   // and its slots per lane
    std::vector<int> deriv_slot;
    int *d_deriv_slot = nullptr;
    int deriv_slots = 0;
-   Workspace deriv;
-   // mh_aba_integrate_derivatives_*: d qdd / d q and d qdd / d qd of the call (Hinv and qdd go to `deriv`)
-   Workspace step;
-   // mh_body_poses_* / mh_geometric_jacobian_*: the SoA form of AoS outputs, which a transposition then brings to the caller's rows
-   Workspace kin;
    // mh_model_inertial_parameters / mh_rnea_parameters_* / mh_aba_parameters_*: the description's ten inertial numbers per joint, in
    // mh_model_desc order (host only: the kernels of mh_params_kernels.h take them per configuration from the call)
    std::vector<double> inertial_parameters;
-   Workspace ws;
-   // staging buffers of the *_host entry points
-   Workspace stage;
-   // pipelined host path: copy-in / compute / copy-out streams and per-slot events of a ring of three device chunk slots
-   hipStream_t hs_in = nullptr, hs_run = nullptr, hs_out = nullptr;
-   hipEvent_t ev_in[3] = {}, ev_run[3] = {}, ev_out[3] = {};
    int host_chunk = 0; // MH_HOST_CHUNK: configurations per chunk of the host-pointer pipeline (0 = choose)
-   // mh_rnea_aba_f64 without a fused kernel, small batches: the two launches run side by side, the ABA on this stream with its own workspace
-   hipStream_t pair_stream = nullptr;
-   hipEvent_t pair_fork = nullptr, pair_join = nullptr;
-   Workspace ws_pair;
-   // bias-split forward dynamics (mh_zv_kernels.h): tau - h(q, qd) rows, one flag per 64 configurations (a launch stores its epoch there),
-   // an error word in mapped host memory that a timed-out wait sets (read at the next call of the model)
-   Workspace zv_tau, zv_flags;
-   Workspace zv_cols;     // two-stage hand-off with self-signalling limb columns (identity index maps): [groups][nv][64], holds the sentinel
-                          // between launches (mh_zv_kernels.h: ZV_SENTINEL) -- written by nothing but those launches
-   Workspace zvb_cs;      // two-launch forward dynamics: (cos, sin) of the revolute joints, [2 n_rev][B rounded up to 64]
    int use_rnea_ahead = 1; // MH_RNEA_AHEAD (see rnea_ahead_ok)
    int use_zv_step = 1;    // MH_ZV_STEP=0: simulation steps never ride in the bias-split / fused forward dynamics (the one-job tree-split kernel integrates instead)
    int use_zvb = 1;       // MH_ZVB=0: never; 1: batches of two or more groups of 64 configurations per CU (default); 2: whenever the call qualifies; MH_ZVB_WHICH = 1 | 2: one of the two launches only (timing)
    int zvb_which = 3;
    int use_zvf = 1;       // MH_ZVF=0: never the fused one-launch form; 1: where the two-launch form would be taken (default); 2: whenever the call qualifies
    int use_zvf_pair = 1;  // MH_ZVF_PAIR=0: the pair call of device-filling batches as two launches (A/B measurements)
-   int zv_epoch = 0;
-   int *zv_error_host = nullptr, *zv_error_dev = nullptr;
    int zv_same_l2 = 0;    // MH_ZV_SAME_L2=1 (experiment, off by default; one-stage hand-off only: the two-stage form of identity index maps is write-through): bias rows and flag of a group whose two jobs prove to sit behind the same L2
                           // stay in that L2 (workgroup-scope stores) -- cache behaviour the memory model does not promise, for no measured gain
    unsigned zv_wait_ticks = 200000000u; // MH_ZV_WAIT_MS: how long an inertia job waits for its bias rows (100 MHz ticks; default 2 s)
@@ -341,13 +382,6 @@ struct mh_model
       std::vector<int> xl;       // exchange slots of the limbs attached to the trunk bodies (plain slot numbers)
    } split_rt;
    int use_split_rt = -1; // MH_SPLIT_RT = 0 | 1: never / whenever usable (default: small batches)
-   // AoS -> SoA scratch copies of the state matrices for the run-time-topology kernels (big batches of wide matrices); tr_pair: the
-   // copies of the forward dynamics call that runs beside the inverse dynamics call on pair_stream (they would share addresses otherwise)
-   Workspace tr, tr_pair;
-   // scratch of the composite entry points: efforts of the Newton-Euler sweep behind mh_aba_joint_wrenches_f64, pair lists of
-   // mh_relative_acceleration_f64
-   Workspace aux, pairs;
-   FreshOnCopy<std::vector<int>> pairs_host;
    int use_transpose = -1; // MH_GENERIC_TRANSPOSE = 0 | 1 overrides the size heuristic
    std::string variant = "generic";
    uint32_t warnings = 0;    // MH_WARN_* bits set by mh_model_create (mh_model_warnings)
@@ -413,16 +447,26 @@ mh_status ensure_workspace(mh_model *m, int64_t B, size_t elem)
    return ensure_bytes(m->ws, (size_t)m->n_slots * (size_t)L.lanes * elem);
 }
 
-// Kernels whose per-body columns are independent (mass matrix, Coriolis matrix, centroidal momentum matrix, joint torque regressor), small
-// batches: up to eight waves per group of 64 configurations, each taking every parts-th body (mh_kernels.h) -- as many as keep one
-// wave per SIMD (measured: profiles/r02_regressor_rates.txt, profiles/r02_column_parts.txt)
-static int regressor_parts(const mh_model *model, const Launch &L)
+// The lane-workspace kernels, small batches: `parts` waves per group of 64 configurations (the grid's y), each with a workspace block of
+// its own -- as many as the call wants while they keep one wave per SIMD.  Kernels whose per-body columns are independent (mass matrix,
+// Coriolis matrix, centroidal momentum matrix, joint torque regressor, gravity gradient, dynamics derivatives) want min(8, n), each wave
+// taking every parts-th body (mh_kernels.h; measured: profiles/r02_regressor_rates.txt, profiles/r02_column_parts.txt); the kernels that
+// work through a list want one wave per target or per group of columns.
+static int launch_parts(const mh_model *m, const Launch &L, long want)
 {
-   return (int)std::max<long>(1, std::min<long>(std::min<long>(8, model->n), (long)model->cu_count * 4 / L.grid));
+   return (int)std::max<long>(1, std::min<long>(want, (long)m->cu_count * 4 / L.grid));
 }
-static mh_status ensure_parts_workspace(mh_model *m, const Launch &L, int parts, size_t elem)
+// ... the workspace of such a launch: `slots` entries per lane on L.grid * parts waves
+static size_t lane_ws_bytes(long slots, const Launch &L, int parts, size_t elem)
 {
-   return ensure_bytes(m->ws, (size_t)m->n_slots * (size_t)L.lanes * (size_t)parts * elem);
+   return (size_t)slots * (size_t)L.lanes * (size_t)parts * elem;
+}
+// ... and its bound over EVERY batch up to the one L was planned for and every want up to max_want (mh_reserve): grid * parts is not
+// monotonic in the batch -- a smaller grid may take more parts -- but never exceeds max(grid, min(want * grid, 4 waves per CU))
+static size_t lane_ws_bound(const mh_model *m, long slots, const Launch &L, long max_want, size_t elem)
+{
+   const long waves = std::max<long>(L.grid, std::min<long>(max_want * L.grid, (long)m->cu_count * 4));
+   return (size_t)slots * (size_t)waves * (size_t)L.block * elem;
 }
 
 template <typename T>
@@ -631,8 +675,6 @@ bool zv_ok(const mh_model *m, int64_t B, bool soa, int jobs)
 // for that group and set the model's (context's) error word in mapped host memory.  It is a failure of an ASYNCHRONOUS call, so it is
 // reported where the library next synchronises or is asked to: mh_model_check, mh_stream_synchronize, the *_host entry points after
 // their own synchronisation, the create-time self-check -- and at the latest by the next bias-split call of the same model / context.
-std::mutex g_error_words_mutex;
-std::vector<int *> g_error_words; // every live model's / context's mapped error word (mh_stream_synchronize has no handle to ask)
 mh_status zv_check_error(mh_model *m)
 {
    if (m->zv_error_host && *(volatile int *)m->zv_error_host != 0)
@@ -1659,8 +1701,8 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
          if (model->split_rt.usable && (model->use_split_rt == 1 || groups_of(B) <= (long)model->cu_count * 2))
             return launch_split_rt<T>(algo, model, B, A, stream); // small batches: the tree split over four waves (mh_split_kernels.h)
          {
-            const int parts = regressor_parts(model, L);
-            if (const mh_status sp = ensure_parts_workspace(model, L, parts, sizeof(T)); sp != MH_OK)
+            const int parts = launch_parts(model, L, std::min(8, model->n));
+            if (const mh_status sp = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T))); sp != MH_OK)
                return sp;
             A.ws = (T *)model->ws.ptr;
             hipLaunchKernelGGL((mh::crba_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, stream, A);
@@ -2078,8 +2120,8 @@ mh_status coriolis_impl(mh_model_t model, int64_t B, const T *q, const T *qd, co
    if (!q || !qd || !H_out || !C_out)
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
    const Launch L = plan_launch(model, B);
-   const int parts = regressor_parts(model, L);
-   st = ensure_parts_workspace(model, L, parts, sizeof(T));
+   const int parts = launch_parts(model, L, std::min(8, model->n));
+   st = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
    hipStream_t stream = (hipStream_t)opts.stream;
@@ -2099,7 +2141,7 @@ mh_status coriolis_impl(mh_model_t model, int64_t B, const T *q, const T *qd, co
          Launch G = L;
          G.grid = grid; // small batches: several waves per group of configurations, each writing every parts-th body's columns
          const int rc = model->spec.launch_coriolis_parts
-                           ? model->spec.launch_coriolis_parts(model->ident_maps ? SPEC_IDENT : 0, &A, grid, regressor_parts(model, G), (void *)stream)
+                           ? model->spec.launch_coriolis_parts(model->ident_maps ? SPEC_IDENT : 0, &A, grid, launch_parts(model, G, std::min(8, model->n)), (void *)stream)
                            : model->spec.launch_coriolis(model->ident_maps ? SPEC_IDENT : 0, &A, grid, (void *)stream);
          if (spec_done(rc, "specialised Coriolis kernel launch failed", st))
             return st;
@@ -2123,8 +2165,8 @@ mh_status regressor_impl(mh_model_t model, int64_t B, const T *q, const T *qd, c
    if (!q || !qd || !qdd || !Y_out)
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
    const Launch L = plan_launch(model, B);
-   const int parts = regressor_parts(model, L);
-   st = ensure_parts_workspace(model, L, parts, sizeof(T));
+   const int parts = launch_parts(model, L, std::min(8, model->n));
+   st = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
    hipStream_t stream = (hipStream_t)opts.stream;
@@ -2162,8 +2204,8 @@ mh_status centroidal_impl(mh_model_t model, int64_t B, const T *q, const T *qd, 
    if (!q || !A_out || (b_out && !qd))
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer (the convective term needs qd)");
    const Launch L = plan_launch(model, B);
-   const int parts = regressor_parts(model, L);
-   st = ensure_parts_workspace(model, L, parts, sizeof(T));
+   const int parts = launch_parts(model, L, std::min(8, model->n));
+   st = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
    hipStream_t stream = (hipStream_t)opts.stream;
@@ -2193,7 +2235,7 @@ mh_status centroidal_impl(mh_model_t model, int64_t B, const T *q, const T *qd, 
          Launch G = L;
          G.grid = grid;
          const int rc = model->spec.launch_centroidal_parts
-                           ? model->spec.launch_centroidal_parts(model->ident_maps ? SPEC_IDENT : 0, &A, grid, regressor_parts(model, G), (void *)stream)
+                           ? model->spec.launch_centroidal_parts(model->ident_maps ? SPEC_IDENT : 0, &A, grid, launch_parts(model, G, std::min(8, model->n)), (void *)stream)
                            : model->spec.launch_centroidal(model->ident_maps ? SPEC_IDENT : 0, &A, grid, (void *)stream);
          if (spec_done(rc, "specialised centroidal kernel launch failed", st))
             return st;
@@ -2222,8 +2264,8 @@ mh_status gravity_gradient_impl(mh_model_t model, int64_t B, const T *q, const d
    if (!q)
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL configuration pointer");
    const Launch L = plan_launch(model, B);
-   const int parts = regressor_parts(model, L);
-   st = ensure_parts_workspace(model, L, parts, sizeof(T));
+   const int parts = launch_parts(model, L, std::min(8, model->n));
+   st = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
    mh::GravArgs<T> G{};
@@ -2243,9 +2285,49 @@ mh_status gravity_gradient_impl(mh_model_t model, int64_t B, const T *q, const d
 // Inverse apparent inertia of K target bodies (MultiBodyResponseCalculator): run-time-topology kernel, which writes every entry of W --
 // no memset in front of it.  Targets and their frames travel as kernel arguments; which bodies the sweeps visit is decided on the device
 // from the model's Euler tour, so the call uploads nothing and allocates nothing beyond the workspace mh_reserve covers.
-static int response_parts(const mh_model *model, const Launch &L, int n_targets)
+static double rotation_error(const double *X)
 {
-   return (int)std::max<long>(1, std::min<long>(n_targets, (long)model->cu_count * 4 / L.grid));
+   const double det = X[0] * (X[4] * X[8] - X[5] * X[7]) - X[1] * (X[3] * X[8] - X[5] * X[6]) + X[2] * (X[3] * X[7] - X[4] * X[6]);
+   double worst = std::fabs(det - 1.0);
+   for (int r = 0; r < 3; r++)
+      for (int s = 0; s < 3; s++)
+      {
+         double g = 0.0;
+         for (int t = 0; t < 3; t++)
+            g += X[3 * t + r] * X[3 * t + s];
+         worst = std::max(worst, std::fabs(g - (r == s ? 1.0 : 0.0)));
+      }
+   return worst; // (NaN where an entry is)
+}
+// The frame of a target in the canonical after-joint frame of its body: (body-fixed -> canonical) o (target frame -> body-fixed), where
+// X (NULL: the identity) is the caller's pose of the target frame in the body-fixed frame of engine body e; e = -1 is the root body,
+// whose body-fixed frame is the root frame itself.  False, with `off` set, where the 3 x 3 part of X is no rotation (a NaN fails too).
+template <typename T>
+static bool target_frame(const mh_model *m, int e, const double *X, T pose[12], double &off)
+{
+   static_assert(mh::MC_PF == mh::MC_RF + 9, "the body-fixed frame's rotation and translation are one pose of 12 numbers");
+   const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+   if (!X)
+      X = ident;
+   off = rotation_error(X);
+   if (!(off <= 1.0e-9))
+      return false;
+   const double *c = e < 0 ? ident : &m->consts[(size_t)e * mh::MC_STRIDE + mh::MC_RF];
+   for (int r = 0; r < 3; r++)
+   {
+      double p = c[9 + r];
+      for (int t = 0; t < 3; t++)
+         p += c[3 * r + t] * X[9 + t];
+      pose[9 + r] = (T)p;
+      for (int s = 0; s < 3; s++)
+      {
+         double v = 0.0;
+         for (int t = 0; t < 3; t++)
+            v += c[3 * r + t] * X[3 * t + s];
+         pose[3 * r + s] = (T)v;
+      }
+   }
+   return true;
 }
 template <typename T>
 mh_status apparent_inertia_impl(mh_model_t model, int64_t B, const T *q, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
@@ -2269,36 +2351,9 @@ mh_status apparent_inertia_impl(mh_model_t model, int64_t B, const T *q, int32_t
          return fail(MH_ERR_INVALID_ARGUMENT, "target %d names joint %d (the model has %d joints)", k, i, model->n);
       const int e = model->engine_of[i];
       G.tgt[k] = e;
-      // the target frame in the canonical after-joint frame: (body-fixed -> canonical) o (target frame -> body-fixed)
-      const double *c = &model->consts[(size_t)e * mh::MC_STRIDE];
-      const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-      const double *X = target_poses ? target_poses + 12 * k : ident;
-      double det = X[0] * (X[4] * X[8] - X[5] * X[7]) - X[1] * (X[3] * X[8] - X[5] * X[6]) + X[2] * (X[3] * X[7] - X[4] * X[6]);
-      double worst = std::fabs(det - 1.0);
-      for (int r = 0; r < 3; r++)
-         for (int s = 0; s < 3; s++)
-         {
-            double g = 0.0;
-            for (int t = 0; t < 3; t++)
-               g += X[3 * t + r] * X[3 * t + s];
-            worst = std::max(worst, std::fabs(g - (r == s ? 1.0 : 0.0)));
-         }
-      if (!(worst <= 1.0e-9)) // (a NaN fails too)
-         return fail(MH_ERR_INVALID_ARGUMENT, "target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", k, worst);
-      for (int r = 0; r < 3; r++)
-      {
-         double p = c[mh::MC_PF + r];
-         for (int t = 0; t < 3; t++)
-            p += c[mh::MC_RF + 3 * r + t] * X[9 + t];
-         G.pose[k][9 + r] = (T)p;
-         for (int s = 0; s < 3; s++)
-         {
-            double v = 0.0;
-            for (int t = 0; t < 3; t++)
-               v += c[mh::MC_RF + 3 * r + t] * X[3 * t + s];
-            G.pose[k][3 * r + s] = (T)v;
-         }
-      }
+      double off;
+      if (!target_frame<T>(model, e, target_poses ? target_poses + 12 * k : nullptr, G.pose[k], off))
+         return fail(MH_ERR_INVALID_ARGUMENT, "target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", k, off);
    }
    if (B == 0)
       return MH_OK;
@@ -2307,13 +2362,14 @@ mh_status apparent_inertia_impl(mh_model_t model, int64_t B, const T *q, int32_t
    const bool coupled = blocks == MH_APPARENT_BLOCKS_COUPLED;
    const long wsize = coupled ? 36L * n_targets * n_targets : 36L * n_targets;
    {
-      const char *q0 = (const char *)q, *w0 = (const char *)W_out;
-      if (q0 < w0 + (size_t)B * wsize * sizeof(T) && w0 < q0 + (size_t)B * model->nq * sizeof(T))
-         return fail(MH_ERR_INVALID_ARGUMENT, "W_out overlaps q");
+      const InRange in{"q", q, (size_t)B * model->nq * sizeof(T)};
+      const OutRange out{"W_out", W_out, (size_t)B * wsize * sizeof(T), 0u};
+      if ((st = check_aliasing("mh_apparent_inertia_inverse", &in, 1, &out, 1)) != MH_OK)
+         return st;
    }
    const Launch L = plan_launch(model, B);
-   const int parts = response_parts(model, L, n_targets);
-   st = ensure_bytes(model->ws, (size_t)model->resp_slots * (size_t)L.lanes * (size_t)parts * sizeof(T));
+   const int parts = launch_parts(model, L, n_targets);
+   st = ensure_bytes(model->ws, lane_ws_bytes(model->resp_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
    mh::Args<T> &A = G.a;
@@ -2333,24 +2389,9 @@ mh_status apparent_inertia_impl(mh_model_t model, int64_t B, const T *q, int32_t
 // every entry of their outputs -- no memset in front of them.  Targets, bases and frames travel as kernel arguments.  The kernels store
 // SoA (coalesced) always: AoS outputs are produced in scratch of the context and brought to rows by a transposition, so that no lane
 // writes entries 6 K nv elements apart.
-static size_t kin_ws_bytes(const mh_model *m, long waves, size_t elem) { return (size_t)m->n * mh::KIN_SLOTS * (size_t)waves * 64 * elem; }
 static size_t kin_scratch_entries(const mh_model *m, int n_targets, bool jacobian, bool conv)
 {
    return jacobian ? 6 * (size_t)n_targets * (size_t)m->nv + (conv ? 6 * (size_t)n_targets : 0) : 12 * (size_t)n_targets;
-}
-static double rotation_error(const double *X)
-{
-   const double det = X[0] * (X[4] * X[8] - X[5] * X[7]) - X[1] * (X[3] * X[8] - X[5] * X[6]) + X[2] * (X[3] * X[7] - X[4] * X[6]);
-   double worst = std::fabs(det - 1.0);
-   for (int r = 0; r < 3; r++)
-      for (int s = 0; s < 3; s++)
-      {
-         double g = 0.0;
-         for (int t = 0; t < 3; t++)
-            g += X[3 * t + r] * X[3 * t + s];
-         worst = std::max(worst, std::fabs(g - (r == s ? 1.0 : 0.0)));
-      }
-   return worst; // (NaN where an entry is)
 }
 template <typename T>
 mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int64_t B, const T *q, const T *qd, int32_t n_targets,
@@ -2386,28 +2427,9 @@ mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: base %d names joint %d (the model has %d joints; -1 is the root body)", call, k, ib, model->n);
       G.tgt[k] = i < 0 ? -1 : model->engine_of[i];
       G.base[k] = ib < 0 ? -1 : model->engine_of[ib];
-      const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-      const double *X = target_poses ? target_poses + 12 * k : ident;
-      const double worst = rotation_error(X);
-      if (!(worst <= 1.0e-9)) // (a NaN fails too)
-         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", call, k, worst);
-      // the target frame in the canonical after-joint frame: (body-fixed -> canonical) o (target frame -> body-fixed); the root body's
-      // body-fixed frame is the root frame itself
-      const double *c = i < 0 ? ident : &model->consts[(size_t)G.tgt[k] * mh::MC_STRIDE + mh::MC_RF];
-      for (int r = 0; r < 3; r++)
-      {
-         double p = c[9 + r];
-         for (int t = 0; t < 3; t++)
-            p += c[3 * r + t] * X[9 + t];
-         G.pose[k][9 + r] = (T)p;
-         for (int s = 0; s < 3; s++)
-         {
-            double v = 0.0;
-            for (int t = 0; t < 3; t++)
-               v += c[3 * r + t] * X[3 * t + s];
-            G.pose[k][3 * r + s] = (T)v;
-         }
-      }
+      double off;
+      if (!target_frame<T>(model, G.tgt[k], target_poses ? target_poses + 12 * k : nullptr, G.pose[k], off))
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", call, k, off);
    }
    if (B == 0)
       return MH_OK;
@@ -2426,8 +2448,8 @@ mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int
          return st;
    }
    const Launch L = plan_launch(model, B);
-   const int parts = jacobian ? response_parts(model, L, n_targets) : 1;
-   st = ensure_bytes(model->ws, kin_ws_bytes(model, (long)L.grid * parts, sizeof(T)));
+   const int parts = jacobian ? launch_parts(model, L, n_targets) : 1;
+   st = ensure_bytes(model->ws, lane_ws_bytes((long)model->n * mh::KIN_SLOTS, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
    // B = 1: the two layouts are the same memory
@@ -2505,13 +2527,14 @@ mh_status mass_matrix_inverse_impl(mh_model_t model, int64_t B, const T *q, int3
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL configuration / output pointer");
    const long hsize = (long)model->nv * n_columns;
    {
-      const char *q0 = (const char *)q, *h0 = (const char *)Hinv_out;
-      if (q0 < h0 + (size_t)B * hsize * sizeof(T) && h0 < q0 + (size_t)B * model->nq * sizeof(T))
-         return fail(MH_ERR_INVALID_ARGUMENT, "Hinv_out overlaps q");
+      const InRange in{"q", q, (size_t)B * model->nq * sizeof(T)};
+      const OutRange out{"Hinv_out", Hinv_out, (size_t)B * hsize * sizeof(T), 0u};
+      if ((st = check_aliasing("mh_mass_matrix_inverse", &in, 1, &out, 1)) != MH_OK)
+         return st;
    }
    const Launch L = plan_launch(model, B);
-   const int parts = response_parts(model, L, minv_groups(n_columns));
-   st = ensure_bytes(model->ws, (size_t)model->resp_slots * (size_t)L.lanes * (size_t)parts * sizeof(T));
+   const int parts = launch_parts(model, L, minv_groups(n_columns));
+   st = ensure_bytes(model->ws, lane_ws_bytes(model->resp_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
    mh::Args<T> &A = G.a;
@@ -2595,10 +2618,6 @@ mh_status parameters_impl(Algo algo, mh_model_t model, int64_t B, const T *q, co
 }
 // Derivatives of the inverse dynamics with respect to q and qd (mh_rnea_deriv_kernels.h): run-time-topology kernel, which writes every
 // entry of its outputs -- no memset in front of it -- in a slot plan of its own (more per body than the model's common plan holds)
-static size_t deriv_ws_bytes(const mh_model *m, const Launch &L, int parts, size_t elem)
-{
-   return (size_t)m->deriv_slots * (size_t)L.lanes * (size_t)parts * elem;
-}
 // the scratch mh_reserve sets aside for the forward form (Hinv and qdd the caller does not ask for) stays within this; a larger need is
 // met at the first such call
 constexpr size_t kDerivReserveCap = (size_t)4 << 30;
@@ -2623,23 +2642,15 @@ mh_status rnea_derivatives_impl(mh_model_t model, int64_t B, const T *q, const T
    {
       const size_t nq = (size_t)B * model->nq * sizeof(T), nvb = (size_t)B * model->nv * sizeof(T), nm = nvb * model->nv,
                    nf = (size_t)B * model->n * 6 * sizeof(T);
-      const void *in[4] = {q, opts.consider_coriolis ? qd : nullptr, opts.consider_accelerations ? qdd : nullptr, f_ext};
-      const size_t in_bytes[4] = {nq, nvb, nvb, nf};
-      const void *out[3] = {tau_out, dq_out, dqd_out};
-      const size_t out_bytes[3] = {nvb, nm, nm};
-      for (int o = 0; o < 3; o++)
-      {
-         for (int i = 0; i < 4; i++)
-            if (ranges_overlap(out[o], out_bytes[o], in[i], in_bytes[i]))
-               return fail(MH_ERR_INVALID_ARGUMENT, "an output overlaps an input");
-         for (int p = o + 1; p < 3; p++)
-            if (ranges_overlap(out[o], out_bytes[o], out[p], out_bytes[p]))
-               return fail(MH_ERR_INVALID_ARGUMENT, "two outputs overlap");
-      }
+      const InRange ins[4] = {{"q", q, nq}, {"qd", opts.consider_coriolis ? qd : nullptr, nvb}, {"qdd", opts.consider_accelerations ? qdd : nullptr, nvb},
+                              {"f_ext", f_ext, nf}};
+      const OutRange outs[3] = {{"tau_out", tau_out, nvb, 0u}, {"dtau_dq_out", dq_out, nm, 0u}, {"dtau_dqd_out", dqd_out, nm, 0u}};
+      if ((st = check_aliasing("mh_rnea_derivatives", ins, 4, outs, 3)) != MH_OK)
+         return st;
    }
    const Launch L = plan_launch(model, B);
-   const int parts = regressor_parts(model, L);
-   st = ensure_bytes(model->ws, deriv_ws_bytes(model, L, parts, sizeof(T)));
+   const int parts = launch_parts(model, L, std::min(8, model->n));
+   st = ensure_bytes(model->ws, lane_ws_bytes(model->deriv_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
    mh::DerivArgs<T> G{};
@@ -2681,19 +2692,10 @@ mh_status aba_derivatives_impl(mh_model_t model, int64_t B, const T *q, const T 
       return fail(MH_ERR_INVALID_ARGUMENT, "nv = %d is beyond the %d DoFs the product kernel takes", model->nv, mh::NEG_SOLVE_LDS_ENTRIES);
    const size_t nvb = (size_t)B * model->nv * sizeof(T), nm = nvb * model->nv;
    {
-      const void *in[4] = {q, qd, tau, f_ext};
-      const size_t in_bytes[4] = {(size_t)B * model->nq * sizeof(T), nvb, nvb, (size_t)B * model->n * 6 * sizeof(T)};
-      const void *out[4] = {qdd_out, dq_out, dqd_out, Hinv_out};
-      const size_t out_bytes[4] = {nvb, nm, nm, nm};
-      for (int a = 0; a < 4; a++)
-      {
-         for (int i = 0; i < 4; i++)
-            if (ranges_overlap(out[a], out_bytes[a], in[i], in_bytes[i]))
-               return fail(MH_ERR_INVALID_ARGUMENT, "an output overlaps an input");
-         for (int b = a + 1; b < 4; b++)
-            if (ranges_overlap(out[a], out_bytes[a], out[b], out_bytes[b]))
-               return fail(MH_ERR_INVALID_ARGUMENT, "two outputs overlap");
-      }
+      const InRange ins[4] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"qd", qd, nvb}, {"tau", tau, nvb}, {"f_ext", f_ext, (size_t)B * model->n * 6 * sizeof(T)}};
+      const OutRange outs[4] = {{"qdd_out", qdd_out, nvb, 0u}, {"dqdd_dq_out", dq_out, nm, 0u}, {"dqdd_dqd_out", dqd_out, nm, 0u}, {"Hinv_out", Hinv_out, nm, 0u}};
+      if ((st = check_aliasing("mh_aba_derivatives", ins, 4, outs, 4)) != MH_OK)
+         return st;
    }
    T *qdd = qdd_out, *Hinv = Hinv_out;
    if (!qdd || !Hinv)
@@ -3563,65 +3565,6 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
    return MH_OK;
 }
 
-// everything compute calls write: owned by a model (its default context) and by every context
-static void free_scratch(mh_model *m)
-{
-   (void)hipFree(m->ws.ptr);
-   (void)hipFree(m->ws_pair.ptr);
-   (void)hipFree(m->tr_pair.ptr);
-   (void)hipFree(m->zv_tau.ptr);
-   (void)hipFree(m->zv_cols.ptr);
-   (void)hipFree(m->zvb_cs.ptr);
-   (void)hipFree(m->zv_flags.ptr);
-   if (m->zv_error_host)
-   {
-      {
-         std::lock_guard<std::mutex> lock(g_error_words_mutex);
-         g_error_words.erase(std::remove(g_error_words.begin(), g_error_words.end(), m->zv_error_host), g_error_words.end());
-      }
-      (void)hipHostFree(m->zv_error_host);
-   }
-   if (m->pair_stream)
-   {
-      (void)hipStreamDestroy(m->pair_stream);
-      (void)hipEventDestroy(m->pair_fork);
-      (void)hipEventDestroy(m->pair_join);
-   }
-   (void)hipFree(m->stage.ptr);
-   for (int k = 0; k < 3; k++)
-   {
-      if (m->ev_in[k])
-         (void)hipEventDestroy(m->ev_in[k]);
-      if (m->ev_run[k])
-         (void)hipEventDestroy(m->ev_run[k]);
-      if (m->ev_out[k])
-         (void)hipEventDestroy(m->ev_out[k]);
-   }
-   if (m->hs_in)
-      (void)hipStreamDestroy(m->hs_in);
-   if (m->hs_run)
-      (void)hipStreamDestroy(m->hs_run);
-   if (m->hs_out)
-      (void)hipStreamDestroy(m->hs_out);
-   (void)hipFree(m->tr.ptr);
-   (void)hipFree(m->aux.ptr);
-   (void)hipFree(m->pairs.ptr);
-   (void)hipFree(m->deriv.ptr);
-   (void)hipFree(m->step.ptr);
-   (void)hipFree(m->kin.ptr);
-}
-// a fresh set of the above for a copy of a handle
-static void reset_scratch(mh_model *m)
-{
-   m->ws = m->stage = m->ws_pair = m->zv_tau = m->zv_cols = m->zv_flags = m->zvb_cs = m->tr = m->tr_pair = m->aux = m->pairs = m->deriv = m->step = m->kin = Workspace{};
-   m->hs_in = m->hs_run = m->hs_out = nullptr;
-   for (int k = 0; k < 3; k++)
-      m->ev_in[k] = m->ev_run[k] = m->ev_out[k] = nullptr;
-   m->pair_stream = nullptr, m->pair_fork = m->pair_join = nullptr;
-   m->zv_epoch = 0, m->zv_error_host = m->zv_error_dev = nullptr;
-   m->pairs_host.clear();
-   m->lds_attr.clear();
-}
 // the device records, the code object and the host-side description: released once, by whoever holds the last reference
 static void release_model(mh_model *m)
 {
@@ -3641,7 +3584,7 @@ static void release_model(mh_model *m)
    (void)hipFree(m->d_grav_zero_cols);
    (void)hipFree(m->d_resp_info);
    (void)hipFree(m->d_minv_owner);
-   free_scratch(m);
+   free_scratch(*m);
    if (m->spec.handle)
       dlclose(m->spec.handle);
    delete m;
@@ -3682,7 +3625,7 @@ mh_status mh_context_create(mh_model_t model, mh_context_t *ctx_out)
          return fail(MH_ERR_INVALID_ARGUMENT, "mh_context_create: the model has been destroyed (it lives on only for its remaining contexts)");
       // The copy reads the immutable description only: what the default context's calls (or another context's first depth-first call, under
       // dfs_mutex) may be inserting into at this moment -- dfs_plans, lds_attr, pairs_host -- is FreshOnCopy and starts empty here; the
-      // plain scratch words (Workspace, streams, events) are overwritten by reset_scratch below whatever was read.
+      // plain scratch words (Workspace, streams, events) are overwritten by the fresh ContextState below whatever was read.
       c = new (std::nothrow) mh_model(*root);
       if (!c)
          return fail(MH_ERR_OUT_OF_MEMORY, "out of host memory");
@@ -3691,7 +3634,7 @@ mh_status mh_context_create(mh_model_t model, mh_context_t *ctx_out)
    c->parent = root;
    c->n_contexts = 0;
    c->destroy_pending = false;
-   reset_scratch(c);
+   static_cast<ContextState &>(*c) = ContextState{}; // (its FreshOnCopy members came out of the copy empty: assignment leaves those alone)
    mh_context *ctx = new (std::nothrow) mh_context{c};
    if (!ctx)
    {
@@ -3709,7 +3652,7 @@ void mh_context_destroy(mh_context_t ctx)
       return;
    mh_model *c = ctx->m;
    mh_model *root = c->parent;
-   free_scratch(c);
+   free_scratch(*c);
    bool last = false;
    {
       std::lock_guard<std::mutex> lock(g_context_mutex);
@@ -3926,36 +3869,30 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
    st = ensure_workspace(m, max_batch, sizeof(double)); // (mh_rnea_parameters_* / mh_aba_parameters_* work in this plan too)
    if (st != MH_OK)
       return st;
-   { // mh_regressor_*: one workspace block per wave, several waves per group of configurations on small batches
+   { // the lane-workspace kernels: (slots per lane, the most waves per group of configurations a call may want), bounded over every
+      // batch up to max_batch (lane_ws_bound)
       const Launch L = plan_launch(m, max_batch);
-      st = ensure_bytes(m->ws, (size_t)m->n_slots * (size_t)L.lanes * regressor_parts(m, L) * sizeof(double));
-      if (st != MH_OK)
-         return st;
-      // mh_apparent_inertia_inverse_*: its own slots behind the model's, one block per wave, up to one wave per target
-      // (grid * parts is not monotonic in the batch: the bound over every batch up to max_batch); mh_mass_matrix_inverse_* works in
-      // the same slots with up to one wave per group of six columns
-      const long resp_parts = std::max<long>(MH_MAX_APPARENT_TARGETS, minv_groups(std::max<int>(m->nv, MH_MAX_INVERSE_COLUMNS)));
-      const long resp_waves = std::max<long>(L.grid, std::min<long>(resp_parts * L.grid, (long)m->cu_count * 4));
-      st = ensure_bytes(m->ws, (size_t)m->resp_slots * (size_t)resp_waves * 64 * sizeof(double));
-      if (st != MH_OK)
-         return st;
-      // mh_rnea_derivatives_* / mh_aba_derivatives_*: the kernel's own slot plan, parts as the regressor's (grid * parts is bounded as
-      // above), and the scratch of the forward form
-      const long deriv_waves = std::max<long>(L.grid, std::min<long>(8L * L.grid, (long)m->cu_count * 4));
-      st = ensure_bytes(m->ws, (size_t)m->deriv_slots * (size_t)deriv_waves * 64 * sizeof(double));
-      if (st == MH_OK && m->nv > 0 && deriv_scratch_bytes(m, max_batch, sizeof(double)) <= kDerivReserveCap)
+      const long lane_plans[4][2] = {
+         {m->n_slots, std::min(8, m->n)}, // mh_regressor_*, mh_crba_coriolis_*, mh_centroidal_*, mh_gravity_gradient_*, the mass matrix
+         // mh_apparent_inertia_inverse_*: its own slots behind the model's, up to one wave per target; mh_mass_matrix_inverse_* works in
+         // the same slots with up to one wave per group of six columns
+         {m->resp_slots, std::max<long>(MH_MAX_APPARENT_TARGETS, minv_groups(std::max<int>(m->nv, MH_MAX_INVERSE_COLUMNS)))},
+         {m->deriv_slots, std::min(8, m->n)}, // mh_rnea_derivatives_* / mh_aba_derivatives_*: the kernel's own slot plan
+         // mh_body_poses_* / mh_geometric_jacobian_*: pose and twist of every body per lane, up to one wave per target
+         {(long)m->n * mh::KIN_SLOTS, MH_MAX_KINEMATIC_TARGETS}};
+      for (const auto &plan : lane_plans)
+         if ((st = ensure_bytes(m->ws, lane_ws_bound(m, plan[0], L, plan[1], sizeof(double)))) != MH_OK)
+            return st;
+      // mh_aba_derivatives_*: the scratch of the forward form
+      if (m->nv > 0 && deriv_scratch_bytes(m, max_batch, sizeof(double)) <= kDerivReserveCap)
          st = ensure_bytes(m->deriv, deriv_scratch_bytes(m, max_batch, sizeof(double)));
       // mh_aba_integrate_derivatives_*: the two derivative matrices beside them, under the same cap
       if (st == MH_OK && m->nv > 0 && deriv_scratch_bytes(m, max_batch, sizeof(double)) + step_scratch_bytes(m, max_batch, sizeof(double)) <= kDerivReserveCap)
          st = ensure_bytes(m->step, step_scratch_bytes(m, max_batch, sizeof(double)));
       if (st != MH_OK)
          return st;
-      // mh_body_poses_* / mh_geometric_jacobian_*: pose and twist of every body per lane, up to one wave per target (bounded as above),
-      // and the SoA form of their AoS outputs for the largest target list, while it stays within the cap of the scratch above
-      const long kin_waves = std::max<long>(L.grid, std::min<long>((long)MH_MAX_KINEMATIC_TARGETS * L.grid, (long)m->cu_count * 4));
-      st = ensure_bytes(m->ws, kin_ws_bytes(m, kin_waves, sizeof(double)));
-      if (st != MH_OK)
-         return st;
+      // mh_body_poses_* / mh_geometric_jacobian_*: the SoA form of their AoS outputs for the largest target list, while it stays within
+      // the cap of the scratch above
       const size_t kin_entries = std::max(kin_scratch_entries(m, MH_MAX_KINEMATIC_TARGETS, true, true), kin_scratch_entries(m, std::max(m->n, MH_MAX_KINEMATIC_TARGETS), false, false));
       if ((size_t)max_batch * kin_entries * sizeof(double) <= kDerivReserveCap)
          st = ensure_bytes(m->kin, (size_t)max_batch * kin_entries * sizeof(double));
@@ -4294,16 +4231,6 @@ mh_status mh_aba_locked_f64(mh_model_t model, int64_t B, const double *q, const 
 }
 // The pair calls run their two algorithms side by side (or phase by phase in one workgroup): an output that overlaps an input of the OTHER
 // algorithm would be read half-written.  (mh_rnea_* then mh_aba_* is the call sequence for in-place use.)
-static bool pair_outputs_overlap(const void *q, const void *qd, const void *qdd, const void *tau, const void *tau_out, const void *qdd_out, size_t bq, size_t bv)
-{
-   auto overlap = [](const void *a, size_t na, const void *b, size_t nb) { return (const char *)a < (const char *)b + nb && (const char *)b < (const char *)a + na; };
-   const void *ins[4] = {q, qd, qdd, tau};
-   const size_t nin[4] = {bq, bv, bv, bv};
-   for (int i = 0; i < 4; i++)
-      if (overlap(tau_out, bv, ins[i], nin[i]) || overlap(qdd_out, bv, ins[i], nin[i]))
-         return true;
-   return overlap(tau_out, bv, qdd_out, bv);
-}
 mh_status mh_rnea_aba_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double *tau,
                           const double gravity[3], const double *f_ext, const mh_options *opts_in, double *tau_out, double *qdd_out)
 {
@@ -4315,8 +4242,13 @@ mh_status mh_rnea_aba_f64(mh_model_t model, int64_t B, const double *q, const do
       return MH_OK;
    if (!q || !qd || !qdd || !tau || (!gravity && !opts.use_root_acceleration) || !tau_out || !qdd_out)
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
-   if (pair_outputs_overlap(q, qd, qdd, tau, tau_out, qdd_out, (size_t)B * model->nq * sizeof(double), (size_t)B * model->nv * sizeof(double)))
-      return fail(MH_ERR_INVALID_ARGUMENT, "mh_rnea_aba_f64: tau_out / qdd_out must not overlap q, qd, qdd, tau or each other (the two algorithms run concurrently)");
+   {
+      const size_t bq = (size_t)B * model->nq * sizeof(double), bv = (size_t)B * model->nv * sizeof(double);
+      const InRange ins[4] = {{"q", q, bq}, {"qd", qd, bv}, {"qdd", qdd, bv}, {"tau", tau, bv}};
+      const OutRange outs[2] = {{"tau_out", tau_out, bv, 0u}, {"qdd_out", qdd_out, bv, 0u}};
+      if ((st = check_aliasing("mh_rnea_aba_f64", ins, 4, outs, 2)) != MH_OK)
+         return st;
+   }
    const long waves = groups_of(B);
    const bool fusable = model->n_locked == 0 && model->spec.launch_fused && model->use_spec && model->dense_maps && opts.layout == MH_LAYOUT_AOS
                         && opts.consider_coriolis && opts.consider_accelerations && 2 * waves <= (long)model->cu_count * kFusedFactor
@@ -4474,9 +4406,14 @@ mh_status mh_crba_f32(mh_model_t model, int64_t B, const float *q, const mh_opti
 mh_status mh_rnea_aba_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const float *tau,
                           const double gravity[3], const float *f_ext, const mh_options *opts_in, float *tau_out, float *qdd_out)
 {
-   if (model && B > 0 && q && qd && qdd && tau && tau_out && qdd_out
-       && pair_outputs_overlap(q, qd, qdd, tau, tau_out, qdd_out, (size_t)B * model->nq * sizeof(float), (size_t)B * model->nv * sizeof(float)))
-      return fail(MH_ERR_INVALID_ARGUMENT, "mh_rnea_aba_f32: tau_out / qdd_out must not overlap q, qd, qdd, tau or each other (the two algorithms run concurrently)");
+   if (model && B > 0 && q && qd && qdd && tau && tau_out && qdd_out)
+   {
+      const size_t bq = (size_t)B * model->nq * sizeof(float), bv = (size_t)B * model->nv * sizeof(float);
+      const InRange ins[4] = {{"q", q, bq}, {"qd", qd, bv}, {"qdd", qdd, bv}, {"tau", tau, bv}};
+      const OutRange outs[2] = {{"tau_out", tau_out, bv, 0u}, {"qdd_out", qdd_out, bv, 0u}};
+      if (const mh_status sa = check_aliasing("mh_rnea_aba_f32", ins, 4, outs, 2); sa != MH_OK)
+         return sa;
+   }
    mh_options opts;
    mh_status st = begin_call(model, B, opts_in, opts); // (the two single calls below check again, on the context's copy)
    if (st != MH_OK)

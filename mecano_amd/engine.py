@@ -139,6 +139,28 @@ class HipModel:
         if tuple(f_ext.shape) != want and not (layout == _lib.LAYOUT_AOS and tuple(f_ext.shape) == (B, self.n_joints * 6)):
             raise _lib.MecanoHipError(2, f"external wrenches have shape {tuple(f_ext.shape)}, expected {want}")
 
+    def _device_tensor(self, t, dt):
+        if not self._is_torch(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+
+    def _output(self, out, shape, dt, device, name=""):
+        """``out`` checked as an output of ``shape``, or a new tensor where it is None."""
+        import torch
+        if out is None:
+            return torch.empty(shape, dtype=dt, device=device)
+        self._device_tensor(out, dt)
+        if tuple(out.shape) != shape:
+            raise _lib.MecanoHipError(2, f"{name and name + ' '}output has shape {tuple(out.shape)}, expected {shape}")
+        return out
+
+    def _outputs(self, out, shapes, names, dt, device):
+        """The outputs of a call that returns several: ``out`` a tuple with None for what is not wanted, or None for all of them."""
+        if out is None:
+            return tuple(self._output(None, s, dt, device) for s in shapes)
+        if len(out) != len(names):
+            raise _lib.MecanoHipError(2, f"out must hold {len(names)} entries ({', '.join(names)})")
+        return tuple(t if t is None else self._output(t, s, dt, device, name) for t, s, name in zip(out, shapes, names))
+
     def _run(self, kind, q, qd, x3, gravity, f_ext, layout, consider_coriolis, consider_accelerations):
         lib = _lib.load()
         g, ra = self._root(gravity)
@@ -522,28 +544,20 @@ class HipModel:
         319-351): (tau [B, nv], grad [B, nv, nv]) with tau(q + dq) = tau(q) + grad(q) dq, dq in velocity space, the wrenches held constant
         in the world.  Device tensors (fp64 / fp32); SoA: tau [nv, B], grad [nv * nv, B].  ``gravity`` is the 3-vector g.  ``out``: a
         (tau, grad) pair of tensors to write into; either may be None (that output is then not computed), not both."""
-        import torch
         B, dt, sfx, stream = self._device_inputs([q], layout)
         a = [float(v) for v in np.asarray(gravity, dtype=np.float64).reshape(-1)]
         if len(a) != 3:
             raise _lib.MecanoHipError(2, f"gravity must have 3 entries, got {len(a)}")
-        if f_ext is not None and (not self._is_torch(f_ext) or not f_ext.is_cuda or f_ext.dtype != dt or not f_ext.is_contiguous()):
-            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+        if f_ext is not None:
+            self._device_tensor(f_ext, dt)
         self._check_f_ext(f_ext, B, layout)
         aos = layout == _lib.LAYOUT_AOS
         shapes = ((B, self.nv) if aos else (self.nv, B), (B, self.nv, self.nv) if aos else (self.nv * self.nv, B))
-        if out is None:
-            out = tuple(torch.empty(s, dtype=dt, device=q.device) for s in shapes)
-        tau, grad = out
-        if tau is None and grad is None:
-            raise _lib.MecanoHipError(1, "both outputs are None")
-        for t, s, name in ((tau, shapes[0], "tau"), (grad, shapes[1], "grad")):
-            if t is None:
-                continue
-            if not self._is_torch(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
-            if tuple(t.shape) != s:
-                raise _lib.MecanoHipError(2, f"{name} output has shape {tuple(t.shape)}, expected {s}")
+        if out is not None:
+            tau, grad = out  # (a pair: anything else fails to unpack, here)
+            if tau is None and grad is None:
+                raise _lib.MecanoHipError(1, "both outputs are None")
+        tau, grad = self._outputs(out, shapes, ("tau", "grad"), dt, q.device)
         opts = self._options(layout, stream=stream)
         _lib.check(getattr(_lib.load(), f"mh_gravity_gradient_{sfx}")(self._h, B, q.data_ptr(), (ctypes.c_double * 3)(*a),
                                                                      None if f_ext is None else f_ext.data_ptr(), ctypes.byref(opts),
@@ -574,13 +588,7 @@ class HipModel:
         size = 36 * K * K if coupled else 36 * K
         aos_shape = (B, 6 * K, 6 * K) if coupled else (B, K, 6, 6)
         shape = aos_shape if layout == _lib.LAYOUT_AOS else (size, B)
-        if out is None:
-            out = torch.empty(shape, dtype=dt, device=q.device)
-        else:
-            if not self._is_torch(out) or not out.is_cuda or out.dtype != dt or not out.is_contiguous():
-                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
-            if tuple(out.shape) != shape:
-                raise _lib.MecanoHipError(2, f"W output has shape {tuple(out.shape)}, expected {shape}")
+        out = self._output(out, shape, dt, q.device, "W")
         opts = self._options(layout, stream=stream)
         _lib.check(getattr(_lib.load(), f"mh_apparent_inertia_inverse_{sfx}")(
             self._h, B, q.data_ptr(), K, tgt.ctypes.data, None if poses is None else poses.ctypes.data,
@@ -603,16 +611,6 @@ class HipModel:
                 raise _lib.MecanoHipError(2, f"poses must hold 12 numbers per target ({12 * K}), got {poses.shape[0]}")
         return tgt, K, bases, poses
 
-    def _kinematic_output(self, out, shape, dt, device, name):
-        import torch
-        if out is None:
-            return torch.empty(shape, dtype=dt, device=device)
-        if not self._is_torch(out) or not out.is_cuda or out.dtype != dt or not out.is_contiguous():
-            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
-        if tuple(out.shape) != shape:
-            raise _lib.MecanoHipError(2, f"{name} output has shape {tuple(out.shape)}, expected {shape}")
-        return out
-
     def body_poses(self, q, targets=None, poses=None, layout=_lib.LAYOUT_AOS, out=None):
         """Poses of frames fixed in bodies, in the root body frame (the frame ``gravity`` is expressed in): [B, K, 12], R row-major then p,
         x_root = R x + p; SoA: [12 K, B].  ``targets``: 1 to 16 positions in the joint list (the joint's successor body; -1 = the root
@@ -629,7 +627,7 @@ class HipModel:
             tgt, K = None, self.n_joints
         else:
             tgt, K, _, poses = self._kinematic_targets(targets, None, poses)
-        out = self._kinematic_output(out, (B, K, 12) if layout == _lib.LAYOUT_AOS else (12 * K, B), dt, q.device, "pose")
+        out = self._output(out, (B, K, 12) if layout == _lib.LAYOUT_AOS else (12 * K, B), dt, q.device, "pose")
         opts = self._options(layout, stream=stream)
         _lib.check(getattr(_lib.load(), f"mh_body_poses_{sfx}")(
             self._h, B, q.data_ptr(), K, None if tgt is None else tgt.ctypes.data, None if poses is None else poses.ctypes.data,
@@ -655,8 +653,8 @@ class HipModel:
         tgt, K, bases, poses = self._kinematic_targets(targets, bases, poses)
         aos = layout == _lib.LAYOUT_AOS
         J_out, c_out = (out if convective else (out, None)) if out is not None else (None, None)
-        J = self._kinematic_output(J_out, (B, 6 * K, self.nv) if aos else (6 * K * self.nv, B), dt, q.device, "J")
-        c = self._kinematic_output(c_out, (B, K, 6) if aos else (6 * K, B), dt, q.device, "convective term") if convective else None
+        J = self._output(J_out, (B, 6 * K, self.nv) if aos else (6 * K * self.nv, B), dt, q.device, "J")
+        c = self._output(c_out, (B, K, 6) if aos else (6 * K, B), dt, q.device, "convective term") if convective else None
         opts = self._options(layout, stream=stream)
         _lib.check(getattr(_lib.load(), f"mh_geometric_jacobian_{sfx}")(
             self._h, B, q.data_ptr(), None if qd is None else qd.data_ptr(), K, None if bases is None else bases.ctypes.data, tgt.ctypes.data,
@@ -677,37 +675,11 @@ class HipModel:
         cols = None if columns is None else np.ascontiguousarray(np.asarray(columns, dtype=np.int32).reshape(-1))
         K = self.nv if cols is None else int(cols.shape[0])
         shape = (B, self.nv, K) if layout == _lib.LAYOUT_AOS else (self.nv * K, B)
-        if out is None:
-            out = torch.empty(shape, dtype=dt, device=q.device)
-        else:
-            if not self._is_torch(out) or not out.is_cuda or out.dtype != dt or not out.is_contiguous():
-                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
-            if tuple(out.shape) != shape:
-                raise _lib.MecanoHipError(2, f"Hinv output has shape {tuple(out.shape)}, expected {shape}")
+        out = self._output(out, shape, dt, q.device, "Hinv")
         opts = self._options(layout, stream=stream)
         _lib.check(getattr(_lib.load(), f"mh_mass_matrix_inverse_{sfx}")(
             self._h, B, q.data_ptr(), K, None if cols is None else cols.ctypes.data, ctypes.byref(opts), out.data_ptr()))
         return out
-
-    def _derivative_outputs(self, q, B, dt, layout, out, names):
-        """The outputs of the two derivative calls: a vector [B, nv], then nv x nv matrices; ``out`` a tuple with None for what is not
-        wanted, or None for all of them."""
-        import torch
-        aos = layout == _lib.LAYOUT_AOS
-        vec, mat = (B, self.nv) if aos else (self.nv, B), (B, self.nv, self.nv) if aos else (self.nv * self.nv, B)
-        shapes = (vec,) + (mat,) * (len(names) - 1)
-        if out is None:
-            return tuple(torch.empty(s, dtype=dt, device=q.device) for s in shapes)
-        if len(out) != len(names):
-            raise _lib.MecanoHipError(2, f"out must hold {len(names)} entries ({', '.join(names)})")
-        for t, s, name in zip(out, shapes, names):
-            if t is None:
-                continue
-            if not self._is_torch(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
-                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
-            if tuple(t.shape) != s:
-                raise _lib.MecanoHipError(2, f"{name} output has shape {tuple(t.shape)}, expected {s}")
-        return tuple(out)
 
     def rnea_derivatives(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, consider_coriolis=True,
                          consider_accelerations=True, out=None):
@@ -721,10 +693,12 @@ class HipModel:
         B, dt, sfx, stream = self._device_inputs(given, layout)
         if (consider_coriolis and qd is None) or (consider_accelerations and qdd is None):
             raise _lib.MecanoHipError(1, "qd / qdd may be None only with their switch off")
-        if f_ext is not None and (not self._is_torch(f_ext) or not f_ext.is_cuda or f_ext.dtype != dt or not f_ext.is_contiguous()):
-            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+        if f_ext is not None:
+            self._device_tensor(f_ext, dt)
         self._check_f_ext(f_ext, B, layout)
-        tau, dq, dqd = self._derivative_outputs(q, B, dt, layout, out, ("tau", "dtau_dq", "dtau_dqd"))
+        aos = layout == _lib.LAYOUT_AOS
+        vec, mat = (B, self.nv) if aos else (self.nv, B), (B, self.nv, self.nv) if aos else (self.nv * self.nv, B)
+        tau, dq, dqd = self._outputs(out, (vec, mat, mat), ("tau", "dtau_dq", "dtau_dqd"), dt, q.device)
         if dq is None and dqd is None:
             raise _lib.MecanoHipError(1, "both matrices are None")
         g, ra = self._root(gravity)
@@ -741,10 +715,12 @@ class HipModel:
         for ``rnea_derivatives``.  ``out``: a (qdd, dqdd_dq, dqdd_dqd, Hinv) tuple to write into; any may be None (qdd and Hinv then go to
         scratch of the model), not both derivative matrices.  A model with acceleration-source joints is refused."""
         B, dt, sfx, stream = self._device_inputs([q, qd, tau], layout)
-        if f_ext is not None and (not self._is_torch(f_ext) or not f_ext.is_cuda or f_ext.dtype != dt or not f_ext.is_contiguous()):
-            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+        if f_ext is not None:
+            self._device_tensor(f_ext, dt)
         self._check_f_ext(f_ext, B, layout)
-        qdd, dq, dqd, Hinv = self._derivative_outputs(q, B, dt, layout, out, ("qdd", "dqdd_dq", "dqdd_dqd", "Hinv"))
+        aos = layout == _lib.LAYOUT_AOS
+        vec, mat = (B, self.nv) if aos else (self.nv, B), (B, self.nv, self.nv) if aos else (self.nv * self.nv, B)
+        qdd, dq, dqd, Hinv = self._outputs(out, (vec, mat, mat, mat), ("qdd", "dqdd_dq", "dqdd_dqd", "Hinv"), dt, q.device)
         if dq is None and dqd is None:
             raise _lib.MecanoHipError(1, "both derivative matrices are None")
         g, ra = self._root(gravity)
@@ -755,21 +731,13 @@ class HipModel:
         return qdd, dq, dqd, Hinv
 
     def _chart_call(self, name, a, b, b_cols, out_cols, layout, out):
-        import torch
         B, dt, sfx, stream = self._device_inputs([a], layout)
         aos = layout == _lib.LAYOUT_AOS
         shape_of = lambda n: (B, n) if aos else (n, B)
-        if not self._is_torch(b) or not b.is_cuda or b.dtype != dt or not b.is_contiguous():
-            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+        self._device_tensor(b, dt)
         if tuple(b.shape) != shape_of(b_cols):
             raise _lib.MecanoHipError(2, f"second input has shape {tuple(b.shape)}, expected {shape_of(b_cols)}")
-        if out is None:
-            out = torch.empty(shape_of(out_cols), dtype=dt, device=a.device)
-        else:
-            if not self._is_torch(out) or not out.is_cuda or out.dtype != dt or not out.is_contiguous():
-                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
-            if tuple(out.shape) != shape_of(out_cols):
-                raise _lib.MecanoHipError(2, f"output has shape {tuple(out.shape)}, expected {shape_of(out_cols)}")
+        out = self._output(out, shape_of(out_cols), dt, a.device)
         opts = self._options(layout, stream=stream)
         _lib.check(getattr(_lib.load(), f"{name}_{sfx}")(self._h, B, a.data_ptr(), b.data_ptr(), ctypes.byref(opts), out.data_ptr()))
         return out
@@ -794,8 +762,8 @@ class HipModel:
         (not returned), not both matrices, q_next and qd_next only together.  A model with acceleration-source joints is refused."""
         import torch
         B, dtp, sfx, stream = self._device_inputs([q, qd, tau], layout)
-        if f_ext is not None and (not self._is_torch(f_ext) or not f_ext.is_cuda or f_ext.dtype != dtp or not f_ext.is_contiguous()):
-            raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+        if f_ext is not None:
+            self._device_tensor(f_ext, dtp)
         self._check_f_ext(f_ext, B, layout)
         aos, nv = layout == _lib.LAYOUT_AOS, self.nv
         shapes = ((B, nv), (B, self.nq), (B, nv), (B, 2 * nv, 2 * nv), (B, 2 * nv, nv)) if aos else \
@@ -805,15 +773,7 @@ class HipModel:
             out = tuple(torch.empty(s, dtype=dtp, device=q.device) for s in shapes)
             out = (out[0], q.clone(), qd.clone()) + out[3:]  # entries no joint owns are passed through unchanged
         else:
-            if len(out) != 5:
-                raise _lib.MecanoHipError(2, f"out must hold 5 entries ({', '.join(names)})")
-            for t, s, name in zip(out, shapes, names):
-                if t is None:
-                    continue
-                if not self._is_torch(t) or not t.is_cuda or t.dtype != dtp or not t.is_contiguous():
-                    raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
-                if tuple(t.shape) != s:
-                    raise _lib.MecanoHipError(2, f"{name} output has shape {tuple(t.shape)}, expected {s}")
+            out = self._outputs(out, shapes, names, dtp, q.device)
         g, ra = self._root(gravity)
         opts = self._options(layout, True, True, stream, root_acceleration=ra)
         ptr = lambda t: None if t is None else t.data_ptr()
@@ -844,21 +804,15 @@ class HipModel:
         B, dt, sfx, stream = self._device_inputs([q, qd, x3], layout)
         aos = layout == _lib.LAYOUT_AOS
         for t in (pi, f_ext):
-            if t is not None and (not self._is_torch(t) or not t.is_cuda or t.dtype != dt or not t.is_contiguous()):
-                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
+            if t is not None:
+                self._device_tensor(t, dt)
         if pi is None:
             raise _lib.MecanoHipError(1, "pi is None")
         want = ((B, self.n_joints, 10), (B, self.n_joints * 10)) if aos else ((self.n_joints * 10, B),)
         if tuple(pi.shape) not in want:
             raise _lib.MecanoHipError(2, f"inertial parameters have shape {tuple(pi.shape)}, expected {want[0]}")
         self._check_f_ext(f_ext, B, layout)
-        if out is None:
-            out = torch.empty_like(qd)
-        else:
-            if not self._is_torch(out) or not out.is_cuda or out.dtype != dt or not out.is_contiguous():
-                raise ValueError("device tensors must be contiguous, on the HIP device and of one dtype")
-            if tuple(out.shape) != tuple(qd.shape):
-                raise _lib.MecanoHipError(2, f"output has shape {tuple(out.shape)}, expected {tuple(qd.shape)}")
+        out = self._output(out, tuple(qd.shape), dt, qd.device)
         g, ra = self._root(gravity)
         opts = self._options(layout, consider_coriolis, consider_accelerations, stream, root_acceleration=ra)
         _lib.check(getattr(_lib.load(), f"mh_{kind}_parameters_{sfx}")(

@@ -225,3 +225,31 @@ def check_cover(out, guard, idx, ref, tol=1.0e-10, absolute=False, label=None, r
     bound = tol if absolute else tol * max(1.0, float(np.abs(ref).max()) if ref.size else 0.0)
     assert err <= bound, f"{label}: max err {err:.3e} > {bound:.3e}"
     return err
+
+
+def bad_outputs(torch, shape, dt=None):
+    """The four ways a tensor handed in as ``out`` can be wrong for an output of `shape` and dtype `dt` (fp64), with what the engine raises
+    for each: [(what, tensor, exception class)].  The first three are device tensors; none is ever written."""
+    from mecano_amd import _lib
+    dt = dt or torch.float64
+    other = torch.float32 if dt == torch.float64 else torch.float64
+    wide = torch.empty(tuple(shape[:-1]) + (2 * shape[-1],), dtype=dt, device="cuda")
+    return [("wrong shape", torch.empty(tuple(shape[:-1]) + (shape[-1] + 1,), dtype=dt, device="cuda"), _lib.MecanoHipError),
+            ("wrong dtype", torch.empty(shape, dtype=other, device="cuda"), ValueError),
+            ("not contiguous", wide[..., ::2], ValueError),
+            ("on the host", torch.empty(shape, dtype=dt), ValueError)]
+
+
+def check_bad_outputs(torch, shapes, call):
+    """call(out) must raise for every bad tensor in every place of the output tuple `shapes` describes (the other places hold good
+    tensors); a single shape stands for a call whose ``out`` is one tensor."""
+    import pytest
+    single = not isinstance(shapes[0], (tuple, list))
+    places = [tuple(shapes)] if single else [tuple(s) for s in shapes]
+    for k, shape in enumerate(places):
+        for what, bad, exc in bad_outputs(torch, shape):
+            good = [torch.empty(s, dtype=torch.float64, device="cuda") for s in places]
+            good[k] = bad
+            with pytest.raises(exc):
+                call(good[0] if single else tuple(good))
+                raise AssertionError(f"output {k} {what}: accepted")

@@ -148,7 +148,8 @@ def model(name, **env):
 # the last len(outputs) arguments are the output pointers
 STATE = {"rnea": (0, 1, 2), "aba": (0, 1, 3), "rnea_parameters": (0, 1, 2), "aba_parameters": (0, 1, 3), "aba_locked": (0, 1, 3, 2),
          "rnea_bodies": (0, 1, 2), "aba_bodies": (0, 1, 3), "rnea_joint_wrenches": (0, 1, 2), "aba_joint_wrenches": (0, 1, 3),
-         "rnea_crba": (0, 1, 2), "integrate": (0, 1, 2), "aba_integrate": (0, 1, 3)}
+         "rnea_crba": (0, 1, 2), "integrate": (0, 1, 2), "aba_integrate": (0, 1, 3), "rnea_aba": (0, 1, 2, 3),
+         "rnea_derivatives": (0, 1, 2), "aba_derivatives": (0, 1, 3)}
 
 
 def out_shapes(hm, name):
@@ -156,7 +157,8 @@ def out_shapes(hm, name):
     return {"rnea": [(nv,)], "aba": [(nv,)], "rnea_parameters": [(nv,)], "aba_parameters": [(nv,)], "aba_locked": [(nv,), (nv,)],
             "rnea_bodies": [(nv,), (nj, 6), (nj, 6)], "aba_bodies": [(nv,), (nj, 6), (nj, 6)], "rnea_joint_wrenches": [(nv,), (nj, 6)],
             "aba_joint_wrenches": [(nv,), (nj, 6)], "rnea_crba": [(nv,), (nv, nv)], "integrate": [(nq,), (nv,), (nv,)],
-            "aba_integrate": [(nv,), (nq,), (nv,)]}[name]
+            "aba_integrate": [(nv,), (nq,), (nv,)], "rnea_aba": [(nv,), (nv,)], "rnea_derivatives": [(nv,), (nv, nv), (nv, nv)],
+            "aba_derivatives": [(nv,), (nv, nv), (nv, nv), (nv, nv)]}[name]
 
 
 def bind(torch, hm, name, B, state, soa=False, pi=None):
@@ -460,7 +462,26 @@ BODIES = [("partial overlap with qdd / tau", {0: ("in", 2, 1)}), ("body_acc_out 
           ("body_twist_out over body_acc_out", {2: ("out", 1, 0)}), ("body_acc_out over the joint output", {1: ("out", 0, 0)}), ("body_acc_out over f_ext", {1: ("f", 0, 0)})]
 WRENCHES = [("partial overlap with qd", {0: ("in", 1, 1)}), ("joint_wrench_out over the third input", {1: ("in", 2, 0)}), ("joint_wrench_out over q", {1: ("in", 0, 0)}),
             ("joint_wrench_out over the joint output", {1: ("out", 0, 0)})]
+
+
+def every_pair(outs, ins, f_ext):
+    """every (output, input) and (output, output) pair of a call whose outputs may be none of its inputs, each output at the start of the
+    other argument"""
+    pairs = [(f"{o} over {i}", {a: ("in", b, 0)}) for a, o in enumerate(outs) for b, i in enumerate(ins)]
+    pairs += [(f"{o} over f_ext", {a: ("f", 0, 0)}) for a, o in enumerate(outs) if f_ext]
+    return pairs + [(f"{o} over {p}", {a: ("out", b, 0)}) for a, o in enumerate(outs) for b, p in enumerate(outs) if b > a]
+
+
+PAIR = every_pair(("tau_out", "qdd_out"), ("q", "qd", "qdd", "tau"), False) + [("partial overlap of qdd_out with tau", {1: ("in", 3, 1)})]
+RNEA_DERIVATIVES = every_pair(("tau_out", "dtau_dq_out", "dtau_dqd_out"), ("q", "qd", "qdd"), True) \
+    + [("partial overlap of dtau_dq_out with dtau_dqd_out", {1: ("out", 2, 1)})]
+ABA_DERIVATIVES = every_pair(("qdd_out", "dqdd_dq_out", "dqdd_dqd_out", "Hinv_out"), ("q", "qd", "tau"), True) \
+    + [("partial overlap of Hinv_out with qd", {3: ("in", 1, 1)})]
+# (..., batch size) where it is not 70
 REFUSALS = [
+    ("rnea_aba", ("f64", "f32"), "humanoid", PAIR, 5), ("rnea_aba", ("f64", "f32"), "arm7", PAIR, 5),
+    ("rnea_derivatives", ("f64", "f32"), "humanoid", RNEA_DERIVATIVES, 5), ("rnea_derivatives", ("f64", "f32"), "arm7", RNEA_DERIVATIVES, 5),
+    ("aba_derivatives", ("f64", "f32"), "humanoid", ABA_DERIVATIVES, 5), ("aba_derivatives", ("f64", "f32"), "arm7", ABA_DERIVATIVES, 5),
     ("rnea", ("f64", "f32"), "humanoid", ONE), ("aba", ("f64", "f32"), "humanoid", ONE),
     ("rnea", ("f64", "f32"), "perm12", [("q where prismatic coordinates are read again", {0: ("in", 0, 0)})]),
     ("aba", ("f64", "f32"), "perm12", [("q where prismatic coordinates are read again", {0: ("in", 0, 0)})]),
@@ -493,7 +514,7 @@ def test_forbidden_overlaps_are_refused(torch_cuda, entry):
     torch = torch_cuda
     from mecano_amd import _lib
     from mecano_amd.engine import HipModel
-    name, precisions, name_robot, cases = entry
+    name, precisions, name_robot, cases = entry[:4]
     rb = case(name_robot)
     some_locked = name == "aba_locked_some"
     name = "aba_locked" if some_locked else name
@@ -502,7 +523,7 @@ def test_forbidden_overlaps_are_refused(torch_cuda, entry):
         hm.set_joint_source_modes((np.arange(rb.d.n_joints) % 3 == 0).astype(np.int32))
     else:
         hm = model(name_robot)
-    B = 70
+    B = entry[4] if len(entry) > 4 else 70
     lib = _lib.load()
     for sfx in precisions:
         dt = torch.float64 if sfx == "f64" else torch.float32

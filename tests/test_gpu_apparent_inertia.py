@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import apparent_inertia_check as ac
-from helpers import DistinctRows, check_cover, f32_aba_forward_factor, group_cover, poisoned, record_parity
+from helpers import DistinctRows, check_bad_outputs, check_cover, f32_aba_forward_factor, group_cover, poisoned, record_parity
 from test_apparent_inertia_cpu import CASES, HUMANOID_TARGETS, WELL_CONDITIONED, make_case, states, targets_of
 
 pytestmark = pytest.mark.gpu
@@ -289,11 +289,13 @@ def test_refusals_leave_the_output_untouched(torch_cuda):
     refusals = {"NULL q": dict(q=None), "NULL W_out": dict(out=None), "NULL target_joints": dict(t=None), "no targets": dict(n=0),
                 "too many targets": dict(n=17), "joint out of range": dict(t=bad_joint.ctypes.data), "negative joint": dict(t=negative.ctypes.data),
                 "unknown blocks": dict(blocks=2), "pose not orthonormal": dict(p=skewed.ctypes.data), "pose a reflection": dict(p=mirrored.ctypes.data),
-                "W_out overlaps q": dict(out=q.data_ptr())}
+                "W_out overlaps q": dict(out=q.data_ptr()),
+                "W_out overlaps a q inside it": dict(q=W[1].data_ptr())}
     for fn in (lib.mh_apparent_inertia_inverse_f64, lib.mh_apparent_inertia_inverse_f32):
         for what, kw in refusals.items():
             assert call(fn=fn, **kw) == INVALID, what
             assert lib.mh_last_error(), what
+            assert "overlaps" not in what or b"overlap" in lib.mh_last_error(), what
             assert torch.isnan(W).all() and torch.isnan(guard).all(), what
     q_before = q.clone()
     assert call(B=0) == 0 and call(B=0, q=None, out=None) == 0
@@ -302,5 +304,6 @@ def test_refusals_leave_the_output_untouched(torch_cuda):
     assert not torch.isnan(W).any() and torch.isnan(guard).all()
     with pytest.raises(_lib.MecanoHipError):
         hm.apparent_inertia_inverse(q, [1, 2], out=torch.empty((B, 3, 6, 6), dtype=torch.float64, device="cuda"))
+    check_bad_outputs(torch, (B, 2, 6, 6), lambda out: hm.apparent_inertia_inverse(q, [1, 2], out=out))
     with pytest.raises(_lib.MecanoHipError):
         hm.apparent_inertia_inverse(q, [1, 2], poses=np.zeros(12))

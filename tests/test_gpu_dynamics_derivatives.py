@@ -6,7 +6,7 @@ import pytest
 
 import dynamics_derivatives_check as dc
 import gravity_gradient_check as gc
-from helpers import DistinctRows, check_cover, close, close_aba, f32_forward_tol, group_cover, poisoned
+from helpers import DistinctRows, check_bad_outputs, check_cover, close, close_aba, f32_forward_tol, group_cover, poisoned
 from mecano_amd import random_tools as rt
 from oracle.cpu_oracle import OracleModel
 from test_gravity_gradient_cpu import CASES, GRAVITY, make_case, random_wrenches, system_of
@@ -351,6 +351,9 @@ def test_wrong_shapes_are_rejected_before_any_launch(torch_cuda):
     for bad_out in ((None, None, None, z(B, nv, nv)), (z(B, nv), z(B, nv, nv + 1), None, None), (None, z(B, nv, nv), None, z(B, nv))):
         with pytest.raises(_lib.MecanoHipError):
             hm.aba_derivatives(q, qd, tau, GRAVITY, None, out=bad_out)
+    vec, mat = (B, nv), (B, nv, nv)
+    check_bad_outputs(torch, [vec, mat, mat], lambda out: hm.rnea_derivatives(q, qd, qdd, GRAVITY, None, out=out))
+    check_bad_outputs(torch, [vec, mat, mat, mat], lambda out: hm.aba_derivatives(q, qd, tau, GRAVITY, None, out=out))
     with pytest.raises(_lib.MecanoHipError):
         hm.rnea_derivatives(q, z(B, nv + 1), qdd, GRAVITY)
     with pytest.raises(_lib.MecanoHipError):

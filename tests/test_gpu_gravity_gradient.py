@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import gravity_gradient_check as gc
-from helpers import DistinctRows, check_cover, close, f32_forward_tol, group_cover, poisoned
+from helpers import DistinctRows, check_bad_outputs, check_cover, close, f32_forward_tol, group_cover, poisoned
 from test_gravity_gradient_cpu import CASES, GRAVITY, make_case, random_wrenches, states, system_of
 
 pytestmark = pytest.mark.gpu
@@ -230,6 +230,7 @@ def test_wrong_shapes_are_rejected_before_any_launch(torch_cuda):
     for bad_out in ((z(B, nv + 1), z(B, nv, nv)), (z(B, nv), z(B, nv, nv - 1)), (z(B - 1, nv), None), (None, z(nv * nv, B))):
         with pytest.raises(_lib.MecanoHipError):
             hm.gravity_gradient(q, GRAVITY, None, out=bad_out)
+    check_bad_outputs(torch, [(B, nv), (B, nv, nv)], lambda out: hm.gravity_gradient(q, GRAVITY, None, out=out))
     with pytest.raises(_lib.MecanoHipError):
         hm.gravity_gradient(z(B, desc.nq + 1), GRAVITY)
     with pytest.raises(_lib.MecanoHipError):

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import inertial_parameters_check as ipc
-from helpers import (DistinctRows, check_cover, close, close_aba, f32_aba_backward_tol, f32_forward_tol, group_cover,
+from helpers import (DistinctRows, check_bad_outputs, check_cover, close, close_aba, f32_aba_backward_tol, f32_forward_tol, group_cover,
                      poisoned, record_parity)
 from test_inertial_parameters_cpu import CASES, GRAVITY, batch, make_case
 
@@ -293,6 +293,8 @@ def test_refusals_leave_the_output_untouched(torch_cuda):
         hm.aba_parameters(q, qd, tau, pi[:-1].contiguous(), GRAVITY, out=out)
     with pytest.raises(_lib.MecanoHipError):
         hm.aba_parameters(q, qd, tau, pi, GRAVITY, out=torch.empty(B, nv + 1, dtype=torch.float64, device="cuda"))
+    check_bad_outputs(torch, (B, nv), lambda o: hm.rnea_parameters(q, qd, qdd, pi, GRAVITY, out=o))
+    check_bad_outputs(torch, (B, nv), lambda o: hm.aba_parameters(q, qd, tau, pi, GRAVITY, out=o))
     modes = [0] * n
     modes[3] = 1
     hm.set_joint_source_modes(modes)

@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import kinematics_check as kc
-from helpers import DistinctRows, check_cover, close, f32_forward_tol, group_cover, poisoned
+from helpers import DistinctRows, check_bad_outputs, check_cover, close, f32_forward_tol, group_cover, poisoned
 from test_kinematics_cpu import HUMANOID_TARGETS, make_case, states, targets_of
 
 pytestmark = pytest.mark.gpu
@@ -338,6 +338,9 @@ def test_refusals_leave_the_outputs_untouched(torch_cuda):
         assert not torch.isnan(t).any() and torch.isnan(g).all()
     with pytest.raises(_lib.MecanoHipError):
         hm.geometric_jacobian(q, [1, 2], out=torch.empty((B, 6, desc.nv), dtype=torch.float64, device="cuda"))
+    check_bad_outputs(torch, (B, 12, desc.nv), lambda out: hm.geometric_jacobian(q, [1, 2], out=out))
+    check_bad_outputs(torch, [(B, 12, desc.nv), (B, 2, 6)], lambda out: hm.geometric_jacobian(q, [1, 2], qd=qd, convective=True, out=out))
+    check_bad_outputs(torch, (B, 2, 12), lambda out: hm.body_poses(q, [1, 2], out=out))
     with pytest.raises(_lib.MecanoHipError):
         hm.body_poses(q, [1, 2], poses=np.zeros(12))
     with pytest.raises(_lib.MecanoHipError):

@@ -7,7 +7,7 @@ import pytest
 
 import apparent_inertia_check as ac
 import mass_matrix_inverse_check as mc
-from helpers import DistinctRows, check_cover, close, f32_aba_forward_factor, group_cover, poisoned, record_parity
+from helpers import DistinctRows, check_bad_outputs, check_cover, close, f32_aba_forward_factor, group_cover, poisoned, record_parity
 from test_apparent_inertia_cpu import CASES, WELL_CONDITIONED, make_case, states, system_of
 
 pytestmark = pytest.mark.gpu
@@ -297,11 +297,13 @@ def test_refusals_leave_the_output_untouched(torch_cuda):
 
     refusals = {"NULL q": dict(q=None), "NULL Hinv_out": dict(out=None), "no columns": dict(n=0, c=good.ctypes.data),
                 "too many columns": dict(n=65, c=many.ctypes.data), "index beyond nv": dict(n=2, c=beyond.ctypes.data),
-                "negative index": dict(n=2, c=negative.ctypes.data), "Hinv_out overlaps q": dict(out=q.data_ptr())}
+                "negative index": dict(n=2, c=negative.ctypes.data), "Hinv_out overlaps q": dict(out=q.data_ptr()),
+                "Hinv_out overlaps a q inside it": dict(q=H[1].data_ptr())}
     for fn in (lib.mh_mass_matrix_inverse_f64, lib.mh_mass_matrix_inverse_f32):
         for what, kw in refusals.items():
             assert call(fn=fn, **kw) == INVALID, what
             assert lib.mh_last_error(), what
+            assert "overlaps" not in what or b"overlap" in lib.mh_last_error(), what
             assert torch.isnan(H).all() and torch.isnan(guard).all(), what
     q_before = q.clone()
     assert call(B=0) == 0 and call(B=0, q=None, out=None) == 0 and call(B=0, n=3, c=good.ctypes.data) == 0
@@ -309,6 +311,7 @@ def test_refusals_leave_the_output_untouched(torch_cuda):
     assert call(n=-5) == 0  # n_columns is ignored without a list
     assert not torch.isnan(H).any() and torch.isnan(guard).all()
     assert call(n=64, c=many.ctypes.data, out=torch.empty((B, 7, 64), dtype=torch.float64, device="cuda").data_ptr()) == 0
+    check_bad_outputs(torch, (B, 7, 7), lambda out: hm.mass_matrix_inverse(q, out=out))
     with pytest.raises(_lib.MecanoHipError):
         hm.mass_matrix_inverse(q, out=q)  # aliasing: refused by shape here, by the overlap check in the library above
     with pytest.raises(_lib.MecanoHipError):

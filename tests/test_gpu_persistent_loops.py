@@ -428,3 +428,75 @@ def test_reserve_then_capture_every_batch_class(torch_cuda, cu, case):
             for (rows, guard), (wrows, _) in zip(outs, want):
                 assert torch.isnan(guard).all(), (name, soa, B)
                 assert torch.equal(rows, wrows), (case, name, "soa" if soa else "aos", B, replay)
+
+
+def _lane_workspace_calls(torch, hm, B, ins):
+    """The entry points whose kernels take `parts` waves per group of configurations, each on a workspace block of its own, bound to
+    preallocated outputs: [(name, call, outputs)].  call() issues the entry point on the current stream."""
+    from mecano_amd import _lib
+    lib = _lib.load()
+    q, qd, qdd, tau = ins
+    nv, nq, nj = hm.nv, hm.nq, hm.n_joints
+    new = lambda *shape: torch.full((B,) + shape, float("nan"), dtype=q.dtype, device=q.device)
+    targets = np.arange(16) % nj
+    g, _ = hm._root(G)
+    opts = lambda: ctypes.byref(hm._options(_lib.LAYOUT_AOS, stream=torch.cuda.current_stream().cuda_stream))
+    p = lambda t: t.data_ptr()
+    Y, H, C, A, b, com = new(nv, 10 * nj), new(nv, nv), new(nv, nv), new(6, nv), new(6), new(3)
+    grav, W, Hinv, poses, jac = (new(nv), new(nv, nv)), new(16, 6, 6), new(nv, nv), new(nj, 12), (new(6 * 16, nv), new(16, 6))
+    rd, ad = (new(nv), new(nv, nv), new(nv, nv)), (new(nv), new(nv, nv), new(nv, nv), new(nv, nv))
+    sd = (new(nv), q.clone(), qd.clone(), new(2 * nv, 2 * nv), new(2 * nv, nv))
+    return [
+        ("regressor", lambda: _lib.check(lib.mh_regressor_f64(hm._h, B, p(q), p(qd), p(qdd), g, opts(), 0, p(Y))), (Y,)),
+        ("crba_coriolis", lambda: _lib.check(lib.mh_crba_coriolis_f64(hm._h, B, p(q), p(qd), opts(), p(H), p(C))), (H, C)),
+        ("centroidal", lambda: _lib.check(lib.mh_centroidal_f64(hm._h, B, p(q), p(qd), None, _lib.CENTROIDAL_FRAME_FIXED, opts(), p(A), p(b),
+                                                                 p(com))), (A, b, com)),
+        ("gravity_gradient", lambda: hm.gravity_gradient(q, G, out=grav), grav),
+        ("apparent_inertia_inverse", lambda: hm.apparent_inertia_inverse(q, targets, coupled=False, out=W), (W,)),
+        ("mass_matrix_inverse", lambda: hm.mass_matrix_inverse(q, out=Hinv), (Hinv,)),
+        ("rnea_derivatives", lambda: hm.rnea_derivatives(q, qd, qdd, G, out=rd), rd),
+        ("aba_derivatives", lambda: hm.aba_derivatives(q, qd, tau, G, out=ad), ad),
+        ("step_derivatives", lambda: hm.step_derivatives(DT, q, qd, tau, G, out=sd), sd),
+        ("body_poses", lambda: hm.body_poses(q, out=poses), (poses,)),
+        ("geometric_jacobian", lambda: hm.geometric_jacobian(q, targets, qd=qd, convective=True, out=jac), jac),
+    ]
+
+
+def test_reserve_covers_every_smaller_batch_of_the_lane_workspace_kernels(torch_cuda):
+    """mh_reserve(max_batch) covers every B <= max_batch, not max_batch alone: the kernels that put several waves on a group of 64
+    configurations take grid * parts workspace blocks, and that product is not monotonic in the batch.  With 3 CUs (12 waves):
+    B = 320 is grid 5 x 2 parts = 10 waves, B = 191 is grid 3 x 4 parts = 12.  After reserve(320) and first calls at 64, every such entry
+    point is captured at 191 and at 320 -- an allocation inside the capture makes the call fail -- and replays to the bits of eager calls
+    on another model of the same robot."""
+    torch = torch_cuda
+    rb = robot("humanoid")
+    hm, ref = rb.model(MH_FAKE_CU_COUNT=3), rb.model(MH_FAKE_CU_COUNT=3)
+    hm.reserve(320)
+    for _name, call, _outs in _lane_workspace_calls(torch, hm, 64, rb.rows.device(torch, 64, torch.float64)):
+        call()
+    s = torch.cuda.Stream()
+    bound = []
+    with torch.cuda.stream(s):
+        for B in (191, 320):
+            ins = rb.rows.device(torch, B, torch.float64)
+            bound += [(B, ins) + c for c in _lane_workspace_calls(torch, hm, B, ins)]
+        torch.cuda.synchronize()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, stream=s):
+            for B, _ins, _name, call, _outs in bound:
+                call()
+    torch.cuda.synchronize()
+    graph.replay()
+    torch.cuda.synchronize()
+    for B in (191, 320):
+        ins = next(i for b, i, *_ in bound if b == B)
+        eager = _lane_workspace_calls(torch, ref, B, ins)
+        for _name, call, _outs in eager:
+            call()
+        torch.cuda.synchronize()
+        want = {name: outs for name, _call, outs in eager}
+        for b, _ins, name, _call, outs in bound:
+            if b == B:
+                for k, (got, exp) in enumerate(zip(outs, want[name])):
+                    assert not torch.isnan(exp).any(), (name, B, k)
+                    assert torch.equal(got, exp), (name, B, k)

@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 
 import step_derivatives_check as sc
-from helpers import close, close_aba, poisoned
+from helpers import check_bad_outputs, close, close_aba, poisoned
 from mecano_amd import random_tools as rt
 from oracle.cpu_oracle import OracleModel
 from test_gravity_gradient_cpu import CASES, GRAVITY, make_case, random_wrenches
@@ -405,6 +405,10 @@ def test_refusals_leave_the_outputs_untouched(torch_cuda):
     for bad_f in (z(B, n - 1, 6), z(B + 1, n, 6)):
         with pytest.raises(_lib.MecanoHipError):
             hm.step_derivatives(0.01, q, qd, tau, GRAVITY, bad_f)
+    check_bad_outputs(torch, [(B, nv), (B, nq), (B, nv), (B, 2 * nv, 2 * nv), (B, 2 * nv, nv)],
+                      lambda out: hm.step_derivatives(0.01, q, qd, tau, GRAVITY, None, out=out))
+    check_bad_outputs(torch, (B, nq), lambda out: hm.configuration_add(q, qd, out=out))
+    check_bad_outputs(torch, (B, nv), lambda out: hm.configuration_difference(q, q.clone(), out=out))
     with pytest.raises(_lib.MecanoHipError):
         hm.configuration_add(q, z(B, nv + 1))
     with pytest.raises(_lib.MecanoHipError):
