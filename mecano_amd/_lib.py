@@ -119,6 +119,8 @@ def _load_locked():
     lib.mh_model_warnings.restype = ctypes.c_uint32
     lib.mh_model_warning_text.argtypes = [P]
     lib.mh_model_warning_text.restype = ctypes.c_char_p
+    # not in include/mecano_hip.h: the host-side tables of a description, without a device (tests/test_model_tables_cpu.py)
+    lib.mh_internal_model_table.argtypes = [ctypes.POINTER(MhModelDesc), ctypes.c_char_p, P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
     lib.mh_topology_key.argtypes = [ctypes.POINTER(MhModelDesc), ctypes.c_char_p, P, P]
     lib.mh_build_code_object.argtypes = [ctypes.POINTER(MhModelDesc), ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
     lib.mh_reserve.argtypes = [P, I64]

@@ -1,7 +1,7 @@
 // mh_api.hip -- host side of the C-ABI declared in include/mecano_hip.h.
 //
 // Model build (once per MultiBodySystemReadOnly): validation, parents-first ordering, canonical joint frames,
-// workspace slot assignment, upload.  Compute calls: argument checks, workspace, kernel launch on the caller's
+// workspace slot assignment (all host arithmetic: mh_model_tables.h), upload.  Compute calls: argument checks, workspace, kernel launch on the caller's
 // stream.  No CPU implementation of the algorithms exists in this library: without a HIP device the compute
 // entry points return MH_ERR_NO_DEVICE.
 #include "../../include/mecano_hip.h"
@@ -14,6 +14,7 @@
 #include "mh_rnea_deriv_kernels.h"
 #include "mh_params_kernels.h"
 #include "mh_step_kernels.h"
+#include "mh_model_tables.h"
 
 #include <dlfcn.h>
 #include <spawn.h>
@@ -39,16 +40,6 @@ extern char **environ;
 
 namespace
 {
-thread_local char g_err[512] = "";
-
-mh_status fail(mh_status code, const char *fmt, ...)
-{
-   va_list ap;
-   va_start(ap, fmt);
-   vsnprintf(g_err, sizeof g_err, fmt, ap);
-   va_end(ap);
-   return code;
-}
 #define HIP_TRY(expr)                                                                                      \
    do                                                                                                      \
    {                                                                                                       \
@@ -56,42 +47,6 @@ mh_status fail(mh_status code, const char *fmt, ...)
       if (e_ != hipSuccess)                                                                                \
          return fail(e_ == hipErrorOutOfMemory ? MH_ERR_OUT_OF_MEMORY : MH_ERR_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
    } while (0)
-
-// ------------------------------------------------------------------ tiny host 3x3 helpers (double)
-struct M3d
-{
-   double m[9];
-};
-M3d m3_identity() { return M3d{{1, 0, 0, 0, 1, 0, 0, 0, 1}}; }
-M3d m3_mul(const M3d &a, const M3d &b)
-{
-   M3d o;
-   for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++)
-         o.m[3 * i + j] = a.m[3 * i] * b.m[j] + a.m[3 * i + 1] * b.m[3 + j] + a.m[3 * i + 2] * b.m[6 + j];
-   return o;
-}
-M3d m3_T(const M3d &a) { return M3d{{a.m[0], a.m[3], a.m[6], a.m[1], a.m[4], a.m[7], a.m[2], a.m[5], a.m[8]}}; }
-void m3_mulv(const M3d &a, const double v[3], double o[3])
-{
-   double x = a.m[0] * v[0] + a.m[1] * v[1] + a.m[2] * v[2];
-   double y = a.m[3] * v[0] + a.m[4] * v[1] + a.m[5] * v[2];
-   double z = a.m[6] * v[0] + a.m[7] * v[1] + a.m[8] * v[2];
-   o[0] = x, o[1] = y, o[2] = z;
-}
-// rotation Q with Q * ez = k (k unit): columns (x', y', k) of a right-handed orthonormal basis
-M3d frame_with_z(const double k[3])
-{
-   int least = std::fabs(k[0]) <= std::fabs(k[1]) ? (std::fabs(k[0]) <= std::fabs(k[2]) ? 0 : 2) : (std::fabs(k[1]) <= std::fabs(k[2]) ? 1 : 2);
-   double h[3] = {0, 0, 0};
-   h[least] = 1.0;
-   double d = h[0] * k[0] + h[1] * k[1] + h[2] * k[2];
-   double x[3] = {h[0] - d * k[0], h[1] - d * k[1], h[2] - d * k[2]};
-   double n = std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
-   x[0] /= n, x[1] /= n, x[2] /= n;
-   double y[3] = {k[1] * x[2] - k[2] * x[1], k[2] * x[0] - k[0] * x[2], k[0] * x[1] - k[1] * x[0]};
-   return M3d{{x[0], y[0], k[0], x[1], y[1], k[1], x[2], y[2], k[2]}};
-}
 
 // NaN tests on raw 64-bit words that never pass through a `double` value: this translation unit is built with -ffinite-math-only, under
 // which x != x folds to false AND double parameters carry nofpclass(nan), so that even a bit test on a double argument may be folded away
@@ -152,8 +107,6 @@ bool hash_spec_sources(const std::string &csrc_dir, char out[18])
    snprintf(out, 18, "h%016llx", (unsigned long long)h);
    return true;
 }
-int joint_ndof(int t) { return mh::dof_count(t); }
-int joint_ncfg(int t) { return mh::cfg_count(t); }
 
 struct Workspace
 {
@@ -239,6 +192,85 @@ void free_scratch(ContextState &c)
       if (s)
          (void)hipStreamDestroy(s);
 }
+
+// The device copies of a model's tables: one member here and one row in device_rows() -- upload (mh_model_create) and release
+// (release_model) walk that list.  A context shares its model's (mh_context_create).
+struct DeviceTables
+{
+   int *d_meta = nullptr, *d_dof = nullptr, *d_cfg = nullptr, *d_prog = nullptr, *d_prog_seq = nullptr;
+   double *d_consts64 = nullptr;
+   float *d_consts32 = nullptr;
+   double *d_sub_mass64 = nullptr;
+   float *d_sub_mass32 = nullptr;
+   int *d_grav_zero_ofs = nullptr, *d_grav_zero_cols = nullptr;
+   int *d_resp_info = nullptr;
+   int *d_minv_owner = nullptr;
+   int *d_deriv_slot = nullptr;
+};
+
+// What the MH_* environment variables set, read once per model by read_switches() (mh_model_create).  The variables read elsewhere or per
+// call are not here: MH_CRBA_LPG, MH_SPEC_DIR, MH_AUTO_BUILD, MH_SPEC_SELFCHECK.
+struct Switches
+{
+   int cu_count = 256;    // the device's (mh_model_create); MH_FAKE_CU_COUNT (measurements): shrink every grid so that one workgroup loops over the batch
+   int use_spec = 1;        // MH_DISABLE_SPEC=1 in the environment forces the generic kernels (A/B measurements)
+   int use_split = -1;      // MH_SPEC_SPLIT = 0 | 1: never / whenever possible use the tree-split kernels (default: small batches)
+   int force_io = -1, force_st = -1; // MH_SPEC_IO / MH_SPEC_ST = 0 | 1 override the heuristics (measurements)
+   int use_split_rt = -1; // MH_SPLIT_RT = 0 | 1: never / whenever usable (default: small batches)
+   int use_transpose = -1; // MH_GENERIC_TRANSPOSE = 0 | 1 overrides the size heuristic
+   int use_dfs = 1;       // MH_DFS=0: the sweep kernels of mh_kernels.h serve plain RNEA / ABA calls too (A/B measurements)
+   int use_dfs_pair = 1;  // MH_DFS_PAIR=0: mh_rnea_aba_f32 on big batches issues the two depth-first kernels one after the other, as before round 5
+   int dfs_place = -1;    // MH_DFS_PLACE = 0 | 1 | 2: force all-LDS / stack in LDS + hand-over global / all global
+   bool dfs_place_greedy = false; // MH_DFS_GREEDY=1: the frames' homes from the leaves upwards as in rounds 2-4 (A/B measurements; dfs_plan)
+   int dfs_budget = -1;   // MH_DFS_BUDGET: cap of the stack's LDS budget in slots per wave (measurements)
+   int dfs_aba64 = 0;     // fp64 forward dynamics on the depth-first kernel too: bushy trees (mh_model_create), or MH_DFS_ABA64=0|1
+   int host_chunk = 0; // MH_HOST_CHUNK: configurations per chunk of the host-pointer pipeline (0 = choose)
+   int use_rnea_ahead = 1; // MH_RNEA_AHEAD (see rnea_ahead_ok)
+   int use_zv = 1;        // MH_ZV=0: never; 1: while every job's workgroup gets a CU of its own (default); 2: whenever the call qualifies
+   int use_zv_step = 1;    // MH_ZV_STEP=0: simulation steps never ride in the bias-split / fused forward dynamics (the one-job tree-split kernel integrates instead)
+   int use_zvb = 1;       // MH_ZVB=0: never; 1: batches of two or more groups of 64 configurations per CU (default); 2: whenever the call qualifies; MH_ZVB_WHICH = 1 | 2: one of the two launches only (timing)
+   int zvb_which = 3;
+   int use_zvf = 1;       // MH_ZVF=0: never the fused one-launch form; 1: where the two-launch form would be taken (default); 2: whenever the call qualifies
+   int use_zvf_pair = 1;  // MH_ZVF_PAIR=0: the pair call of device-filling batches as two launches (A/B measurements)
+   int zv_same_l2 = 0;    // MH_ZV_SAME_L2=1 (experiment, off by default; one-stage hand-off only: the two-stage form of identity index maps is write-through): bias rows and flag of a group whose two jobs prove to sit behind the same L2
+                          // stay in that L2 (workgroup-scope stores) -- cache behaviour the memory model does not promise, for no measured gain
+   unsigned zv_wait_ticks = 200000000u; // MH_ZV_WAIT_MS: how long an inertia job waits for its bias rows (100 MHz ticks; default 2 s)
+};
+// Every switch keeps its default where its variable is unset.  mh_model_create calls this AFTER it has put the device's CU count and the
+// bushiness heuristic into cu_count and dfs_aba64: MH_FAKE_CU_COUNT and MH_DFS_ABA64 override those.
+void read_switches(Switches &s)
+{
+   auto set = [](const char *e, auto &member, auto parse) {
+      if (e)
+         member = parse(e);
+   };
+   auto number = [](const char *e) { return atoi(e); };
+   auto boolean = [](const char *e) { return atoi(e) != 0; };
+   auto at_least_0 = [](const char *e) { return std::max(0, atoi(e)); };
+   set(getenv("MH_DISABLE_SPEC"), s.use_spec, [](const char *e) { return atoi(e) ? 0 : 1; });
+   set(getenv("MH_SPEC_SPLIT"), s.use_split, number);
+   set(getenv("MH_ZV"), s.use_zv, number);
+   set(getenv("MH_ZV_SAME_L2"), s.zv_same_l2, boolean);
+   set(getenv("MH_ZV_WAIT_MS"), s.zv_wait_ticks, [](const char *e) { return (unsigned)std::max<long long>(1, std::min<long long>(40000, atoll(e))) * 100000u; });
+   set(getenv("MH_ZVB"), s.use_zvb, number);
+   set(getenv("MH_ZVF"), s.use_zvf, number);
+   set(getenv("MH_ZVF_PAIR"), s.use_zvf_pair, number);
+   set(getenv("MH_RNEA_AHEAD"), s.use_rnea_ahead, number);
+   set(getenv("MH_ZV_STEP"), s.use_zv_step, boolean);
+   set(getenv("MH_ZVB_WHICH"), s.zvb_which, [](const char *e) { return std::max(1, std::min(3, atoi(e))); });
+   set(getenv("MH_SPEC_IO"), s.force_io, number);
+   set(getenv("MH_FAKE_CU_COUNT"), s.cu_count, [](const char *e) { return std::max(1, atoi(e)); });
+   set(getenv("MH_GENERIC_TRANSPOSE"), s.use_transpose, boolean);
+   set(getenv("MH_SPEC_ST"), s.force_st, number);
+   set(getenv("MH_DFS"), s.use_dfs, boolean);
+   set(getenv("MH_DFS_PAIR"), s.use_dfs_pair, boolean);
+   set(getenv("MH_DFS_ABA64"), s.dfs_aba64, boolean);
+   set(getenv("MH_DFS_BUDGET"), s.dfs_budget, at_least_0);
+   set(getenv("MH_DFS_PLACE"), s.dfs_place, number);
+   set(getenv("MH_DFS_GREEDY"), s.dfs_place_greedy, boolean);
+   set(getenv("MH_HOST_CHUNK"), s.host_chunk, at_least_0);
+   set(getenv("MH_SPLIT_RT"), s.use_split_rt, number);
+}
 } // namespace
 
 // entry points of a topology-specialised code object (mh_spec.hip), resolved with dlsym
@@ -291,25 +323,20 @@ enum : int
    SPEC_OCC3 = 32
 };
 
-struct mh_model : ContextState
+// A model is four things, each stated once: what mh_model_create compiles from the description (ModelTables, mh_model_tables.h), its copies
+// on the device, the switches of the environment, and what compute calls write.  Declared here: lifecycle, code object and launch plans.
+struct mh_model : ModelTables, DeviceTables, Switches, ContextState
 {
-   int n = 0, nq = 0, nv = 0, n_slots = 0;
-   SpecLib spec;
-   std::string topo_key;
    int device = 0;
-   int cu_count = 256;
-   std::vector<int> meta, dof_map, cfg_map;
-   std::vector<int> engine_of; // caller joint index -> engine index
-   std::vector<double> consts;
-   int *d_meta = nullptr, *d_dof = nullptr, *d_cfg = nullptr, *d_prog = nullptr;
-   std::vector<int> prog; // event program of the depth-first kernels
-   std::vector<int> prog_seq; // the same walk with the siblings in engine order (the kernels that read AoS rows through LDS windows)
-   int *d_prog_seq = nullptr;
-   int rnea_stack = 0, aba_stack = 0, aba_hand = 0; // per-lane slots: depth stacks, ABA hand-over
-   int pair_stack = 0;    // ... of the fused RNEA + ABA walk (aba_dfs_kernel<.., PAIR>)
-   int use_dfs_pair = 1;  // MH_DFS_PAIR=0: mh_rnea_aba_f32 on big batches issues the two depth-first kernels one after the other, as before round 5
-   int use_dfs = 1;       // MH_DFS=0: the sweep kernels of mh_kernels.h serve plain RNEA / ABA calls too (A/B measurements)
-   double nonleaf_fraction = 1.0; // share of bodies with children: those are the ones that touch the depth stack
+   // mh_context_create: a context is a copy of the model's host-side description that SHARES its device records (parent owns them) and
+   // owns everything compute calls write -- a ContextState of its own
+   mh_model *parent = nullptr;
+   int n_contexts = 0; // live contexts of this model (guarded by g_context_mutex)
+   bool destroy_pending = false; // mh_model_destroy was called while contexts were alive: the last mh_context_destroy releases the model
+   int n_locked = 0;        // joints in MH_ACCELERATION_SOURCE mode (mh_model_set_joint_source_modes)
+   SpecLib spec;
+   bool spec_minimal = false; // the loaded code object is a minimal (fast) build
+   std::string variant = "generic";
    // depth-first kernels: frame homes for a given LDS budget (slots per wave), one copy of the body records per (algorithm, budget) on
    // the device; built on first use (dfs_plan), dropped when the records change (joint source modes)
    struct DfsPlan
@@ -324,52 +351,6 @@ struct mh_model : ContextState
       PlainMutex(const PlainMutex &) : std::mutex() {}
       PlainMutex &operator=(const PlainMutex &) { return *this; }
    } dfs_mutex;
-   // mh_context_create: a context is a copy of the model's host-side description that SHARES its device records (parent owns them) and
-   // owns everything compute calls write -- a ContextState of its own
-   mh_model *parent = nullptr;
-   int n_contexts = 0; // live contexts of this model (guarded by g_context_mutex)
-   bool destroy_pending = false; // mh_model_destroy was called while contexts were alive: the last mh_context_destroy releases the model
-   int dfs_place = -1;    // MH_DFS_PLACE = 0 | 1 | 2: force all-LDS / stack in LDS + hand-over global / all global
-   bool dfs_place_greedy = false; // MH_DFS_GREEDY=1: the frames' homes from the leaves upwards as in rounds 2-4 (A/B measurements; dfs_plan)
-   int dfs_budget = -1;   // MH_DFS_BUDGET: cap of the stack's LDS budget in slots per wave (measurements)
-   int dfs_aba64 = 0;     // fp64 forward dynamics on the depth-first kernel too: bushy trees (below), or MH_DFS_ABA64=0|1
-   int n_nonadjacent = 0; // bodies whose parent is not the body before them in engine order (branch points of the tree)
-   double *d_consts64 = nullptr;
-   float *d_consts32 = nullptr;
-   // mh_gravity_gradient_*: subtree masses (engine order) and, per body, the matrix columns of unrelated joints (mh_gravity_kernels.h)
-   std::vector<double> sub_mass;
-   std::vector<int> grav_zero_ofs, grav_zero_cols;
-   double *d_sub_mass64 = nullptr;
-   float *d_sub_mass32 = nullptr;
-   int *d_grav_zero_ofs = nullptr, *d_grav_zero_cols = nullptr;
-   // mh_apparent_inertia_inverse_*: Euler tour of the tree and the slots of the six-column accelerations (mh_response_kernels.h), and
-   // the workspace slots per lane of that kernel: the model's, 36 per body with a child that does not directly follow it, 6 per DoF
-   std::vector<int> resp_info;
-   int *d_resp_info = nullptr;
-   int resp_slots = 0, resp_a_base = 0, resp_u_base = 0;
-   // mh_mass_matrix_inverse_*: per DoF index of the model's index map, 8 * engine index of the joint that owns it + its place among the
-   // joint's DoFs (-1: no joint); the kernel (mh_minv_kernels.h) works in the workspace slots of the apparent-inertia kernel
-   std::vector<int> minv_owner;
-   int *d_minv_owner = nullptr;
-   // mh_rnea_derivatives_* / mh_aba_derivatives_*: first workspace slot of every body in that kernel's own plan (mh_rnea_deriv_kernels.h)
-   // and its slots per lane
-   std::vector<int> deriv_slot;
-   int *d_deriv_slot = nullptr;
-   int deriv_slots = 0;
-   // mh_model_inertial_parameters / mh_rnea_parameters_* / mh_aba_parameters_*: the description's ten inertial numbers per joint, in
-   // mh_model_desc order (host only: the kernels of mh_params_kernels.h take them per configuration from the call)
-   std::vector<double> inertial_parameters;
-   int host_chunk = 0; // MH_HOST_CHUNK: configurations per chunk of the host-pointer pipeline (0 = choose)
-   int use_rnea_ahead = 1; // MH_RNEA_AHEAD (see rnea_ahead_ok)
-   int use_zv_step = 1;    // MH_ZV_STEP=0: simulation steps never ride in the bias-split / fused forward dynamics (the one-job tree-split kernel integrates instead)
-   int use_zvb = 1;       // MH_ZVB=0: never; 1: batches of two or more groups of 64 configurations per CU (default); 2: whenever the call qualifies; MH_ZVB_WHICH = 1 | 2: one of the two launches only (timing)
-   int zvb_which = 3;
-   int use_zvf = 1;       // MH_ZVF=0: never the fused one-launch form; 1: where the two-launch form would be taken (default); 2: whenever the call qualifies
-   int use_zvf_pair = 1;  // MH_ZVF_PAIR=0: the pair call of device-filling batches as two launches (A/B measurements)
-   int zv_same_l2 = 0;    // MH_ZV_SAME_L2=1 (experiment, off by default; one-stage hand-off only: the two-stage form of identity index maps is write-through): bias rows and flag of a group whose two jobs prove to sit behind the same L2
-                          // stay in that L2 (workgroup-scope stores) -- cache behaviour the memory model does not promise, for no measured gain
-   unsigned zv_wait_ticks = 200000000u; // MH_ZV_WAIT_MS: how long an inertia job waits for its bias rows (100 MHz ticks; default 2 s)
-   int use_zv = 1;        // MH_ZV=0: never; 1: while every job's workgroup gets a CU of its own (default); 2: whenever the call qualifies
    // run-time tree split (mh_split_kernels.h): plan made at creation, device copies, workspace blocks
    struct SplitRt
    {
@@ -381,22 +362,6 @@ struct mh_model : ContextState
       std::vector<int> meta;     // (body, field, value) patches of the adapted records
       std::vector<int> xl;       // exchange slots of the limbs attached to the trunk bodies (plain slot numbers)
    } split_rt;
-   int use_split_rt = -1; // MH_SPLIT_RT = 0 | 1: never / whenever usable (default: small batches)
-   int use_transpose = -1; // MH_GENERIC_TRANSPOSE = 0 | 1 overrides the size heuristic
-   std::string variant = "generic";
-   uint32_t warnings = 0;    // MH_WARN_* bits set by mh_model_create (mh_model_warnings)
-   std::string warning_text; // ... and what they mean for this model
-   int use_split = -1;      // MH_SPEC_SPLIT = 0 | 1: never / whenever possible use the tree-split kernels (default: small batches)
-   int use_spec = 1;        // MH_DISABLE_SPEC=1 in the environment forces the generic kernels (A/B measurements)
-   bool spec_minimal = false; // the loaded code object is a minimal (fast) build
-   int ident_maps = 0;      // the engine-order index maps are the identity
-   int dense_maps = 0;      // nq / nv equal the joints' totals (no unused matrix rows): rows can be staged as dense blocks
-   int force_io = -1, force_st = -1; // MH_SPEC_IO / MH_SPEC_ST = 0 | 1 override the heuristics (measurements)
-   int n_locked = 0;        // joints in MH_ACCELERATION_SOURCE mode (mh_model_set_joint_source_modes)
-   // an output of nv columns may be q itself: nq == nv, every joint with DoFs is revolute, and its row of q is its row of qd.  A kernel
-   // reads a revolute joint's angle once (cos, sin live on in registers or workspace) and writes only that joint's entry of the output;
-   // prismatic and planar coordinates are read from q again after the joint's output has been stored (joint_again, mh_kernels.h)
-   int q_may_be_out = 0;
 };
 
 struct mh_context
@@ -406,6 +371,24 @@ struct mh_context
 namespace
 {
 std::mutex g_context_mutex;
+// The device tables of a model, in upload order: where the pointer lives and what it is a copy of.  consts and sub_mass go up twice, the
+// fp32 copies made by the caller at upload (release_model reads the pointers only and passes none).
+struct DeviceRow
+{
+   void **ptr;
+   const void *host;
+   size_t bytes;
+};
+template <class T>
+DeviceRow device_row(T *&ptr, const std::vector<T> &host) { return DeviceRow{(void **)&ptr, host.data(), host.size() * sizeof(T)}; }
+std::vector<DeviceRow> device_rows(mh_model *m, const std::vector<float> &consts32 = {}, const std::vector<float> &sub_mass32 = {})
+{
+   return {device_row(m->d_meta, m->meta), device_row(m->d_dof, m->dof_map), device_row(m->d_cfg, m->cfg_map), device_row(m->d_prog, m->prog),
+           device_row(m->d_prog_seq, m->prog_seq), device_row(m->d_consts64, m->consts), device_row(m->d_consts32, consts32),
+           device_row(m->d_sub_mass64, m->sub_mass), device_row(m->d_sub_mass32, sub_mass32), device_row(m->d_grav_zero_ofs, m->grav_zero_ofs),
+           device_row(m->d_grav_zero_cols, m->grav_zero_cols), device_row(m->d_resp_info, m->resp_info),
+           device_row(m->d_minv_owner, m->minv_owner), device_row(m->d_deriv_slot, m->deriv_slot)};
+}
 mh_status ensure_bytes(Workspace &w, size_t bytes)
 {
    if (w.bytes >= bytes)
@@ -1909,107 +1892,8 @@ mh_status launch_host(int kind, mh_model_t model, int64_t B, const T *q, const T
 }
 } // namespace
 
-
 namespace
 {
-// Host-only part of model creation: validation and the engine's joint order (depth-first, parents first).
-struct Plan
-{
-   std::vector<int> order;     // engine index -> caller index
-   std::vector<int> engine_of; // caller index -> engine index
-   std::vector<int> dofo, cfgo; // per caller joint: offsets into the concatenated index maps
-   std::vector<std::vector<int>> children; // by caller index
-   std::vector<int> eparent, etype;        // engine order
-   std::string key;
-};
-
-mh_status plan_model(const mh_model_desc *d, Plan &P)
-{
-   if (!d)
-      return fail(MH_ERR_INVALID_ARGUMENT, "desc is NULL");
-   const int n = d->n_joints;
-   if (n <= 0)
-      return fail(MH_ERR_INVALID_ARGUMENT, "n_joints = %d", n);
-   if (!d->parent || !d->joint_type || !d->axis || !d->X_before || !d->X_com || !d->inertia_J || !d->inertia_mass || !d->inertia_com
-       || !d->dof_indices || !d->cfg_indices)
-      return fail(MH_ERR_INVALID_ARGUMENT, "a model array is NULL");
-   if (d->nq < 0 || d->nv < 0)
-      return fail(MH_ERR_BAD_DIMENSION, "nq = %d, nv = %d", d->nq, d->nv);
-   P.dofo.assign(n + 1, 0), P.cfgo.assign(n + 1, 0);
-   for (int i = 0; i < n; i++)
-   {
-      const int t = d->joint_type[i];
-      if (t < MH_JOINT_REVOLUTE || t > MH_JOINT_SPHERICAL)
-         return fail(MH_ERR_UNSUPPORTED_JOINT, "joint %d has unsupported kind %d", i, t);
-      if (d->parent[i] < -1 || d->parent[i] >= n || d->parent[i] == i)
-         return fail(MH_ERR_BAD_TOPOLOGY, "joint %d has parent %d", i, d->parent[i]);
-      P.dofo[i + 1] = P.dofo[i] + joint_ndof(t);
-      P.cfgo[i + 1] = P.cfgo[i] + joint_ncfg(t);
-   }
-   {
-      std::vector<char> seen_v(d->nv, 0), seen_q(d->nq, 0);
-      for (int k = 0; k < P.dofo[n]; k++)
-      {
-         const int r = d->dof_indices[k];
-         if (r < 0 || r >= d->nv || seen_v[r])
-            return fail(MH_ERR_BAD_TOPOLOGY, "dof_indices[%d] = %d is out of range or repeated (nv = %d)", k, r, d->nv);
-         seen_v[r] = 1;
-      }
-      for (int k = 0; k < P.cfgo[n]; k++)
-      {
-         const int r = d->cfg_indices[k];
-         if (r < 0 || r >= d->nq || seen_q[r])
-            return fail(MH_ERR_BAD_TOPOLOGY, "cfg_indices[%d] = %d is out of range or repeated (nq = %d)", k, r, d->nq);
-         seen_q[r] = 1;
-      }
-   }
-   // engine order: depth-first pre-order, children in the caller's order (chains stay contiguous)
-   P.children.assign(n, {});
-   std::vector<int> roots;
-   for (int i = 0; i < n; i++)
-      (d->parent[i] < 0 ? roots : P.children[d->parent[i]]).push_back(i);
-   P.order.clear();
-   P.order.reserve(n);
-   {
-      std::vector<int> stack(roots.rbegin(), roots.rend());
-      while (!stack.empty())
-      {
-         int i = stack.back();
-         stack.pop_back();
-         P.order.push_back(i);
-         for (auto it = P.children[i].rbegin(); it != P.children[i].rend(); ++it)
-            stack.push_back(*it);
-      }
-   }
-   if ((int)P.order.size() != n)
-      return fail(MH_ERR_LOOP_CLOSURE, "parent[] contains a cycle: %d of %d joints are reachable from the root", (int)P.order.size(), n);
-   P.engine_of.assign(n, 0);
-   for (int e = 0; e < n; e++)
-      P.engine_of[P.order[e]] = e;
-   P.eparent.assign(n, -1), P.etype.assign(n, 0);
-   unsigned long long h = 1469598103934665603ull; // FNV-1a over (n, parents, kinds) in engine order
-   auto mix = [&](int v) {
-      for (int b = 0; b < 4; b++)
-      {
-         h ^= (unsigned long long)((v >> (8 * b)) & 0xff);
-         h *= 1099511628211ull;
-      }
-   };
-   mix(n);
-   for (int e = 0; e < n; e++)
-   {
-      const int i = P.order[e];
-      P.eparent[e] = d->parent[i] < 0 ? -1 : P.engine_of[d->parent[i]];
-      P.etype[e] = d->joint_type[i];
-      mix(P.eparent[e]);
-      mix(P.etype[e]);
-   }
-   char buf[32];
-   snprintf(buf, sizeof buf, "%016llx", h);
-   P.key = buf;
-   return MH_OK;
-}
-
 // Looks for libmecano_hip_topo_<key>.so next to this library and checks it was built for exactly this tree.
 void try_load_spec(mh_model *m, const Plan &P)
 {
@@ -2932,6 +2816,50 @@ mh_status mh_spec_sources_hash_of(const char *csrc_dir, char out[18])
 const char *mh_last_error(void) { return g_err; }
 // the library's other translation units (mh_comm.hip) report through the same thread-local message
 mh_status mh_internal_fail(mh_status code, const char *message) { return fail(code, "%s", message); }
+// What mh_model_create compiles from a description, for tests on machines without a device (not in include/mecano_hip.h either): runs
+// plan_model and compile_model and copies out the member of ModelTables called `name` -- a vector under its own name (int32 or double
+// entries), "scalars" (int32: n, nq, nv, n_slots, rnea_stack, aba_stack, pair_stack, aba_hand, n_nonadjacent, resp_slots, resp_a_base,
+// resp_u_base, deriv_slots, ident_maps, dense_maps, q_may_be_out, warnings), "nonleaf_fraction" (one double), "topo_key" and "warning_text"
+// (characters, no terminator).  *bytes_out is the table's size; `out` may be NULL to ask for it alone, otherwise capacity_bytes must hold it.
+mh_status mh_internal_model_table(const mh_model_desc *desc, const char *name, void *out, size_t capacity_bytes, size_t *bytes_out)
+{
+   if (!name || !bytes_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "name / bytes_out is NULL");
+   Plan P;
+   ModelTables t;
+   mh_status st = plan_model(desc, P);
+   if (st == MH_OK)
+      st = compile_model(desc, P, t);
+   if (st != MH_OK)
+      return st;
+   const std::vector<int> scalars = {t.n, t.nq, t.nv, t.n_slots, t.rnea_stack, t.aba_stack, t.pair_stack, t.aba_hand, t.n_nonadjacent, t.resp_slots, t.resp_a_base,
+                                     t.resp_u_base, t.deriv_slots, t.ident_maps, t.dense_maps, t.q_may_be_out, (int)t.warnings};
+   struct Named
+   {
+      const char *name;
+      const void *data;
+      size_t bytes;
+   };
+   auto ints = [](const char *nm, const std::vector<int> &v) { return Named{nm, v.data(), v.size() * sizeof(int)}; };
+   auto doubles = [](const char *nm, const std::vector<double> &v) { return Named{nm, v.data(), v.size() * sizeof(double)}; };
+   auto chars = [](const char *nm, const std::string &v) { return Named{nm, v.data(), v.size()}; };
+   const Named tables[] = {ints("scalars", scalars), ints("meta", t.meta), ints("dof_map", t.dof_map), ints("cfg_map", t.cfg_map), ints("engine_of", t.engine_of),
+                           ints("prog", t.prog), ints("prog_seq", t.prog_seq), ints("grav_zero_ofs", t.grav_zero_ofs), ints("grav_zero_cols", t.grav_zero_cols),
+                           ints("resp_info", t.resp_info), ints("minv_owner", t.minv_owner), ints("deriv_slot", t.deriv_slot), doubles("consts", t.consts),
+                           doubles("sub_mass", t.sub_mass), doubles("inertial_parameters", t.inertial_parameters),
+                           Named{"nonleaf_fraction", &t.nonleaf_fraction, sizeof(double)}, chars("topo_key", t.topo_key), chars("warning_text", t.warning_text)};
+   for (const Named &row : tables)
+      if (strcmp(row.name, name) == 0)
+      {
+         *bytes_out = row.bytes;
+         if (out && capacity_bytes < row.bytes)
+            return fail(MH_ERR_INVALID_ARGUMENT, "mh_internal_model_table: %s takes %zu bytes, the buffer holds %zu", name, row.bytes, capacity_bytes);
+         if (out)
+            std::memcpy(out, row.data, row.bytes);
+         return MH_OK;
+      }
+   return fail(MH_ERR_INVALID_ARGUMENT, "mh_internal_model_table: no table called %s", name);
+}
 
 mh_status mh_device_count(int32_t *count)
 {
@@ -2968,456 +2896,16 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
       return fail(MH_ERR_INVALID_ARGUMENT, "desc / model_out is NULL");
    *model_out = nullptr;
    Plan P;
-   mh_status pst = plan_model(d, P);
-   if (pst != MH_OK)
-      return pst;
-   const int n = d->n_joints;
-   const std::vector<int> &order = P.order, &engine_of = P.engine_of, &dofo = P.dofo, &cfgo = P.cfgo;
-   const std::vector<std::vector<int>> &children = P.children;
-
-   // ---- canonical frames: Q_i maps the canonical after-joint axes of joint i to Mecano's after-joint axes
-   std::vector<M3d> Q(n);
-   for (int e = 0; e < n; e++)
-   {
-      const int i = order[e];
-      const int t = d->joint_type[i];
-      if (t == MH_JOINT_REVOLUTE || t == MH_JOINT_PRISMATIC)
-      {
-         const double *a = d->axis + 3 * i;
-         const double nrm = std::sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);
-         if (!(std::fabs(nrm - 1.0) <= 1.0e-6))
-            return fail(MH_ERR_BAD_AXIS, "joint %d: axis (%g, %g, %g) is not a unit vector", i, a[0], a[1], a[2]);
-         const double k[3] = {a[0] / nrm, a[1] / nrm, a[2] / nrm};
-         Q[e] = frame_with_z(k);
-      }
-      else
-         Q[e] = m3_identity();
-   }
-
-   // The frame after a 1-DoF joint may still turn about and slide along its own axis (both commute with the joint's motion).  That freedom
-   // is spent on the joint's FIRST child (engine order: the next joint): origin and x axis are chosen so that the child's origin lies on the
-   // x axis, p_b(child) = (a, 0, 0) -- two of the three translation components of that child's pose are structural zeros, which the
-   // specialised kernels fold at compile time (Tree<TP>::p_aligned; the run-time-topology kernels just multiply by 0.0).  O[e] = origin of
-   // the canonical frame of joint e in Mecano's after-joint frame (on the axis); children first, because a child's own slide moves its origin.
-   std::vector<std::array<double, 3>> O(n, std::array<double, 3>{0.0, 0.0, 0.0});
-   std::vector<char> aligned(n, 0);
-   for (int e = n - 2; e >= 0; e--)
-   {
-      const int i = order[e], t = d->joint_type[i], ic = order[e + 1];
-      if ((t != MH_JOINT_REVOLUTE && t != MH_JOINT_PRISMATIC) || d->parent[ic] != i)
-         continue;
-      M3d Rbc;
-      std::memcpy(Rbc.m, d->X_before + 12 * ic, sizeof Rbc.m);
-      double w0[3], w[3];
-      m3_mulv(Rbc, O[e + 1].data(), w0);
-      for (int k = 0; k < 3; k++)
-         w0[k] += d->X_before[12 * ic + 9 + k];
-      m3_mulv(m3_T(Q[e]), w0, w);
-      const double delta = w[2], rho = std::hypot(w[0], w[1]);
-      const double cphi = rho > 1.0e-12 ? w[0] / rho : 1.0, sphi = rho > 1.0e-12 ? w[1] / rho : 0.0;
-      const double slide[3] = {0.0, 0.0, delta};
-      m3_mulv(Q[e], slide, O[e].data());
-      M3d Rz = m3_identity();
-      Rz.m[0] = cphi, Rz.m[1] = -sphi, Rz.m[3] = sphi, Rz.m[4] = cphi;
-      Q[e] = m3_mul(Q[e], Rz);
-      aligned[e + 1] = 1;
-   }
-
+   mh_status st = plan_model(d, P);
+   if (st != MH_OK)
+      return st;
    mh_model *m = new mh_model();
-   m->n = n, m->nq = d->nq, m->nv = d->nv;
-   m->engine_of = engine_of;
-   // ---- the two places where this engine consciously departs from the reference: told to the caller, not hidden
+   st = compile_model(d, P, *m);
+   if (st != MH_OK)
    {
-      char buf[512];
-      // (1) tools/MecanoFactories.java:51, 237-248: a revolute axis that geometricallyEquals X, Y or Z within 1e-7 WITHOUT being that axis
-      // gets a joint rotation about the exact coordinate axis while the unit twist keeps the axis as given; the engine uses the given axis for both
-      for (int i = 0; i < n; i++)
-      {
-         if (d->joint_type[i] != MH_JOINT_REVOLUTE)
-            continue;
-         const double *a = d->axis + 3 * i;
-         for (int k = 0; k < 3; k++)
-         {
-            const double dx = a[0] - (k == 0), dy = a[1] - (k == 1), dz = a[2] - (k == 2);
-            const double dist = std::sqrt(dx * dx + dy * dy + dz * dz);
-            if (dist <= 1.0e-7 && dist > 0.0)
-            {
-               if (!(m->warnings & MH_WARN_NEAR_COORDINATE_AXIS))
-               {
-                  snprintf(buf, sizeof buf,
-                           "joint %d: axis (%.17g, %.17g, %.17g) is within 1e-7 of the %c axis but not on it: Mecano rotates such a joint about the exact "
-                           "coordinate axis and keeps the given axis in its unit twist (MecanoFactories.java:237-248); this engine uses the given axis for "
-                           "both, results differ from Mecano's by up to ~4e-7 relative. ",
-                           i, a[0], a[1], a[2], "XYZ"[k]);
-                  m->warning_text += buf;
-               }
-               m->warnings |= MH_WARN_NEAR_COORDINATE_AXIS;
-               break;
-            }
-         }
-      }
-      // (2) spatial/interfaces/FixedFrameSpatialInertiaBasics.java:167-176: SpatialInertia.add skips the renormalisation of the centre of
-      // mass when the summed mass is under 1e-7; the mass matrix of a body whose composite with a child's subtree stays under it differs
-      std::vector<double> sub(n, 0.0);
-      for (int e = n - 1; e >= 0; e--)
-      {
-         const int i = order[e];
-         sub[i] += d->inertia_mass[i];
-         if (d->parent[i] >= 0)
-            sub[d->parent[i]] += sub[i];
-      }
-      for (int i = 0; i < n; i++)
-         for (int ch : children[i])
-            if (std::fabs(d->inertia_mass[i] + sub[ch]) < 1.0e-7)
-            {
-               if (!(m->warnings & MH_WARN_TINY_COMPOSITE_MASS))
-               {
-                  snprintf(buf, sizeof buf,
-                           "joint %d: the body's mass plus the subtree of joint %d is %.3g < 1e-7: Mecano's SpatialInertia.add leaves such a composite's "
-                           "centre of mass un-normalised (FixedFrameSpatialInertiaBasics.java:174-175); this engine's mass matrix stays consistent "
-                           "with its inverse dynamics and differs from Mecano's by less than the masses involved (<= 1e-6). ",
-                           i, ch, d->inertia_mass[i] + sub[ch]);
-                  m->warning_text += buf;
-               }
-               m->warnings |= MH_WARN_TINY_COMPOSITE_MASS;
-            }
+      delete m;
+      return st;
    }
-   m->meta.assign((size_t)n * mh::MI_STRIDE, 0);
-   m->consts.assign((size_t)n * mh::MC_STRIDE, 0.0);
-   // index maps re-concatenated in ENGINE order: the offset of a joint in them is then a function of the topology alone
-   std::vector<int> edofo(n + 1, 0), ecfgo(n + 1, 0);
-   for (int e = 0; e < n; e++)
-   {
-      const int i = order[e];
-      edofo[e + 1] = edofo[e] + (dofo[i + 1] - dofo[i]);
-      ecfgo[e + 1] = ecfgo[e] + (cfgo[i + 1] - cfgo[i]);
-      for (int k = dofo[i]; k < dofo[i + 1]; k++)
-         m->dof_map.push_back(d->dof_indices[k]);
-      for (int k = cfgo[i]; k < cfgo[i + 1]; k++)
-         m->cfg_map.push_back(d->cfg_indices[k]);
-   }
-   m->dense_maps = (edofo[n] == d->nv && ecfgo[n] == d->nq);
-   m->ident_maps = m->dense_maps;
-   for (int k = 0; m->ident_maps && k < edofo[n]; k++)
-      m->ident_maps = m->dof_map[k] == k;
-   for (int k = 0; m->ident_maps && k < ecfgo[n]; k++)
-      m->ident_maps = m->cfg_map[k] == k;
-   m->q_may_be_out = d->nq == d->nv;
-   for (int i = 0; m->q_may_be_out && i < n; i++)
-      if (dofo[i + 1] > dofo[i])
-         m->q_may_be_out = d->joint_type[i] == MH_JOINT_REVOLUTE && d->cfg_indices[cfgo[i]] == d->dof_indices[dofo[i]];
-   if (m->dof_map.empty())
-      m->dof_map.push_back(0);
-   if (m->cfg_map.empty())
-      m->cfg_map.push_back(0);
-
-   int slots = 0;
-   for (int e = 0; e < n; e++)
-   {
-      const int i = order[e];
-      const int t = d->joint_type[i];
-      const int pe = d->parent[i] < 0 ? -1 : engine_of[d->parent[i]];
-      int *mi = &m->meta[(size_t)e * mh::MI_STRIDE];
-      double *c = &m->consts[(size_t)e * mh::MC_STRIDE];
-      mi[mh::MI_PARENT] = pe;
-      mi[mh::MI_TYPE] = t;
-      mi[mh::MI_DOF] = edofo[e];
-      mi[mh::MI_CFG] = ecfgo[e];
-      mi[mh::MI_EXT] = i;
-      int flags = 0;
-      if (pe >= 0 && pe == e - 1)
-         flags |= mh::MF_PARENT_ADJ;
-      else if (pe >= 0)
-         m->n_nonadjacent++;
-      bool nonadj_child = false;
-      for (int ch : children[i])
-         if (engine_of[ch] != e + 1)
-            nonadj_child = true;
-      if (nonadj_child)
-         flags |= mh::MF_STORE_VA | mh::MF_HAS_ACC;
-      if (pe >= 0 && pe != e - 1)
-      {
-         // first contributor = highest engine index among the non-adjacent children of the parent
-         int hi = -1;
-         for (int ch : children[d->parent[i]])
-            if (engine_of[ch] != pe + 1)
-               hi = std::max(hi, engine_of[ch]);
-         if (hi == e)
-            flags |= mh::MF_ACC_FIRST;
-      }
-      mi[mh::MI_FLAGS] = flags;
-      mi[mh::MI_SLOT_JP] = slots, slots += (t == MH_JOINT_REVOLUTE ? 2 : 0);
-      mi[mh::MI_SLOT_F] = slots, slots += 8;
-      mi[mh::MI_SLOT_C] = slots, slots += 6;
-      mi[mh::MI_SLOT_VA] = slots, slots += (nonadj_child ? 12 : 0);
-      mi[mh::MI_SLOT_IA] = slots, slots += (nonadj_child ? 40 : 0); // ABA: 21 | CRBA: 10 | Coriolis: 10 + 30
-      mi[mh::MI_SLOT_LK] = slots, slots += (mh::dof_count(t) >= 3 ? 27 : 0); // multi-DoF joints: U, D^-1, u | locked: IA, pA
-
-      // X_before' = Qp^T X_before Q : canonical before-joint frame in the parent's canonical after-joint frame
-      const M3d Qp = pe < 0 ? m3_identity() : Q[pe];
-      M3d Rb;
-      std::memcpy(Rb.m, d->X_before + 12 * i, sizeof Rb.m);
-      const M3d Rb2 = m3_mul(m3_mul(m3_T(Qp), Rb), Q[e]);
-      double pb2[3], pb0[3];
-      m3_mulv(Rb, O[e].data(), pb0); // the canonical origin of this joint, then relative to the parent's canonical origin
-      for (int k = 0; k < 3; k++)
-         pb0[k] += d->X_before[12 * i + 9 + k] - (pe < 0 ? 0.0 : O[pe][k]);
-      m3_mulv(m3_T(Qp), pb0, pb2);
-      if (aligned[e])
-         pb2[1] = 0.0, pb2[2] = 0.0; // (a, 0, 0) by construction: what is left is rounding
-      for (int k = 0; k < 9; k++)
-         c[mh::MC_RB + k] = Rb2.m[k];
-      for (int k = 0; k < 3; k++)
-         c[mh::MC_PB + k] = pb2[k];
-      // body-fixed -> canonical after-joint: R' = Q^T Rc, p' = Q^T pc
-      M3d Rc;
-      std::memcpy(Rc.m, d->X_com + 12 * i, sizeof Rc.m);
-      const M3d Rf = m3_mul(m3_T(Q[e]), Rc);
-      double pf[3], pf0[3];
-      for (int k = 0; k < 3; k++)
-         pf0[k] = d->X_com[12 * i + 9 + k] - O[e][k];
-      m3_mulv(m3_T(Q[e]), pf0, pf);
-      for (int k = 0; k < 9; k++)
-         c[mh::MC_RF + k] = Rf.m[k];
-      for (int k = 0; k < 3; k++)
-         c[mh::MC_PF + k] = pf[k];
-      // canonical after-joint -> Mecano's after-joint frame: x = Q x' + O (joint wrench outputs)
-      for (int k = 0; k < 9; k++)
-         c[mh::MC_QA + k] = Q[e].m[k];
-      for (int k = 0; k < 3; k++)
-         c[mh::MC_OA + k] = O[e][k];
-      // spatial inertia about the canonical after-joint origin.  J is the rotational inertia about the ORIGIN of the
-      // body-fixed frame with the CoM at c_b there (spatial/interfaces/SpatialInertiaReadOnly.java:394-415).
-      const double mass = d->inertia_mass[i];
-      const double *cb = d->inertia_com + 3 * i;
-      M3d J;
-      std::memcpy(J.m, d->inertia_J + 9 * i, sizeof J.m);
-      const M3d Jr = m3_mul(m3_mul(Rf, J), m3_T(Rf)); // about the body-fixed origin, canonical axes
-      double cr[3];
-      m3_mulv(Rf, cb, cr); // CoM relative to the body-fixed origin, canonical axes
-      // shift the origin from the body-fixed origin (at pf) to the after-joint origin: c' = cr + pf
-      const double h0[3] = {mass * cr[0], mass * cr[1], mass * cr[2]};
-      const double dd = 2.0 * (pf[0] * h0[0] + pf[1] * h0[1] + pf[2] * h0[2]) + mass * (pf[0] * pf[0] + pf[1] * pf[1] + pf[2] * pf[2]);
-      double I[9];
-      for (int r = 0; r < 3; r++)
-         for (int s = 0; s < 3; s++)
-            I[3 * r + s] = Jr.m[3 * r + s] + (r == s ? dd : 0.0) - (pf[r] * h0[s] + h0[r] * pf[s] + mass * pf[r] * pf[s]);
-      c[mh::MC_M] = mass;
-      for (int k = 0; k < 3; k++)
-         c[mh::MC_H + k] = h0[k] + mass * pf[k];
-      // (mh_params_kernels.h, inertia_from_parameters: the same map on the device, per configuration)
-      c[mh::MC_I + 0] = I[0], c[mh::MC_I + 1] = 0.5 * (I[1] + I[3]), c[mh::MC_I + 2] = 0.5 * (I[2] + I[6]);
-      c[mh::MC_I + 3] = I[4], c[mh::MC_I + 4] = 0.5 * (I[5] + I[7]), c[mh::MC_I + 5] = I[8];
-   }
-   m->n_slots = std::max(slots, 1);
-   m->inertial_parameters.resize((size_t)n * mh::PARAMS_PER_BODY);
-   for (int i = 0; i < n; i++)
-   {
-      double *p = &m->inertial_parameters[(size_t)i * mh::PARAMS_PER_BODY];
-      const double *J = d->inertia_J + 9 * i;
-      p[0] = d->inertia_mass[i];
-      for (int k = 0; k < 3; k++)
-         p[1 + k] = d->inertia_com[3 * i + k];
-      p[4] = J[0], p[5] = 0.5 * (J[1] + J[3]), p[6] = 0.5 * (J[2] + J[6]), p[7] = J[4], p[8] = 0.5 * (J[5] + J[7]), p[9] = J[8];
-   }
-
-   // ---- gravity gradient (mh_gravity_kernels.h): the subtree masses do not depend on q; the zero pattern of its matrix is the topology's
-   {
-      m->sub_mass.assign(n, 0.0);
-      for (int e = n - 1; e >= 0; e--)
-      {
-         m->sub_mass[e] += m->consts[(size_t)e * mh::MC_STRIDE + mh::MC_M];
-         if (P.eparent[e] >= 0)
-            m->sub_mass[P.eparent[e]] += m->sub_mass[e];
-      }
-      std::vector<char> owned(d->nv, 0);
-      for (int k = 0; k < edofo[n]; k++)
-         owned[m->dof_map[k]] = 1;
-      std::vector<char> related((size_t)n * n, 0); // related[a * n + b]: a == b or one is an ancestor of the other
-      for (int e = 0; e < n; e++)
-         for (int a = e; a >= 0; a = P.eparent[a])
-            related[(size_t)e * n + a] = related[(size_t)a * n + e] = 1;
-      m->grav_zero_ofs.assign(n + 2, 0);
-      for (int e = 0; e < n; e++)
-      {
-         if (edofo[e + 1] > edofo[e]) // (a joint without DoFs has no rows)
-         {
-            for (int b = 0; b < n; b++)
-               if (!related[(size_t)e * n + b])
-                  for (int k = edofo[b]; k < edofo[b + 1]; k++)
-                     m->grav_zero_cols.push_back(m->dof_map[k]);
-            for (int r = 0; r < d->nv; r++)
-               if (!owned[r])
-                  m->grav_zero_cols.push_back(r);
-         }
-         m->grav_zero_ofs[e + 1] = (int)m->grav_zero_cols.size();
-      }
-      for (int r = 0; r < d->nv; r++)
-         if (!owned[r])
-            m->grav_zero_cols.push_back(r);
-      m->grav_zero_ofs[n + 1] = (int)m->grav_zero_cols.size();
-      if (m->grav_zero_cols.empty())
-         m->grav_zero_cols.push_back(0);
-   }
-
-   // ---- apparent inertia inverses (mh_response_kernels.h): which body lies under which is the topology's
-   {
-      std::vector<std::vector<int>> kids(n);
-      std::vector<int> roots;
-      for (int e = 0; e < n; e++)
-         (P.eparent[e] >= 0 ? kids[P.eparent[e]] : roots).push_back(e);
-      m->resp_info.assign((size_t)n * mh::RI_STRIDE, 0);
-      int clock = 0, n_a = 0;
-      std::vector<std::pair<int, size_t>> stack; // (body, next child)
-      for (int r : roots)
-      {
-         stack.push_back({r, 0});
-         m->resp_info[(size_t)r * mh::RI_STRIDE + mh::RI_TIN] = clock++;
-         while (!stack.empty())
-         {
-            auto &[e, next] = stack.back();
-            if (next < kids[e].size())
-            {
-               const int ch = kids[e][next++];
-               m->resp_info[(size_t)ch * mh::RI_STRIDE + mh::RI_TIN] = clock++;
-               stack.push_back({ch, 0});
-            }
-            else
-            {
-               m->resp_info[(size_t)e * mh::RI_STRIDE + mh::RI_TOUT] = clock++;
-               stack.pop_back();
-            }
-         }
-      }
-      for (int e = 0; e < n; e++)
-         m->resp_info[(size_t)e * mh::RI_STRIDE + mh::RI_SLOT_A] = (m->meta[(size_t)e * mh::MI_STRIDE + mh::MI_FLAGS] & mh::MF_STORE_VA) ? 36 * n_a++ : -1;
-      m->resp_a_base = m->n_slots;
-      m->resp_u_base = m->resp_a_base + 36 * n_a;
-      m->resp_slots = m->resp_u_base + 6 * edofo[n];
-   }
-   // ---- inverse of the joint-space inertia matrix (mh_minv_kernels.h): which joint owns which DoF index
-   m->minv_owner.assign((size_t)std::max(1, d->nv), -1);
-   for (int e = 0; e < n; e++)
-      for (int k = edofo[e]; k < edofo[e + 1]; k++)
-         m->minv_owner[m->dof_map[k]] = 8 * e + (k - edofo[e]);
-
-   // ---- derivatives of the inverse dynamics (mh_rnea_deriv_kernels.h): that kernel's own slot plan
-   m->deriv_slot.assign((size_t)std::max(1, n), 0);
-   m->deriv_slots = 0;
-   for (int e = 0; e < n; e++)
-   {
-      m->deriv_slot[e] = m->deriv_slots;
-      m->deriv_slots += (m->meta[(size_t)e * mh::MI_STRIDE + mh::MI_FLAGS] & mh::MF_STORE_VA) ? mh::DS_BRANCH : mh::DS_BODY;
-   }
-   m->deriv_slots = std::max(m->deriv_slots, 1);
-
-   // ---- depth-first kernels: children counts, stack-frame / hand-over offsets, event program (mh_dfs_kernels.h)
-   {
-      std::vector<int> nch(n, 0), ofs_r(n, 0), ofs_a(n, 0), ofs_p(n, 0);
-      for (int e = 0; e < n; e++)
-         if (P.eparent[e] >= 0)
-            nch[P.eparent[e]]++;
-      int hand = 0;
-      for (int e = 0; e < n; e++)
-      {
-         const int pe = P.eparent[e], t = P.etype[e];
-         ofs_r[e] = pe < 0 ? 0 : ofs_r[pe] + mh::rnea_frame_slots(P.etype[pe], nch[pe]);
-         ofs_a[e] = pe < 0 ? 0 : ofs_a[pe] + mh::aba_frame_slots(P.etype[pe], nch[pe]);
-         m->rnea_stack = std::max(m->rnea_stack, ofs_r[e] + mh::rnea_frame_slots(t, nch[e]));
-         m->aba_stack = std::max(m->aba_stack, ofs_a[e] + mh::aba_frame_slots(t, nch[e]));
-         ofs_p[e] = pe < 0 ? 0 : ofs_p[pe] + mh::pair_frame_slots(P.etype[pe], nch[pe]);
-         m->pair_stack = std::max(m->pair_stack, ofs_p[e] + mh::pair_frame_slots(t, nch[e]));
-         int *mi = &m->meta[(size_t)e * mh::MI_STRIDE];
-         mi[mh::MI_NCH] = nch[e], mi[mh::MI_DFS_R] = ofs_r[e], mi[mh::MI_DFS_A] = ofs_a[e], mi[mh::MI_HAND] = hand;
-         hand += mh::aba_hand_slots(t, nch[e]);
-         if (pe >= 0)
-         {
-            const int pj = mh::jx_slots(P.etype[pe]);
-            mi[mh::MI_PFR_R] = ofs_r[pe], mi[mh::MI_PVA_R] = ofs_r[pe] + 6 + pj;
-            mi[mh::MI_PFR_A] = ofs_a[pe], mi[mh::MI_PV_A] = ofs_a[pe] + 12 + pj, mi[mh::MI_PACC_A] = ofs_a[pe] + 18 + pj;
-         }
-         if (t == MH_JOINT_REVOLUTE || t == MH_JOINT_PRISMATIC)
-            mi[mh::MI_ROW_Q] = m->cfg_map[mi[mh::MI_CFG]], mi[mh::MI_ROW_V] = m->dof_map[mi[mh::MI_DOF]];
-      }
-      m->aba_hand = std::max(hand, 1);
-      m->nonleaf_fraction = (double)std::count_if(nch.begin(), nch.end(), [](int c) { return c > 0; }) / (double)n;
-      m->rnea_stack = std::max(m->rnea_stack, 1), m->aba_stack = std::max(m->aba_stack, 6);
-      // The walk: depth-first, the children of a body in the order [those with children of their own | the leaves].  A child's contribution
-      // to its parent (wrench; articulated inertia + bias wrench) is either accumulated in the parent's frame (read-modify-write of 6 / 27 /
-      // 33 slots) or handed over in registers, the carry.  The carry survives a LEAF sibling's two events (they never touch it), so the
-      // last child with children of its own sets it and every leaf behind it adds to it: only the other children with subtrees go through
-      // the frame (128-body tree of configs[4]: 26 of 127 child pops, before the leaves were sorted behind: 64).
-      // (The kernels that read AoS rows through LDS windows consume the matrices in engine order and refill synchronously on a jump: they
-      // keep a program in engine order -- prog_seq --, with the same carry rule applied to whatever leaves happen to come last.)
-      auto build_program = [&](bool leaves_last, std::vector<int> &prog) {
-         std::vector<std::vector<int>> kids(n);
-         std::vector<int> roots;
-         for (int e = 0; e < n; e++)
-            (P.eparent[e] >= 0 ? kids[P.eparent[e]] : roots).push_back(e);
-         if (leaves_last)
-            for (int e = 0; e < n; e++)
-               std::stable_partition(kids[e].begin(), kids[e].end(), [&](int c) { return nch[c] > 0; });
-         std::vector<size_t> pop_at(n, 0);
-         auto visit = [&](int e) {
-            int ev = e << mh::EV_BODY_SHIFT;
-            if (!prog.empty() && P.eparent[e] >= 0 && !(prog.back() & mh::EV_POP) && (prog.back() >> mh::EV_BODY_SHIFT) == P.eparent[e])
-               ev |= mh::EV_PARENT_REGS;
-            prog.push_back(ev);
-         };
-         auto pop = [&](int e) {
-            int pv = (e << mh::EV_BODY_SHIFT) | mh::EV_POP;
-            if (prog.back() == (e << mh::EV_BODY_SHIFT) + (prog.back() & mh::EV_PARENT_REGS))
-               pv |= mh::EV_LEAF; // the previous event is VISIT(e)
-            pop_at[e] = prog.size();
-            prog.push_back(pv);
-         };
-         std::vector<std::pair<int, size_t>> path; // (body, next child to walk): an explicit stack -- a chain of 100 000 bodies is a model too
-         for (int r : roots)
-         {
-            visit(r);
-            path.emplace_back(r, 0);
-            while (!path.empty())
-            {
-               const int e = path.back().first;
-               if (path.back().second < kids[e].size())
-               {
-                  const int c = kids[e][path.back().second++];
-                  visit(c);
-                  path.emplace_back(c, 0);
-               }
-               else
-               {
-                  pop(e);
-                  path.pop_back();
-               }
-            }
-         }
-         for (int e = 0; e < n; e++)
-         {
-            const std::vector<int> &k = kids[e];
-            if (k.empty())
-               continue;
-            int first_carried = 0; // the last child with children of its own (only leaves behind it), or the first child
-            for (size_t i = 0; i < k.size(); i++)
-               if (nch[k[i]] > 0)
-                  first_carried = (int)i;
-            for (size_t i = 0; i < k.size(); i++)
-            {
-               int &ev = prog[pop_at[k[i]]];
-               if ((int)i < first_carried)
-                  ev |= i == 0 ? mh::EV_ACC_FIRST : 0;
-               else
-                  ev |= (int)i == first_carried ? mh::EV_LAST_CHILD : mh::EV_CARRY_ADD;
-            }
-            if (first_carried > 0)
-               prog[pop_at[e]] |= mh::EV_ACC_USED;
-         }
-      };
-      build_program(true, m->prog);
-      build_program(false, m->prog_seq);
-   }
-
-   // ---- device side
    int dev = 0, ndev = 0;
    const hipError_t dc = hipGetDeviceCount(&ndev);
    if (dc != hipSuccess || ndev == 0)
@@ -3433,99 +2921,25 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
          m->cu_count = prop.multiProcessorCount;
    }
    m->device = dev;
-   m->topo_key = P.key;
-   std::vector<float> c32(m->consts.begin(), m->consts.end());
-   std::vector<float> sm32(m->sub_mass.begin(), m->sub_mass.end());
-   auto up = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
-      hipError_t r = hipMalloc(dst, bytes);
-      if (r != hipSuccess)
-         return r;
-      return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-   };
-   if (e == hipSuccess)
-      e = up((void **)&m->d_meta, m->meta.data(), m->meta.size() * sizeof(int));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_dof, m->dof_map.data(), m->dof_map.size() * sizeof(int));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_cfg, m->cfg_map.data(), m->cfg_map.size() * sizeof(int));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_prog, m->prog.data(), m->prog.size() * sizeof(int));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_prog_seq, m->prog_seq.data(), m->prog_seq.size() * sizeof(int));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_consts64, m->consts.data(), m->consts.size() * sizeof(double));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_consts32, c32.data(), c32.size() * sizeof(float));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_sub_mass64, m->sub_mass.data(), m->sub_mass.size() * sizeof(double));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_sub_mass32, sm32.data(), sm32.size() * sizeof(float));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_grav_zero_ofs, m->grav_zero_ofs.data(), m->grav_zero_ofs.size() * sizeof(int));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_grav_zero_cols, m->grav_zero_cols.data(), m->grav_zero_cols.size() * sizeof(int));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_resp_info, m->resp_info.data(), m->resp_info.size() * sizeof(int));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_minv_owner, m->minv_owner.data(), m->minv_owner.size() * sizeof(int));
-   if (e == hipSuccess)
-      e = up((void **)&m->d_deriv_slot, m->deriv_slot.data(), m->deriv_slot.size() * sizeof(int));
+   const std::vector<float> c32(m->consts.begin(), m->consts.end()), sm32(m->sub_mass.begin(), m->sub_mass.end());
+   for (const DeviceRow &r : device_rows(m, c32, sm32))
+   {
+      if (e == hipSuccess)
+         e = hipMalloc(r.ptr, r.bytes);
+      if (e == hipSuccess)
+         e = hipMemcpy(*r.ptr, r.host, r.bytes, hipMemcpyHostToDevice);
+   }
    if (e != hipSuccess)
    {
       mh_model_destroy(m);
       return fail(MH_ERR_HIP, "model upload failed: %s", hipGetErrorString(e));
    }
-   if (const char *e = getenv("MH_DISABLE_SPEC"))
-      m->use_spec = atoi(e) ? 0 : 1;
-   if (const char *e = getenv("MH_SPEC_SPLIT"))
-      m->use_split = atoi(e);
-   if (const char *e = getenv("MH_ZV"))
-      m->use_zv = atoi(e);
-   if (const char *e = getenv("MH_ZV_SAME_L2"))
-      m->zv_same_l2 = atoi(e) ? 1 : 0;
-   if (const char *e = getenv("MH_ZV_WAIT_MS"))
-      m->zv_wait_ticks = (unsigned)std::max<long long>(1, std::min<long long>(40000, atoll(e))) * 100000u;
-   if (const char *e = getenv("MH_ZVB"))
-      m->use_zvb = atoi(e);
-   if (const char *e = getenv("MH_ZVF"))
-      m->use_zvf = atoi(e);
-   if (const char *e = getenv("MH_ZVF_PAIR"))
-      m->use_zvf_pair = atoi(e);
-   if (const char *e = getenv("MH_RNEA_AHEAD"))
-      m->use_rnea_ahead = atoi(e);
-   if (const char *e = getenv("MH_ZV_STEP"))
-      m->use_zv_step = atoi(e) ? 1 : 0;
-   if (const char *e = getenv("MH_ZVB_WHICH"))
-      m->zvb_which = std::max(1, std::min(3, atoi(e)));
-   if (const char *e = getenv("MH_SPEC_IO"))
-      m->force_io = atoi(e);
-   if (const char *e = getenv("MH_FAKE_CU_COUNT")) // measurements: shrink every grid so that one workgroup loops over the batch
-      m->cu_count = std::max(1, atoi(e));
-   if (const char *e = getenv("MH_GENERIC_TRANSPOSE"))
-      m->use_transpose = atoi(e) != 0;
-   if (const char *e = getenv("MH_SPEC_ST"))
-      m->force_st = atoi(e);
-   if (const char *e = getenv("MH_DFS"))
-      m->use_dfs = atoi(e) != 0;
-   if (const char *e = getenv("MH_DFS_PAIR"))
-      m->use_dfs_pair = atoi(e) != 0;
    // fp64 forward dynamics at device-filling batches: the sweep kernel accumulates the children of a branching body through the workspace
    // (read-modify-write per extra child), the depth-first one keeps them on its stack -- measured on the reference's 30-joint shapes at
    // B = 262 144 (profiles/r02_generic_fp64_rates.txt): random trees 1253 -> 989 us and 1384 -> 1288 us on the depth-first kernel, chains
    // and the humanoid (4 branches in 24 joints) 3-12 % faster on the sweep.  Bushy = at least three branching bodies in ten.
    m->dfs_aba64 = m->n_nonadjacent * 10 >= 3 * std::max(1, m->n - 1);
-   if (const char *e = getenv("MH_DFS_ABA64"))
-      m->dfs_aba64 = atoi(e) != 0;
-   if (const char *e = getenv("MH_DFS_BUDGET"))
-      m->dfs_budget = std::max(0, atoi(e));
-   if (const char *e = getenv("MH_DFS_PLACE"))
-      m->dfs_place = atoi(e);
-   if (const char *e = getenv("MH_DFS_GREEDY"))
-      m->dfs_place_greedy = atoi(e) != 0;
-   if (const char *e = getenv("MH_HOST_CHUNK"))
-      m->host_chunk = std::max(0, atoi(e));
-   if (const char *e = getenv("MH_SPLIT_RT"))
-      m->use_split_rt = atoi(e);
+   read_switches(*m); // after the device's CU count and the heuristic above: MH_FAKE_CU_COUNT and MH_DFS_ABA64 override them
    if (m->use_split_rt != 0)
       split_rt_plan(m);
    try_load_spec(m, P);
@@ -3570,20 +2984,8 @@ static void release_model(mh_model *m)
 {
    dfs_plans_drop(m);
    split_rt_free(m);
-   (void)hipFree(m->d_meta);
-   (void)hipFree(m->d_dof);
-   (void)hipFree(m->d_cfg);
-   (void)hipFree(m->d_prog);
-   (void)hipFree(m->d_prog_seq);
-   (void)hipFree(m->d_consts64);
-   (void)hipFree(m->d_consts32);
-   (void)hipFree(m->d_sub_mass64);
-   (void)hipFree(m->d_sub_mass32);
-   (void)hipFree(m->d_grav_zero_ofs);
-   (void)hipFree(m->d_deriv_slot);
-   (void)hipFree(m->d_grav_zero_cols);
-   (void)hipFree(m->d_resp_info);
-   (void)hipFree(m->d_minv_owner);
+   for (const DeviceRow &r : device_rows(m))
+      (void)hipFree(*r.ptr);
    free_scratch(*m);
    if (m->spec.handle)
       dlclose(m->spec.handle);
