@@ -671,6 +671,64 @@ mh_status mh_aba_parameters_f32(mh_model_t model, int64_t B, const float *q, con
                                 const double gravity[3], const float *f_ext, const mh_options *opts, float *qdd_out);
 
 /*
+ * ---- forward dynamics under bilateral constraints on body frames, and the velocity-level twin for touch-down (the consumer of the
+ *      apparent inertias: MultiBodyResponseCalculator's applyRigidBodyWrench / propagateImpulse are the pieces, the reference has no
+ *      calculator that solves for the wrench; algorithms/MultiBodyResponseCalculator.java:39-41, 608-627, 640, 836) ----
+ * "How does the robot accelerate while these frames are held", "what is its velocity after these frames are stopped": the equality-
+ * constrained solve underneath every contact method.  Inequalities, friction cones and complementarity stay with the caller.
+ * Targets: n_targets K = 1 ... MH_MAX_CONSTRAINT_TARGETS; target_joints (HOST, [K]) and target_poses (HOST, [K][12] or NULL = identity)
+ * exactly as in mh_apparent_inertia_inverse_*: a position names that joint's successor body, duplicates are allowed, the pose is
+ * relative to the body-fixed frame, R must be a rotation to 1e-9, the root body is no target.
+ * Rows: target_rows (HOST, [K]) is a 6-bit mask per target, bit i constrains row i of the target frame (rows 0-2 angular, 3-5 linear):
+ * 0b111000 is a point contact, 0b111111 a weld.  At least one bit must be set over all targets; m = the number of bits set <= 48.
+ * active (DEVICE int32, [B][K]; MH_LAYOUT_SOA: [K][B]; NULL = every row active): a mask of the same form per configuration.  A row takes
+ * part in configuration r only where its bit is set in both masks; bits outside target_rows[k] are ignored.
+ * The constrained motion is that of the target frame relative to the root body, expressed in the target frame, as
+ * mh_geometric_jacobian_* defines it with every base at the root: J qdd + Jdot qd (its conv_out), respectively J qd.  Gravity and the
+ * root acceleration enter through the dynamics only.
+ * compliance eps (>= 0) is added to the diagonal of the constraint-space matrix.  With eps = 0 a rank-deficient set of rows is the
+ * caller's error: a configuration whose factorisation meets a pivot that is not positive and finite gets quiet NaN in all its outputs;
+ * no other configuration is affected and no error is raised.
+ *
+ * mh_aba_constrained_*: with J_c the active selected rows of J and c those of Jdot qd,
+ *    H qdd + h(q, qd, g, f_ext) = tau + J_c^T lambda,     J_c qdd + c + eps lambda = a_des
+ * a_des (DEVICE) [B][K][6] (MH_LAYOUT_SOA: [6 K][B]; NULL = zeros; entries of rows that are not constrained are not read).  qdd_out
+ * [B][nv].  lambda_out [B][K][6] (same layout; may be NULL): the wrench (moment, force) the constraint applies to target k's body, acting
+ * at and expressed in the target frame; unconstrained and inactive rows hold exactly 0.0.  Equivalently qdd_out = mh_aba_*(q, qd, tau,
+ * g, f_ext + sum_k X_k^T lambda_k) with X_k the body-to-target motion transform of pose k.  opts->use_root_acceleration is honoured as in
+ * mh_aba_* (gravity may then be NULL).
+ * mh_constraint_impulse_*: qd_out = qd + H^-1 J_c^T Lambda with J_c qd_out + eps Lambda = v_des (same shape as a_des; NULL = zeros: the
+ * frames stop; restitution is the caller's choice of v_des).  impulse_out as lambda_out.  The change of velocity is the forward dynamics
+ * at rest, without gravity, with Lambda as the only wrench.  Entries of qd_out no joint owns hold those of qd.
+ *
+ * Both: launches composed on opts->stream -- forward dynamics with per-body accelerations (impulse: the inverse dynamics' outward sweep
+ * for the twists), mh_apparent_inertia_inverse_* (COUPLED) into scratch, one constraint kernel (L D L^T in place, one lane per
+ * configuration), forward dynamics again (whichever plan mh_aba_* takes).  Scratch of the context: B * ((6 K)^2 + 6 K + 12 n_joints + nv)
+ * elements; mh_reserve / mh_context_reserve set it aside for K = MH_MAX_CONSTRAINT_TARGETS in fp64 while that stays within 4 GiB (a
+ * larger need is met by the first call) -- 21.5 KB per configuration for the 30-DoF humanoid, 88 MB at max_batch = 4096.  After reserve
+ * and one first call the entry points only enqueue work (graph-capturable).  The outputs overlap neither the inputs (active and a_des /
+ * v_des among them: the second launch reads the state again) nor each other.  MH_ERR_INVALID_ARGUMENT: such an overlap; NULL q / qd /
+ * tau / qdd_out / target_joints / target_rows; K out of range; a joint index outside 0 ... n_joints - 1; a mask with bits >= 6, or no bit
+ * set at all; a negative or NaN compliance; a pose that is no rotation; MH_ACCELERATION_SOURCE joints in the model (as by mh_aba_*).
+ * B = 0 returns MH_OK and touches nothing.  Index maps, MH_LAYOUT_SOA and contexts are honoured as everywhere else.
+ */
+#define MH_MAX_CONSTRAINT_TARGETS 8
+mh_status mh_aba_constrained_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
+                                 const double *f_ext, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
+                                 const int32_t *target_rows, const int32_t *active, const double *a_des, double compliance, const mh_options *opts,
+                                 double *qdd_out, double *lambda_out);
+mh_status mh_aba_constrained_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const double gravity[3],
+                                 const float *f_ext, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
+                                 const int32_t *target_rows, const int32_t *active, const float *a_des, double compliance, const mh_options *opts,
+                                 float *qdd_out, float *lambda_out);
+mh_status mh_constraint_impulse_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_targets, const int32_t *target_joints,
+                                    const double *target_poses, const int32_t *target_rows, const int32_t *active, const double *v_des,
+                                    double compliance, const mh_options *opts, double *qd_out, double *impulse_out);
+mh_status mh_constraint_impulse_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_targets, const int32_t *target_joints,
+                                    const double *target_poses, const int32_t *target_rows, const int32_t *active, const float *v_des,
+                                    double compliance, const mh_options *opts, float *qd_out, float *impulse_out);
+
+/*
  * ---- state integration (MultiBodySystemStateIntegrator.doubleIntegrateFromAcceleration, tools/MultiBodySystemStateIntegrator.java:365-441,
  *      503-575, 710-733): the step downstream of forward dynamics, so that a simulation loop never leaves the device ----
  * One explicit constant-acceleration step of size dt for every joint of every configuration: 1-DoF q' = q + dt qd + dt^2/2 qdd,

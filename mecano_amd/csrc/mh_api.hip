@@ -14,6 +14,7 @@
 #include "mh_rnea_deriv_kernels.h"
 #include "mh_params_kernels.h"
 #include "mh_step_kernels.h"
+#include "mh_constraint_kernels.h"
 #include "mh_model_tables.h"
 
 #include <dlfcn.h>
@@ -157,6 +158,9 @@ struct ContextState
    Workspace step;
    // mh_body_poses_* / mh_geometric_jacobian_*: the SoA form of AoS outputs, which a transposition then brings to the caller's rows
    Workspace kin;
+   // mh_aba_constrained_* / mh_constraint_impulse_*: W and its factor, the right-hand side, the per-body motions of the free launch, the
+   // wrenches of the second launch, a row of zeros (constraint_scratch_entries)
+   Workspace con;
    // bias-split forward dynamics (mh_zv_kernels.h): tau - h(q, qd) rows, one flag per 64 configurations (a launch stores its epoch there),
    // an error word in mapped host memory that a timed-out wait sets (read at the next call of the model)
    Workspace zv_tau, zv_flags;
@@ -169,7 +173,7 @@ struct ContextState
 };
 void free_scratch(ContextState &c)
 {
-   for (Workspace *w : {&c.ws, &c.ws_pair, &c.stage, &c.tr, &c.tr_pair, &c.aux, &c.pairs, &c.deriv, &c.step, &c.kin, &c.zv_tau, &c.zv_flags, &c.zv_cols, &c.zvb_cs})
+   for (Workspace *w : {&c.ws, &c.ws_pair, &c.stage, &c.tr, &c.tr_pair, &c.aux, &c.pairs, &c.deriv, &c.step, &c.kin, &c.con, &c.zv_tau, &c.zv_flags, &c.zv_cols, &c.zvb_cs})
       (void)hipFree(w->ptr);
    if (c.zv_error_host)
    {
@@ -2215,8 +2219,8 @@ static bool target_frame(const mh_model *m, int e, const double *X, T pose[12], 
 }
 template <typename T>
 mh_status apparent_inertia_impl(mh_model_t model, int64_t B, const T *q, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
-                                int32_t blocks, const mh_options *opts_in, T *W_out)
-{
+                                int32_t blocks, const mh_options *opts_in, T *W_out, bool w_soa = false)
+{ // w_soa: W goes out as [entries][B] whatever the call's layout (scratch of the constrained dynamics)
    mh_options opts;
    mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
@@ -2261,7 +2265,7 @@ mh_status apparent_inertia_impl(mh_model_t model, int64_t B, const T *q, int32_t
    A.q = q, A.out = W_out;
    A.ws = (T *)model->ws.ptr;
    A.ws_stride = L.lanes;
-   set_strides(G.w_bs, G.w_es, opts.layout == MH_LAYOUT_SOA, B, wsize);
+   set_strides(G.w_bs, G.w_es, w_soa || opts.layout == MH_LAYOUT_SOA, B, wsize);
    G.info = model->d_resp_info;
    G.slots = model->resp_slots, G.a_base = model->resp_a_base, G.u_base = model->resp_u_base;
    G.n_targets = n_targets, G.coupled = coupled;
@@ -2377,6 +2381,127 @@ mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int
       }
       HIP_TRY(hipGetLastError());
    }
+   return MH_OK;
+}
+// Forward dynamics under bilateral constraints on body frames, and its velocity-level twin (mh_constraint_kernels.h): launches composed
+// on the caller's stream -- the free forward dynamics with per-body accelerations (velocity form: the inverse dynamics with per-body
+// twists), the COUPLED inverse apparent inertia into SoA scratch, the constraint kernel (right-hand side, L D L^T in place, lambda, the
+// wrenches of the next launch), and forward dynamics again, whichever plan mh_aba_* takes.  Scratch per configuration, in elements of the
+// call's precision: (6 K)^2 for W, 6 K for the right-hand side, 6 n_joints each for the per-body motions and the wrenches, nv zeros.
+static size_t constraint_scratch_entries(const mh_model *m, int K)
+{
+   return 36 * (size_t)K * K + 6 * (size_t)K + 12 * (size_t)m->n + (size_t)m->nv;
+}
+template <typename T>
+mh_status constrained_impl(bool velocity, mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const double *gravity, const T *f_ext,
+                           int32_t n_targets, const int32_t *target_joints, const double *target_poses, const int32_t *target_rows,
+                           const int32_t *active, const T *des, const double &compliance, const mh_options *opts_in, T *out, T *lambda_out)
+{
+   const char *call = velocity ? "mh_constraint_impulse" : "mh_aba_constrained";
+   // the scratch below belongs to the CONTEXT of the call: resolve it before anything mutable is touched
+   mh_options o;
+   mh_status st = begin_call(model, B, opts_in, o);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: %d joint(s) are acceleration sources: the constrained dynamics take none", call, model->n_locked);
+   if (n_targets < 1 || n_targets > MH_MAX_CONSTRAINT_TARGETS)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: n_targets = %d is outside 1 ... %d", call, n_targets, MH_MAX_CONSTRAINT_TARGETS);
+   if (!target_joints || !target_rows)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: target_joints / target_rows is NULL", call);
+   if (!(compliance >= 0.0)) // (a NaN fails too)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: compliance must be >= 0", call);
+   if (!velocity && !gravity && !o.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: gravity is NULL and no root acceleration is set", call);
+   mh::ConArgs<T> G{};
+   const int K = n_targets;
+   int rows_total = 0;
+   for (int k = 0; k < K; k++)
+   {
+      const int i = target_joints[k], rk = target_rows[k];
+      if (i < 0 || i >= model->n)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d names joint %d (the model has %d joints; the root body is no target)", call, k, i, model->n);
+      if (rk < 0 || rk > 0x3f)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: row mask 0x%x has bits beyond the six rows of a frame", call, k, (unsigned)rk);
+      double off;
+      T canonical[12]; // (validates the pose as mh_apparent_inertia_inverse_* does; the kernel takes it relative to the body-fixed frame)
+      if (!target_frame<T>(model, model->engine_of[i], target_poses ? target_poses + 12 * k : nullptr, canonical, off))
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", call, k, off);
+      G.tgt[k] = model->engine_of[i], G.ext[k] = i, G.rows[k] = rk;
+      for (int r = 0; r < 12; r++)
+         G.pose[k][r] = target_poses ? (T)target_poses[12 * k + r] : (T)(r == 0 || r == 4 || r == 8 ? 1 : 0);
+      for (int r = 0; r < 6; r++)
+         if ((rk >> r) & 1)
+            G.idx[rows_total++] = (signed char)(6 * k + r);
+   }
+   if (rows_total == 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: no row is constrained (every entry of target_rows is 0)", call);
+   if (B == 0)
+      return MH_OK;
+   if (!q || !qd || (!velocity && !tau) || !out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: NULL state / output pointer", call);
+   const size_t n6 = (size_t)model->n * 6, nv = (size_t)model->nv;
+   {
+      const size_t bv = (size_t)B * nv * sizeof(T), bd = (size_t)B * 6 * K * sizeof(T);
+      const InRange ins[6] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"qd", qd, bv}, {"tau", tau, bv}, {"f_ext", f_ext, (size_t)B * n6 * sizeof(T)},
+                              {"active", active, (size_t)B * K * sizeof(int32_t)}, {velocity ? "v_des" : "a_des", des, bd}};
+      const OutRange outs[2] = {{velocity ? "qd_out" : "qdd_out", out, bv, 0u}, {velocity ? "impulse_out" : "lambda_out", lambda_out, bd, 0u}};
+      if ((st = check_aliasing(call, ins, 6, outs, 2)) != MH_OK)
+         return st;
+   }
+   st = ensure_bytes(model->con, (size_t)B * constraint_scratch_entries(model, K) * sizeof(T));
+   if (st != MH_OK)
+      return st;
+   T *W = (T *)model->con.ptr, *rhs = W + (size_t)B * 36 * K * K, *body = rhs + (size_t)B * 6 * K, *wrench = body + (size_t)B * n6,
+     *zeros = wrench + (size_t)B * n6;
+   hipStream_t stream = (hipStream_t)o.stream;
+   const double no_gravity[3] = {0.0, 0.0, 0.0};
+   mh_options of = o; // the launches below see the state as it is: both switches of the inverse dynamics on
+   of.consider_coriolis = 1, of.consider_accelerations = 1;
+   if (velocity)
+   { // per-body twists of (q, qd): the inverse dynamics' outward sweep (its efforts go to qd_out, which the last launches overwrite)
+      of.use_root_acceleration = 0;
+      st = launch<T>(ALGO_RNEA, model, B, q, qd, qd, no_gravity, nullptr, &of, out, body_outputs<T>(nullptr, body));
+   }
+   else
+      st = launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &of, out, body_outputs<T>(body, nullptr));
+   if (st != MH_OK)
+      return st;
+   st = apparent_inertia_impl<T>(model, B, q, K, target_joints, target_poses, MH_APPARENT_BLOCKS_COUPLED, &o, W, true);
+   if (st != MH_OK)
+      return st;
+   const bool soa = o.layout == MH_LAYOUT_SOA;
+   G.m = dev_model<T>(model);
+   G.B = B;
+   G.q = q;
+   set_strides(G.q_bs, G.q_es, soa, B, model->nq);
+   G.body = body, G.fext = velocity ? nullptr : f_ext, G.wrench = wrench;
+   set_strides(G.f_bs, G.f_es, soa, B, (long)n6);
+   G.W = W, G.rhs = rhs;
+   G.active = active;
+   set_strides(G.a_bs, G.a_es, soa, B, K);
+   G.des = des, G.lambda = lambda_out;
+   set_strides(G.d_bs, G.d_es, soa, B, 6L * K);
+   G.eps = (T)compliance;
+   if (!velocity)
+      set_root_acceleration(G, o, gravity);
+   G.K = K, G.rows_total = rows_total, G.velocity = velocity;
+   const int grid = (int)std::max<long>(1, std::min<long>(groups_of(B), (long)model->cu_count * 8));
+   hipLaunchKernelGGL((mh::constraint_solve_kernel<T>), dim3(grid), dim3(64), 0, stream, G);
+   HIP_TRY(hipGetLastError());
+   if (!velocity)
+      return launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, wrench, &of, out);
+   // the change of velocity: forward dynamics at rest, without gravity, with the impulses as the only wrenches; then qd_out += qd
+   // (entries of qd_out no joint owns are cleared first: forward dynamics does not write them)
+   HIP_TRY(hipMemsetAsync(zeros, 0, (size_t)B * nv * sizeof(T), stream));
+   HIP_TRY(hipMemsetAsync(out, 0, (size_t)B * nv * sizeof(T), stream));
+   st = launch<T>(ALGO_ABA, model, B, q, zeros, zeros, no_gravity, wrench, &of, out);
+   if (st != MH_OK || nv == 0)
+      return st;
+   const long n_out = (long)B * (long)nv;
+   hipLaunchKernelGGL((mh::add_in_place_kernel<T>), dim3((int)std::min<long>((n_out + 255) / 256, (long)model->cu_count * 8)), dim3(256), 0, stream, out,
+                      qd, n_out);
+   HIP_TRY(hipGetLastError());
    return MH_OK;
 }
 // Inverse of the joint-space inertia matrix, all columns or a list of them: run-time-topology kernel, which writes every entry of its
@@ -3300,6 +3425,10 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
          st = ensure_bytes(m->kin, (size_t)max_batch * kin_entries * sizeof(double));
       if (st != MH_OK)
          return st;
+      // mh_aba_constrained_* / mh_constraint_impulse_*: their scratch for the largest target list, under the same cap
+      const size_t con_bytes = (size_t)max_batch * constraint_scratch_entries(m, MH_MAX_CONSTRAINT_TARGETS) * sizeof(double);
+      if (con_bytes <= kDerivReserveCap && (st = ensure_bytes(m->con, con_bytes)) != MH_OK)
+         return st;
    }
    // the whole-tree specialised ABA keeps its hand-over store in the same workspace (more slots than the run-time-topology plan of a
    // chain), and big AoS batches of wide matrices go through transposed scratch copies: reserve both, so that compute calls allocate nothing
@@ -3945,6 +4074,36 @@ mh_status mh_rnea_derivatives_f32(mh_model_t model, int64_t B, const float *q, c
                                   const float *f_ext, const mh_options *opts, float *tau_out, float *dtau_dq_out, float *dtau_dqd_out)
 {
    return rnea_derivatives_impl<float>(model, B, q, qd, qdd, gravity, f_ext, opts, tau_out, dtau_dq_out, dtau_dqd_out);
+}
+mh_status mh_aba_constrained_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
+                                 const double *f_ext, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
+                                 const int32_t *target_rows, const int32_t *active, const double *a_des, double compliance, const mh_options *opts,
+                                 double *qdd_out, double *lambda_out)
+{
+   return constrained_impl<double>(false, model, B, q, qd, tau, gravity, f_ext, n_targets, target_joints, target_poses, target_rows, active, a_des,
+                                   compliance, opts, qdd_out, lambda_out);
+}
+mh_status mh_aba_constrained_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const double gravity[3],
+                                 const float *f_ext, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
+                                 const int32_t *target_rows, const int32_t *active, const float *a_des, double compliance, const mh_options *opts,
+                                 float *qdd_out, float *lambda_out)
+{
+   return constrained_impl<float>(false, model, B, q, qd, tau, gravity, f_ext, n_targets, target_joints, target_poses, target_rows, active, a_des,
+                                  compliance, opts, qdd_out, lambda_out);
+}
+mh_status mh_constraint_impulse_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_targets, const int32_t *target_joints,
+                                    const double *target_poses, const int32_t *target_rows, const int32_t *active, const double *v_des,
+                                    double compliance, const mh_options *opts, double *qd_out, double *impulse_out)
+{
+   return constrained_impl<double>(true, model, B, q, qd, nullptr, nullptr, nullptr, n_targets, target_joints, target_poses, target_rows, active,
+                                   v_des, compliance, opts, qd_out, impulse_out);
+}
+mh_status mh_constraint_impulse_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_targets, const int32_t *target_joints,
+                                    const double *target_poses, const int32_t *target_rows, const int32_t *active, const float *v_des,
+                                    double compliance, const mh_options *opts, float *qd_out, float *impulse_out)
+{
+   return constrained_impl<float>(true, model, B, q, qd, nullptr, nullptr, nullptr, n_targets, target_joints, target_poses, target_rows, active,
+                                  v_des, compliance, opts, qd_out, impulse_out);
 }
 mh_status mh_aba_derivatives_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
                                  const double *f_ext, const mh_options *opts, double *qdd_out, double *dqdd_dq_out, double *dqdd_dqd_out,

@@ -681,6 +681,70 @@ class HipModel:
             self._h, B, q.data_ptr(), K, None if cols is None else cols.ctypes.data, ctypes.byref(opts), out.data_ptr()))
         return out
 
+    # ------------------------------------------------------------------ dynamics under bilateral constraints on body frames
+    def _constraint_call(self, name, states, targets, rows, poses, active, des, compliance, layout, out, out_names):
+        """What ``aba_constrained`` and ``constraint_impulse`` share: the target lists as host arrays, the device arguments checked, the
+        outputs made.  Returns (B, sfx, stream, host arrays to keep alive, pointers of the target arguments, active, des, outputs)."""
+        import torch
+        B, dt, sfx, stream = self._device_inputs(states, layout)
+        tgt, K, _, poses = self._kinematic_targets(targets, None, poses)
+        row_masks = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
+        if row_masks.shape[0] != K:
+            raise _lib.MecanoHipError(2, f"rows must hold one mask per target ({K}), got {row_masks.shape[0]}")
+        aos = layout == _lib.LAYOUT_AOS
+        if active is not None:
+            self._device_tensor(active, torch.int32)
+            if tuple(active.shape) != ((B, K) if aos else (K, B)):
+                raise _lib.MecanoHipError(2, f"active has shape {tuple(active.shape)}, expected {(B, K) if aos else (K, B)}")
+        wrench_shape = (B, K, 6) if aos else (6 * K, B)
+        if des is not None:
+            self._device_tensor(des, dt)
+            if tuple(des.shape) != wrench_shape:
+                raise _lib.MecanoHipError(2, f"{name} has shape {tuple(des.shape)}, expected {wrench_shape}")
+        first, lam = self._outputs(out, ((B, self.nv) if aos else (self.nv, B), wrench_shape), out_names, dt, states[0].device)
+        if first is None:
+            raise _lib.MecanoHipError(1, f"the {out_names[0]} output is None")
+        if not float(compliance) >= 0.0:
+            raise _lib.MecanoHipError(1, "compliance must be >= 0")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        args = (K, tgt.ctypes.data, None if poses is None else poses.ctypes.data, row_masks.ctypes.data, ptr(active), ptr(des), float(compliance))
+        return B, sfx, stream, (tgt, poses, row_masks), args, first, lam
+
+    def aba_constrained(self, q, qd, tau, targets, rows, poses=None, active=None, a_des=None, compliance=0.0, gravity=(0.0, 0.0, -9.81),
+                        f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Forward dynamics while frames fixed in bodies are held: (qdd [B, nv], lam [B, K, 6]) with
+        H qdd + h = tau + J_c^T lam and J_c qdd + c + compliance lam = a_des, J_c the constrained rows of ``geometric_jacobian`` with every
+        base at the root and c those of its convective term.  ``targets``: 1 to 8 positions in the joint list (the joint's successor
+        body, duplicates allowed), ``poses`` [K, 12] their frames relative to the body-fixed frames (None: identity), ``rows`` one 6-bit
+        mask per target (bit i: row i of the target frame, rows 0-2 angular, 3-5 linear; 0b111000 a point contact, 0b111111 a weld).
+        ``active`` (int32 device tensor [B, K], None = all): the same mask per configuration; a row takes part where both have its bit.
+        ``a_des`` [B, K, 6] (None: zeros).  lam is the wrench (moment, force) the constraint applies to the target's body, at and in the
+        target frame; rows that take no part hold 0.  SoA: [nv, B], [6 K, B], active [K, B].  ``gravity`` as for ``aba``.  A singular
+        system (compliance = 0 and dependent rows) gives NaN in that configuration only.  ``out``: a (qdd, lam) pair to write into; lam
+        may be None."""
+        B, sfx, stream, keep, args, qdd, lam = self._constraint_call("a_des", [q, qd, tau], targets, rows, poses, active, a_des, compliance, layout,
+                                                                     out, ("qdd", "lambda"))
+        if f_ext is not None:
+            self._device_tensor(f_ext, q.dtype)
+        self._check_f_ext(f_ext, B, layout)
+        g, ra = self._root(gravity)
+        opts = self._options(layout, True, True, stream, root_acceleration=ra)
+        _lib.check(getattr(_lib.load(), f"mh_aba_constrained_{sfx}")(
+            self._h, B, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), g, None if f_ext is None else f_ext.data_ptr(), *args, ctypes.byref(opts),
+            qdd.data_ptr(), None if lam is None else lam.data_ptr()))
+        return qdd, lam
+
+    def constraint_impulse(self, q, qd, targets, rows, poses=None, active=None, v_des=None, compliance=0.0, layout=_lib.LAYOUT_AOS, out=None):
+        """The velocity after frames fixed in bodies are stopped: (qd_next [B, nv], impulse [B, K, 6]) with qd_next = qd + H^-1 J_c^T impulse
+        and J_c qd_next + compliance impulse = v_des (None: zeros; restitution is the caller's choice of v_des).  Arguments as for
+        ``aba_constrained``."""
+        B, sfx, stream, keep, args, qd_next, imp = self._constraint_call("v_des", [q, qd], targets, rows, poses, active, v_des, compliance, layout,
+                                                                         out, ("qd_next", "impulse"))
+        opts = self._options(layout, stream=stream)
+        _lib.check(getattr(_lib.load(), f"mh_constraint_impulse_{sfx}")(
+            self._h, B, q.data_ptr(), qd.data_ptr(), *args, ctypes.byref(opts), qd_next.data_ptr(), None if imp is None else imp.data_ptr()))
+        return qd_next, imp
+
     def rnea_derivatives(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, consider_coriolis=True,
                          consider_accelerations=True, out=None):
         """Inverse dynamics and its first-order derivatives at a moving state, one analytic launch: (tau [B, nv], dtau_dq [B, nv, nv],
