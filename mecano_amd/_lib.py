@@ -122,6 +122,9 @@ def _load_locked():
     lib.mh_model_warning_text.restype = ctypes.c_char_p
     # not in include/mecano_hip.h: the host-side tables of a description, without a device (tests/test_model_tables_cpu.py)
     lib.mh_internal_model_table.argtypes = [ctypes.POINTER(MhModelDesc), ctypes.c_char_p, P, ctypes.c_size_t, ctypes.POINTER(ctypes.c_size_t)]
+    # ... and what the launch planners make of them (tests/test_launch_plans_cpu.py): plan name, int64 parameters, int32 words out
+    lib.mh_internal_launch_plan.argtypes = [ctypes.POINTER(MhModelDesc), ctypes.c_char_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, P, ctypes.c_size_t,
+                                            ctypes.POINTER(ctypes.c_size_t)]
     lib.mh_topology_key.argtypes = [ctypes.POINTER(MhModelDesc), ctypes.c_char_p, P, P]
     lib.mh_build_code_object.argtypes = [ctypes.POINTER(MhModelDesc), ctypes.c_char_p, ctypes.c_char_p, ctypes.c_size_t]
     lib.mh_reserve.argtypes = [P, I64]

@@ -27,7 +27,7 @@ LIB_HEADERS = HEADERS + [os.path.join(CSRC, "mh_dfs_kernels.h"), os.path.join(CS
                          os.path.join(CSRC, "mh_gravity_kernels.h"), os.path.join(CSRC, "mh_response_kernels.h"), os.path.join(CSRC, "mh_minv_kernels.h"),
                          os.path.join(CSRC, "mh_kinematics_kernels.h"), os.path.join(CSRC, "mh_constraint_kernels.h"),
                          os.path.join(CSRC, "mh_params_kernels.h"), os.path.join(CSRC, "mh_rnea_deriv_kernels.h"), os.path.join(CSRC, "mh_step_kernels.h"),  # the library's own kernels
-                         os.path.join(CSRC, "mh_model_tables.h")]  # ... and its host-side model compiler
+                         os.path.join(CSRC, "mh_model_tables.h"), os.path.join(CSRC, "mh_launch_plans.h")]  # ... and its host-side model compiler and launch planners
 SPEC_SOURCE = os.path.join(CSRC, "mh_spec.hip")
 SPEC_HEADERS = HEADERS + [os.path.join(CSRC, "mh_spec_kernels.h"), os.path.join(CSRC, "mh_zv_kernels.h")]
 # what a code object is hashed over, in this order (mh_api.hip: kSpecHashFiles / kSpecCodegenFlags hold the same lists: the library's

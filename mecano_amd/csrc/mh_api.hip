@@ -16,6 +16,7 @@
 #include "mh_step_kernels.h"
 #include "mh_constraint_kernels.h"
 #include "mh_model_tables.h"
+#include "mh_launch_plans.h"
 
 #include <dlfcn.h>
 #include <spawn.h>
@@ -212,34 +213,7 @@ struct DeviceTables
    int *d_deriv_slot = nullptr;
 };
 
-// What the MH_* environment variables set, read once per model by read_switches() (mh_model_create).  The variables read elsewhere or per
-// call are not here: MH_CRBA_LPG, MH_SPEC_DIR, MH_AUTO_BUILD, MH_SPEC_SELFCHECK.
-struct Switches
-{
-   int cu_count = 256;    // the device's (mh_model_create); MH_FAKE_CU_COUNT (measurements): shrink every grid so that one workgroup loops over the batch
-   int use_spec = 1;        // MH_DISABLE_SPEC=1 in the environment forces the generic kernels (A/B measurements)
-   int use_split = -1;      // MH_SPEC_SPLIT = 0 | 1: never / whenever possible use the tree-split kernels (default: small batches)
-   int force_io = -1, force_st = -1; // MH_SPEC_IO / MH_SPEC_ST = 0 | 1 override the heuristics (measurements)
-   int use_split_rt = -1; // MH_SPLIT_RT = 0 | 1: never / whenever usable (default: small batches)
-   int use_transpose = -1; // MH_GENERIC_TRANSPOSE = 0 | 1 overrides the size heuristic
-   int use_dfs = 1;       // MH_DFS=0: the sweep kernels of mh_kernels.h serve plain RNEA / ABA calls too (A/B measurements)
-   int use_dfs_pair = 1;  // MH_DFS_PAIR=0: mh_rnea_aba_f32 on big batches issues the two depth-first kernels one after the other, as before round 5
-   int dfs_place = -1;    // MH_DFS_PLACE = 0 | 1 | 2: force all-LDS / stack in LDS + hand-over global / all global
-   bool dfs_place_greedy = false; // MH_DFS_GREEDY=1: the frames' homes from the leaves upwards as in rounds 2-4 (A/B measurements; dfs_plan)
-   int dfs_budget = -1;   // MH_DFS_BUDGET: cap of the stack's LDS budget in slots per wave (measurements)
-   int dfs_aba64 = 0;     // fp64 forward dynamics on the depth-first kernel too: bushy trees (mh_model_create), or MH_DFS_ABA64=0|1
-   int host_chunk = 0; // MH_HOST_CHUNK: configurations per chunk of the host-pointer pipeline (0 = choose)
-   int use_rnea_ahead = 1; // MH_RNEA_AHEAD (see rnea_ahead_ok)
-   int use_zv = 1;        // MH_ZV=0: never; 1: while every job's workgroup gets a CU of its own (default); 2: whenever the call qualifies
-   int use_zv_step = 1;    // MH_ZV_STEP=0: simulation steps never ride in the bias-split / fused forward dynamics (the one-job tree-split kernel integrates instead)
-   int use_zvb = 1;       // MH_ZVB=0: never; 1: batches of two or more groups of 64 configurations per CU (default); 2: whenever the call qualifies; MH_ZVB_WHICH = 1 | 2: one of the two launches only (timing)
-   int zvb_which = 3;
-   int use_zvf = 1;       // MH_ZVF=0: never the fused one-launch form; 1: where the two-launch form would be taken (default); 2: whenever the call qualifies
-   int use_zvf_pair = 1;  // MH_ZVF_PAIR=0: the pair call of device-filling batches as two launches (A/B measurements)
-   int zv_same_l2 = 0;    // MH_ZV_SAME_L2=1 (experiment, off by default; one-stage hand-off only: the two-stage form of identity index maps is write-through): bias rows and flag of a group whose two jobs prove to sit behind the same L2
-                          // stay in that L2 (workgroup-scope stores) -- cache behaviour the memory model does not promise, for no measured gain
-   unsigned zv_wait_ticks = 200000000u; // MH_ZV_WAIT_MS: how long an inertia job waits for its bias rows (100 MHz ticks; default 2 s)
-};
+// The switches of the environment (struct Switches: mh_launch_plans.h, whose planners read some of them).
 // Every switch keeps its default where its variable is unset.  mh_model_create calls this AFTER it has put the device's CU count and the
 // bushiness heuristic into cu_count and dfs_aba64: MH_FAKE_CU_COUNT and MH_DFS_ABA64 override those.
 void read_switches(Switches &s)
@@ -355,16 +329,11 @@ struct mh_model : ModelTables, DeviceTables, Switches, ContextState
       PlainMutex(const PlainMutex &) : std::mutex() {}
       PlainMutex &operator=(const PlainMutex &) { return *this; }
    } dfs_mutex;
-   // run-time tree split (mh_split_kernels.h): plan made at creation, device copies, workspace blocks
-   struct SplitRt
+   // run-time tree split (mh_split_kernels.h): plan made at creation (mh_launch_plans.h), device copies (split_rt_rows)
+   struct SplitRt : SplitPlan
    {
-      bool usable = false;
-      int n_trunk = 0, n_limbs = 0, slots = 0, est = 0, total = 0;
-      int n_seg[mh::SPLIT_WAVES] = {};
       int *d_meta[3] = {nullptr, nullptr, nullptr}, *d_trunk = nullptr, *d_seg = nullptr, *d_xl_ofs = nullptr, *d_xl[3] = {nullptr, nullptr, nullptr}; // [0] fp32, [1] fp64, [2] no LDS share
       int lds_slots[3] = {0, 0, 0}; // slots below this number live in LDS (the slot codes of the records say so), per record set
-      std::vector<int> meta;     // (body, field, value) patches of the adapted records
-      std::vector<int> xl;       // exchange slots of the limbs attached to the trunk bodies (plain slot numbers)
    } split_rt;
 };
 
@@ -405,55 +374,15 @@ mh_status ensure_bytes(Workspace &w, size_t bytes)
    return MH_OK;
 }
 
-// resident waves per CU the run-time-topology sweep kernels are launched with (plan_launch; the depth-first kernels take what their
-// registers allow instead: dfs_choose)
-constexpr int kWavesPerCu = 8;
 // one launch for RNEA + ABA (and the tree-split RNEA / ABA of a code object) while 2 * ceil(B / 64) workgroups <= cu_count * kFusedFactor
 constexpr int kFusedFactor = 4;
 // whole-tree forward dynamics of a code object: hand-over in LDS while waves <= cu_count * kAbaLdsFactor
 constexpr int kAbaLdsFactor = 1;
 
-struct Launch
-{
-   int block, grid;
-   long lanes;
-};
-Launch plan_launch(const mh_model *m, int64_t B)
-{
-   Launch L;
-   L.block = 64; // one wave per workgroup: a small batch spreads over as many CUs as it has waves
-   long waves = (B + 63) / 64;
-   long cap = (long)m->cu_count * kWavesPerCu; // resident waves: the workspace is sized by the grid, not by B
-   L.grid = (int)std::max<long>(1, std::min(waves, cap));
-   L.lanes = (long)L.grid * L.block;
-   return L;
-}
 mh_status ensure_workspace(mh_model *m, int64_t B, size_t elem)
 {
-   Launch L = plan_launch(m, B);
+   Launch L = plan_launch(m->cu_count, B);
    return ensure_bytes(m->ws, (size_t)m->n_slots * (size_t)L.lanes * elem);
-}
-
-// The lane-workspace kernels, small batches: `parts` waves per group of 64 configurations (the grid's y), each with a workspace block of
-// its own -- as many as the call wants while they keep one wave per SIMD.  Kernels whose per-body columns are independent (mass matrix,
-// Coriolis matrix, centroidal momentum matrix, joint torque regressor, gravity gradient, dynamics derivatives) want min(8, n), each wave
-// taking every parts-th body (mh_kernels.h; measured: profiles/r02_regressor_rates.txt, profiles/r02_column_parts.txt); the kernels that
-// work through a list want one wave per target or per group of columns.
-static int launch_parts(const mh_model *m, const Launch &L, long want)
-{
-   return (int)std::max<long>(1, std::min<long>(want, (long)m->cu_count * 4 / L.grid));
-}
-// ... the workspace of such a launch: `slots` entries per lane on L.grid * parts waves
-static size_t lane_ws_bytes(long slots, const Launch &L, int parts, size_t elem)
-{
-   return (size_t)slots * (size_t)L.lanes * (size_t)parts * elem;
-}
-// ... and its bound over EVERY batch up to the one L was planned for and every want up to max_want (mh_reserve): grid * parts is not
-// monotonic in the batch -- a smaller grid may take more parts -- but never exceeds max(grid, min(want * grid, 4 waves per CU))
-static size_t lane_ws_bound(const mh_model *m, long slots, const Launch &L, long max_want, size_t elem)
-{
-   const long waves = std::max<long>(L.grid, std::min<long>(max_want * L.grid, (long)m->cu_count * 4));
-   return (size_t)slots * (size_t)waves * (size_t)L.block * elem;
 }
 
 template <typename T>
@@ -521,8 +450,6 @@ mh_status begin_call(mh_model_t &model, int64_t B, const mh_options *opts_in, mh
    return check_common(model, B, &opts);
 }
 
-// groups of 64 configurations: one wave, or one workgroup of four waves, each
-long groups_of(int64_t B) { return (B + 63) / 64; }
 
 // ---- the aliasing contract of the compute calls (include/mecano_hip.h, "Aliasing").  Host-side pointer comparisons, made after the NULL
 // checks and before anything is launched or allocated: a refused call leaves its outputs untouched.
@@ -802,24 +729,9 @@ mh_status zvb_launch(mh_model *m, mh::Args<double> &A, hipStream_t stream, bool 
    return st;
 }
 
-enum Algo
-{
-   ALGO_RNEA,
-   ALGO_ABA,
-   ALGO_CRBA
-};
 
-// Depth-first run-time-topology kernels (mh_dfs_kernels.h): homes of the stack frames, where ABA's hand-over lives, grid, launch.
-//
-// Frame homes.  A frame (non-leaf bodies only) is written when its body is visited and read when the body is popped, plus one
-// read-modify-write per child that is not the last: stack traffic is proportional to the number of non-leaf bodies, and most of those
-// sit near the leaves.  On an all-global stack the 128-body tree of BASELINE.json's configs[4] moved 5.3x (RNEA) and 17.7x (ABA) its
-// algorithmic bytes through HBM at 4.2 / 5.7 TB/s (profiles/r02_config5_dfs_hbm_pmc.json): the kernels were bound by their own
-// workspace.  An all-LDS stack needs 37 KB (RNEA) / 100+ KB (ABA) per wave there, i.e. 1-4 waves per CU, and loses more than it saves.
-// So LDS is given a BUDGET per wave (what is left of 160 KB at the occupancy the launch wants) and filled from the leaves upwards: a
-// frame is placed in LDS if it fits on top of the deepest LDS path below it.  The live frames of a walk are one root-to-leaf path, so
-// every path keeps its LDS sum within the budget; the frames that do not fit -- few, near the root -- go to the wave's global block,
-// whose offsets count global-homed ancestors only.
+// Depth-first run-time-topology kernels (mh_dfs_kernels.h): the frame plan of (algorithm, LDS budget) -- dfs_frames, mh_launch_plans.h --
+// with its copy of the body records on the device.
 const mh_model::DfsPlan *dfs_plan(mh_model *m, int algo, int budget)
 {
    if (m->parent)
@@ -828,127 +740,11 @@ const mh_model::DfsPlan *dfs_plan(mh_model *m, int algo, int budget)
    for (const mh_model::DfsPlan &p : m->dfs_plans)
       if (p.algo == algo && p.budget == budget)
          return &p;
-   const int n = m->n;
-   std::vector<int> meta = m->meta, frame(n), below(n, 0), lofs(n, 0), gofs(n, 0);
-   std::vector<char> home(n, 0);
-   auto MI = [&](int e, int k) -> int & { return meta[(size_t)e * mh::MI_STRIDE + k]; };
-   for (int e = 0; e < n; e++) // algo 2: the fused RNEA + ABA walk (the forward dynamics' frame + the inverse dynamics' wrench and acceleration)
-      frame[e] = algo == 0 ? mh::rnea_frame_slots(MI(e, mh::MI_TYPE), MI(e, mh::MI_NCH))
-                           : (algo == 1 ? mh::aba_frame_slots(MI(e, mh::MI_TYPE), MI(e, mh::MI_NCH)) : mh::pair_frame_slots(MI(e, mh::MI_TYPE), MI(e, mh::MI_NCH)));
-   // (The inverse dynamics at twelve waves per CU -- 48 slots per lane -- keeps the old placement: it waits on its frames more than it
-   // moves them, and the frames next to the leaves are the ones read back right after they were written: 2.92 ms against 3.00 at 1 M
-   // configurations, while at eight waves the knapsack wins 2 %: profiles/r05_c5_frame_placement.txt.)
-   bool all_fit = true;
-   { // rounds 2-4: from the leaves upwards, whatever the frame is worth
-      for (int e = n - 1; e >= 0; e--)
-      { // engine order is depth-first: children come after their parent
-         int need = below[e];
-         if (frame[e] > 0 && below[e] + frame[e] <= budget)
-            home[e] = 1, need += frame[e];
-         else if (frame[e] > 0)
-            all_fit = false;
-         const int pe = MI(e, mh::MI_PARENT);
-         if (pe >= 0)
-            below[pe] = std::max(below[pe], need);
-      }
-   }
-   if (!(m->dfs_place_greedy || (algo == 0 && budget < 64) || all_fit)) // (every frame in LDS already: nothing to choose)
-   { // Round 5: by what a frame in LDS SAVES.  A frame is touched 2 (6 + jx) times under a single child, but under k children it is
-     // written at the visit, re-read by every later child (v, w / a), read and written by the pop of every child that is not the last
-     // (the 27 accumulators of the forward dynamics, the 6 of the inverse dynamics) and read at its own pop: 100 accesses for 47 slots at
-     // k = 2, 500 at k = 8, against 16 for 14 under one child.  The budget binds along every root-to-leaf path, so the best set of homes
-     // is a knapsack on the tree: best[e][b] = the accesses saved in e's subtree with b slots left for it = max(sum of best[c][b] over
-     // the children (e global), worth(e) + sum of best[c][b - frame(e)] (e in LDS)).  128-body tree of configs[4], 80 slots per lane:
-     // 5 314 -> 4 680 global slot accesses per configuration in the fused walk (model), 5 144 -> 4 134 for the forward dynamics at 48.
-      std::vector<int> worth(n, 0);
-      std::vector<int> with_subtree(n, 0); // children that have children of their own: all but the last of them accumulate in the frame
-      for (int e = 0; e < n; e++)          // (the leaves are walked behind them and add to the carry: mh_model_create, build_program)
-         if (MI(e, mh::MI_PARENT) >= 0 && MI(e, mh::MI_NCH) > 0)
-            with_subtree[MI(e, mh::MI_PARENT)]++;
-      for (int e = 0; e < n; e++)
-      {
-         const int k = MI(e, mh::MI_NCH), jx = mh::jx_slots(MI(e, mh::MI_TYPE)), in_frame = std::max(0, with_subtree[e] - 1);
-         if (k == 0)
-            continue;
-         if (algo == 0)
-            worth[e] = k == 1 ? 2 * (6 + jx) : (6 + jx + 12) + (k - 1) * 12 + 6 + in_frame * 12 + (6 + jx);
-         else
-         {
-            const int id = algo == 2 ? 6 : 0; // the inverse dynamics' wrench (and acceleration) beside the forward dynamics' slots
-            const int acc = 27 + id;
-            worth[e] = k == 1 ? 2 * (6 + jx) + 2 * id
-                              : (12 + jx + 6 + id) + (k - 1) * (12 + id) + (in_frame > 0 ? acc + (in_frame - 1) * 2 * acc + acc : 0) + (12 + jx);
-         }
-      }
-      const int W = budget + 1;
-      std::vector<long> best((size_t)n * W, 0);
-      std::vector<char> take((size_t)n * W, 0);
-      std::vector<std::vector<int>> kids(n);
-      for (int e = 0; e < n; e++)
-         if (MI(e, mh::MI_PARENT) >= 0)
-            kids[MI(e, mh::MI_PARENT)].push_back(e);
-      for (int e = n - 1; e >= 0; e--) // children come after their parent: their rows are complete
-         for (int b = 0; b <= budget; b++)
-         {
-            long out = 0, in = -1;
-            for (int c : kids[e])
-               out += best[(size_t)c * W + b];
-            if (frame[e] > 0 && frame[e] <= b)
-            {
-               in = worth[e];
-               for (int c : kids[e])
-                  in += best[(size_t)c * W + b - frame[e]];
-            }
-            best[(size_t)e * W + b] = std::max(out, in);
-            take[(size_t)e * W + b] = in > out;
-         }
-      std::vector<int> left(n, budget);
-      for (int e = 0; e < n; e++)
-      {
-         const int pe = MI(e, mh::MI_PARENT);
-         if (pe >= 0)
-            left[e] = left[pe] - (home[pe] ? frame[pe] : 0);
-         home[e] = take[(size_t)e * W + left[e]];
-      }
-   }
-   mh_model::DfsPlan plan{algo, budget, 0, 0, 0, nullptr};
-   for (int e = 0; e < n; e++)
-   {
-      const int pe = MI(e, mh::MI_PARENT);
-      if (pe >= 0)
-         lofs[e] = lofs[pe] + (home[pe] ? frame[pe] : 0), gofs[e] = gofs[pe] + (home[pe] ? 0 : frame[pe]);
-      if (home[e])
-         plan.lds_slots = std::max(plan.lds_slots, lofs[e] + frame[e]);
-      else if (frame[e] > 0)
-         plan.glb_slots = std::max(plan.glb_slots, gofs[e] + frame[e]), plan.glb_frames++;
-   }
-   auto code = [&](int e) { return home[e] ? (lofs[e] | mh::DFS_LDS) : gofs[e]; };
-   for (int e = 0; e < n; e++)
-   {
-      const int pe = MI(e, mh::MI_PARENT);
-      const int pj = pe >= 0 ? mh::jx_slots(MI(pe, mh::MI_TYPE)) : 0;
-      if (algo == 0)
-      {
-         MI(e, mh::MI_DFS_R) = code(e);
-         if (pe >= 0)
-            MI(e, mh::MI_PFR_R) = code(pe), MI(e, mh::MI_PVA_R) = code(pe) + 6 + pj;
-      }
-      else
-      {
-         MI(e, mh::MI_DFS_A) = code(e);
-         if (pe >= 0)
-            MI(e, mh::MI_PFR_A) = code(pe), MI(e, mh::MI_PV_A) = code(pe) + 12 + pj, MI(e, mh::MI_PACC_A) = code(pe) + 18 + pj;
-         if (algo == 2 && pe >= 0)
-         { // the inverse dynamics' slots of the parent's frame: behind the forward dynamics' part
-            const int pa = mh::aba_frame_slots(MI(pe, mh::MI_TYPE), MI(pe, mh::MI_NCH));
-            MI(e, mh::MI_PFR_R) = code(pe) + pa, MI(e, mh::MI_PVA_R) = code(pe) + pa + 6;
-         }
-      }
-   }
-   plan.glb_slots = std::max(plan.glb_slots, 6);
-   if (hipMalloc((void **)&plan.d_meta, meta.size() * sizeof(int)) != hipSuccess)
+   const FramePlan frames = dfs_frames(m->meta, m->n, algo, budget, m->dfs_place_greedy);
+   mh_model::DfsPlan plan{algo, budget, frames.lds_slots, frames.glb_slots, frames.glb_frames, nullptr};
+   if (hipMalloc((void **)&plan.d_meta, frames.meta.size() * sizeof(int)) != hipSuccess)
       return nullptr;
-   if (hipMemcpy(plan.d_meta, meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
+   if (hipMemcpy(plan.d_meta, frames.meta.data(), frames.meta.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess)
    {
       (void)hipFree(plan.d_meta);
       return nullptr;
@@ -964,257 +760,56 @@ void dfs_plans_drop(mh_model *m)
    m->dfs_plans.clear();
 }
 
-// Launch policy.  Occupancy first: the grid wants min(resident cap, waves of the batch) waves, spread over the CUs; the LDS a wave may
-// use is 160 KB divided by the waves per CU that follow from it (ABA in fp64 holds the whole register file: 4 waves per CU at most).
-// Out of that come the row windows (RNEA on AoS matrices), ABA's hand-over if all of it fits (small models at one wave per CU: measured
-// 106 vs 116 us on the humanoid at B = 4096), and the rest is the stack's budget.  MH_DFS_PLACE = 0 | 1 | 2 forces an all-LDS stack
-// with the hand-over in LDS / an all-LDS stack / an all-global stack (measurements, tests); MH_DFS_BUDGET=<slots> the budget itself.
-// ---- run-time tree split (mh_split_kernels.h): trunk / limbs / owners from the tree alone, made once per model.
-// Greedy: the limbs start as the trees of the forest; the largest limb is split at its first branching (the chain down to it joins the
-// trunk, the branches become limbs) as long as that shortens the estimated critical path  (trunk bodies) + (bodies of the busiest wave).
+// ---- run-time tree split (mh_split_kernels.h): the plan made at creation (split_rt_plan, split_rt_records: mh_launch_plans.h) and its
+// device arrays, in upload order: one row each, walked by the upload and by the release (which reads the pointers only and passes no records)
+std::vector<DeviceRow> split_rt_rows(mh_model *m, const SplitRecords *records = nullptr)
+{
+   mh_model::SplitRt &S = m->split_rt;
+   static const SplitRecords none;
+   std::vector<DeviceRow> rows = {device_row(S.d_trunk, S.trunk_list), device_row(S.d_seg, S.seg), device_row(S.d_xl_ofs, S.xl_ofs)};
+   for (int k = 0; k < 3; k++)
+   {
+      const SplitRecords &r = records ? records[k] : none;
+      rows.push_back(device_row(S.d_meta[k], r.meta));
+      rows.push_back(device_row(S.d_xl[k], r.xl));
+   }
+   return rows;
+}
 void split_rt_free(mh_model *m)
 {
-   mh_model::SplitRt &S = m->split_rt;
-   for (int k = 0; k < 3; k++)
-      (void)hipFree(S.d_meta[k]), (void)hipFree(S.d_xl[k]), S.d_meta[k] = S.d_xl[k] = nullptr;
-   (void)hipFree(S.d_trunk), (void)hipFree(S.d_seg), (void)hipFree(S.d_xl_ofs);
-   S.d_trunk = S.d_seg = S.d_xl_ofs = nullptr;
-   S.usable = false;
+   for (const DeviceRow &r : split_rt_rows(m))
+      (void)hipFree(*r.ptr), *r.ptr = nullptr;
+   m->split_rt.usable = false;
 }
-mh_status split_rt_upload_meta(mh_model *m)
-{ // the adapted body records: the model's with the (body, field, value) patches of the plan applied, then every workspace slot number
-  // turned into a slot CODE (home bit) for the precision's LDS share
-   mh_model::SplitRt &S = m->split_rt;
-   if (!S.usable)
-      return MH_OK;
-   static const int slot_fields[] = {mh::MI_SLOT_JP, mh::MI_SLOT_F, mh::MI_SLOT_VA, mh::MI_SLOT_C, mh::MI_SLOT_IA, mh::MI_SLOT_LK, mh::MI_HAND};
-   for (int k = 0; k < 3; k++)
-   {
-      const long elem = k == 0 ? 4 : 8;
-      const long cap = 160 * 1024 / (64 * elem);
-      S.lds_slots[k] = k == 2 ? 0 : (int)(S.slots <= cap ? S.slots : cap - mh::SPLIT_LDS_MARGIN); // everything, or a share with room for a group
-      std::vector<int> meta = m->meta;
-      for (size_t i = 0; i + 2 < S.meta.size(); i += 3)
-         meta[(size_t)S.meta[i] * mh::MI_STRIDE + S.meta[i + 1]] = S.meta[i + 2];
-      auto code = [&](int slot) { return slot >= 0 && slot < S.lds_slots[k] ? (slot | mh::DFS_LDS) : slot; };
-      for (int e = 0; e < m->n; e++)
-         for (int f : slot_fields)
-            meta[(size_t)e * mh::MI_STRIDE + f] = code(meta[(size_t)e * mh::MI_STRIDE + f]);
-      std::vector<int> xl = S.xl;
-      for (int &x : xl)
-         x = code(x);
-      if (!S.d_meta[k])
-         HIP_TRY(hipMalloc((void **)&S.d_meta[k], meta.size() * sizeof(int)));
-      HIP_TRY(hipMemcpy(S.d_meta[k], meta.data(), meta.size() * sizeof(int), hipMemcpyHostToDevice));
-      if (!S.d_xl[k])
-         HIP_TRY(hipMalloc((void **)&S.d_xl[k], xl.size() * sizeof(int)));
-      HIP_TRY(hipMemcpy(S.d_xl[k], xl.data(), xl.size() * sizeof(int), hipMemcpyHostToDevice));
-   }
-   return MH_OK;
-}
-void split_rt_plan(mh_model *m)
+void split_rt_create(mh_model *m)
 {
    mh_model::SplitRt &S = m->split_rt;
-   const int n = m->n, W = mh::SPLIT_WAVES;
-   auto MI = [&](int e, int k) { return m->meta[(size_t)e * mh::MI_STRIDE + k]; };
-   std::vector<std::vector<int>> ch(n);
-   std::vector<int> sz(n, 1), cnt(n, 1), roots; // sz: cost of the subtree in tenths of a 1-DoF body step; cnt: bodies in it
-   for (int e = 0; e < n; e++)
-   { // measured on the sweep kernels: a 6-DoF joint (LDL^T solve, general transforms) costs about 2.5 revolute steps, a 3-DoF joint 2
-      const int t = MI(e, mh::MI_TYPE);
-      sz[e] = t == MH_JOINT_SIXDOF ? 25 : ((t == MH_JOINT_PLANAR || t == MH_JOINT_SPHERICAL) ? 20 : (t == MH_JOINT_FIXED ? 4 : 10));
-   }
-   const std::vector<int> own = sz;
-   for (int e = n - 1; e >= 0; e--)
-   {
-      const int pe = MI(e, mh::MI_PARENT);
-      if (pe >= 0)
-         sz[pe] += sz[e], cnt[pe] += cnt[e];
-   }
-   for (int e = 0; e < n; e++)
-   {
-      const int pe = MI(e, mh::MI_PARENT);
-      (pe >= 0 ? ch[pe] : roots).push_back(e);
-   }
-   const int trunk_weight = 2; // in half bodies; measured in round 2 (DESIGN_HISTORY.md, run-time tree split): 1..3 tie, 4+ splits too little
-   std::vector<char> trunk(n, 0);
-   std::vector<int> limbs = roots;
-   auto estimate = [&](const std::vector<int> &L, int nt, std::vector<int> *owner) {
-      std::vector<int> order(L.size());
-      for (size_t i = 0; i < L.size(); i++)
-         order[i] = (int)i;
-      std::sort(order.begin(), order.end(), [&](int a, int b) { return sz[L[a]] != sz[L[b]] ? sz[L[a]] > sz[L[b]] : L[a] < L[b]; });
-      int load[mh::SPLIT_WAVES] = {}, cnt[mh::SPLIT_WAVES] = {};
-      if (owner)
-         owner->assign(L.size(), 0);
-      for (int i : order)
-      {
-         int w = 0;
-         for (int k = 1; k < W; k++)
-            if (load[k] < load[w])
-               w = k;
-         load[w] += sz[L[i]], cnt[w]++;
-         if (owner)
-            (*owner)[i] = w;
-      }
-      int mx = 0, mc = 0;
-      for (int k = 0; k < W; k++)
-         mx = std::max(mx, load[k]), mc = std::max(mc, cnt[k]);
-      return mc > mh::SPLIT_MAX_SEG ? 1 << 30 : (trunk_weight * nt + 1) / 2 + mx; // a trunk body: light outward steps on every wave + its fold on one while three wait
-   };
-   int best = estimate(limbs, 0, nullptr), nt = 0, ntc = 0; // trunk cost / trunk bodies
-   std::vector<int> best_limbs = limbs;
-   std::vector<char> best_trunk = trunk;
-   int best_nt = 0, best_ntc = 0;
-   for (int iter = 0; iter < n; iter++)
-   {
-      int big = -1;
-      for (size_t i = 0; i < limbs.size(); i++)
-         if (big < 0 || sz[limbs[i]] > sz[limbs[big]])
-            big = (int)i;
-      if (big < 0)
-         break;
-      int r = limbs[big];
-      while (ch[r].size() == 1)
-         r = ch[r][0];
-      if (ch[r].empty())
-         break; // the largest limb is a chain: it cannot be split
-      for (int b = limbs[big];; b = ch[b][0])
-      {
-         trunk[b] = 1, nt += own[b], ntc++;
-         if (b == r)
-            break;
-      }
-      limbs.erase(limbs.begin() + big);
-      for (int c : ch[r])
-         limbs.push_back(c);
-      const int est = estimate(limbs, nt, nullptr);
-      if (est < best)
-         best = est, best_limbs = limbs, best_trunk = trunk, best_nt = nt, best_ntc = ntc;
-   }
-   int sz_total = 0;
-   for (int r0 : roots)
-      sz_total += sz[r0];
-   S.usable = false;
-   if (best_limbs.size() < 2 || best > (3 * sz_total) / 4)
-      return; // a chain, or nothing to gain
-   limbs = best_limbs, trunk = best_trunk;
-   std::vector<int> owner;
-   S.est = estimate(limbs, best_nt, &owner);
-   // per wave: limbs in ascending order; exchange records behind the sweep kernels' slots
-   std::vector<int> seg((size_t)W * mh::SPLIT_MAX_SEG * 2, 0), xslot(n, -1), trunk_list;
-   for (int k = 0; k < W; k++)
-      S.n_seg[k] = 0;
-   std::vector<int> by_start(limbs.size());
-   for (size_t i = 0; i < limbs.size(); i++)
-      by_start[i] = (int)i;
-   std::sort(by_start.begin(), by_start.end(), [&](int a, int b) { return limbs[a] < limbs[b]; });
-   int slots = m->n_slots;
-   for (int i : by_start)
-   {
-      const int w = owner[i], r = limbs[i];
-      seg[((size_t)w * mh::SPLIT_MAX_SEG + S.n_seg[w]) * 2] = r, seg[((size_t)w * mh::SPLIT_MAX_SEG + S.n_seg[w]) * 2 + 1] = r + cnt[r];
-      S.n_seg[w]++;
-      if (MI(r, mh::MI_PARENT) >= 0)
-         xslot[r] = slots, slots += 27;
-   }
-   for (int e = 0; e < n; e++)
-      if (trunk[e])
-         trunk_list.push_back(e);
-   // adapted records: (body, field, value) triples applied on top of the model's records
-   std::vector<int> nflags(n), nva(n, -1), nia(n, -1);
-   for (int e = 0; e < n; e++)
-      nflags[e] = MI(e, mh::MI_FLAGS);
-   for (int e = 0; e < n; e++)
-   {
-      if (xslot[e] >= 0)
-         nflags[e] &= ~mh::MF_PARENT_ADJ; // a limb root: its parent's state comes from the workspace, its contribution goes to the exchange record
-      if (!trunk[e])
-         continue;
-      bool limb_child = false, nonadj_trunk_child = false;
-      int first_acc = -1;
-      for (int c : ch[e])
-      {
-         if (!trunk[c])
-            limb_child = true;
-         else if (c != e + 1)
-            nonadj_trunk_child = true, first_acc = std::max(first_acc, c);
-      }
-      nflags[e] &= ~(mh::MF_HAS_ACC | mh::MF_STORE_VA);
-      if (nonadj_trunk_child)
-         nflags[e] |= mh::MF_HAS_ACC;
-      if (limb_child || nonadj_trunk_child)
-      {
-         nflags[e] |= mh::MF_STORE_VA;
-         if (!(MI(e, mh::MI_FLAGS) & mh::MF_STORE_VA))
-            nva[e] = slots, slots += 12; // the model's records hold no slots for it
-      }
-      if (nonadj_trunk_child && !(MI(e, mh::MI_FLAGS) & mh::MF_HAS_ACC))
-         nia[e] = slots, slots += 40;
-      for (int c : ch[e])
-         if (trunk[c] && c != e + 1) // first contributor of the trunk-only fold: the highest index
-            nflags[c] = (nflags[c] & ~mh::MF_ACC_FIRST) | (c == first_acc ? mh::MF_ACC_FIRST : 0);
-   }
-   S.meta.clear();
-   auto patch = [&](int e, int field, int value) { S.meta.push_back(e), S.meta.push_back(field), S.meta.push_back(value); };
-   std::vector<int> xl_ofs(trunk_list.size() + 1, 0), xl;
-   for (int e = 0; e < n; e++)
-   {
-      patch(e, mh::MI_HAND, xslot[e]);
-      patch(e, mh::MI_FLAGS, nflags[e]);
-      if (nva[e] >= 0)
-         patch(e, mh::MI_SLOT_VA, nva[e]);
-      if (nia[e] >= 0)
-         patch(e, mh::MI_SLOT_IA, nia[e]);
-   }
-   for (size_t k = 0; k < trunk_list.size(); k++)
-   {
-      for (size_t i = 0; i < limbs.size(); i++)
-         if (MI(limbs[i], mh::MI_PARENT) == trunk_list[k])
-            xl.push_back(xslot[limbs[i]]);
-      xl_ofs[k + 1] = (int)xl.size();
-   }
-   if (xl.empty())
-      xl.push_back(0);
-   if (trunk_list.empty())
-      trunk_list.push_back(0);
-   S.n_trunk = best_ntc, S.n_limbs = (int)limbs.size(), S.slots = slots, S.est = (S.est + 5) / 10, S.total = (sz_total + 5) / 10;
-   auto up = [&](int **dst, const std::vector<int> &v) {
-      return hipMalloc((void **)dst, v.size() * sizeof(int)) == hipSuccess && hipMemcpy(*dst, v.data(), v.size() * sizeof(int), hipMemcpyHostToDevice) == hipSuccess;
-   };
-   S.xl = xl;
-   S.usable = up(&S.d_trunk, trunk_list) && up(&S.d_seg, seg) && up(&S.d_xl_ofs, xl_ofs);
-   if (S.usable && split_rt_upload_meta(m) != MH_OK)
-      S.usable = false;
+   static_cast<SplitPlan &>(S) = split_rt_plan(m->meta, m->n, m->n_slots);
    if (!S.usable)
+      return;
+   SplitRecords records[3];
+   for (int k = 0; k < 3; k++)
+      records[k] = split_rt_records(S, m->meta, m->n, k), S.lds_slots[k] = records[k].lds_slots;
+   hipError_t e = hipSuccess;
+   for (const DeviceRow &r : split_rt_rows(m, records))
+   {
+      if (e == hipSuccess)
+         e = hipMalloc(r.ptr, r.bytes);
+      if (e == hipSuccess)
+         e = hipMemcpy(*r.ptr, r.host, r.bytes, hipMemcpyHostToDevice);
+   }
+   if (e != hipSuccess)
       split_rt_free(m);
 }
-// Workgroups of a run-time tree-split launch: single calls put `wgs` on every CU at most; the pair call (launch_split_rt with pair) one per
-// algorithm and group of 64 configurations, taken while they fit the CUs.  Each has a workspace block of its own.
-int split_rt_grid(const mh_model *m, int64_t B, int wgs) { return (int)std::max<long>(1, std::min<long>(groups_of(B), (long)m->cu_count * wgs)); }
-size_t split_rt_ws_bytes(const mh_model *m, long grid, size_t elem) { return (size_t)m->split_rt.slots * (size_t)grid * 64 * elem; }
 // pair: both algorithms of mh_rnea_aba_f64 in ONE launch (mh::pair_split_kernel), for a model without a code object at small batches:
 // A.in3 = qdd, A.out = tau, A.in3b = tau, A.outb = qdd.
 template <typename T>
 mh_status launch_split_rt(Algo algo, mh_model *model, int64_t B, mh::Args<T> &A, hipStream_t stream, bool pair = false)
 {
    const mh_model::SplitRt &S = model->split_rt;
-   const long groups = groups_of(B);
-   // workgroups per CU: the fp64 ABA holds ~300 registers (one wave per SIMD), the others fit two workgroups (measured on the humanoid at
-   // B = 32768, two groups per CU: RNEA 47 us with two resident workgroups against 66 looping one; round 2, DESIGN_HISTORY.md)
-   const int grid = pair ? (int)(2 * groups) : split_rt_grid(model, B, (algo == ALGO_ABA && sizeof(T) == 8) ? 1 : 2);
-   // Which record set: everything in LDS when the block fits (no branches); else a share in LDS once the blocks of the workgroups of an
-   // XCD outgrow its L2 (measured on the fp64 humanoid: 44 us all-global vs 47 with a share at B = 4096, 71 vs 50 at 8192); else all global.
-   // The pair call keys on its groups: it then takes the record set (hence the kernel instantiation) of the single calls of its batch, and
-   // the two agree bit for bit with it (its grid never exceeds the CUs).
-   const long key = pair ? groups : grid;
-   int k = sizeof(T) == 4 ? 0 : 1;
-   if (S.lds_slots[k] < S.slots && (size_t)S.slots * 64 * sizeof(T) * ((size_t)key / 8 + 1) <= (size_t)3 << 20)
-      k = 2;
-   if (grid > model->cu_count && (size_t)std::min(S.slots, S.lds_slots[k] + mh::SPLIT_LDS_MARGIN) * 64 * sizeof(T) > 80 * 1024)
-      k = 2; // two workgroups per CU: an LDS share above half the CU's would serialise them
-   const int mode = S.lds_slots[k] >= S.slots ? 0 : (S.lds_slots[k] == 0 ? 1 : 2);
-   mh_status st = ensure_bytes(model->ws, split_rt_ws_bytes(model, grid, sizeof(T)));
+   const SplitShape shape = split_rt_shape(S.slots, S.lds_slots, model->cu_count, sizeof(T), algo, B, pair);
+   const int k = shape.k, mode = shape.mode, grid = shape.grid;
+   mh_status st = ensure_bytes(model->ws, split_rt_ws_bytes(S.slots, grid, sizeof(T)));
    if (st != MH_OK)
       return st;
    A.ws = (T *)model->ws.ptr;
@@ -1223,7 +818,7 @@ mh_status launch_split_rt(Algo algo, mh_model *model, int64_t B, mh::Args<T> &A,
    P.n_trunk = S.n_trunk, P.slots = S.slots;
    for (int w = 0; w < mh::SPLIT_WAVES; w++)
       P.n_seg[w] = S.n_seg[w];
-   const size_t lds = mode == 1 ? 0 : (size_t)std::min(S.slots, S.lds_slots[k] + mh::SPLIT_LDS_MARGIN) * 64 * sizeof(T);
+   const size_t lds = shape.lds;
 #define MH_SPLIT_KERN(NAME) (mode == 0 ? (const void *)&mh::NAME<T, 0> : (mode == 1 ? (const void *)&mh::NAME<T, 1> : (const void *)&mh::NAME<T, 2>))
    const void *kern = algo == ALGO_RNEA ? MH_SPLIT_KERN(rnea_split_kernel) : (algo == ALGO_ABA ? MH_SPLIT_KERN(aba_split_kernel) : MH_SPLIT_KERN(crba_split_kernel));
    if constexpr (sizeof(T) == 8)
@@ -1240,61 +835,6 @@ mh_status launch_split_rt(Algo algo, mh_model *model, int64_t B, mh::Args<T> &A,
    return MH_OK;
 }
 
-struct DfsChoice
-{
-   long per_cu, budget, hand, b_win, slot_bytes;
-   bool hand_lds, occ3;
-};
-DfsChoice dfs_choose(const mh_model *model, Algo algo, size_t elem, int64_t B, bool win, bool pair = false)
-{
-   DfsChoice c{};
-   const long waves = groups_of(B);
-   c.b_win = win ? 3L * mh::ROW_WIN * mh::ROW_PITCH * (long)elem : 0;
-   c.slot_bytes = 64 * (long)elem;
-   const long cus = model->cu_count;
-   // resident waves per CU the kernel's registers allow (hipcc -Rpass-analysis=kernel-resource-usage, round 5): fp32 inverse dynamics on
-   // SoA / transposed rows 134-136 VGPRs = three waves per SIMD (with the LDS windows of AoS rows 232-234: two); fp32 forward dynamics
-   // 181-184 = two, or 168 in the OCC3 build (48 bytes of scratch) = three, taken beyond eight waves per CU, the fused pair walk 216-219 = two; fp64
-   // 254-256 = one.  The grid used to be sized for eight everywhere: an inverse dynamics that could keep twelve waves per CU resident ran
-   // with eight (1.88 against 1.56 ms at 524 288 configurations of the 128-body tree, profiles/r05_c5_occ.txt), and a fp64 walk planned
-   // its LDS for eight waves of which four were resident.
-   // Twelve resident waves per CU finish a round 1.32 x later than eight (measured: 13 % more throughput for 50 % more waves), and the
-   // waves loop over the groups of 64 configurations: twelve are taken where they save enough ROUNDS to pay for that -- 196 608 (one round
-   // of twelve instead of two of eight) and from 393 216 configurations upwards, not at 262 144 (two rounds either way: 2.05 against 1.9 ms)
-   long reg_cap = elem == 8 ? 4 : 8;
-   const long wpc = (waves + cus - 1) / cus;
-   const bool twelve_pays = ((wpc + 11) / 12) * 132 < ((wpc + 7) / 8) * 100;
-   if (elem == 4 && algo == ALGO_RNEA && !win && twelve_pays)
-      reg_cap = 12;
-   if (elem == 4 && algo == ALGO_ABA && !pair && twelve_pays)
-      reg_cap = 12, c.occ3 = true; // the build with a register budget for three waves per SIMD (mh_dfs_kernels.h: OCC3)
-   c.per_cu = std::max<long>(1, std::min<long>(reg_cap, (waves + cus - 1) / cus));
-   const long full_stack = pair ? model->pair_stack : (algo == ALGO_RNEA ? model->rnea_stack : model->aba_stack);
-   c.hand = algo == ALGO_RNEA ? 0 : model->aba_hand;
-   if (model->dfs_place >= 0)
-   { // forced placements: give the stack what it needs and let the occupancy follow
-      c.budget = model->dfs_place == 2 ? 0 : full_stack;
-      c.hand_lds = model->dfs_place == 0 && algo == ALGO_ABA && (full_stack + c.hand) * c.slot_bytes + c.b_win <= 160 * 1024;
-      if (c.budget * c.slot_bytes + c.b_win > 160 * 1024)
-         c.budget = (160 * 1024 - c.b_win) / c.slot_bytes;
-   }
-   else
-   {
-      // (a wave's share of the 160 KB, rounded DOWN to 2 KB: LDS is allocated in blocks, and a share that fills 160 KB / per_cu to the byte
-      // left room for per_cu - 1 workgroups only -- 98 304 configurations of the 128-body tree, six waves per CU wanted, five resident: 0.99 ms
-      // against 0.61 with eight slots less, profiles/r05_c5_rnea_budget.txt)
-      const long avail = (160 * 1024 / c.per_cu) / 2048 * 2048 - c.b_win;
-      c.hand_lds = algo == ALGO_ABA && (full_stack + c.hand) * c.slot_bytes <= avail;
-      c.budget = std::max<long>(0, std::min<long>(full_stack, (avail - (c.hand_lds ? c.hand * c.slot_bytes : 0)) / c.slot_bytes));
-      if (model->dfs_budget >= 0)
-         c.budget = std::min<long>(model->dfs_budget, c.budget);
-   }
-   return c;
-}
-bool dfs_windows(const mh_model *model, Algo algo, size_t elem, bool aos)
-{ // AoS matrices with identity index maps and rows that span many cache lines: RNEA reads them through LDS windows (mh_dfs_kernels.h)
-   return algo == ALGO_RNEA && aos && model->ident_maps && (long)model->nv * (long)elem >= 512;
-}
 // Everything of a depth-first launch but the launch itself: the frame plan (uploaded at its first use), the grid, the global blocks
 // behind it in model->ws and the kernel with its LDS attribute.  launch_dfs runs it for the call at hand, mh_reserve for every plan a
 // batch up to its max_batch may get -- so that such a call finds all of it in place and only enqueues its kernel.
@@ -1310,25 +850,18 @@ struct DfsSetup
 template <typename T>
 mh_status dfs_setup(Algo algo, mh_model *model, int64_t B, bool aos, bool pair, DfsSetup &S)
 {
-   const long waves = groups_of(B);
-   const bool win = !pair && dfs_windows(model, algo, sizeof(T), aos);
-   const DfsChoice ch = dfs_choose(model, algo, sizeof(T), B, win, pair);
-   const long b_win = ch.b_win, slot_bytes = ch.slot_bytes, hand = ch.hand, budget = ch.budget, cus = model->cu_count;
-   long per_cu = ch.per_cu;
+   const bool win = !pair && dfs_windows(*model, algo, sizeof(T), aos);
+   const DfsChoice ch = dfs_choose(*model, *model, algo, sizeof(T), B, win, pair);
    const bool hand_lds = ch.hand_lds;
-   const mh_model::DfsPlan *plan = dfs_plan(model, pair ? 2 : (algo == ALGO_RNEA ? 0 : 1), (int)budget);
+   const mh_model::DfsPlan *plan = dfs_plan(model, pair ? 2 : (algo == ALGO_RNEA ? 0 : 1), (int)ch.budget);
    if (!plan)
       return fail(MH_ERR_HIP, "depth-first kernels: the body records of the frame plan could not be uploaded");
-   const long lds = (plan->lds_slots + (hand_lds ? hand : 0)) * slot_bytes + b_win;
-   if (lds > 0)
-      per_cu = std::max<long>(1, std::min<long>(per_cu, (160 * 1024) / lds));
-   const int grid = (int)std::max<long>(1, std::min(waves, cus * per_cu));
-   const long gslots = (hand_lds ? 0 : hand) + plan->glb_slots;
+   const DfsGeometry geo = dfs_geometry(ch, plan->lds_slots, plan->glb_slots, plan->glb_frames, groups_of(B), model->cu_count);
+   const long lds = geo.lds, gslots = geo.gslots;
+   const int grid = geo.grid, mode = geo.mode;
    mh_status st = ensure_bytes(model->ws, (size_t)gslots * (size_t)grid * 64 * sizeof(T));
    if (st != MH_OK)
       return st;
-   // every frame in LDS / every frame global: builds without the per-group branch
-   const int mode = plan->glb_frames == 0 ? 0 : (plan->lds_slots == 0 ? 1 : 2);
    const void *kern = nullptr;
    if (algo == ALGO_RNEA)
    {
@@ -1453,7 +986,7 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
       if (st != MH_OK)
          return st;
    }
-   const Launch L = plan_launch(model, B);
+   const Launch L = plan_launch(model->cu_count, B);
    hipStream_t stream = (hipStream_t)opts.stream;
 
    mh::Args<T> A = make_args<T>(model, B, opts, gravity);
@@ -1688,7 +1221,7 @@ mh_status launch(Algo algo, mh_model_t model, int64_t B, const T *q, const T *qd
          if (model->split_rt.usable && (model->use_split_rt == 1 || groups_of(B) <= (long)model->cu_count * 2))
             return launch_split_rt<T>(algo, model, B, A, stream); // small batches: the tree split over four waves (mh_split_kernels.h)
          {
-            const int parts = launch_parts(model, L, std::min(8, model->n));
+            const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
             if (const mh_status sp = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T))); sp != MH_OK)
                return sp;
             A.ws = (T *)model->ws.ptr;
@@ -2007,8 +1540,8 @@ mh_status coriolis_impl(mh_model_t model, int64_t B, const T *q, const T *qd, co
       return MH_OK;
    if (!q || !qd || !H_out || !C_out)
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
-   const Launch L = plan_launch(model, B);
-   const int parts = launch_parts(model, L, std::min(8, model->n));
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
    st = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
@@ -2029,7 +1562,7 @@ mh_status coriolis_impl(mh_model_t model, int64_t B, const T *q, const T *qd, co
          Launch G = L;
          G.grid = grid; // small batches: several waves per group of configurations, each writing every parts-th body's columns
          const int rc = model->spec.launch_coriolis_parts
-                           ? model->spec.launch_coriolis_parts(model->ident_maps ? SPEC_IDENT : 0, &A, grid, launch_parts(model, G, std::min(8, model->n)), (void *)stream)
+                           ? model->spec.launch_coriolis_parts(model->ident_maps ? SPEC_IDENT : 0, &A, grid, launch_parts(model->cu_count, G, std::min(8, model->n)), (void *)stream)
                            : model->spec.launch_coriolis(model->ident_maps ? SPEC_IDENT : 0, &A, grid, (void *)stream);
          if (spec_done(rc, "specialised Coriolis kernel launch failed", st))
             return st;
@@ -2052,8 +1585,8 @@ mh_status regressor_impl(mh_model_t model, int64_t B, const T *q, const T *qd, c
       return MH_OK;
    if (!q || !qd || !qdd || !Y_out)
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
-   const Launch L = plan_launch(model, B);
-   const int parts = launch_parts(model, L, std::min(8, model->n));
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
    st = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
@@ -2091,8 +1624,8 @@ mh_status centroidal_impl(mh_model_t model, int64_t B, const T *q, const T *qd, 
       return MH_OK;
    if (!q || !A_out || (b_out && !qd))
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer (the convective term needs qd)");
-   const Launch L = plan_launch(model, B);
-   const int parts = launch_parts(model, L, std::min(8, model->n));
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
    st = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
@@ -2123,7 +1656,7 @@ mh_status centroidal_impl(mh_model_t model, int64_t B, const T *q, const T *qd, 
          Launch G = L;
          G.grid = grid;
          const int rc = model->spec.launch_centroidal_parts
-                           ? model->spec.launch_centroidal_parts(model->ident_maps ? SPEC_IDENT : 0, &A, grid, launch_parts(model, G, std::min(8, model->n)), (void *)stream)
+                           ? model->spec.launch_centroidal_parts(model->ident_maps ? SPEC_IDENT : 0, &A, grid, launch_parts(model->cu_count, G, std::min(8, model->n)), (void *)stream)
                            : model->spec.launch_centroidal(model->ident_maps ? SPEC_IDENT : 0, &A, grid, (void *)stream);
          if (spec_done(rc, "specialised centroidal kernel launch failed", st))
             return st;
@@ -2151,8 +1684,8 @@ mh_status gravity_gradient_impl(mh_model_t model, int64_t B, const T *q, const d
       return MH_OK;
    if (!q)
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL configuration pointer");
-   const Launch L = plan_launch(model, B);
-   const int parts = launch_parts(model, L, std::min(8, model->n));
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
    st = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
@@ -2255,8 +1788,8 @@ mh_status apparent_inertia_impl(mh_model_t model, int64_t B, const T *q, int32_t
       if ((st = check_aliasing("mh_apparent_inertia_inverse", &in, 1, &out, 1)) != MH_OK)
          return st;
    }
-   const Launch L = plan_launch(model, B);
-   const int parts = launch_parts(model, L, n_targets);
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = launch_parts(model->cu_count, L, n_targets);
    st = ensure_bytes(model->ws, lane_ws_bytes(model->resp_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
@@ -2335,8 +1868,8 @@ mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int
       if ((st = check_aliasing(call, ins, 2, outs, 3)) != MH_OK)
          return st;
    }
-   const Launch L = plan_launch(model, B);
-   const int parts = jacobian ? launch_parts(model, L, n_targets) : 1;
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = jacobian ? launch_parts(model->cu_count, L, n_targets) : 1;
    st = ensure_bytes(model->ws, lane_ws_bytes((long)model->n * mh::KIN_SLOTS, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
@@ -2541,8 +2074,8 @@ mh_status mass_matrix_inverse_impl(mh_model_t model, int64_t B, const T *q, int3
       if ((st = check_aliasing("mh_mass_matrix_inverse", &in, 1, &out, 1)) != MH_OK)
          return st;
    }
-   const Launch L = plan_launch(model, B);
-   const int parts = launch_parts(model, L, minv_groups(n_columns));
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = launch_parts(model->cu_count, L, minv_groups(n_columns));
    st = ensure_bytes(model->ws, lane_ws_bytes(model->resp_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
@@ -2590,7 +2123,7 @@ mh_status parameters_impl(Algo algo, mh_model_t model, int64_t B, const T *q, co
    st = ensure_workspace(model, B, sizeof(T));
    if (st != MH_OK)
       return st;
-   const Launch L = plan_launch(model, B);
+   const Launch L = plan_launch(model->cu_count, B);
    hipStream_t stream = (hipStream_t)opts.stream;
    const bool soa = opts.layout == MH_LAYOUT_SOA;
    mh::ParamArgs<T> G{};
@@ -2657,8 +2190,8 @@ mh_status rnea_derivatives_impl(mh_model_t model, int64_t B, const T *q, const T
       if ((st = check_aliasing("mh_rnea_derivatives", ins, 4, outs, 3)) != MH_OK)
          return st;
    }
-   const Launch L = plan_launch(model, B);
-   const int parts = launch_parts(model, L, std::min(8, model->n));
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
    st = ensure_bytes(model->ws, lane_ws_bytes(model->deriv_slots, L, parts, sizeof(T)));
    if (st != MH_OK)
       return st;
@@ -2985,6 +2518,113 @@ mh_status mh_internal_model_table(const mh_model_desc *desc, const char *name, v
       }
    return fail(MH_ERR_INVALID_ARGUMENT, "mh_internal_model_table: no table called %s", name);
 }
+// What the planners of mh_launch_plans.h make of a description's tables, for the same tests (tests/test_launch_plans_cpu.py): runs
+// plan_model, compile_model and the planner called `plan` on `params`, and copies out its result as int32 words, with the protocol above.
+//   "dfs_frames"       (algo 0 | 1 | 2, budget, greedy): lds_slots, glb_slots, glb_frames, then the adapted body records
+//   "dfs_choice"       (cu_count, algo 0 | 1, elem 4 | 8, B, aos, pair, dfs_place, dfs_budget): win; per_cu, budget, hand, b_win, slot_bytes,
+//                      hand_lds, occ3 (dfs_choose); lds_slots, glb_slots, glb_frames of that budget's frames; lds, per_cu, grid, gslots, mode
+//                      (dfs_geometry)
+//   "split_rt"         (): usable, n_trunk, n_limbs, slots, est, total, n_seg[4], the sizes of trunk_list, seg, xl_ofs, xl and patches, then
+//                      those five
+//   "split_rt_records" (k 0 | 1 | 2): lds_slots, the sizes of meta and xl, then those two (a model with a usable split only)
+//   "split_rt_shape"   (cu_count, elem, algo 0 | 1 | 2, B, pair): k, mode, lds, grid (a model with a usable split only)
+//   "lane_ws"          (cu_count, B, want): block, grid, lanes of plan_launch; launch_parts; lane_ws_bytes and lane_ws_bound of one slot of
+//                      one byte (the bound with B and want as the largest batch and want)
+mh_status mh_internal_launch_plan(const mh_model_desc *desc, const char *plan, const int64_t *params, int32_t n_params, void *out, size_t capacity_bytes,
+                                  size_t *bytes_out)
+{
+   if (!plan || !bytes_out || (n_params > 0 && !params))
+      return fail(MH_ERR_INVALID_ARGUMENT, "plan / bytes_out / params is NULL");
+   Plan P;
+   ModelTables t;
+   mh_status st = plan_model(desc, P);
+   if (st == MH_OK)
+      st = compile_model(desc, P, t);
+   if (st != MH_OK)
+      return st;
+   const std::string name = plan;
+   auto takes = [&](int count) { return n_params == count; };
+   auto among = [&](int i, std::initializer_list<int64_t> allowed) { return std::find(allowed.begin(), allowed.end(), params[i]) != allowed.end(); };
+   const char *const bad = "mh_internal_launch_plan: %s does not take these parameters";
+   std::vector<int> w;
+   auto append = [&](const std::vector<int> &v) { w.insert(w.end(), v.begin(), v.end()); };
+   if (name == "dfs_frames")
+   {
+      if (!takes(3) || !among(0, {0, 1, 2}) || params[1] < 0 || params[1] > (1 << 16) || !among(2, {0, 1}))
+         return fail(MH_ERR_INVALID_ARGUMENT, bad, plan);
+      const FramePlan f = dfs_frames(t.meta, t.n, (int)params[0], (int)params[1], params[2] != 0);
+      w = {f.lds_slots, f.glb_slots, f.glb_frames};
+      append(f.meta);
+   }
+   else if (name == "dfs_choice")
+   {
+      if (!takes(8) || params[0] < 1 || params[0] > (1 << 20) || !among(1, {0, 1}) || !among(2, {4, 8}) || params[3] < 0 || !among(4, {0, 1}) || !among(5, {0, 1})
+          || (params[5] && (params[1] != 1 || params[2] != 4)) || !among(6, {-1, 0, 1, 2}) || params[7] < -1 || params[7] > (1 << 16))
+         return fail(MH_ERR_INVALID_ARGUMENT, bad, plan);
+      Switches sw;
+      sw.cu_count = (int)params[0], sw.dfs_place = (int)params[6], sw.dfs_budget = (int)params[7];
+      const Algo algo = params[1] == 0 ? ALGO_RNEA : ALGO_ABA;
+      const size_t elem = (size_t)params[2];
+      const bool pair = params[5] != 0, win = !pair && dfs_windows(t, algo, elem, params[4] != 0);
+      const DfsChoice c = dfs_choose(t, sw, algo, elem, params[3], win, pair);
+      const FramePlan f = dfs_frames(t.meta, t.n, pair ? 2 : (algo == ALGO_RNEA ? 0 : 1), (int)c.budget, sw.dfs_place_greedy);
+      const DfsGeometry g = dfs_geometry(c, f.lds_slots, f.glb_slots, f.glb_frames, groups_of(params[3]), sw.cu_count);
+      w = {win, (int)c.per_cu, (int)c.budget, (int)c.hand, (int)c.b_win, (int)c.slot_bytes, c.hand_lds, c.occ3, f.lds_slots, f.glb_slots, f.glb_frames,
+           (int)g.lds, (int)g.per_cu, g.grid, (int)g.gslots, g.mode};
+   }
+   else if (name == "split_rt" || name == "split_rt_records" || name == "split_rt_shape")
+   {
+      const SplitPlan S = split_rt_plan(t.meta, t.n, t.n_slots);
+      if (name == "split_rt")
+      {
+         if (!takes(0))
+            return fail(MH_ERR_INVALID_ARGUMENT, bad, plan);
+         w = {S.usable, S.n_trunk, S.n_limbs, S.slots, S.est, S.total};
+         w.insert(w.end(), S.n_seg, S.n_seg + mh::SPLIT_WAVES);
+         for (const std::vector<int> *v : {&S.trunk_list, &S.seg, &S.xl_ofs, &S.xl, &S.patches})
+            w.push_back((int)v->size());
+         for (const std::vector<int> *v : {&S.trunk_list, &S.seg, &S.xl_ofs, &S.xl, &S.patches})
+            append(*v);
+      }
+      else if (!S.usable)
+         return fail(MH_ERR_INVALID_ARGUMENT, "mh_internal_launch_plan: %s: the tree has no usable run-time split", plan);
+      else if (name == "split_rt_records")
+      {
+         if (!takes(1) || !among(0, {0, 1, 2}))
+            return fail(MH_ERR_INVALID_ARGUMENT, bad, plan);
+         const SplitRecords R = split_rt_records(S, t.meta, t.n, (int)params[0]);
+         w = {R.lds_slots, (int)R.meta.size(), (int)R.xl.size()};
+         append(R.meta), append(R.xl);
+      }
+      else
+      {
+         if (!takes(5) || params[0] < 1 || params[0] > (1 << 20) || !among(1, {4, 8}) || !among(2, {0, 1, 2}) || params[3] < 0 || !among(4, {0, 1}))
+            return fail(MH_ERR_INVALID_ARGUMENT, bad, plan);
+         int lds_slots[3];
+         for (int k = 0; k < 3; k++)
+            lds_slots[k] = split_rt_records(S, t.meta, t.n, k).lds_slots;
+         const SplitShape s = split_rt_shape(S.slots, lds_slots, (int)params[0], (size_t)params[1], (Algo)params[2], params[3], params[4] != 0);
+         w = {s.k, s.mode, (int)s.lds, s.grid};
+      }
+   }
+   else if (name == "lane_ws")
+   {
+      if (!takes(3) || params[0] < 1 || params[0] > (1 << 20) || params[1] < 0 || params[1] > (1 << 30) || params[2] < 1 || params[2] > 4096)
+         return fail(MH_ERR_INVALID_ARGUMENT, bad, plan);
+      const int cus = (int)params[0];
+      const Launch L = plan_launch(cus, params[1]);
+      const int parts = launch_parts(cus, L, (long)params[2]);
+      w = {L.block, L.grid, (int)L.lanes, parts, (int)lane_ws_bytes(1, L, parts, 1), (int)lane_ws_bound(cus, 1, L, (long)params[2], 1)};
+   }
+   else
+      return fail(MH_ERR_INVALID_ARGUMENT, "mh_internal_launch_plan: no plan called %s", plan);
+   *bytes_out = w.size() * sizeof(int);
+   if (out && capacity_bytes < *bytes_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "mh_internal_launch_plan: %s takes %zu bytes, the buffer holds %zu", plan, *bytes_out, capacity_bytes);
+   if (out)
+      std::memcpy(out, w.data(), *bytes_out);
+   return MH_OK;
+}
 
 mh_status mh_device_count(int32_t *count)
 {
@@ -3066,7 +2706,7 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
    m->dfs_aba64 = m->n_nonadjacent * 10 >= 3 * std::max(1, m->n - 1);
    read_switches(*m); // after the device's CU count and the heuristic above: MH_FAKE_CU_COUNT and MH_DFS_ABA64 override them
    if (m->use_split_rt != 0)
-      split_rt_plan(m);
+      split_rt_create(m);
    try_load_spec(m, P);
    // MH_AUTO_BUILD: no usable code object for this tree (none there, or one refused for its ABI stamp / tree) -> build one now (hipcc on the
    // box; 1: the fast form, seconds; 2: the full set, minutes -- also when only a minimal object was found)
@@ -3397,8 +3037,8 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
    if (st != MH_OK)
       return st;
    { // the lane-workspace kernels: (slots per lane, the most waves per group of configurations a call may want), bounded over every
-      // batch up to max_batch (lane_ws_bound)
-      const Launch L = plan_launch(m, max_batch);
+      // batch up to max_batch (lane_ws_bound; swept by tests/test_launch_plans_cpu.py)
+      const Launch L = plan_launch(m->cu_count, max_batch);
       const long lane_plans[4][2] = {
          {m->n_slots, std::min(8, m->n)}, // mh_regressor_*, mh_crba_coriolis_*, mh_centroidal_*, mh_gravity_gradient_*, the mass matrix
          // mh_apparent_inertia_inverse_*: its own slots behind the model's, up to one wave per target; mh_mass_matrix_inverse_* works in
@@ -3408,7 +3048,7 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
          // mh_body_poses_* / mh_geometric_jacobian_*: pose and twist of every body per lane, up to one wave per target
          {(long)m->n * mh::KIN_SLOTS, MH_MAX_KINEMATIC_TARGETS}};
       for (const auto &plan : lane_plans)
-         if ((st = ensure_bytes(m->ws, lane_ws_bound(m, plan[0], L, plan[1], sizeof(double)))) != MH_OK)
+         if ((st = ensure_bytes(m->ws, lane_ws_bound(m->cu_count, plan[0], L, plan[1], sizeof(double)))) != MH_OK)
             return st;
       // mh_aba_derivatives_*: the scratch of the forward form
       if (m->nv > 0 && deriv_scratch_bytes(m, max_batch, sizeof(double)) <= kDerivReserveCap)
@@ -3434,7 +3074,7 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
    // chain), and big AoS batches of wide matrices go through transposed scratch copies: reserve both, so that compute calls allocate nothing
    if (m->spec.aba_slots)
    {
-      const Launch L = plan_launch(m, max_batch);
+      const Launch L = plan_launch(m->cu_count, max_batch);
       st = ensure_bytes(m->ws, (size_t)std::max(m->n_slots, m->spec.aba_slots()) * (size_t)L.lanes * sizeof(double));
       if (st != MH_OK)
          return st;
@@ -3446,7 +3086,8 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       return st;
    // the depth-first kernels: every frame plan a batch of up to max_batch configurations can get, with the global blocks behind it and
    // its kernel's LDS attribute (dfs_setup).  A plan is cached per LDS budget, and dfs_choose picks the budget from the waves per CU: all
-   // batches of one count of waves per CU get the same plans, the largest of them the largest grid -- so one setup per class, both
+   // batches of one count of waves per CU get the same plans, the largest of them the largest grid (tests/test_launch_plans_cpu.py checks
+   // both statements on dfs_choose and dfs_geometry) -- so one setup per class, both
    // algorithms, both precisions, both layouts, and the fp32 fused pair walk of mh_rnea_aba_f32 (batches from 8192 configurations on).
    // Largest class first: the workspace is allocated once, at its final size, where it can be.
    size_t dfs_bytes = 0;
@@ -3472,7 +3113,7 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       }
    }
    if (m->split_rt.usable) // the run-time tree split: one workspace block per workgroup
-      dfs_bytes = std::max(dfs_bytes, split_rt_ws_bytes(m, split_rt_grid(m, max_batch, 2), sizeof(double)));
+      dfs_bytes = std::max(dfs_bytes, split_rt_ws_bytes(m->split_rt.slots, split_rt_grid(m->cu_count, max_batch, 2), sizeof(double)));
    if (dfs_bytes > 0)
       st = ensure_bytes(m->ws, dfs_bytes);
    if (st == MH_OK && groups_of(max_batch) <= (long)m->cu_count)
@@ -3493,7 +3134,7 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
          st = ensure_bytes(m->zvb_cs, std::max<size_t>(1, (size_t)m->spec.zvb_cs_rows()) * (size_t)(groups_of(max_batch) * 64) * sizeof(double));
    }
    if (st == MH_OK && m->split_rt.usable) // the pair call's grid
-      st = ensure_bytes(m->ws, split_rt_ws_bytes(m, std::min<long>(2 * groups_of(max_batch), (long)m->cu_count), sizeof(double)));
+      st = ensure_bytes(m->ws, split_rt_ws_bytes(m->split_rt.slots, std::min<long>(2 * groups_of(max_batch), (long)m->cu_count), sizeof(double)));
    if (st == MH_OK && transposed && m->use_dfs)
       st = ensure_bytes(m->tr_pair, (size_t)max_batch * ((size_t)m->nq + 5 * (size_t)m->nv) * sizeof(float));
    return st;

@@ -12,7 +12,7 @@
 //     frame of the body / its parent;
 //   * stack frames exist for non-leaf bodies only; their offsets are a function of the tree (sum of the ancestors' frame sizes), so the
 //     stack a lane needs is (deepest path) x (frame), not (bodies) x (record): 146 slots instead of ~2500 on the 128-body tree.  Every
-//     frame has a HOME chosen by the host (mh_api.hip: dfs_plan): LDS (slot-major, [slot][64 lanes]: conflict-free) or this wave's block
+//     frame has a HOME chosen by the host (mh_launch_plans.h: dfs_frames): LDS (slot-major, [slot][64 lanes]: conflict-free) or this wave's block
 //     of a global slot-major workspace.  A slot number in the body's record carries its home (DFS_LDS bit).  The host fills LDS from the
 //     leaves upwards: a frame goes to LDS when it still fits on top of the deepest LDS path below it, so with a budget of 20 KB per wave
 //     (8 waves per CU) the many small subtrees near the leaves -- most of the frames, hence most of the traffic -- never leave the CU,
@@ -506,7 +506,7 @@ __global__ void __launch_bounds__(64) rnea_dfs_kernel(Args<T> A)
 // dynamics' outward sweep needs -- joint transform, velocity v, bias acceleration c = v x vJ, bias wrench p = v x* I v - f_ext
 // (ForwardDynamicsCalculator.java:1085-1127 against InverseDynamicsCalculator.java:873-917) -- so the inverse dynamics costs one more
 // motion transform (its acceleration), one product I a and, inwards, one force transform per body, and q / qd are read once.  Frames:
-// pair_frame_slots; MI_PFR_R / MI_PVA_R hold the parent's wrench / acceleration slots of the inverse dynamics (dfs_plan, algo 2).
+// pair_frame_slots; MI_PFR_R / MI_PVA_R hold the parent's wrench / acceleration slots of the inverse dynamics (dfs_frames, algo 2).
 // OCC3: a register budget for three waves per SIMD (168 VGPRs; the plain build takes 181-184 and keeps two).  The walk waits on its own
 // workspace more than it computes, so a third wave per SIMD pays where the batch has one to offer: forward dynamics at 524 288
 // configurations 3.86 -> 3.38 ms, at 1 M 7.35 -> 6.48 (profiles/r05_c5_occ.txt), for 48 bytes of scratch per lane -- which cost 2 % where

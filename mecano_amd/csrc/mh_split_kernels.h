@@ -3,7 +3,7 @@
 // A batch of a few thousand configurations puts one wave per 64 configurations on the device: 64 waves on 1024 SIMDs at B = 4096, each
 // walking all n bodies one after the other.  The topology-specialised code objects split the tree over four waves at compile time
 // (mh_spec_kernels.h, Split<TP>); these kernels do the same for ANY model from a plan the host makes when the model is created
-// (mh_api.hip: split_rt_plan): the TRUNK (bodies the split goes through: the root side of every branching that is used) and the LIMBS
+// (mh_launch_plans.h: split_rt_plan): the TRUNK (bodies the split goes through: the root side of every branching that is used) and the LIMBS
 // (whole subtrees hanging off trunk bodies; joints are stored depth-first, so a limb is a contiguous index range), dealt to the waves
 // largest first.
 //
