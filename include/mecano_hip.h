@@ -729,6 +729,45 @@ mh_status mh_constraint_impulse_f32(mh_model_t model, int64_t B, const float *q,
                                     double compliance, const mh_options *opts, float *qd_out, float *impulse_out);
 
 /*
+ * ---- the same between two moving bodies: a hand on the other hand, a tool in a hand, the closing joint of a four-bar or of a parallel
+ *      linkage (the reference's forward dynamics skips loop-closure joints) ----
+ * Arguments as mh_aba_constrained_* / mh_constraint_impulse_* with base_joints (HOST, [K]) behind target_joints: a position in the joint
+ * list names that joint's successor body, -1 the root body; NULL = the root for every target.  The constrained motion is that of target
+ * frame k relative to the body of base_joints[k], expressed in the target frame, exactly as mh_geometric_jacobian_* defines it for that
+ * base: J qdd + Jdot qd (its conv_out), respectively J qd.  The equations are those above with this J_c and c.
+ * lambda_out[k] / impulse_out[k] is the wrench on the TARGET body, at and in the target frame; the base body receives the opposite wrench
+ * at the same point: qdd_out = mh_aba_*(q, qd, tau, g, f_ext + sum_k (X_k^T lambda_k on the target body - Z_k^T lambda_k on the base
+ * body)) with X_k the constant body-to-target motion transform of pose k and Z_k the motion transform from the base's body-fixed frame
+ * to the target frame at q.  Nothing is applied for a root base.
+ * Row masks, active, a_des / v_des, compliance, the NaN rule of a bad pivot, exact zeros in rows that take no part, layouts, index maps,
+ * contexts and the aliasing rule are those of the rooted calls.  With base_joints NULL or all -1 the call is the rooted one, bit for bit.
+ * Composition: as above, with per-body twists beside the accelerations, the apparent inertia inverse for n_app = K + (non-root bases)
+ * frames -- the K target frames, then the body-fixed frame of every non-root base, at most 16 -- and a second instantiation of the
+ * constraint kernel that forms the relative right-hand side, reduces W to that of the relative motions in place and adds the base's
+ * wrench.  Scratch of the context: B * ((6 n_app)^2 + 6 K + 18 n_joints + nv + 12 K) elements, the 12 K for the poses of the target
+ * frames in their bases.  mh_reserve / mh_context_reserve keep the size of the rooted calls: a larger need is met by the first call at
+ * that batch; after one such call the entry points only enqueue work (graph-capturable).
+ * MH_ERR_INVALID_ARGUMENT: everything the rooted calls refuse; a base outside -1 ... n_joints - 1; base_joints[k] == target_joints[k]
+ * (the Jacobian would be zero).  B = 0 returns MH_OK and touches nothing.
+ */
+mh_status mh_aba_constrained_between_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
+                                         const double *f_ext, int32_t n_targets, const int32_t *target_joints, const int32_t *base_joints,
+                                         const double *target_poses, const int32_t *target_rows, const int32_t *active, const double *a_des,
+                                         double compliance, const mh_options *opts, double *qdd_out, double *lambda_out);
+mh_status mh_aba_constrained_between_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const double gravity[3],
+                                         const float *f_ext, int32_t n_targets, const int32_t *target_joints, const int32_t *base_joints,
+                                         const double *target_poses, const int32_t *target_rows, const int32_t *active, const float *a_des,
+                                         double compliance, const mh_options *opts, float *qdd_out, float *lambda_out);
+mh_status mh_constraint_impulse_between_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_targets,
+                                            const int32_t *target_joints, const int32_t *base_joints, const double *target_poses,
+                                            const int32_t *target_rows, const int32_t *active, const double *v_des, double compliance,
+                                            const mh_options *opts, double *qd_out, double *impulse_out);
+mh_status mh_constraint_impulse_between_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_targets,
+                                            const int32_t *target_joints, const int32_t *base_joints, const double *target_poses,
+                                            const int32_t *target_rows, const int32_t *active, const float *v_des, double compliance,
+                                            const mh_options *opts, float *qd_out, float *impulse_out);
+
+/*
  * ---- state integration (MultiBodySystemStateIntegrator.doubleIntegrateFromAcceleration, tools/MultiBodySystemStateIntegrator.java:365-441,
  *      503-575, 710-733): the step downstream of forward dynamics, so that a simulation loop never leaves the device ----
  * One explicit constant-acceleration step of size dt for every joint of every configuration: 1-DoF q' = q + dt qd + dt^2/2 qdd,

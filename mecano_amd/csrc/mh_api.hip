@@ -159,8 +159,9 @@ struct ContextState
    Workspace step;
    // mh_body_poses_* / mh_geometric_jacobian_*: the SoA form of AoS outputs, which a transposition then brings to the caller's rows
    Workspace kin;
-   // mh_aba_constrained_* / mh_constraint_impulse_*: W and its factor, the right-hand side, the per-body motions of the free launch, the
-   // wrenches of the second launch, a row of zeros (constraint_scratch_entries)
+   // mh_aba_constrained_* / mh_constraint_impulse_* and their _between_ forms: W and its factor, the right-hand side, the per-body motions
+   // of the free launch, the wrenches of the second launch, a row of zeros; between two moving bodies also the per-body twists and the
+   // poses of the target frames in their bases (constraint_scratch_entries)
    Workspace con;
    // bias-split forward dynamics (mh_zv_kernels.h): tau - h(q, qd) rows, one flag per 64 configurations (a launch stores its epoch there),
    // an error word in mapped host memory that a timed-out wait sets (read at the next call of the model)
@@ -1921,16 +1922,24 @@ mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int
 // twists), the COUPLED inverse apparent inertia into SoA scratch, the constraint kernel (right-hand side, L D L^T in place, lambda, the
 // wrenches of the next launch), and forward dynamics again, whichever plan mh_aba_* takes.  Scratch per configuration, in elements of the
 // call's precision: (6 K)^2 for W, 6 K for the right-hand side, 6 n_joints each for the per-body motions and the wrenches, nv zeros.
-static size_t constraint_scratch_entries(const mh_model *m, int K)
+// The _between_ entry points with n_app = K + (non-root bases) frames in W: (6 n_app)^2 + 6 K + 18 n_joints + nv + 12 K -- the per-body
+// twists and the K relative poses come on top.  mh_reserve covers the rooted form at K = MH_MAX_CONSTRAINT_TARGETS; the first call of a
+// larger need grows the buffer (ensure_bytes), after which the calls only enqueue.
+static size_t constraint_scratch_entries(const mh_model *m, int K, int n_app = 0)
 {
+   if (n_app > K)
+      return 36 * (size_t)n_app * n_app + 18 * (size_t)K + 18 * (size_t)m->n + (size_t)m->nv;
    return 36 * (size_t)K * K + 6 * (size_t)K + 12 * (size_t)m->n + (size_t)m->nv;
 }
+// between: the _between_ entry points (base_joints may still be NULL = every base the root: the rooted launches, bit for bit)
 template <typename T>
 mh_status constrained_impl(bool velocity, mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const double *gravity, const T *f_ext,
                            int32_t n_targets, const int32_t *target_joints, const double *target_poses, const int32_t *target_rows,
-                           const int32_t *active, const T *des, const double &compliance, const mh_options *opts_in, T *out, T *lambda_out)
+                           const int32_t *active, const T *des, const double &compliance, const mh_options *opts_in, T *out, T *lambda_out,
+                           bool between = false, const int32_t *base_joints = nullptr)
 {
-   const char *call = velocity ? "mh_constraint_impulse" : "mh_aba_constrained";
+   const char *call = between ? (velocity ? "mh_constraint_impulse_between" : "mh_aba_constrained_between")
+                              : (velocity ? "mh_constraint_impulse" : "mh_aba_constrained");
    // the scratch below belongs to the CONTEXT of the call: resolve it before anything mutable is touched
    mh_options o;
    mh_status st = begin_call(model, B, opts_in, o);
@@ -1946,14 +1955,24 @@ mh_status constrained_impl(bool velocity, mh_model_t model, int64_t B, const T *
       return fail(MH_ERR_INVALID_ARGUMENT, "%s: compliance must be >= 0", call);
    if (!velocity && !gravity && !o.use_root_acceleration)
       return fail(MH_ERR_INVALID_ARGUMENT, "%s: gravity is NULL and no root acceleration is set", call);
-   mh::ConArgs<T> G{};
+   mh::ConRelArgs<T> G{}; // (the rooted launch takes its ConArgs part)
    const int K = n_targets;
-   int rows_total = 0;
+   int rows_total = 0, n_app = K;
+   int32_t app_joints[MH_MAX_APPARENT_TARGETS];
+   double app_poses[MH_MAX_APPARENT_TARGETS][12];
    for (int k = 0; k < K; k++)
    {
-      const int i = target_joints[k], rk = target_rows[k];
+      const int i = target_joints[k], rk = target_rows[k], ib = base_joints ? base_joints[k] : -1;
       if (i < 0 || i >= model->n)
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d names joint %d (the model has %d joints; the root body is no target)", call, k, i, model->n);
+      if (ib < -1 || ib >= model->n)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: base %d names joint %d (the model has %d joints; -1 is the root body)", call, k, ib, model->n);
+      if (ib == i)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d is held against its own body (joint %d): the Jacobian is zero", call, k, i);
+      G.base[k] = ib < 0 ? -1 : model->engine_of[ib], G.bext[k] = ib, G.bslot[k] = -1;
+      app_joints[k] = i;
+      for (int r = 0; r < 12; r++)
+         app_poses[k][r] = target_poses ? target_poses[12 * k + r] : (r == 0 || r == 4 || r == 8 ? 1.0 : 0.0);
       if (rk < 0 || rk > 0x3f)
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: row mask 0x%x has bits beyond the six rows of a frame", call, k, (unsigned)rk);
       double off;
@@ -1969,6 +1988,17 @@ mh_status constrained_impl(bool velocity, mh_model_t model, int64_t B, const T *
    }
    if (rows_total == 0)
       return fail(MH_ERR_INVALID_ARGUMENT, "%s: no row is constrained (every entry of target_rows is 0)", call);
+   for (int k = 0; k < K; k++)
+      if (G.base[k] >= 0)
+      { // one more frame of W per non-root base: its body-fixed frame
+         G.bslot[k] = n_app;
+         app_joints[n_app] = G.bext[k];
+         for (int r = 0; r < 12; r++)
+            app_poses[n_app][r] = r == 0 || r == 4 || r == 8 ? 1.0 : 0.0;
+         n_app++;
+      }
+   const bool rel = n_app > K;
+   G.n_app = n_app;
    if (B == 0)
       return MH_OK;
    if (!q || !qd || (!velocity && !tau) || !out)
@@ -1982,11 +2012,12 @@ mh_status constrained_impl(bool velocity, mh_model_t model, int64_t B, const T *
       if ((st = check_aliasing(call, ins, 6, outs, 2)) != MH_OK)
          return st;
    }
-   st = ensure_bytes(model->con, (size_t)B * constraint_scratch_entries(model, K) * sizeof(T));
+   st = ensure_bytes(model->con, (size_t)B * constraint_scratch_entries(model, K, n_app) * sizeof(T));
    if (st != MH_OK)
       return st;
-   T *W = (T *)model->con.ptr, *rhs = W + (size_t)B * 36 * K * K, *body = rhs + (size_t)B * 6 * K, *wrench = body + (size_t)B * n6,
+   T *W = (T *)model->con.ptr, *rhs = W + (size_t)B * 36 * n_app * n_app, *body = rhs + (size_t)B * 6 * K, *wrench = body + (size_t)B * n6,
      *zeros = wrench + (size_t)B * n6;
+   T *twist = zeros + (size_t)B * nv, *zpose = twist + (size_t)B * n6; // (relative form only)
    hipStream_t stream = (hipStream_t)o.stream;
    const double no_gravity[3] = {0.0, 0.0, 0.0};
    mh_options of = o; // the launches below see the state as it is: both switches of the inverse dynamics on
@@ -1997,10 +2028,13 @@ mh_status constrained_impl(bool velocity, mh_model_t model, int64_t B, const T *
       st = launch<T>(ALGO_RNEA, model, B, q, qd, qd, no_gravity, nullptr, &of, out, body_outputs<T>(nullptr, body));
    }
    else
-      st = launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &of, out, body_outputs<T>(body, nullptr));
+      st = launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &of, out, body_outputs<T>(body, rel ? twist : nullptr));
    if (st != MH_OK)
       return st;
-   st = apparent_inertia_impl<T>(model, B, q, K, target_joints, target_poses, MH_APPARENT_BLOCKS_COUPLED, &o, W, true);
+   if (rel)
+      st = apparent_inertia_impl<T>(model, B, q, n_app, app_joints, &app_poses[0][0], MH_APPARENT_BLOCKS_COUPLED, &o, W, true);
+   else
+      st = apparent_inertia_impl<T>(model, B, q, K, target_joints, target_poses, MH_APPARENT_BLOCKS_COUPLED, &o, W, true);
    if (st != MH_OK)
       return st;
    const bool soa = o.layout == MH_LAYOUT_SOA;
@@ -2020,7 +2054,11 @@ mh_status constrained_impl(bool velocity, mh_model_t model, int64_t B, const T *
       set_root_acceleration(G, o, gravity);
    G.K = K, G.rows_total = rows_total, G.velocity = velocity;
    const int grid = (int)std::max<long>(1, std::min<long>(groups_of(B), (long)model->cu_count * 8));
-   hipLaunchKernelGGL((mh::constraint_solve_kernel<T>), dim3(grid), dim3(64), 0, stream, G);
+   G.twist = twist, G.zpose = zpose;
+   if (rel)
+      hipLaunchKernelGGL((mh::constraint_solve_kernel<T, true>), dim3(grid), dim3(64), 0, stream, G);
+   else
+      hipLaunchKernelGGL((mh::constraint_solve_kernel<T>), dim3(grid), dim3(64), 0, stream, static_cast<const mh::ConArgs<T> &>(G));
    HIP_TRY(hipGetLastError());
    if (!velocity)
       return launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, wrench, &of, out);
@@ -3731,6 +3769,38 @@ mh_status mh_aba_constrained_f32(mh_model_t model, int64_t B, const float *q, co
 {
    return constrained_impl<float>(false, model, B, q, qd, tau, gravity, f_ext, n_targets, target_joints, target_poses, target_rows, active, a_des,
                                   compliance, opts, qdd_out, lambda_out);
+}
+mh_status mh_aba_constrained_between_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
+                                         const double *f_ext, int32_t n_targets, const int32_t *target_joints, const int32_t *base_joints,
+                                         const double *target_poses, const int32_t *target_rows, const int32_t *active, const double *a_des,
+                                         double compliance, const mh_options *opts, double *qdd_out, double *lambda_out)
+{
+   return constrained_impl<double>(false, model, B, q, qd, tau, gravity, f_ext, n_targets, target_joints, target_poses, target_rows, active, a_des,
+                                   compliance, opts, qdd_out, lambda_out, true, base_joints);
+}
+mh_status mh_aba_constrained_between_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const double gravity[3],
+                                         const float *f_ext, int32_t n_targets, const int32_t *target_joints, const int32_t *base_joints,
+                                         const double *target_poses, const int32_t *target_rows, const int32_t *active, const float *a_des,
+                                         double compliance, const mh_options *opts, float *qdd_out, float *lambda_out)
+{
+   return constrained_impl<float>(false, model, B, q, qd, tau, gravity, f_ext, n_targets, target_joints, target_poses, target_rows, active, a_des,
+                                  compliance, opts, qdd_out, lambda_out, true, base_joints);
+}
+mh_status mh_constraint_impulse_between_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_targets,
+                                            const int32_t *target_joints, const int32_t *base_joints, const double *target_poses,
+                                            const int32_t *target_rows, const int32_t *active, const double *v_des, double compliance,
+                                            const mh_options *opts, double *qd_out, double *impulse_out)
+{
+   return constrained_impl<double>(true, model, B, q, qd, nullptr, nullptr, nullptr, n_targets, target_joints, target_poses, target_rows, active,
+                                   v_des, compliance, opts, qd_out, impulse_out, true, base_joints);
+}
+mh_status mh_constraint_impulse_between_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_targets,
+                                            const int32_t *target_joints, const int32_t *base_joints, const double *target_poses,
+                                            const int32_t *target_rows, const int32_t *active, const float *v_des, double compliance,
+                                            const mh_options *opts, float *qd_out, float *impulse_out)
+{
+   return constrained_impl<float>(true, model, B, q, qd, nullptr, nullptr, nullptr, n_targets, target_joints, target_poses, target_rows, active,
+                                  v_des, compliance, opts, qd_out, impulse_out, true, base_joints);
 }
 mh_status mh_constraint_impulse_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_targets, const int32_t *target_joints,
                                     const double *target_poses, const int32_t *target_rows, const int32_t *active, const double *v_des,

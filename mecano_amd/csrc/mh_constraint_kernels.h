@@ -17,6 +17,21 @@
 //      call's layout: f_ext (or 0) of every body plus X_k^T lambda_k of the targets on it (force transform of the target pose).
 // A pivot that is not positive and finite makes every output of that configuration a quiet NaN: lambda directly, the accelerations
 // through a NaN in every wrench of the row.  The test reads the pivot's bits: the translation unit is compiled with -ffinite-math-only.
+//
+// REL = true: mh_aba_constrained_between_* and mh_constraint_impulse_between_*, where target frame k is held relative to the body of
+// base[k] (the root where base[k] < 0, with the arithmetic above).  A second instantiation: the rooted one keeps its code.
+//   0. Z_k, the pose of target frame k in the body-fixed frame of its base, from two climbs to the root (body_pose_in_root); parked in
+//      scratch ([12 K][B]) for steps 2 and 4.
+//   1. acceleration form: the acceleration of the target body relative to the base body with the arithmetic of
+//      relative_acceleration_kernel, velocity terms included (per-body twists of the free launch), then the target pose; velocity form:
+//      X_k v_t - Z_k v_b.
+//   2. W arrives for n_app = K + (non-root bases) frames: the K target frames, then every non-root base's body-fixed frame.  With
+//      J_rel,k = J_t - Z_k J_b every block pair k >= l becomes, in place over W[t_k, t_l],
+//         W[t_k, t_l] - Z_k W[b_k, t_l] - W[t_k, b_l] Z_l^T + Z_k W[b_k, b_l] Z_l^T
+//      (first the columns of [W[t_k, t_l]  W[t_k, b_l]] minus Z_k times those of the base's rows, then the rows of the first minus Z_l times
+//      those of the second; W[t_k, b_l] is read by this pair alone, so it is the scratch of the first stage).  The factorisation then
+//      runs on the leading blocks with ld = 6 n_app and the same index list.
+//   4. the base body receives -Z_k^T lambda_k.
 #pragma once
 #include "mh_kernels.h"
 
@@ -30,7 +45,7 @@ struct ConArgs
 {
    DevModel m;
    long B;
-   const T *q;          // acceleration form only (the root acceleration is brought to the bodies)
+   const T *q;          // rooted targets: acceleration form only (the root acceleration is brought to the bodies)
    long q_bs, q_es;
    const T *body;       // [B][n_joints][6] with (f_bs, f_es): per-body accelerations (acceleration form) or twists (velocity form)
    const T *fext;       // caller's external wrenches with (f_bs, f_es), or NULL
@@ -53,6 +68,43 @@ struct ConArgs
    T pose[CON_MAX_TARGETS][12];  // the target frame in the body-fixed frame (R row-major, p)
 };
 
+// the relative form's additions
+template <typename T>
+struct ConRelArgs : ConArgs<T>
+{
+   const T *twist;               // acceleration form: per-body twists of the free launch, laid out as `body` (velocity form: body holds them)
+   T *zpose;                     // [12 K][B]: Z_k of the targets with a non-root base
+   int n_app;                    // frames of W: K targets, then the non-root bases
+   int base[CON_MAX_TARGETS];    // engine index of the base's body, -1 = the root body
+   int bext[CON_MAX_TARGETS];    // its joint in the caller's order
+   int bslot[CON_MAX_TARGETS];   // its frame in W (>= K), -1 = the root body
+};
+
+// pose of frame j in frame t from their poses in a common frame: x_t = R_t^T (R_j x_j + p_j - p_t)
+template <typename T>
+MH_DEV XF<T> con_relative(const XF<T> &Xt, const XF<T> &Xj)
+{
+   const M3<T> &A = Xt.R, &B = Xj.R;
+   XF<T> o;
+   o.R = M3<T>{A.xx * B.xx + A.yx * B.yx + A.zx * B.zx, A.xx * B.xy + A.yx * B.yy + A.zx * B.zy, A.xx * B.xz + A.yx * B.yz + A.zx * B.zz,
+               A.xy * B.xx + A.yy * B.yx + A.zy * B.zx, A.xy * B.xy + A.yy * B.yy + A.zy * B.zy, A.xy * B.xz + A.yy * B.yz + A.zy * B.zz,
+               A.xz * B.xx + A.yz * B.yx + A.zz * B.zx, A.xz * B.xy + A.yz * B.yy + A.zz * B.zy, A.xz * B.xz + A.yz * B.yz + A.zz * B.zz};
+   o.p = tmul(A, Xj.p - Xt.p);
+   return o;
+}
+template <typename T>
+MH_DEV XF<T> con_load_pose(const T *z, long B)
+{
+   return XF<T>{M3<T>{z[0], z[B], z[2 * B], z[3 * B], z[4 * B], z[5 * B], z[6 * B], z[7 * B], z[8 * B]}, V3<T>{z[9 * B], z[10 * B], z[11 * B]}};
+}
+// x[0 .. 5] (stride s) -= Z (x'[0 .. 5], stride s), both motion vectors
+template <typename T>
+MH_DEV void con_sub_moved(const XF<T> &Z, T *x, const T *from, long s)
+{
+   const SV<T> v = motion_to_child(Z, SV<T>{V3<T>{from[0], from[s], from[2 * s]}, V3<T>{from[3 * s], from[4 * s], from[5 * s]}});
+   x[0] -= v.a.x, x[s] -= v.a.y, x[2 * s] -= v.a.z, x[3 * s] -= v.l.x, x[4 * s] -= v.l.y, x[5 * s] -= v.l.z;
+}
+
 MH_DEV bool pivot_ok(double d)
 {
    const long long b = __double_as_longlong(d);
@@ -66,14 +118,17 @@ MH_DEV bool pivot_ok(float d)
 MH_DEV double quiet_nan(double) { return __longlong_as_double(0x7ff8000000000000ll); }
 MH_DEV float quiet_nan(float) { return __int_as_float(0x7fc00000); }
 
-template <typename T>
-__global__ void __launch_bounds__(64) constraint_solve_kernel(ConArgs<T> G)
+template <typename T, bool REL = false>
+__global__ void __launch_bounds__(64) constraint_solve_kernel(std::conditional_t<REL, ConRelArgs<T>, ConArgs<T>> G)
 {
    const DevModel &m = G.m;
    const T *CB = (const T *)m.consts;
    const ciptr meta = as_const(m.meta), cfg_map = as_const(m.cfg_map);
    const long nlanes = (long)gridDim.x * blockDim.x;
-   const long B = G.B, ld = 6L * G.K;
+   long ld = 6L * G.K;
+   if constexpr (REL)
+      ld = 6L * G.n_app;
+   const long B = G.B;
    const int K = G.K, M = G.rows_total;
 
    for (long cfg = (long)blockIdx.x * blockDim.x + threadIdx.x; cfg < B; cfg += nlanes)
@@ -89,14 +144,49 @@ __global__ void __launch_bounds__(64) constraint_solve_kernel(ConArgs<T> G)
          const long e = (long)G.ext[k] * 6;
          SV<T> v{V3<T>{brow[(e + 0) * G.f_es], brow[(e + 1) * G.f_es], brow[(e + 2) * G.f_es]},
                  V3<T>{brow[(e + 3) * G.f_es], brow[(e + 4) * G.f_es], brow[(e + 5) * G.f_es]}};
-         if (!G.velocity)
+         bool rooted = true;
+         if constexpr (REL)
+            if (G.base[k] >= 0)
+            { // ---- 0. + 1. against a moving base
+               rooted = false;
+               const T *ps = G.pose[k];
+               const XF<T> Xt{M3<T>{ps[0], ps[1], ps[2], ps[3], ps[4], ps[5], ps[6], ps[7], ps[8]}, V3<T>{ps[9], ps[10], ps[11]}};
+               const T *qrow = G.q + cfg * G.q_bs;
+               const XF<T> X_b = body_pose_in_root<T>(m, meta, cfg_map, CB, qrow, G.q_es, G.base[k]);
+               const XF<T> X12 = con_relative(body_pose_in_root<T>(m, meta, cfg_map, CB, qrow, G.q_es, G.tgt[k]), X_b); // base's frame in the target body's
+               const XF<T> Z = con_relative(X12, Xt);
+               T *z = G.zpose + 12L * k * B + cfg;
+               z[0] = Z.R.xx, z[B] = Z.R.xy, z[2 * B] = Z.R.xz, z[3 * B] = Z.R.yx, z[4 * B] = Z.R.yy, z[5 * B] = Z.R.yz;
+               z[6 * B] = Z.R.zx, z[7 * B] = Z.R.zy, z[8 * B] = Z.R.zz, z[9 * B] = Z.p.x, z[10 * B] = Z.p.y, z[11 * B] = Z.p.z;
+               const long eb = (long)G.bext[k] * 6;
+               auto load6 = [&](const T *row, long at) {
+                  return SV<T>{V3<T>{row[(at + 0) * G.f_es], row[(at + 1) * G.f_es], row[(at + 2) * G.f_es]},
+                               V3<T>{row[(at + 3) * G.f_es], row[(at + 4) * G.f_es], row[(at + 5) * G.f_es]}};
+               };
+               if (G.velocity)
+                  v = motion_to_child(Xt, v) - motion_to_child(Z, load6(brow, eb));
+               else
+               { // relative_acceleration_kernel with (b1, b2) = (base, target body)
+                  const T *trow = G.twist + cfg * G.f_bs;
+                  const SV<T> t1 = load6(trow, eb), t2 = load6(trow, e);
+                  SV<T> a1 = load6(brow, eb);
+                  const SV<T> d = t1 - motion_to_child(X12, t2);
+                  a1.l = a1.l + cross(d.l, t1.a) + cross(d.a, t1.l);
+                  a1.a = a1.a + cross(d.a, t1.a);
+                  v = motion_to_child(Xt, v - motion_to_parent(X12, a1));
+               }
+            }
+         if (rooted)
          {
-            const XF<T> Xb = body_pose_in_root<T>(m, meta, cfg_map, CB, G.q + cfg * G.q_bs, G.q_es, G.tgt[k]);
-            v = v - motion_to_child(Xb, root_acceleration(G));
+            if (!G.velocity)
+            {
+               const XF<T> Xb = body_pose_in_root<T>(m, meta, cfg_map, CB, G.q + cfg * G.q_bs, G.q_es, G.tgt[k]);
+               v = v - motion_to_child(Xb, root_acceleration(G));
+            }
+            const T *ps = G.pose[k];
+            const XF<T> Xt{M3<T>{ps[0], ps[1], ps[2], ps[3], ps[4], ps[5], ps[6], ps[7], ps[8]}, V3<T>{ps[9], ps[10], ps[11]}};
+            v = motion_to_child(Xt, v);
          }
-         const T *ps = G.pose[k];
-         const XF<T> Xt{M3<T>{ps[0], ps[1], ps[2], ps[3], ps[4], ps[5], ps[6], ps[7], ps[8]}, V3<T>{ps[9], ps[10], ps[11]}};
-         v = motion_to_child(Xt, v);
          const T free6[6] = {v.a.x, v.a.y, v.a.z, v.l.x, v.l.y, v.l.z};
 #pragma unroll
          for (int r = 0; r < 6; r++)
@@ -107,6 +197,40 @@ __global__ void __launch_bounds__(64) constraint_solve_kernel(ConArgs<T> G)
                rhs[(long)a * B] = on ? want - free6[r] : T(0);
                act |= (unsigned long long)on << a;
                a++;
+            }
+      }
+      if constexpr (REL)
+      { // ---- 2. W of the relative motions, block pair by block pair, in place over the targets' blocks.  (The six-fold loops stay
+        // rolled: unrolled, their loads in flight take the kernel from 202 to 256 + 14 registers in fp64, one wave per SIMD.)
+         const long cs = ld * B; // from one row of W to the next
+         for (int k = 0; k < K; k++)
+            for (int l = 0; l <= k; l++)
+            {
+               const int bk = G.bslot[k], bl = G.bslot[l];
+               T *Wtt = W + (6L * k * ld + 6L * l) * B;
+               T *Wtb = bl >= 0 ? W + (6L * k * ld + 6L * bl) * B : nullptr;
+               if (bk >= 0)
+               {
+                  const XF<T> Zk = con_load_pose(G.zpose + 12L * k * B + cfg, B);
+                  const T *Wbt = W + (6L * bk * ld + 6L * l) * B;
+#pragma nounroll
+                  for (int c = 0; c < 6; c++)
+                     con_sub_moved(Zk, Wtt + c * B, Wbt + c * B, cs);
+                  if (bl >= 0)
+                  {
+                     const T *Wbb = W + (6L * bk * ld + 6L * bl) * B;
+#pragma nounroll
+                     for (int c = 0; c < 6; c++)
+                        con_sub_moved(Zk, Wtb + c * B, Wbb + c * B, cs);
+                  }
+               }
+               if (bl >= 0)
+               {
+                  const XF<T> Zl = con_load_pose(G.zpose + 12L * l * B + cfg, B);
+#pragma nounroll
+                  for (int r = 0; r < 6; r++)
+                     con_sub_moved(Zl, Wtt + r * cs, Wtb + r * cs, B);
+               }
             }
       }
       // ---- 2. + 3. L D L^T of the masked system, row by row, in place; y = L^-1 b rides along
@@ -177,6 +301,13 @@ __global__ void __launch_bounds__(64) constraint_solve_kernel(ConArgs<T> G)
          T *o = wrow + (long)G.ext[k] * 6 * G.f_es; // (two targets on one body: the lane reads back its own store)
          const long es = G.f_es;
          o[0] += f.a.x, o[es] += f.a.y, o[2 * es] += f.a.z, o[3 * es] += f.l.x, o[4 * es] += f.l.y, o[5 * es] += f.l.z;
+         if constexpr (REL)
+            if (G.base[k] >= 0)
+            { // the opposite wrench at the same point, on the base body
+               const SV<T> fb = force_to_parent(con_load_pose(G.zpose + 12L * k * B + cfg, B), SV<T>{V3<T>{lam[0], lam[1], lam[2]}, V3<T>{lam[3], lam[4], lam[5]}});
+               T *ob = wrow + (long)G.bext[k] * 6 * es;
+               ob[0] -= fb.a.x, ob[es] -= fb.a.y, ob[2 * es] -= fb.a.z, ob[3 * es] -= fb.l.x, ob[4 * es] -= fb.l.y, ob[5 * es] -= fb.l.z;
+            }
       }
    }
 }

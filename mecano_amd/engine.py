@@ -682,12 +682,13 @@ class HipModel:
         return out
 
     # ------------------------------------------------------------------ dynamics under bilateral constraints on body frames
-    def _constraint_call(self, name, states, targets, rows, poses, active, des, compliance, layout, out, out_names):
+    def _constraint_call(self, name, states, targets, rows, poses, active, des, compliance, layout, out, out_names, bases=None):
         """What ``aba_constrained`` and ``constraint_impulse`` share: the target lists as host arrays, the device arguments checked, the
-        outputs made.  Returns (B, sfx, stream, host arrays to keep alive, pointers of the target arguments, active, des, outputs)."""
+        outputs made.  Returns (B, entry-point suffix, stream, host arrays to keep alive, pointers of the target arguments, outputs);
+        with ``bases`` the suffix and the pointers are those of the ``_between_`` entry points."""
         import torch
         B, dt, sfx, stream = self._device_inputs(states, layout)
-        tgt, K, _, poses = self._kinematic_targets(targets, None, poses)
+        tgt, K, bases, poses = self._kinematic_targets(targets, bases, poses)
         row_masks = np.ascontiguousarray(np.asarray(rows, dtype=np.int32).reshape(-1))
         if row_masks.shape[0] != K:
             raise _lib.MecanoHipError(2, f"rows must hold one mask per target ({K}), got {row_masks.shape[0]}")
@@ -707,11 +708,13 @@ class HipModel:
         if not float(compliance) >= 0.0:
             raise _lib.MecanoHipError(1, "compliance must be >= 0")
         ptr = lambda t: None if t is None else t.data_ptr()
-        args = (K, tgt.ctypes.data, None if poses is None else poses.ctypes.data, row_masks.ctypes.data, ptr(active), ptr(des), float(compliance))
-        return B, sfx, stream, (tgt, poses, row_masks), args, first, lam
+        args = (None if poses is None else poses.ctypes.data, row_masks.ctypes.data, ptr(active), ptr(des), float(compliance))
+        if bases is None:
+            return B, sfx, stream, (tgt, poses, row_masks), (K, tgt.ctypes.data) + args, first, lam
+        return B, "between_" + sfx, stream, (tgt, bases, poses, row_masks), (K, tgt.ctypes.data, bases.ctypes.data) + args, first, lam
 
     def aba_constrained(self, q, qd, tau, targets, rows, poses=None, active=None, a_des=None, compliance=0.0, gravity=(0.0, 0.0, -9.81),
-                        f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
+                        f_ext=None, layout=_lib.LAYOUT_AOS, out=None, bases=None):
         """Forward dynamics while frames fixed in bodies are held: (qdd [B, nv], lam [B, K, 6]) with
         H qdd + h = tau + J_c^T lam and J_c qdd + c + compliance lam = a_des, J_c the constrained rows of ``geometric_jacobian`` with every
         base at the root and c those of its convective term.  ``targets``: 1 to 8 positions in the joint list (the joint's successor
@@ -721,9 +724,11 @@ class HipModel:
         ``a_des`` [B, K, 6] (None: zeros).  lam is the wrench (moment, force) the constraint applies to the target's body, at and in the
         target frame; rows that take no part hold 0.  SoA: [nv, B], [6 K, B], active [K, B].  ``gravity`` as for ``aba``.  A singular
         system (compliance = 0 and dependent rows) gives NaN in that configuration only.  ``out``: a (qdd, lam) pair to write into; lam
-        may be None."""
+        may be None.  ``bases`` (None: every frame is held relative to the root body): one position in the joint list per target, -1 =
+        the root body; target k is then held relative to that body -- J_c and c those of ``geometric_jacobian`` with these bases -- and
+        the base body receives the opposite of lam[k] at the same point (a hand on the other hand, the closing joint of a four-bar)."""
         B, sfx, stream, keep, args, qdd, lam = self._constraint_call("a_des", [q, qd, tau], targets, rows, poses, active, a_des, compliance, layout,
-                                                                     out, ("qdd", "lambda"))
+                                                                     out, ("qdd", "lambda"), bases)
         if f_ext is not None:
             self._device_tensor(f_ext, q.dtype)
         self._check_f_ext(f_ext, B, layout)
@@ -734,12 +739,13 @@ class HipModel:
             qdd.data_ptr(), None if lam is None else lam.data_ptr()))
         return qdd, lam
 
-    def constraint_impulse(self, q, qd, targets, rows, poses=None, active=None, v_des=None, compliance=0.0, layout=_lib.LAYOUT_AOS, out=None):
+    def constraint_impulse(self, q, qd, targets, rows, poses=None, active=None, v_des=None, compliance=0.0, layout=_lib.LAYOUT_AOS, out=None,
+                           bases=None):
         """The velocity after frames fixed in bodies are stopped: (qd_next [B, nv], impulse [B, K, 6]) with qd_next = qd + H^-1 J_c^T impulse
         and J_c qd_next + compliance impulse = v_des (None: zeros; restitution is the caller's choice of v_des).  Arguments as for
         ``aba_constrained``."""
         B, sfx, stream, keep, args, qd_next, imp = self._constraint_call("v_des", [q, qd], targets, rows, poses, active, v_des, compliance, layout,
-                                                                         out, ("qd_next", "impulse"))
+                                                                         out, ("qd_next", "impulse"), bases)
         opts = self._options(layout, stream=stream)
         _lib.check(getattr(_lib.load(), f"mh_constraint_impulse_{sfx}")(
             self._h, B, q.data_ptr(), qd.data_ptr(), *args, ctypes.byref(opts), qd_next.data_ptr(), None if imp is None else imp.data_ptr()))
