@@ -675,7 +675,8 @@ mh_status mh_aba_parameters_f32(mh_model_t model, int64_t B, const float *q, con
  *      apparent inertias: MultiBodyResponseCalculator's applyRigidBodyWrench / propagateImpulse are the pieces, the reference has no
  *      calculator that solves for the wrench; algorithms/MultiBodyResponseCalculator.java:39-41, 608-627, 640, 836) ----
  * "How does the robot accelerate while these frames are held", "what is its velocity after these frames are stopped": the equality-
- * constrained solve underneath every contact method.  Inequalities, friction cones and complementarity stay with the caller.
+ * constrained solve underneath every contact method.  Inequalities and friction cones of point contacts: mh_contact_impulse_* below;
+ * other inequalities and complementarity conditions stay with the caller.
  * Targets: n_targets K = 1 ... MH_MAX_CONSTRAINT_TARGETS; target_joints (HOST, [K]) and target_poses (HOST, [K][12] or NULL = identity)
  * exactly as in mh_apparent_inertia_inverse_*: a position names that joint's successor body, duplicates are allowed, the pose is
  * relative to the body-fixed frame, R must be a rotation to 1e-9, the root body is no target.
@@ -766,6 +767,60 @@ mh_status mh_constraint_impulse_between_f32(mh_model_t model, int64_t B, const f
                                             const int32_t *target_joints, const int32_t *base_joints, const double *target_poses,
                                             const int32_t *target_rows, const int32_t *active, const float *v_des, double compliance,
                                             const mh_options *opts, float *qd_out, float *impulse_out);
+
+/*
+ * ---- frictional point contacts: the inequality-constrained twin of mh_constraint_impulse_* -- a foot that can lift off, press or slide ----
+ * K = 1 ... MH_MAX_CONTACT_TARGETS contact points; target_joints and target_poses (HOST) exactly as in mh_constraint_impulse_*.  The
+ * contact point is the origin of the target frame.  Per configuration, with
+ *    u_k      linear velocity of target frame k relative to the root body, in the target frame (rows 3-5 of J qd of
+ *             mh_geometric_jacobian_* with every base at the root),
+ *    lambda_k the impulse on the target body at that point, in the target frame,
+ *    n_k      the unit contact normal: given per configuration in the ROOT BODY frame, pointing from the obstacle into the robot,
+ *             normalised on input and brought into the target frame, n_k = R_pose^T R_body(q)^T n^_k,
+ *    mu_k >= 0 the friction coefficient, v_k the least normal velocity after the impulse (Baumgarte and restitution terms are the
+ *             caller's choice of v_k), eps >= 0 the compliance,
+ * the call returns the unique minimiser of the cone-constrained convex problem (Anitescu's time-stepping relaxation, the model MuJoCo uses)
+ *    minimise 1/2 lambda^T (S + eps I) lambda + lambda^T b   subject to   n_k.lambda_k >= 0,  |lambda_k - (n_k.lambda_k) n_k| <= mu_k n_k.lambda_k
+ *    b_k = u_k(qd) - v_k n_k,        qd_out = qd + H^-1 J_c^T lambda,
+ * S the symmetrised 3 K x 3 K linear part of W = J H^-1 J^T (mh_apparent_inertia_inverse_*, COUPLED): block (k, l) with l < k as computed,
+ * its transpose for (l, k), the lower triangle of a diagonal block mirrored.  At mu = 0 this is the exact frictionless complementarity
+ * solution 0 <= n.lambda  _|_  n.u+ - v + eps n.lambda >= 0.  A contact whose stick solution lies inside its cone sticks exactly.  A sliding
+ * contact has |lambda_t| = mu lambda_n, opposed to its tangential velocity; the relaxation's known artefact is that a sliding contact
+ * also lifts off along the normal, at mu times its sliding speed.
+ * The iteration: lambda^0 = the linear rows of impulse_init (NULL = zeros), each projected onto its cone (a stale warm start is safe);
+ * then n_iterations projected block Gauss-Seidel sweeps, k = 0 ... K - 1 in list order with the newest lambda, closed contacts only,
+ *    u = b_k + sum_l S_kl lambda_l + eps lambda_k,    rho_k = 1 / (trace S_kk + eps),    lambda_k = Pi_k(lambda_k - rho_k u)
+ * (rho_k <= 1 / lambda_max: each block step descends the objective).  Pi_k(x) is the Euclidean projection onto the cone: with s = n.x,
+ * t = x - s n, r = |t|: x if r <= mu s; 0 if mu r <= -s; otherwise s' n + (mu s' / r) t with s' = (s + mu r) / (1 + mu^2) -- nonexpansive,
+ * with no discontinuous branch.  The caller chooses n_iterations (1 ... MH_MAX_CONTACT_ITERATIONS) and reads residual_out.
+ * mu (HOST, [K]).  normals (DEVICE) [B][K][3] (MH_LAYOUT_SOA: [3 K][B]; NULL = (0, 0, 1)).  active (DEVICE int32) [B][K] (SoA [K][B];
+ * nonzero = contact k is closed in this configuration; NULL = all): an open contact keeps lambda = 0 exactly.  v_normal (DEVICE) [B][K]
+ * (SoA [K][B]; NULL = zeros).  impulse_init (DEVICE): the shape of impulse_out; it may be impulse_out itself (in-place warm start).
+ * qd_out [B][nv]: qd plus the forward dynamics at rest, without gravity, with sum_k X_k^T impulse_k as the only wrenches; entries no joint
+ * owns hold those of qd.  impulse_out [B][K][6] (SoA [6 K][B]; may be NULL): the wrench on the target body at and in the target frame;
+ * rows 0-2 and every row of an open contact hold exactly 0.0.  residual_out [B] (may be NULL): the largest |change of an impulse
+ * component| in the last sweep.
+ * A configuration gets quiet NaN in all of its outputs when trace S_kk + eps of a closed contact is not positive and finite, or when the
+ * norm of the n^ of a closed contact is not positive and finite; no other configuration changes and no error is raised.
+ * Launches composed on opts->stream as for mh_constraint_impulse_*, with the contact solve (one lane per configuration, S in LDS while
+ * it fits, otherwise streamed from scratch: the same bits either way) in the place of the factorisation.  Scratch of the context:
+ * B * ((6 K)^2 + 6 K + 12 n_joints + nv) elements, which mh_reserve / mh_context_reserve cover; after reserve and one first call the entry
+ * point only enqueues work (graph-capturable).  MH_ERR_INVALID_ARGUMENT, outputs untouched: NULL q / qd / qd_out / target_joints / mu;
+ * K outside 1 ... MH_MAX_CONTACT_TARGETS; a joint outside 0 ... n_joints - 1; a pose that is no rotation; a mu that is negative or not
+ * finite; a negative or NaN compliance; n_iterations outside 1 ... MH_MAX_CONTACT_ITERATIONS; MH_ACCELERATION_SOURCE joints in the model;
+ * any overlap of an output with an input or another output, except impulse_out == impulse_init exactly.  B = 0 returns MH_OK and
+ * touches nothing.  Index maps, MH_LAYOUT_SOA and contexts are honoured as everywhere else.
+ */
+#define MH_MAX_CONTACT_TARGETS 8
+#define MH_MAX_CONTACT_ITERATIONS 4096
+mh_status mh_contact_impulse_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_targets, const int32_t *target_joints,
+                                 const double *target_poses, const double *mu, const double *normals, const int32_t *active, const double *v_normal,
+                                 const double *impulse_init, double compliance, int32_t n_iterations, const mh_options *opts, double *qd_out,
+                                 double *impulse_out, double *residual_out);
+mh_status mh_contact_impulse_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_targets, const int32_t *target_joints,
+                                 const double *target_poses, const double *mu, const float *normals, const int32_t *active, const float *v_normal,
+                                 const float *impulse_init, double compliance, int32_t n_iterations, const mh_options *opts, float *qd_out,
+                                 float *impulse_out, float *residual_out);
 
 /*
  * ---- state integration (MultiBodySystemStateIntegrator.doubleIntegrateFromAcceleration, tools/MultiBodySystemStateIntegrator.java:365-441,

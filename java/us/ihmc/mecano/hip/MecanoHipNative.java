@@ -217,6 +217,21 @@ public final class MecanoHipNative
    static final MethodHandle MASS_MATRIX_INVERSE = handle("mh_mass_matrix_inverse_f64", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
    /** the same in fp32 (float q / Hinv_out on the device) */
    static final MethodHandle MASS_MATRIX_INVERSE_F32 = handle("mh_mass_matrix_inverse_f32", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS));
+   /** mh_contact_impulse_*: at most this many contact points and sweeps per call */
+   static final int MAX_CONTACT_TARGETS = 8, MAX_CONTACT_ITERATIONS = 4096;
+   /**
+    * The velocity after frictional point contacts have acted, for B configurations: (model, B, q, qd, n_targets, target_joints (host int[]),
+    * target_poses (host double[n_targets][12])|NULL, mu (host double[n_targets]), normals|NULL, active|NULL, v_normal|NULL, impulse_init|NULL,
+    * compliance, n_iterations, opts|NULL, qd_out, impulse_out|NULL, residual_out|NULL); normals [B][n_targets][3] in the root body frame,
+    * active (int) and v_normal [B][n_targets], impulse_init / impulse_out [B][n_targets][6], residual_out [B].
+    */
+   static final MethodHandle CONTACT_IMPULSE = handle("mh_contact_impulse_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
+                                                                                       ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_DOUBLE, JAVA_INT, ADDRESS, ADDRESS,
+                                                                                       ADDRESS, ADDRESS));
+   /** the same in fp32 (float state, normals, v_normal and impulses on the device; poses, mu and the compliance stay double) */
+   static final MethodHandle CONTACT_IMPULSE_F32 = handle("mh_contact_impulse_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
+                                                                                           ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_DOUBLE, JAVA_INT, ADDRESS, ADDRESS,
+                                                                                           ADDRESS, ADDRESS));
    /** (model, B, dt, q, qd, qdd, opts, q_out, qd_out, qdd_out|NULL) */
    static final MethodHandle INTEGRATE = handle("mh_integrate_f64", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                            ADDRESS));

@@ -15,6 +15,7 @@
 #include "mh_params_kernels.h"
 #include "mh_step_kernels.h"
 #include "mh_constraint_kernels.h"
+#include "mh_contact_kernels.h"
 #include "mh_model_tables.h"
 #include "mh_launch_plans.h"
 
@@ -2075,6 +2076,114 @@ mh_status constrained_impl(bool velocity, mh_model_t model, int64_t B, const T *
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
+// Frictional contact impulses (mh_contact_kernels.h): the composition of the velocity form above with the contact solve between the
+// launches.  Scratch as the rooted form's: the 6 K rows behind W hold b and the normals in the target frames.
+template <typename T>
+mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
+                       const double *mu, const T *normals, const int32_t *active, const T *v_normal, const T *impulse_init, const double &compliance,
+                       int32_t n_iterations, const mh_options *opts_in, T *out, T *impulse_out, T *residual_out)
+{
+   const char *call = "mh_contact_impulse";
+   mh_options o;
+   mh_status st = begin_call(model, B, opts_in, o);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: %d joint(s) are acceleration sources: the contact dynamics take none", call, model->n_locked);
+   if (n_targets < 1 || n_targets > MH_MAX_CONTACT_TARGETS)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: n_targets = %d is outside 1 ... %d", call, n_targets, MH_MAX_CONTACT_TARGETS);
+   if (!target_joints || !mu)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: target_joints / mu is NULL", call);
+   if (!(compliance >= 0.0)) // (a NaN fails too)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: compliance must be >= 0", call);
+   if (n_iterations < 1 || n_iterations > MH_MAX_CONTACT_ITERATIONS)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: n_iterations = %d is outside 1 ... %d", call, n_iterations, MH_MAX_CONTACT_ITERATIONS);
+   mh::ContactArgs<T> G{};
+   const int K = n_targets;
+   for (int k = 0; k < K; k++)
+   {
+      const int i = target_joints[k];
+      if (i < 0 || i >= model->n)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d names joint %d (the model has %d joints; the root body is no target)", call, k, i, model->n);
+      uint64_t mu_bits; // (read as bits: the translation unit is compiled with -ffinite-math-only)
+      std::memcpy(&mu_bits, &mu[k], sizeof mu_bits);
+      if (mu_bits >= 0x7ff0000000000000ull && mu_bits != 0x8000000000000000ull) // infinite, NaN or negative
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the friction coefficient must be finite and >= 0", call, k);
+      double off;
+      T canonical[12];
+      if (!target_frame<T>(model, model->engine_of[i], target_poses ? target_poses + 12 * k : nullptr, canonical, off))
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", call, k, off);
+      G.tgt[k] = model->engine_of[i], G.ext[k] = i, G.mu[k] = (T)mu[k];
+      for (int r = 0; r < 12; r++)
+         G.pose[k][r] = target_poses ? (T)target_poses[12 * k + r] : (T)(r == 0 || r == 4 || r == 8 ? 1 : 0);
+   }
+   if (B == 0)
+      return MH_OK;
+   if (!q || !qd || !out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: NULL state / output pointer", call);
+   const size_t n6 = (size_t)model->n * 6, nv = (size_t)model->nv;
+   {
+      const size_t bv = (size_t)B * nv * sizeof(T), bk = (size_t)B * K * sizeof(T), bd = 6 * bk;
+      const InRange ins[6] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"qd", qd, bv}, {"normals", normals, 3 * bk},
+                              {"active", active, (size_t)B * K * sizeof(int32_t)}, {"v_normal", v_normal, bk}, {"impulse_init", impulse_init, bd}};
+      const OutRange outs[3] = {{"qd_out", out, bv, 0u}, {"impulse_out", impulse_out, bd, 1u << 5}, {"residual_out", residual_out, (size_t)B * sizeof(T), 0u}};
+      if ((st = check_aliasing(call, ins, 6, outs, 3)) != MH_OK)
+         return st;
+   }
+   st = ensure_bytes(model->con, (size_t)B * constraint_scratch_entries(model, K) * sizeof(T));
+   if (st != MH_OK)
+      return st;
+   const ContactPlan P = contact_plan(K, sizeof(T), model->contact_path, model->cu_count, B);
+   const void *kern;
+   if (P.kmax == 4)
+      kern = P.resident ? (const void *)&mh::contact_solve_kernel<T, true, 4> : (const void *)&mh::contact_solve_kernel<T, false, 4>;
+   else
+      kern = P.resident ? (const void *)&mh::contact_solve_kernel<T, true, 8> : (const void *)&mh::contact_solve_kernel<T, false, 8>;
+   if ((st = raise_lds_limit(model, kern, (size_t)P.lds)) != MH_OK)
+      return st;
+   T *W = (T *)model->con.ptr, *rhs = W + (size_t)B * 36 * K * K, *body = rhs + (size_t)B * 6 * K, *wrench = body + (size_t)B * n6, *zeros = wrench + (size_t)B * n6;
+   hipStream_t stream = (hipStream_t)o.stream;
+   const double no_gravity[3] = {0.0, 0.0, 0.0};
+   mh_options of = o;
+   of.consider_coriolis = 1, of.consider_accelerations = 1, of.use_root_acceleration = 0;
+   // per-body twists of (q, qd): the inverse dynamics' outward sweep (its efforts go to qd_out, which the last launches overwrite)
+   st = launch<T>(ALGO_RNEA, model, B, q, qd, qd, no_gravity, nullptr, &of, out, body_outputs<T>(nullptr, body));
+   if (st != MH_OK)
+      return st;
+   st = apparent_inertia_impl<T>(model, B, q, K, target_joints, target_poses, MH_APPARENT_BLOCKS_COUPLED, &o, W, true);
+   if (st != MH_OK)
+      return st;
+   const bool soa = o.layout == MH_LAYOUT_SOA;
+   G.m = dev_model<T>(model);
+   G.B = B;
+   G.q = q;
+   set_strides(G.q_bs, G.q_es, soa, B, model->nq);
+   G.body = body, G.wrench = wrench;
+   set_strides(G.f_bs, G.f_es, soa, B, (long)n6);
+   G.W = W, G.bvec = rhs, G.nvec = rhs + (size_t)B * 3 * K;
+   G.active = active, G.v_normal = v_normal;
+   set_strides(G.a_bs, G.a_es, soa, B, K);
+   G.normals = normals;
+   set_strides(G.n_bs, G.n_es, soa, B, 3L * K);
+   G.init = impulse_init, G.impulse = impulse_out;
+   set_strides(G.d_bs, G.d_es, soa, B, 6L * K);
+   G.residual = residual_out;
+   G.eps = (T)compliance;
+   G.K = K, G.n_iter = n_iterations;
+   void *args[] = {(void *)&G};
+   HIP_TRY(hipLaunchKernel(kern, dim3(P.grid), dim3(64), args, (size_t)P.lds, stream));
+   // the change of velocity: forward dynamics at rest, without gravity, with the impulses as the only wrenches; then qd_out += qd
+   HIP_TRY(hipMemsetAsync(zeros, 0, (size_t)B * nv * sizeof(T), stream));
+   HIP_TRY(hipMemsetAsync(out, 0, (size_t)B * nv * sizeof(T), stream));
+   st = launch<T>(ALGO_ABA, model, B, q, zeros, zeros, no_gravity, wrench, &of, out);
+   if (st != MH_OK || nv == 0)
+      return st;
+   const long n_out = (long)B * (long)nv;
+   hipLaunchKernelGGL((mh::add_in_place_kernel<T>), dim3((int)std::min<long>((n_out + 255) / 256, (long)model->cu_count * 8)), dim3(256), 0, stream, out,
+                      qd, n_out);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
 // Inverse of the joint-space inertia matrix, all columns or a list of them: run-time-topology kernel, which writes every entry of its
 // output -- no memset in front of it.  The listed columns travel as kernel arguments (resolved here to joint and place); the call
 // uploads nothing and allocates nothing beyond the workspace mh_reserve covers.
@@ -2644,6 +2753,14 @@ mh_status mh_internal_launch_plan(const mh_model_desc *desc, const char *plan, c
          const SplitShape s = split_rt_shape(S.slots, lds_slots, (int)params[0], (size_t)params[1], (Algo)params[2], params[3], params[4] != 0);
          w = {s.k, s.mode, (int)s.lds, s.grid};
       }
+   }
+   else if (name == "contact_solve")
+   { // (K, bytes per element, force, CUs, batch)
+      if (!takes(5) || params[0] < 1 || params[0] > MH_MAX_CONTACT_TARGETS || !among(1, {4, 8}) || !among(2, {-1, 0, 1}) || params[3] < 1
+          || params[3] > (1 << 20) || params[4] < 0)
+         return fail(MH_ERR_INVALID_ARGUMENT, bad, plan);
+      const ContactPlan c = contact_plan((int)params[0], (size_t)params[1], (int)params[2], (int)params[3], params[4]);
+      w = {c.resident, (int)c.lds, c.per_cu, c.grid, c.kmax};
    }
    else if (name == "lane_ws")
    {
@@ -3827,6 +3944,31 @@ mh_status mh_aba_derivatives_f32(mh_model_t model, int64_t B, const float *q, co
                                  float *Hinv_out)
 {
    return aba_derivatives_impl<float>(model, B, q, qd, tau, gravity, f_ext, opts, qdd_out, dqdd_dq_out, dqdd_dqd_out, Hinv_out);
+}
+mh_status mh_contact_impulse_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_targets, const int32_t *target_joints,
+                                 const double *target_poses, const double *mu, const double *normals, const int32_t *active, const double *v_normal,
+                                 const double *impulse_init, double compliance, int32_t n_iterations, const mh_options *opts, double *qd_out,
+                                 double *impulse_out, double *residual_out)
+{
+   return contact_impl<double>(model, B, q, qd, n_targets, target_joints, target_poses, mu, normals, active, v_normal, impulse_init, compliance,
+                               n_iterations, opts, qd_out, impulse_out, residual_out);
+}
+mh_status mh_contact_impulse_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_targets, const int32_t *target_joints,
+                                 const double *target_poses, const double *mu, const float *normals, const int32_t *active, const float *v_normal,
+                                 const float *impulse_init, double compliance, int32_t n_iterations, const mh_options *opts, float *qd_out,
+                                 float *impulse_out, float *residual_out)
+{
+   return contact_impl<float>(model, B, q, qd, n_targets, target_joints, target_poses, mu, normals, active, v_normal, impulse_init, compliance,
+                              n_iterations, opts, qd_out, impulse_out, residual_out);
+}
+// not in include/mecano_hip.h: where the contact solve of this model (or context) reads S from now on -- -1 = contact_plan chooses,
+// 0 = streamed, 1 = LDS-resident where it fits (tests/test_gpu_contact_dynamics.py holds the two to the same bits)
+mh_status mh_internal_contact_path(mh_model_t model, int32_t path)
+{
+   if (!model || path < -1 || path > 1)
+      return fail(MH_ERR_INVALID_ARGUMENT, "mh_internal_contact_path: model is NULL, or path is outside -1 ... 1");
+   model->contact_path = path;
+   return MH_OK;
 }
 mh_status mh_configuration_add_f64(mh_model_t model, int64_t B, const double *q, const double *dq, const mh_options *opts, double *q_out)
 {

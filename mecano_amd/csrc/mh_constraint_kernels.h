@@ -105,6 +105,16 @@ MH_DEV void con_sub_moved(const XF<T> &Z, T *x, const T *from, long s)
    x[0] -= v.a.x, x[s] -= v.a.y, x[2 * s] -= v.a.z, x[3 * s] -= v.l.x, x[4 * s] -= v.l.y, x[5 * s] -= v.l.z;
 }
 
+// wrench row of joint `ext` (entries es apart) += X^T lam: lam acts at and in the frame at `ps` (R row-major, p) of that joint's body
+template <typename T>
+MH_DEV void con_add_wrench(T *wrow, int ext, long es, const T *ps, const SV<T> &lam)
+{
+   const XF<T> Xt{M3<T>{ps[0], ps[1], ps[2], ps[3], ps[4], ps[5], ps[6], ps[7], ps[8]}, V3<T>{ps[9], ps[10], ps[11]}};
+   const SV<T> f = force_to_parent(Xt, lam);
+   T *o = wrow + (long)ext * 6 * es; // (two targets on one body: the lane reads back its own store)
+   o[0] += f.a.x, o[es] += f.a.y, o[2 * es] += f.a.z, o[3 * es] += f.l.x, o[4 * es] += f.l.y, o[5 * es] += f.l.z;
+}
+
 MH_DEV bool pivot_ok(double d)
 {
    const long long b = __double_as_longlong(d);
@@ -295,12 +305,8 @@ __global__ void __launch_bounds__(64) constraint_solve_kernel(std::conditional_t
             if (G.lambda)
                G.lambda[cfg * G.d_bs + (6L * k + r) * G.d_es] = lam[r];
          }
-         const T *ps = G.pose[k];
-         const XF<T> Xt{M3<T>{ps[0], ps[1], ps[2], ps[3], ps[4], ps[5], ps[6], ps[7], ps[8]}, V3<T>{ps[9], ps[10], ps[11]}};
-         const SV<T> f = force_to_parent(Xt, SV<T>{V3<T>{lam[0], lam[1], lam[2]}, V3<T>{lam[3], lam[4], lam[5]}});
-         T *o = wrow + (long)G.ext[k] * 6 * G.f_es; // (two targets on one body: the lane reads back its own store)
          const long es = G.f_es;
-         o[0] += f.a.x, o[es] += f.a.y, o[2 * es] += f.a.z, o[3 * es] += f.l.x, o[4 * es] += f.l.y, o[5 * es] += f.l.z;
+         con_add_wrench(wrow, G.ext[k], es, G.pose[k], SV<T>{V3<T>{lam[0], lam[1], lam[2]}, V3<T>{lam[3], lam[4], lam[5]}});
          if constexpr (REL)
             if (G.base[k] >= 0)
             { // the opposite wrench at the same point, on the base body

@@ -43,6 +43,7 @@ struct Switches
    int use_zvf_pair = 1;  // MH_ZVF_PAIR=0: the pair call of device-filling batches as two launches (A/B measurements)
    int zv_same_l2 = 0;    // MH_ZV_SAME_L2=1 (experiment, off by default; one-stage hand-off only: the two-stage form of identity index maps is write-through): bias rows and flag of a group whose two jobs prove to sit behind the same L2
                           // stay in that L2 (workgroup-scope stores) -- cache behaviour the memory model does not promise, for no measured gain
+   int contact_path = -1; // no variable of the environment: mh_internal_contact_path (tests, measurements) forces the streamed (0) or the LDS-resident (1) contact solve
    unsigned zv_wait_ticks = 200000000u; // MH_ZV_WAIT_MS: how long an inertia job waits for its bias rows (100 MHz ticks; default 2 s)
 };
 
@@ -566,5 +567,28 @@ SplitShape split_rt_shape(int slots, const int lds_slots[3], int cu_count, size_
    s.mode = lds_slots[k] >= slots ? 0 : (lds_slots[k] == 0 ? 1 : 2);
    s.lds = s.mode == 1 ? 0 : (size_t)std::min(slots, lds_slots[k] + mh::SPLIT_LDS_MARGIN) * 64 * elem;
    return s;
+}
+
+// ---- frictional contact solve (mh_contact_kernels.h): where the sweeps read S.  The lower block triangle of S is 9 K (K + 1) / 2 entries
+// per lane; a wave (one workgroup) keeps it in LDS while that fits the 160 KB of a CU -- 46 KB at K = 4 in fp64, 83 KB at K = 8 in fp32;
+// 166 KB at K = 8 in fp64 do not -- and otherwise streams it from W in the SoA scratch.  force: -1 = choose, 0 = stream, 1 = resident
+// where it fits (tests and measurements: both forms give the same bits).  The grid: the waves of the batch, capped at what is resident per
+// CU -- the kernel's registers allow two waves per SIMD, the LDS copy floor(160 KB / bytes) workgroups.
+struct ContactPlan
+{
+   bool resident;
+   long lds;
+   int per_cu, grid, kmax;
+};
+ContactPlan contact_plan(int K, size_t elem, int force, int cu_count, int64_t B)
+{
+   ContactPlan p{};
+   const long bytes = 9L * K * (K + 1) / 2 * 64 * (long)elem;
+   p.resident = force != 0 && bytes <= 160 * 1024;
+   p.lds = p.resident ? bytes : 0;
+   p.per_cu = p.resident ? (int)std::max<long>(1, std::min<long>(kWavesPerCu, 160 * 1024 / bytes)) : kWavesPerCu;
+   p.grid = (int)std::max<long>(1, std::min<long>(groups_of(B), (long)cu_count * p.per_cu));
+   p.kmax = K <= 4 ? 4 : 8; // the kernel build: contacts the unrolled loops cover
+   return p;
 }
 } // namespace

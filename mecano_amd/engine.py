@@ -751,6 +751,42 @@ class HipModel:
             self._h, B, q.data_ptr(), qd.data_ptr(), *args, ctypes.byref(opts), qd_next.data_ptr(), None if imp is None else imp.data_ptr()))
         return qd_next, imp
 
+    def contact_impulse(self, q, qd, targets, mu, poses=None, normals=None, active=None, v_normal=None, compliance=0.0, iterations=50, init=None,
+                        layout=_lib.LAYOUT_AOS, out=None):
+        """The velocity after frictional point contacts have acted: (qd_next [B, nv], impulse [B, K, 6], residual [B]).  The contact points
+        are the origins of the target frames (``targets``, ``poses`` as for ``constraint_impulse``, 1 to 8 of them); ``mu`` one friction
+        coefficient per target; ``normals`` [B, K, 3] the contact normals in the root body frame, pointing from the obstacle into the robot
+        (None: (0, 0, 1)); ``active`` (int32 [B, K], None = all) which contacts are closed; ``v_normal`` [B, K] the least normal velocity
+        after the impulse (None: zeros).  The impulses minimise 1/2 lam^T (S + compliance I) lam + lam^T b over the friction cones
+        (include/mecano_hip.h, mh_contact_impulse_*) by ``iterations`` projected Gauss-Seidel sweeps from ``init`` (an impulse of an earlier
+        call, None: zeros; it may be the impulse output itself); residual is the largest change of an impulse component in the last sweep.
+        impulse[:, k] is the wrench on the target's body at and in the target frame: rows 0-2 and open contacts hold 0.  SoA: [nv, B],
+        [6 K, B], [B]; normals [3 K, B], active and v_normal [K, B].  ``out``: a (qd_next, impulse, residual) triple to write into; the
+        last two may be None."""
+        import torch
+        B, dt, sfx, stream = self._device_inputs([q, qd], layout)
+        tgt, K, _, poses = self._kinematic_targets(targets, None, poses)
+        mus = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1))
+        if mus.shape[0] != K:
+            raise _lib.MecanoHipError(2, f"mu must hold one coefficient per target ({K}), got {mus.shape[0]}")
+        aos = layout == _lib.LAYOUT_AOS
+        wrench_shape = (B, K, 6) if aos else (6 * K, B)
+        for name, t, tdt, shape in (("normals", normals, dt, (B, K, 3) if aos else (3 * K, B)), ("active", active, torch.int32, (B, K) if aos else (K, B)),
+                                    ("v_normal", v_normal, dt, (B, K) if aos else (K, B)), ("init", init, dt, wrench_shape)):
+            if t is not None:
+                self._device_tensor(t, tdt)
+                if tuple(t.shape) != shape:
+                    raise _lib.MecanoHipError(2, f"{name} has shape {tuple(t.shape)}, expected {shape}")
+        qd_next, imp, res = self._outputs(out, ((B, self.nv) if aos else (self.nv, B), wrench_shape, (B,)), ("qd_next", "impulse", "residual"), dt, q.device)
+        if qd_next is None:
+            raise _lib.MecanoHipError(1, "the qd_next output is None")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        opts = self._options(layout, stream=stream)
+        _lib.check(getattr(_lib.load(), f"mh_contact_impulse_{sfx}")(
+            self._h, B, q.data_ptr(), qd.data_ptr(), K, tgt.ctypes.data, None if poses is None else poses.ctypes.data, mus.ctypes.data, ptr(normals),
+            ptr(active), ptr(v_normal), ptr(init), float(compliance), int(iterations), ctypes.byref(opts), qd_next.data_ptr(), ptr(imp), ptr(res)))
+        return qd_next, imp, res
+
     def rnea_derivatives(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, consider_coriolis=True,
                          consider_accelerations=True, out=None):
         """Inverse dynamics and its first-order derivatives at a moving state, one analytic launch: (tau [B, nv], dtau_dq [B, nv, nv],
