@@ -792,7 +792,9 @@ mh_status mh_constraint_impulse_between_f32(mh_model_t model, int64_t B, const f
  *    u = b_k + sum_l S_kl lambda_l + eps lambda_k,    rho_k = 1 / (trace S_kk + eps),    lambda_k = Pi_k(lambda_k - rho_k u)
  * (rho_k <= 1 / lambda_max: each block step descends the objective).  Pi_k(x) is the Euclidean projection onto the cone: with s = n.x,
  * t = x - s n, r = |t|: x if r <= mu s; 0 if mu r <= -s; otherwise s' n + (mu s' / r) t with s' = (s + mu r) / (1 + mu^2) -- nonexpansive,
- * with no discontinuous branch.  The caller chooses n_iterations (1 ... MH_MAX_CONTACT_ITERATIONS) and reads residual_out.
+ * with no discontinuous branch.  Where mu > 1 the three cases are evaluated with a = 1 / mu (a r <= s; r <= -a s; s' = a (a s + r) / (1 + a^2),
+ * mu s' / r = (a s + r) / ((1 + a^2) r)): no finite mu overflows, and a very large mu is stick -- the projection onto the half space
+ * n.x >= 0.  The caller chooses n_iterations (1 ... MH_MAX_CONTACT_ITERATIONS) and reads residual_out.
  * mu (HOST, [K]).  normals (DEVICE) [B][K][3] (MH_LAYOUT_SOA: [3 K][B]; NULL = (0, 0, 1)).  active (DEVICE int32) [B][K] (SoA [K][B];
  * nonzero = contact k is closed in this configuration; NULL = all): an open contact keeps lambda = 0 exactly.  v_normal (DEVICE) [B][K]
  * (SoA [K][B]; NULL = zeros).  impulse_init (DEVICE): the shape of impulse_out; it may be impulse_out itself (in-place warm start).
@@ -800,14 +802,16 @@ mh_status mh_constraint_impulse_between_f32(mh_model_t model, int64_t B, const f
  * owns hold those of qd.  impulse_out [B][K][6] (SoA [6 K][B]; may be NULL): the wrench on the target body at and in the target frame;
  * rows 0-2 and every row of an open contact hold exactly 0.0.  residual_out [B] (may be NULL): the largest |change of an impulse
  * component| in the last sweep.
- * A configuration gets quiet NaN in all of its outputs when trace S_kk + eps of a closed contact is not positive and finite, or when the
- * norm of the n^ of a closed contact is not positive and finite; no other configuration changes and no error is raised.
+ * A configuration gets quiet NaN in all of its outputs when trace S_kk + eps of a closed contact is not positive and finite, when the
+ * norm of the n^ of a closed contact is not positive and finite, or when b_k of a closed contact or an impulse after the last sweep is
+ * not finite (a NaN in qd, in v_normal or in impulse_init: residual_out never reads as converged beside an impulse that is no number);
+ * no other configuration changes and no error is raised.
  * Launches composed on opts->stream as for mh_constraint_impulse_*, with the contact solve (one lane per configuration, S in LDS while
  * it fits, otherwise streamed from scratch: the same bits either way) in the place of the factorisation.  Scratch of the context:
  * B * ((6 K)^2 + 6 K + 12 n_joints + nv) elements, which mh_reserve / mh_context_reserve cover; after reserve and one first call the entry
  * point only enqueues work (graph-capturable).  MH_ERR_INVALID_ARGUMENT, outputs untouched: NULL q / qd / qd_out / target_joints / mu;
- * K outside 1 ... MH_MAX_CONTACT_TARGETS; a joint outside 0 ... n_joints - 1; a pose that is no rotation; a mu that is negative or not
- * finite; a negative or NaN compliance; n_iterations outside 1 ... MH_MAX_CONTACT_ITERATIONS; MH_ACCELERATION_SOURCE joints in the model;
+ * K outside 1 ... MH_MAX_CONTACT_TARGETS; a joint outside 0 ... n_joints - 1; a pose that is no rotation; a mu that is negative, not
+ * finite, or beyond the largest finite number of the call's precision (mh_contact_impulse_f32: above 3.4e38); a negative or NaN compliance; n_iterations outside 1 ... MH_MAX_CONTACT_ITERATIONS; MH_ACCELERATION_SOURCE joints in the model;
  * any overlap of an output with an input or another output, except impulse_out == impulse_init exactly.  B = 0 returns MH_OK and
  * touches nothing.  Index maps, MH_LAYOUT_SOA and contexts are honoured as everywhere else.
  */

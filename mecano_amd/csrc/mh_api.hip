@@ -35,6 +35,7 @@ extern char **environ;
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <map>
 #include <deque>
 #include <mutex>
@@ -2109,11 +2110,15 @@ mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int
       std::memcpy(&mu_bits, &mu[k], sizeof mu_bits);
       if (mu_bits >= 0x7ff0000000000000ull && mu_bits != 0x8000000000000000ull) // infinite, NaN or negative
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the friction coefficient must be finite and >= 0", call, k);
+      if (mu[k] > (double)std::numeric_limits<T>::max()) // (finite in fp64, not in T)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the friction coefficient %g is beyond the range of the call's precision", call, k, mu[k]);
       double off;
       T canonical[12];
       if (!target_frame<T>(model, model->engine_of[i], target_poses ? target_poses + 12 * k : nullptr, canonical, off))
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", call, k, off);
-      G.tgt[k] = model->engine_of[i], G.ext[k] = i, G.mu[k] = (T)mu[k];
+      G.tgt[k] = model->engine_of[i], G.ext[k] = i;
+      G.mu[k] = (T)(mu[k] > 1.0 ? 1.0 / mu[k] : mu[k]); // contact_project works a cone wider than 45 degrees with 1 / mu: no finite mu overflows
+      G.wide |= mu[k] > 1.0 ? 1u << k : 0u;
       for (int r = 0; r < 12; r++)
          G.pose[k][r] = target_poses ? (T)target_poses[12 * k + r] : (T)(r == 0 || r == 4 || r == 8 ? 1 : 0);
    }

@@ -30,8 +30,9 @@
 //      (contact_plan in mh_launch_plans.h chooses).
 //   3. impulse_out (rows 0-2 and every row of an inactive contact exactly 0), residual_out (largest |change of a component| in the last
 //      sweep), and the complete wrench matrix of the second launch: zeros plus X_k^T (0, lambda_k).
-// A configuration gets quiet NaN in all its outputs when trace S_kk + eps of an active contact is not positive and finite or the norm
-// of its n^ is not positive and finite; the tests read bits (pivot_ok): the translation unit is compiled with -ffinite-math-only.
+// A configuration gets quiet NaN in all its outputs when trace S_kk + eps of an active contact is not positive and finite, the norm
+// of its n^ is not positive and finite, its b_k is not finite or an impulse after the last sweep is not finite; the tests read bits
+// (pivot_ok, contact_finite): the translation unit is compiled with -ffinite-math-only.
 #pragma once
 #include "mh_constraint_kernels.h"
 
@@ -64,24 +65,44 @@ struct ContactArgs
    int K, n_iter;
    int tgt[CONTACT_MAX_TARGETS]; // engine index of the target's body
    int ext[CONTACT_MAX_TARGETS]; // its joint in the caller's order
-   T mu[CONTACT_MAX_TARGETS];
+   T mu[CONTACT_MAX_TARGETS];    // min(mu_k, 1 / mu_k), formed in fp64 on the host
+   unsigned wide;                // bit k: mu_k > 1
    T pose[CONTACT_MAX_TARGETS][12];
 };
 
-// Euclidean projection of x onto the cone { n.x >= 0, |x - (n.x) n| <= mu n.x }
+// Euclidean projection of x onto the cone { n.x >= 0, |x - (n.x) n| <= mu n.x }.  m = min(mu, 1 / mu), wide = mu > 1 (uniform: the host
+// forms both): a wide cone is worked with a = 1 / mu -- r <= mu s as a r <= s, s' = a (a s + r) / (1 + a^2), the tangential factor
+// (a s + r) / ((1 + a^2) r) -- so that no finite mu overflows (mu^2 does from 1.85e19 in fp32: s' = 0 and the origin where the
+// tangential part belongs) and the limit is the projection onto the half space n.x >= 0.  Up to mu = 1 the operations are the stated ones.
 template <typename T>
-MH_DEV void contact_project(T &x0, T &x1, T &x2, T n0, T n1, T n2, T mu)
+MH_DEV void contact_project(T &x0, T &x1, T &x2, T n0, T n1, T n2, T m, bool wide)
 {
    const T s = fma(n2, x2, fma(n1, x1, n0 * x0));
    const T t0 = fma(-s, n0, x0), t1 = fma(-s, n1, x1), t2 = fma(-s, n2, x2);
    const T r = sqrt(fma(t2, t2, fma(t1, t1, t0 * t0)));
-   const bool inside = r <= mu * s, polar = mu * r <= -s;
-   const T s1 = fma(mu, r, s) / fma(mu, mu, T(1));
-   const T c = mu * s1 / r; // (r = 0 lands in one of the first two cases: this quotient is then discarded)
+   const bool inside = wide ? m * r <= s : r <= m * s, polar = wide ? r <= -(m * s) : m * r <= -s;
+   const T w = (wide ? fma(m, s, r) : fma(m, r, s)) / fma(m, m, T(1));
+   const T s1 = wide ? m * w : w;
+   const T c = (wide ? w : m * w) / r; // (r = 0 lands in one of the first two cases: this quotient is then discarded)
    const T y0 = fma(c, t0, s1 * n0), y1 = fma(c, t1, s1 * n1), y2 = fma(c, t2, s1 * n2);
    x0 = inside ? x0 : (polar ? T(0) : y0);
    x1 = inside ? x1 : (polar ? T(0) : y1);
    x2 = inside ? x2 : (polar ? T(0) : y2);
+}
+
+// neither infinite nor NaN, read from bits the compiler cannot trace back to a floating-point value: under -ffinite-math-only it
+// recognises the mask-and-compare on the bits of an fma's result as a class test and folds it to true (seen in the code object)
+MH_DEV bool contact_finite(double d)
+{
+   long long b = __double_as_longlong(d);
+   asm volatile("" : "+v"(b));
+   return (b & 0x7ff0000000000000ll) != 0x7ff0000000000000ll;
+}
+MH_DEV bool contact_finite(float d)
+{
+   int b = __float_as_int(d);
+   asm volatile("" : "+v"(b));
+   return (b & 0x7f800000) != 0x7f800000;
 }
 
 // where entry (i, j) of S_kl lives in W (row-major with leading dimension ld = 6 K, one entry every B elements)
@@ -141,7 +162,9 @@ __global__ void __launch_bounds__(64, 2) contact_solve_kernel(ContactArgs<T> G)
                                                    V3<T>{brow[(e + 3) * G.f_es], brow[(e + 4) * G.f_es], brow[(e + 5) * G.f_es]}});
          const T vk = G.v_normal ? G.v_normal[cfg * G.a_bs + k * G.a_es] : T(0);
          nv[(3L * k + 0) * B] = n.x, nv[(3L * k + 1) * B] = n.y, nv[(3L * k + 2) * B] = n.z;
-         bv[(3L * k + 0) * B] = fma(-vk, n.x, v.l.x), bv[(3L * k + 1) * B] = fma(-vk, n.y, v.l.y), bv[(3L * k + 2) * B] = fma(-vk, n.z, v.l.z);
+         const T b0 = fma(-vk, n.x, v.l.x), b1 = fma(-vk, n.y, v.l.y), b2 = fma(-vk, n.z, v.l.z);
+         bad = bad || (on && !(contact_finite(b0) && contact_finite(b1) && contact_finite(b2)));
+         bv[(3L * k + 0) * B] = b0, bv[(3L * k + 1) * B] = b1, bv[(3L * k + 2) * B] = b2;
       }
       if constexpr (RESIDENT)
       { // the lower block triangle of S into LDS (one wave per workgroup: the lane's own column, no barrier)
@@ -179,7 +202,7 @@ __global__ void __launch_bounds__(64, 2) contact_solve_kernel(ContactArgs<T> G)
             {
                const T *ip = G.init + cfg * G.d_bs + (6L * k + 3) * G.d_es;
                T x0 = ip[0], x1 = ip[G.d_es], x2 = ip[2 * G.d_es];
-               contact_project(x0, x1, x2, nk[3 * k], nk[3 * k + 1], nk[3 * k + 2], G.mu[k]);
+               contact_project(x0, x1, x2, nk[3 * k], nk[3 * k + 1], nk[3 * k + 2], G.mu[k], (G.wide >> k & 1u) != 0);
                lam[3 * k] = x0, lam[3 * k + 1] = x1, lam[3 * k + 2] = x2;
             }
          }
@@ -207,12 +230,18 @@ __global__ void __launch_bounds__(64, 2) contact_solve_kernel(ContactArgs<T> G)
                   }
                u0 = fma(eps, lam[3 * k], u0), u1 = fma(eps, lam[3 * k + 1], u1), u2 = fma(eps, lam[3 * k + 2], u2);
                T x0 = fma(-rho[k], u0, lam[3 * k]), x1 = fma(-rho[k], u1, lam[3 * k + 1]), x2 = fma(-rho[k], u2, lam[3 * k + 2]);
-               contact_project(x0, x1, x2, nk[3 * k], nk[3 * k + 1], nk[3 * k + 2], G.mu[k]);
+               contact_project(x0, x1, x2, nk[3 * k], nk[3 * k + 1], nk[3 * k + 2], G.mu[k], (G.wide >> k & 1u) != 0);
                x0 = act[k] ? x0 : T(0), x1 = act[k] ? x1 : T(0), x2 = act[k] ? x2 : T(0);
                res = fmax(res, fmax(fabs(x0 - lam[3 * k]), fmax(fabs(x1 - lam[3 * k + 1]), fabs(x2 - lam[3 * k + 2]))));
                lam[3 * k] = x0, lam[3 * k + 1] = x1, lam[3 * k + 2] = x2;
             }
       }
+      // a sweep state that is no number (a NaN in qd, in v_normal or in impulse_init of a closed contact; an overflow) would leave fmax
+      // with the last finite change in res: such a configuration reads as converged.  It is bad like the others
+#pragma unroll
+      for (int k = 0; k < KMAX; k++)
+         if (k < K)
+            bad = bad || !(contact_finite(lam[3 * k]) && contact_finite(lam[3 * k + 1]) && contact_finite(lam[3 * k + 2]));
       // ---- 3. impulse_out, residual_out and the wrenches of the second launch
       if (G.residual)
          G.residual[cfg] = bad ? nan : res;

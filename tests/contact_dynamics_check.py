@@ -17,15 +17,20 @@ import kinematics_check as kc
 
 
 def project(x, n, mu):
-    """Euclidean projection of x [B, 3] onto the cone of normal n [B, 3] and coefficient mu: the three cases of the header, no other."""
+    """Euclidean projection of x [B, 3] onto the cone of normal n [B, 3] and coefficient mu: the three cases of the header, no other.
+    mu > 1 is worked with a = 1 / mu (r <= mu s as a r <= s, s' = a (a s + r) / (1 + a^2), the tangential factor (a s + r) / ((1 + a^2) r)):
+    nothing overflows at any finite mu, and the limit is the projection onto the half space n.x >= 0."""
     s = (n * x).sum(axis=1)
     t = x - s[:, None] * n
     r = np.sqrt((t * t).sum(axis=1))
-    inside = r <= mu * s
-    polar = ~inside & (mu * r <= -s)
+    wide = mu > 1.0
+    m = 1.0 / mu if wide else mu
+    inside = m * r <= s if wide else r <= m * s
+    polar = ~inside & (r <= -(m * s) if wide else m * r <= -s)
     with np.errstate(divide="ignore", invalid="ignore"):
-        s1 = (s + mu * r) / (1.0 + mu * mu)
-        y = s1[:, None] * n + (mu * s1 / r)[:, None] * t
+        w = ((m * s + r) if wide else (s + m * r)) / (1.0 + m * m)
+        s1, c = (m * w, w / r) if wide else (w, m * w / r)
+        y = s1[:, None] * n + c[:, None] * t
     return np.where(inside[:, None], x, np.where(polar[:, None], 0.0, y))
 
 
@@ -91,8 +96,8 @@ def contact_impulse(om, desc, q, qd, targets, mu, poses=None, normals=None, acti
                     history=None, precision=None):
     """dict(qd_next [B, nv], impulse [B, K, 6], residual [B], S, b, n, J, H, cond_H, cond_kkt): what mh_contact_impulse_* returns in AoS, with
     the terms of the problem and the conditioning of the stick system (all K contacts as POINT rows of cc.constraint_impulse with the
-    call's compliance).  A configuration whose trace S_kk + eps or normal length is not positive and finite for a closed contact is NaN
-    throughout.  precision: round S and b to this dtype before the sweeps (how far the call's precision can move the iterates)."""
+    call's compliance).  A configuration whose trace S_kk + eps or normal length is not positive and finite for a closed contact, or whose
+    impulses after the last sweep are not finite, is NaN throughout.  precision: round S and b to this dtype before the sweeps (how far the call's precision can move the iterates)."""
     qd = np.asarray(qd, dtype=float)
     B, K = qd.shape[0], len(targets)
     mu = np.asarray(mu, dtype=float).reshape(K)
@@ -106,7 +111,7 @@ def contact_impulse(om, desc, q, qd, targets, mu, poses=None, normals=None, acti
         lam, res = sweeps(S, b, T["n"], mu, act, compliance, iterations, lam0, history)
         trace = np.stack([S[:, 3 * k, 3 * k] + S[:, 3 * k + 1, 3 * k + 1] + S[:, 3 * k + 2, 3 * k + 2] + compliance for k in range(K)], axis=1)
     ok = lambda x: np.isfinite(x) & (x > 0)
-    bad = (act & ~(ok(trace) & ok(T["norm"]))).any(axis=1)
+    bad = (act & ~(ok(trace) & ok(T["norm"]))).any(axis=1) | ~np.isfinite(lam).all(axis=(1, 2))
     lam[bad], res[bad] = np.nan, np.nan
     impulse = np.zeros((B, K, 6))
     impulse[:, :, 3:] = lam
