@@ -827,6 +827,52 @@ mh_status mh_contact_impulse_f32(mh_model_t model, int64_t B, const float *q, co
                                  float *impulse_out, float *residual_out);
 
 /*
+ * ---- the same between two moving bodies: a hand on the other hand, a foot on the other leg, fingers on an object that is itself a
+ *      floating body of the tree, a link against its neighbour ----
+ * Arguments as mh_contact_impulse_* with base_joints (HOST, [K]) behind target_joints, as in the other _between_ calls: a position in the
+ * joint list names that joint's successor body, -1 the root body; NULL = the root for every contact.  Per configuration, with
+ *    u_k      rows 3-5 of J qd of mh_geometric_jacobian_* for target k with base base_joints[k]: the linear velocity of the contact point
+ *             on the target body relative to the base body, in the target frame,
+ *    S        the symmetrised linear 3 x 3 blocks of W_rel = J_rel H^-1 J_rel^T, J_rel,k = J_t - Z_k J_b, read exactly as above: block (k, l)
+ *             with l < k as computed, its transpose for (l, k), the lower triangle of a diagonal block mirrored,
+ *    n_k      still given per configuration in the ROOT BODY frame, pointing from the base body (the obstacle) into the target body, and
+ *             brought into the target frame by the target body's pose, n_k = R_pose^T R_body(q)^T n^_k,
+ *    lambda_k the impulse on the target body at the origin of the target frame, in the target frame; the base body receives -lambda_k at
+ *             the same point: -Z_k^T (0, lambda_k), Z_k the motion transform from the base's body-fixed frame to the target frame at q, as
+ *             in mh_constraint_impulse_between_*.  Nothing is applied for a root base,
+ * the call returns the minimiser of the same problem with b_k = u_k(qd) - v_k n_k and
+ *    qd_out = qd + H^-1 J_rel^T lambda:
+ * forward dynamics at rest, without gravity, with sum_k (X_k^T impulse_k on the target body - Z_k^T impulse_k on the base body) as the only
+ * wrenches.  Two bodies of the tree exchange momentum and the total is conserved, which no rooted contact can do.
+ * The objective, the cone projection (the mu > 1 form through 1 / mu included), the sweep order, rho_k = 1 / (trace S_kk + eps), the warm
+ * start, active, v_normal, residual_out and the exact zeros in angular rows and open contacts are those of mh_contact_impulse_*.  The NaN
+ * rule is that call's; a configuration whose q makes a pose of either climb non-finite is NaN in all three outputs through b_k.
+ * A target and a base may be any two different bodies: ancestor and descendant, two limbs, or a body that is the target of one contact
+ * and the base of another; duplicated bases are allowed.  With base_joints NULL or all -1 the call takes the rooted launches and returns
+ * the bits of mh_contact_impulse_*.
+ * Composition: as mh_contact_impulse_*, with the apparent inertia inverse for n_app = K + (non-root bases) frames -- the K target frames,
+ * then the body-fixed frame of every non-root base, one per contact, at most 16 -- and a second set of instantiations of the contact
+ * kernel that forms Z_k and the relative b_k, reduces W to W_rel in place over the target blocks (the step of the constraint kernel)
+ * before its sweeps, and loads the base.  S in LDS while it fits (9 K (K + 1) / 2 entries per lane whatever the bases are), otherwise
+ * streamed from the reduced W: the same bits either way.  Scratch of the context: B * ((6 n_app)^2 + 6 K + 12 n_joints + nv + 12 K)
+ * elements, the 12 K for the poses of the target frames in their bases.  mh_reserve / mh_context_reserve keep the size of the rooted call:
+ * a larger need is met by the first call at that batch; after one such call the entry point only enqueues work (graph-capturable).
+ * MH_ERR_INVALID_ARGUMENT, outputs untouched: everything mh_contact_impulse_* refuses; a base outside -1 ... n_joints - 1;
+ * base_joints[k] == target_joints[k] (the Jacobian would be zero).  B = 0 returns MH_OK and touches nothing.  Layouts, index maps,
+ * contexts, the stream and the aliasing rule (impulse_out == impulse_init exactly is the one permitted overlap) are those of the rooted call.
+ */
+mh_status mh_contact_impulse_between_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_targets,
+                                         const int32_t *target_joints, const int32_t *base_joints, const double *target_poses, const double *mu,
+                                         const double *normals, const int32_t *active, const double *v_normal, const double *impulse_init,
+                                         double compliance, int32_t n_iterations, const mh_options *opts, double *qd_out, double *impulse_out,
+                                         double *residual_out);
+mh_status mh_contact_impulse_between_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_targets,
+                                         const int32_t *target_joints, const int32_t *base_joints, const double *target_poses, const double *mu,
+                                         const float *normals, const int32_t *active, const float *v_normal, const float *impulse_init,
+                                         double compliance, int32_t n_iterations, const mh_options *opts, float *qd_out, float *impulse_out,
+                                         float *residual_out);
+
+/*
  * ---- state integration (MultiBodySystemStateIntegrator.doubleIntegrateFromAcceleration, tools/MultiBodySystemStateIntegrator.java:365-441,
  *      503-575, 710-733): the step downstream of forward dynamics, so that a simulation loop never leaves the device ----
  * One explicit constant-acceleration step of size dt for every joint of every configuration: 1-DoF q' = q + dt qd + dt^2/2 qdd,

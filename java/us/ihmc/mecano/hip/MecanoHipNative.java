@@ -232,6 +232,17 @@ public final class MecanoHipNative
    static final MethodHandle CONTACT_IMPULSE_F32 = handle("mh_contact_impulse_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
                                                                                            ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_DOUBLE, JAVA_INT, ADDRESS, ADDRESS,
                                                                                            ADDRESS, ADDRESS));
+   /**
+    * The same between two moving bodies: base_joints (host int[n_targets], -1 = the root body)|NULL behind target_joints; the impulse acts on the
+    * target body and the base body receives its opposite at the same point.
+    */
+   static final MethodHandle CONTACT_IMPULSE_BETWEEN = handle("mh_contact_impulse_between_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
+                                                                                                       ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_DOUBLE,
+                                                                                                       JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle CONTACT_IMPULSE_BETWEEN_F32 = handle("mh_contact_impulse_between_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
+                                                                                                           ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_DOUBLE,
+                                                                                                           JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
    /** (model, B, dt, q, qd, qdd, opts, q_out, qd_out, qdd_out|NULL) */
    static final MethodHandle INTEGRATE = handle("mh_integrate_f64", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                            ADDRESS));

@@ -2079,12 +2079,16 @@ mh_status constrained_impl(bool velocity, mh_model_t model, int64_t B, const T *
 }
 // Frictional contact impulses (mh_contact_kernels.h): the composition of the velocity form above with the contact solve between the
 // launches.  Scratch as the rooted form's: the 6 K rows behind W hold b and the normals in the target frames.
+// between: mh_contact_impulse_between_* (base_joints may still be NULL = every base the root: the rooted launches, bit for bit).  With
+// n_app = K + (non-root bases) frames in W the scratch is (6 n_app)^2 + 6 K + 12 n_joints + nv + 12 K per configuration: the K relative
+// poses come last.  mh_reserve covers the rooted form; the first call of a larger need grows the buffer (ensure_bytes).
 template <typename T>
 mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
                        const double *mu, const T *normals, const int32_t *active, const T *v_normal, const T *impulse_init, const double &compliance,
-                       int32_t n_iterations, const mh_options *opts_in, T *out, T *impulse_out, T *residual_out)
+                       int32_t n_iterations, const mh_options *opts_in, T *out, T *impulse_out, T *residual_out, bool between = false,
+                       const int32_t *base_joints = nullptr)
 {
-   const char *call = "mh_contact_impulse";
+   const char *call = between ? "mh_contact_impulse_between" : "mh_contact_impulse";
    mh_options o;
    mh_status st = begin_call(model, B, opts_in, o);
    if (st != MH_OK)
@@ -2099,13 +2103,24 @@ mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int
       return fail(MH_ERR_INVALID_ARGUMENT, "%s: compliance must be >= 0", call);
    if (n_iterations < 1 || n_iterations > MH_MAX_CONTACT_ITERATIONS)
       return fail(MH_ERR_INVALID_ARGUMENT, "%s: n_iterations = %d is outside 1 ... %d", call, n_iterations, MH_MAX_CONTACT_ITERATIONS);
-   mh::ContactArgs<T> G{};
+   mh::ContactRelArgs<T> G{}; // (the rooted launch takes its ContactArgs part)
    const int K = n_targets;
+   int n_app = K;
+   int32_t app_joints[MH_MAX_APPARENT_TARGETS];
+   double app_poses[MH_MAX_APPARENT_TARGETS][12];
    for (int k = 0; k < K; k++)
    {
-      const int i = target_joints[k];
+      const int i = target_joints[k], ib = base_joints ? base_joints[k] : -1;
       if (i < 0 || i >= model->n)
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d names joint %d (the model has %d joints; the root body is no target)", call, k, i, model->n);
+      if (ib < -1 || ib >= model->n)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: base %d names joint %d (the model has %d joints; -1 is the root body)", call, k, ib, model->n);
+      if (ib == i)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: contact %d is between a body and itself (joint %d): the Jacobian is zero", call, k, i);
+      G.base[k] = ib < 0 ? -1 : model->engine_of[ib], G.bext[k] = ib, G.bslot[k] = -1;
+      app_joints[k] = i;
+      for (int r = 0; r < 12; r++)
+         app_poses[k][r] = target_poses ? target_poses[12 * k + r] : (r == 0 || r == 4 || r == 8 ? 1.0 : 0.0);
       uint64_t mu_bits; // (read as bits: the translation unit is compiled with -ffinite-math-only)
       std::memcpy(&mu_bits, &mu[k], sizeof mu_bits);
       if (mu_bits >= 0x7ff0000000000000ull && mu_bits != 0x8000000000000000ull) // infinite, NaN or negative
@@ -2122,6 +2137,17 @@ mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int
       for (int r = 0; r < 12; r++)
          G.pose[k][r] = target_poses ? (T)target_poses[12 * k + r] : (T)(r == 0 || r == 4 || r == 8 ? 1 : 0);
    }
+   for (int k = 0; k < K; k++)
+      if (G.base[k] >= 0)
+      { // one more frame of W per non-root base: its body-fixed frame
+         G.bslot[k] = n_app;
+         app_joints[n_app] = G.bext[k];
+         for (int r = 0; r < 12; r++)
+            app_poses[n_app][r] = r == 0 || r == 4 || r == 8 ? 1.0 : 0.0;
+         n_app++;
+      }
+   const bool rel = n_app > K;
+   G.n_app = n_app;
    if (B == 0)
       return MH_OK;
    if (!q || !qd || !out)
@@ -2135,18 +2161,29 @@ mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int
       if ((st = check_aliasing(call, ins, 6, outs, 3)) != MH_OK)
          return st;
    }
-   st = ensure_bytes(model->con, (size_t)B * constraint_scratch_entries(model, K) * sizeof(T));
+   // (the relative form: the 12 K relative poses behind the rooted layout at ld = 6 n_app)
+   const size_t entries = rel ? 36 * (size_t)n_app * n_app + 18 * (size_t)K + 2 * n6 + nv : constraint_scratch_entries(model, K);
+   st = ensure_bytes(model->con, (size_t)B * entries * sizeof(T));
    if (st != MH_OK)
       return st;
    const ContactPlan P = contact_plan(K, sizeof(T), model->contact_path, model->cu_count, B);
    const void *kern;
-   if (P.kmax == 4)
+   if (rel)
+   {
+      if (P.kmax == 4)
+         kern = P.resident ? (const void *)&mh::contact_solve_kernel<T, true, 4, true> : (const void *)&mh::contact_solve_kernel<T, false, 4, true>;
+      else
+         kern = P.resident ? (const void *)&mh::contact_solve_kernel<T, true, 8, true> : (const void *)&mh::contact_solve_kernel<T, false, 8, true>;
+   }
+   else if (P.kmax == 4)
       kern = P.resident ? (const void *)&mh::contact_solve_kernel<T, true, 4> : (const void *)&mh::contact_solve_kernel<T, false, 4>;
    else
       kern = P.resident ? (const void *)&mh::contact_solve_kernel<T, true, 8> : (const void *)&mh::contact_solve_kernel<T, false, 8>;
    if ((st = raise_lds_limit(model, kern, (size_t)P.lds)) != MH_OK)
       return st;
-   T *W = (T *)model->con.ptr, *rhs = W + (size_t)B * 36 * K * K, *body = rhs + (size_t)B * 6 * K, *wrench = body + (size_t)B * n6, *zeros = wrench + (size_t)B * n6;
+   T *W = (T *)model->con.ptr, *rhs = W + (size_t)B * 36 * n_app * n_app, *body = rhs + (size_t)B * 6 * K, *wrench = body + (size_t)B * n6,
+     *zeros = wrench + (size_t)B * n6;
+   T *zpose = zeros + (size_t)B * nv; // (relative form only)
    hipStream_t stream = (hipStream_t)o.stream;
    const double no_gravity[3] = {0.0, 0.0, 0.0};
    mh_options of = o;
@@ -2155,7 +2192,10 @@ mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int
    st = launch<T>(ALGO_RNEA, model, B, q, qd, qd, no_gravity, nullptr, &of, out, body_outputs<T>(nullptr, body));
    if (st != MH_OK)
       return st;
-   st = apparent_inertia_impl<T>(model, B, q, K, target_joints, target_poses, MH_APPARENT_BLOCKS_COUPLED, &o, W, true);
+   if (rel)
+      st = apparent_inertia_impl<T>(model, B, q, n_app, app_joints, &app_poses[0][0], MH_APPARENT_BLOCKS_COUPLED, &o, W, true);
+   else
+      st = apparent_inertia_impl<T>(model, B, q, K, target_joints, target_poses, MH_APPARENT_BLOCKS_COUPLED, &o, W, true);
    if (st != MH_OK)
       return st;
    const bool soa = o.layout == MH_LAYOUT_SOA;
@@ -2165,7 +2205,7 @@ mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int
    set_strides(G.q_bs, G.q_es, soa, B, model->nq);
    G.body = body, G.wrench = wrench;
    set_strides(G.f_bs, G.f_es, soa, B, (long)n6);
-   G.W = W, G.bvec = rhs, G.nvec = rhs + (size_t)B * 3 * K;
+   G.W = W, G.Wrel = W, G.zpose = zpose, G.bvec = rhs, G.nvec = rhs + (size_t)B * 3 * K;
    G.active = active, G.v_normal = v_normal;
    set_strides(G.a_bs, G.a_es, soa, B, K);
    G.normals = normals;
@@ -2175,7 +2215,7 @@ mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int
    G.residual = residual_out;
    G.eps = (T)compliance;
    G.K = K, G.n_iter = n_iterations;
-   void *args[] = {(void *)&G};
+   void *args[] = {rel ? (void *)&G : (void *)static_cast<mh::ContactArgs<T> *>(&G)};
    HIP_TRY(hipLaunchKernel(kern, dim3(P.grid), dim3(64), args, (size_t)P.lds, stream));
    // the change of velocity: forward dynamics at rest, without gravity, with the impulses as the only wrenches; then qd_out += qd
    HIP_TRY(hipMemsetAsync(zeros, 0, (size_t)B * nv * sizeof(T), stream));
@@ -3965,6 +4005,24 @@ mh_status mh_contact_impulse_f32(mh_model_t model, int64_t B, const float *q, co
 {
    return contact_impl<float>(model, B, q, qd, n_targets, target_joints, target_poses, mu, normals, active, v_normal, impulse_init, compliance,
                               n_iterations, opts, qd_out, impulse_out, residual_out);
+}
+mh_status mh_contact_impulse_between_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_targets,
+                                         const int32_t *target_joints, const int32_t *base_joints, const double *target_poses, const double *mu,
+                                         const double *normals, const int32_t *active, const double *v_normal, const double *impulse_init,
+                                         double compliance, int32_t n_iterations, const mh_options *opts, double *qd_out, double *impulse_out,
+                                         double *residual_out)
+{
+   return contact_impl<double>(model, B, q, qd, n_targets, target_joints, target_poses, mu, normals, active, v_normal, impulse_init, compliance,
+                               n_iterations, opts, qd_out, impulse_out, residual_out, true, base_joints);
+}
+mh_status mh_contact_impulse_between_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_targets,
+                                         const int32_t *target_joints, const int32_t *base_joints, const double *target_poses, const double *mu,
+                                         const float *normals, const int32_t *active, const float *v_normal, const float *impulse_init,
+                                         double compliance, int32_t n_iterations, const mh_options *opts, float *qd_out, float *impulse_out,
+                                         float *residual_out)
+{
+   return contact_impl<float>(model, B, q, qd, n_targets, target_joints, target_poses, mu, normals, active, v_normal, impulse_init, compliance,
+                              n_iterations, opts, qd_out, impulse_out, residual_out, true, base_joints);
 }
 // not in include/mecano_hip.h: where the contact solve of this model (or context) reads S from now on -- -1 = contact_plan chooses,
 // 0 = streamed, 1 = LDS-resident where it fits (tests/test_gpu_contact_dynamics.py holds the two to the same bits)

@@ -105,6 +105,46 @@ MH_DEV void con_sub_moved(const XF<T> &Z, T *x, const T *from, long s)
    x[0] -= v.a.x, x[s] -= v.a.y, x[2 * s] -= v.a.z, x[3 * s] -= v.l.x, x[4 * s] -= v.l.y, x[5 * s] -= v.l.z;
 }
 
+// W = J H^-1 J^T of n_app = ld / 6 frames (the K target frames, then the body-fixed frames of the non-root bases; bslot[k] the frame of
+// target k's base, -1 = the root body) becomes that of the relative motions J_rel,k = J_t - Z_k J_b, block pair by block pair with k >= l, in
+// place over the targets' blocks (the header's step 2).  W and zpose are the lane's own: entries B apart, Z_k at zpose + 12 k B.  (The
+// six-fold loops stay rolled: unrolled, their loads in flight take the constraint kernel from 202 to 256 + 14 registers in fp64, one wave
+// per SIMD.)
+template <typename T>
+MH_DEV void con_reduce_relative(T *W, const T *zpose, long B, long ld, int K, const int *bslot)
+{
+   const long cs = ld * B; // from one row of W to the next
+   for (int k = 0; k < K; k++)
+      for (int l = 0; l <= k; l++)
+      {
+         const int bk = bslot[k], bl = bslot[l];
+         T *Wtt = W + (6L * k * ld + 6L * l) * B;
+         T *Wtb = bl >= 0 ? W + (6L * k * ld + 6L * bl) * B : nullptr;
+         if (bk >= 0)
+         {
+            const XF<T> Zk = con_load_pose(zpose + 12L * k * B, B);
+            const T *Wbt = W + (6L * bk * ld + 6L * l) * B;
+#pragma nounroll
+            for (int c = 0; c < 6; c++)
+               con_sub_moved(Zk, Wtt + c * B, Wbt + c * B, cs);
+            if (bl >= 0)
+            {
+               const T *Wbb = W + (6L * bk * ld + 6L * bl) * B;
+#pragma nounroll
+               for (int c = 0; c < 6; c++)
+                  con_sub_moved(Zk, Wtb + c * B, Wbb + c * B, cs);
+            }
+         }
+         if (bl >= 0)
+         {
+            const XF<T> Zl = con_load_pose(zpose + 12L * l * B, B);
+#pragma nounroll
+            for (int r = 0; r < 6; r++)
+               con_sub_moved(Zl, Wtt + r * cs, Wtb + r * cs, B);
+         }
+      }
+}
+
 // wrench row of joint `ext` (entries es apart) += X^T lam: lam acts at and in the frame at `ps` (R row-major, p) of that joint's body
 template <typename T>
 MH_DEV void con_add_wrench(T *wrow, int ext, long es, const T *ps, const SV<T> &lam)
@@ -209,40 +249,8 @@ __global__ void __launch_bounds__(64) constraint_solve_kernel(std::conditional_t
                a++;
             }
       }
-      if constexpr (REL)
-      { // ---- 2. W of the relative motions, block pair by block pair, in place over the targets' blocks.  (The six-fold loops stay
-        // rolled: unrolled, their loads in flight take the kernel from 202 to 256 + 14 registers in fp64, one wave per SIMD.)
-         const long cs = ld * B; // from one row of W to the next
-         for (int k = 0; k < K; k++)
-            for (int l = 0; l <= k; l++)
-            {
-               const int bk = G.bslot[k], bl = G.bslot[l];
-               T *Wtt = W + (6L * k * ld + 6L * l) * B;
-               T *Wtb = bl >= 0 ? W + (6L * k * ld + 6L * bl) * B : nullptr;
-               if (bk >= 0)
-               {
-                  const XF<T> Zk = con_load_pose(G.zpose + 12L * k * B + cfg, B);
-                  const T *Wbt = W + (6L * bk * ld + 6L * l) * B;
-#pragma nounroll
-                  for (int c = 0; c < 6; c++)
-                     con_sub_moved(Zk, Wtt + c * B, Wbt + c * B, cs);
-                  if (bl >= 0)
-                  {
-                     const T *Wbb = W + (6L * bk * ld + 6L * bl) * B;
-#pragma nounroll
-                     for (int c = 0; c < 6; c++)
-                        con_sub_moved(Zk, Wtb + c * B, Wbb + c * B, cs);
-                  }
-               }
-               if (bl >= 0)
-               {
-                  const XF<T> Zl = con_load_pose(G.zpose + 12L * l * B + cfg, B);
-#pragma nounroll
-                  for (int r = 0; r < 6; r++)
-                     con_sub_moved(Zl, Wtt + r * cs, Wtb + r * cs, B);
-               }
-            }
-      }
+      if constexpr (REL) // ---- 2. W of the relative motions, in place over the targets' blocks
+         con_reduce_relative(W, G.zpose + cfg, B, ld, K, G.bslot);
       // ---- 2. + 3. L D L^T of the masked system, row by row, in place; y = L^-1 b rides along
       bool bad = false;
       for (int i = 0; i < M; i++)

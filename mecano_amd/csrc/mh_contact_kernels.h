@@ -33,6 +33,16 @@
 // A configuration gets quiet NaN in all its outputs when trace S_kk + eps of an active contact is not positive and finite, the norm
 // of its n^ is not positive and finite, its b_k is not finite or an impulse after the last sweep is not finite; the tests read bits
 // (pivot_ok, contact_finite): the translation unit is compiled with -ffinite-math-only.
+//
+// REL = true: mh_contact_impulse_between_*, where contact k acts between the target body and the body of base[k] (the root where
+// base[k] < 0, with the arithmetic above).  Four more instantiations per precision: the rooted ones keep their code.
+//   0. a contact with a non-root base: Z_k, the pose of target frame k in the body-fixed frame of its base, from two climbs
+//      (body_pose_in_root, con_relative), parked in scratch ([12 K][B]); b_k = linear rows of (X_k v_t - Z_k v_b) - v_k n_k.  n^_k points
+//      from the base body into the target body and is still given in the root body frame: n_k as above, from the target's climb.
+//   1. W arrives for n_app = K + (non-root bases) frames and is reduced to that of the relative motions in place over the target blocks
+//      (con_reduce_relative, the step the constraint kernel runs) BEFORE the sweep state is live; ld = 6 n_app from here on.  The copy
+//      into LDS follows the reduction; the streamed form reads the reduced W: the same bits either way.
+//   3. the base body receives -Z_k^T (0, lambda_k).
 #pragma once
 #include "mh_constraint_kernels.h"
 
@@ -68,6 +78,18 @@ struct ContactArgs
    T mu[CONTACT_MAX_TARGETS];    // min(mu_k, 1 / mu_k), formed in fp64 on the host
    unsigned wide;                // bit k: mu_k > 1
    T pose[CONTACT_MAX_TARGETS][12];
+};
+
+// the relative form's additions
+template <typename T>
+struct ContactRelArgs : ContactArgs<T>
+{
+   T *Wrel;                          // W again, writable: reduced in place to that of the relative motions
+   T *zpose;                         // [12 K][B]: Z_k of the contacts with a non-root base
+   int n_app;                        // frames of W: K targets, then the non-root bases
+   int base[CONTACT_MAX_TARGETS];    // engine index of the base's body, -1 = the root body
+   int bext[CONTACT_MAX_TARGETS];    // its joint in the caller's order
+   int bslot[CONTACT_MAX_TARGETS];   // its frame in W (>= K), -1 = the root body
 };
 
 // Euclidean projection of x onto the cone { n.x >= 0, |x - (n.x) n| <= mu n.x }.  m = min(mu, 1 / mu), wide = mu > 1 (uniform: the host
@@ -120,8 +142,8 @@ MH_DEV constexpr int contact_lds_entry(int k, int l, int i, int j)
    return l <= k ? (k * (k + 1) / 2 + l) * 9 + i * 3 + j : (l * (l + 1) / 2 + k) * 9 + j * 3 + i;
 }
 
-template <typename T, bool RESIDENT, int KMAX>
-__global__ void __launch_bounds__(64, 2) contact_solve_kernel(ContactArgs<T> G)
+template <typename T, bool RESIDENT, int KMAX, bool REL = false>
+__global__ void __launch_bounds__(64, 2) contact_solve_kernel(std::conditional_t<REL, ContactRelArgs<T>, ContactArgs<T>> G)
 {
    extern __shared__ __align__(16) unsigned char contact_lds_raw[];
    T *const sm = reinterpret_cast<T *>(contact_lds_raw) + threadIdx.x; // [entry][lane]
@@ -129,13 +151,18 @@ __global__ void __launch_bounds__(64, 2) contact_solve_kernel(ContactArgs<T> G)
    const T *CB = (const T *)m.consts;
    const ciptr meta = as_const(m.meta), cfg_map = as_const(m.cfg_map);
    const long nlanes = (long)gridDim.x * blockDim.x;
-   const long B = G.B, ld = 6L * G.K;
    const int K = G.K;
+   long ld = 6L * K;
+   if constexpr (REL)
+      ld = 6L * G.n_app;
+   const long B = G.B;
    const T eps = G.eps, nan = quiet_nan(T(0));
 
    for (long cfg = (long)blockIdx.x * blockDim.x + threadIdx.x; cfg < B; cfg += nlanes)
    {
       const T *W = G.W + cfg;
+      if constexpr (REL)
+         W = G.Wrel + cfg; // (read through the pointer the reduction writes through)
       T *bv = G.bvec + cfg, *nv = G.nvec + cfg;
       const T *brow = G.body + cfg * G.f_bs;
       bool bad = false;
@@ -158,14 +185,28 @@ __global__ void __launch_bounds__(64, 2) contact_solve_kernel(ContactArgs<T> G)
          const XF<T> Xb = body_pose_in_root<T>(m, meta, cfg_map, CB, G.q + cfg * G.q_bs, G.q_es, G.tgt[k]);
          const V3<T> n = tmul(Xt.R, tmul(Xb.R, nh));
          const long e = (long)G.ext[k] * 6;
-         const SV<T> v = motion_to_child(Xt, SV<T>{V3<T>{brow[(e + 0) * G.f_es], brow[(e + 1) * G.f_es], brow[(e + 2) * G.f_es]},
-                                                   V3<T>{brow[(e + 3) * G.f_es], brow[(e + 4) * G.f_es], brow[(e + 5) * G.f_es]}});
+         SV<T> v = motion_to_child(Xt, SV<T>{V3<T>{brow[(e + 0) * G.f_es], brow[(e + 1) * G.f_es], brow[(e + 2) * G.f_es]},
+                                             V3<T>{brow[(e + 3) * G.f_es], brow[(e + 4) * G.f_es], brow[(e + 5) * G.f_es]}});
+         if constexpr (REL)
+            if (G.base[k] >= 0)
+            { // against a moving base: Z_k, and the base's twist brought to the target frame
+               const XF<T> X_b = body_pose_in_root<T>(m, meta, cfg_map, CB, G.q + cfg * G.q_bs, G.q_es, G.base[k]);
+               const XF<T> Z = con_relative(con_relative(Xb, X_b), Xt); // (the base's frame in the target body's; the target frame in the base's)
+               T *z = G.zpose + 12L * k * B + cfg;
+               z[0] = Z.R.xx, z[B] = Z.R.xy, z[2 * B] = Z.R.xz, z[3 * B] = Z.R.yx, z[4 * B] = Z.R.yy, z[5 * B] = Z.R.yz;
+               z[6 * B] = Z.R.zx, z[7 * B] = Z.R.zy, z[8 * B] = Z.R.zz, z[9 * B] = Z.p.x, z[10 * B] = Z.p.y, z[11 * B] = Z.p.z;
+               const long eb = (long)G.bext[k] * 6;
+               v = v - motion_to_child(Z, SV<T>{V3<T>{brow[(eb + 0) * G.f_es], brow[(eb + 1) * G.f_es], brow[(eb + 2) * G.f_es]},
+                                                V3<T>{brow[(eb + 3) * G.f_es], brow[(eb + 4) * G.f_es], brow[(eb + 5) * G.f_es]}});
+            }
          const T vk = G.v_normal ? G.v_normal[cfg * G.a_bs + k * G.a_es] : T(0);
          nv[(3L * k + 0) * B] = n.x, nv[(3L * k + 1) * B] = n.y, nv[(3L * k + 2) * B] = n.z;
          const T b0 = fma(-vk, n.x, v.l.x), b1 = fma(-vk, n.y, v.l.y), b2 = fma(-vk, n.z, v.l.z);
          bad = bad || (on && !(contact_finite(b0) && contact_finite(b1) && contact_finite(b2)));
          bv[(3L * k + 0) * B] = b0, bv[(3L * k + 1) * B] = b1, bv[(3L * k + 2) * B] = b2;
       }
+      if constexpr (REL) // ---- 1. W of the relative motions, in place over the targets' blocks, before the sweep state is live
+         con_reduce_relative(G.Wrel + cfg, G.zpose + cfg, B, ld, K, G.bslot);
       if constexpr (RESIDENT)
       { // the lower block triangle of S into LDS (one wave per workgroup: the lane's own column, no barrier)
          for (int k = 0; k < K; k++)
@@ -260,6 +301,14 @@ __global__ void __launch_bounds__(64, 2) contact_solve_kernel(ContactArgs<T> G)
                op[0] = z, op[G.d_es] = z, op[2 * G.d_es] = z, op[3 * G.d_es] = f0, op[4 * G.d_es] = f1, op[5 * G.d_es] = f2;
             }
             con_add_wrench(wrow, G.ext[k], G.f_es, G.pose[k], SV<T>{V3<T>{z, z, z}, V3<T>{f0, f1, f2}});
+            if constexpr (REL)
+               if (G.base[k] >= 0)
+               { // the opposite impulse at the same point, on the base body
+                  const long es = G.f_es;
+                  const SV<T> fb = force_to_parent(con_load_pose(G.zpose + 12L * k * B + cfg, B), SV<T>{V3<T>{z, z, z}, V3<T>{f0, f1, f2}});
+                  T *ob = wrow + (long)G.bext[k] * 6 * es;
+                  ob[0] -= fb.a.x, ob[es] -= fb.a.y, ob[2 * es] -= fb.a.z, ob[3 * es] -= fb.l.x, ob[4 * es] -= fb.l.y, ob[5 * es] -= fb.l.z;
+               }
          }
    }
 }

@@ -763,9 +763,24 @@ class HipModel:
         impulse[:, k] is the wrench on the target's body at and in the target frame: rows 0-2 and open contacts hold 0.  SoA: [nv, B],
         [6 K, B], [B]; normals [3 K, B], active and v_normal [K, B].  ``out``: a (qd_next, impulse, residual) triple to write into; the
         last two may be None."""
+        return self._contact_call(q, qd, targets, None, mu, poses, normals, active, v_normal, compliance, iterations, init, layout, out)
+
+    def contact_impulse_between(self, q, qd, targets, bases, mu, poses=None, normals=None, active=None, v_normal=None, compliance=0.0,
+                                iterations=50, init=None, layout=_lib.LAYOUT_AOS, out=None):
+        """``contact_impulse`` between two moving bodies: (qd_next [B, nv], impulse [B, K, 6], residual [B]).  ``bases``: one position in
+        the joint list per contact, -1 = the root body (None: the root for every contact, the bits of ``contact_impulse``).  Contact k acts
+        between the body of ``targets[k]`` and that of ``bases[k]``: its velocity is that of the contact point on the target body relative
+        to the base body (the linear rows of ``geometric_jacobian`` with these bases), ``normals`` -- still in the root body frame -- point
+        from the base body into the target body, impulse[:, k] acts on the target body and the base body receives its opposite at the
+        same point, so that the momentum two bodies of the tree exchange is conserved.  Everything else as for ``contact_impulse``
+        (include/mecano_hip.h, mh_contact_impulse_between_*)."""
+        return self._contact_call(q, qd, targets, bases, mu, poses, normals, active, v_normal, compliance, iterations, init, layout, out, True)
+
+    def _contact_call(self, q, qd, targets, bases, mu, poses, normals, active, v_normal, compliance, iterations, init, layout, out, between=False):
+        """What ``contact_impulse`` and ``contact_impulse_between`` share."""
         import torch
         B, dt, sfx, stream = self._device_inputs([q, qd], layout)
-        tgt, K, _, poses = self._kinematic_targets(targets, None, poses)
+        tgt, K, bases, poses = self._kinematic_targets(targets, bases, poses)
         mus = np.ascontiguousarray(np.asarray(mu, dtype=np.float64).reshape(-1))
         if mus.shape[0] != K:
             raise _lib.MecanoHipError(2, f"mu must hold one coefficient per target ({K}), got {mus.shape[0]}")
@@ -782,8 +797,9 @@ class HipModel:
             raise _lib.MecanoHipError(1, "the qd_next output is None")
         ptr = lambda t: None if t is None else t.data_ptr()
         opts = self._options(layout, stream=stream)
-        _lib.check(getattr(_lib.load(), f"mh_contact_impulse_{sfx}")(
-            self._h, B, q.data_ptr(), qd.data_ptr(), K, tgt.ctypes.data, None if poses is None else poses.ctypes.data, mus.ctypes.data, ptr(normals),
+        head = (K, tgt.ctypes.data) + ((None if bases is None else bases.ctypes.data,) if between else ())
+        _lib.check(getattr(_lib.load(), f"mh_contact_impulse_{'between_' if between else ''}{sfx}")(
+            self._h, B, q.data_ptr(), qd.data_ptr(), *head, None if poses is None else poses.ctypes.data, mus.ctypes.data, ptr(normals),
             ptr(active), ptr(v_normal), ptr(init), float(compliance), int(iterations), ctypes.byref(opts), qd_next.data_ptr(), ptr(imp), ptr(res)))
         return qd_next, imp, res
 
