@@ -279,8 +279,8 @@ long mh_spec_zv_lds_bytes(int nq, int nv)
 }
 int mh_spec_zv_usable(void) { return SPL::usable() ? 1 : 0; }
 // 1: launches with identity index maps (the two-stage hand-off) expect `taup` to hold the sentinel wherever no column has been published
-// (mh_zv_kernels.h, "Stage one without a flag"); the library keeps a matrix of its own for them and refills it after a give-up
-int mh_spec_zv_self_signal(void) { return MH_ZV_TWO_STAGE && MH_ZV_SELF_SIGNAL ? 1 : 0; }
+// (mh_zv_kernels.h, "The hand-off without flags"); the library keeps a matrix of its own for them and refills it after a give-up
+int mh_spec_zv_self_signal(void) { return MH_ZV_TWO_STAGE ? 1 : 0; }
 #ifdef MH_ZV_PROBE
 int mh_spec_zv_probe_read(void *dst, size_t bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(mh::zv_probe), bytes); }
 int mh_spec_zv_probe_body_read(void *dst, size_t bytes) { return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(mh::zv_probe_body), bytes); }

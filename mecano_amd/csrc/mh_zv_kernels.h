@@ -1220,16 +1220,14 @@ struct RowRegs
 // limbs' folds are the first 1.5 us of what the inertia job does with the rows; the trunk's entries are needed behind them.  So:
 //   * the hand-off matrix of a group is column-major, [nv][64]: a wave publishes a column with one 512-byte store instruction, so
 //     different waves publish different columns at different times without writing any line in pieces;
-//   * waves 1-3 of the bias job publish the limb dofs' columns while wave 0 folds the trunk; each waits for its stores' acknowledgements
-//     and counts itself in (LDS); the last of the three stores flag A.  Wave 0 publishes the trunk dofs' columns behind its pass, waits,
-//     stores flag B;
-//   * every wave of the inertia job polls flag A itself, loads the columns of ITS limbs' dofs into its lanes' LDS rows and folds its
-//     limbs; it polls flag B and requests the trunk's columns behind its early limbs' fold and stores them to its rows behind its late
-//     limbs' fold, in front of the first use (sub-trunk / root fold).
-// Each of the two hand-offs is the form of MI355X_MICROARCH.md's table, first row: every byte stored sc1 and loaded sc1 (8 bytes per
-// lane), every storing wave drains its stores (s_waitcnt vmcnt(0)) before it is counted, ONE lane signals for all the stores the flag
-// covers (the last arrival at the LDS counter: condition (3) of that guide), the flag is an sc1 store polled by sc1 loads, and a wave
-// loads only after ITS OWN poll has matched.
+//   * waves 1-3 of the bias job publish the limb dofs' columns while wave 0 folds the trunk; wave 0 publishes the trunk dofs' columns
+//     behind its pass;
+//   * every wave of the inertia job takes the columns of ITS limbs' dofs into its lanes' LDS rows and folds its limbs; it requests the
+//     trunk's columns in front of its early limbs' fold, looks at them behind it and stores them to its rows behind its late limbs' fold,
+//     in front of the first use (sub-trunk / root fold).
+// At first each stage ran under a flag (waves drain their stores, count themselves in, the last one stores the flag; the consumer polls
+// the flag, then fetches): the form of MI355X_MICROARCH.md's table, first row.  Both stages now signal through the columns themselves:
+// "The hand-off without flags" below.
 #ifndef MH_ZV_TWO_STAGE
 #define MH_ZV_TWO_STAGE 1
 #endif
@@ -1295,9 +1293,9 @@ struct ZvColRegs
             commit<D + 1, K>(row);
       }
    }
-   // the sentinel back into the columns this wave has consumed (self-signalling stage one, below)
+   // the sentinel back into these columns once they have been consumed (the hand-off without flags, below)
    template <int D = 0>
-   MH_DEV void reset(T *dst, int lane) const
+   static MH_DEV void reset(T *dst, int lane)
    {
       if constexpr (D < ZvCols<TP>::NV && sizeof(T) == 8)
       {
@@ -1307,25 +1305,26 @@ struct ZvColRegs
       }
    }
 };
-// ---- Stage one without a flag (round 5): the limb columns SIGNAL THEMSELVES.
-// Stamps of the flag form (profiles/r05_zv_phase_stamps_prepass_rcp.txt): limb barrier of the bias job 7.00 us, columns stored 7.35, stores
-// acknowledged 7.75, flag A stored 7.90, seen by the inertia job 8.30, columns fetched 8.95 -- two round trips on the producer's side (drain,
-// flag) and two on the consumer's (poll, fetch) for 15 KB.  Each element of a column is ONE aligned 8-byte store and one 8-byte load: a
-// reader sees either what was there before or the value, never a mixture.  So the hand-off matrix holds a SENTINEL between launches -- a
+// ---- The hand-off without flags: the columns SIGNAL THEMSELVES.
+// Stamps of stage one's flag form (profiles/r05_zv_phase_stamps_prepass_rcp.txt): limb barrier of the bias job 7.00 us, columns stored 7.35,
+// stores acknowledged 7.75, flag A stored 7.90, seen by the inertia job 8.30, columns fetched 8.95 -- two round trips on the producer's side
+// (drain, flag) and two on the consumer's (poll, fetch) for 15 KB.  Each element of a column is ONE aligned 8-byte store and one 8-byte load:
+// a reader sees either what was there before or the value, never a mixture.  So the hand-off matrix holds a SENTINEL between launches -- a
 // signalling-NaN bit pattern, which no arithmetic instruction can produce (tau - h comes out of a v_add_f64: a NaN result is quieted) --,
-// the producer just stores its columns (sc1, no drain, no count, no flag) and every consumer wave polls THE COLUMNS of its own limbs (sc1
-// loads) until no lane that holds a configuration reads the sentinel any more: one round trip behind the store's arrival.  The wave then
-// writes the sentinel back (sc1; ordered behind its own loads of the same addresses; the next launch on the stream starts behind this
-// kernel's end).  The bit patterns are compared as integers (the build's -ffinite-math-only knows no NaN values).
-// What the epoch in the flag used to give for free -- a producer that publishes AFTER its consumer gave up cannot be taken for the next
-// launch's -- is kept by a poison word: a consumer that runs into the wall-clock limit sets it (device word flags[ZV_POISON_WORD] of the
-// context, and error[1] in mapped host memory beside the error word), every later consumer of the context gives up at once (NaN rows,
-// MH_ERR_HIP at the next synchronisation point) until the host has seen error[1], waited for the device, refilled the matrix with
-// sentinels and cleared both (mh_api.hip: zv_launch).  Stage two (the trunk's columns under flag B) has a microsecond of slack and stays
-// as it was.
-#ifndef MH_ZV_SELF_SIGNAL
-#define MH_ZV_SELF_SIGNAL 1 // 0: stage one under flag A, as in round 4 (A/B measurements)
-#endif
+// the producer just stores its columns (sc1, no drain, no count, no flag) and every consumer wave polls THE COLUMNS it needs (sc1 loads)
+// until no lane that holds a configuration reads the sentinel any more: one round trip behind the store's arrival.  The sentinel is then
+// written back (sc1; the next launch on the stream starts behind this kernel's end): the limbs' columns by the one wave that reads them,
+// right behind its own loads of the same addresses; the trunk's, which all four waves read, by one wave behind the barrier that closes the
+// fold and the outward sweep.  The bit patterns are compared as integers (the build's -ffinite-math-only knows no NaN values).
+// What an epoch in a flag gave for free -- a producer that publishes AFTER its consumer gave up cannot be taken for the next launch's -- is
+// kept by a poison word: a consumer that runs into the wall-clock limit sets it (device word flags[ZV_POISON_WORD] of the context, and
+// error[1] in mapped host memory beside the error word), every later consumer of the context gives up at once (NaN rows, MH_ERR_HIP at the
+// next synchronisation point) until the host has seen error[1], waited for the device, refilled the matrix with sentinels and cleared both
+// (mh_api.hip: zv_launch).  A replay of a captured launch needs nothing: the matrix is all sentinels again when the kernel ends.
+// Stage two, the trunk's nine columns of the humanoid, kept its flag B at first ("a microsecond of slack").  The relay, the wrench duties
+// and the pre-passes took that slack away: on profiles/r05_zv_phase_stamps_self_signal.txt every wave of the inertia job sat behind its
+// early limbs' fold waiting for flag B (drain 0.3 us, flag, poll, and only then the fetch: two dependent round trips for 4.6 KB).  Now the
+// trunk's columns are requested where the first look at flag B was, are in flight during the early limbs' fold and are looked at behind it.
 constexpr unsigned long long ZV_SENTINEL = 0x7ff4a5a57ff4a5a5ull; // (both halves equal: the host fills with a 32-bit pattern)
 constexpr int ZV_POISON_WORD = 3;                                  // index into the context's flag words (group 0's line)
 template <typename T>
@@ -1336,54 +1335,71 @@ MH_DEV bool zv_is_sentinel(T v)
    else
       return false;
 }
-template <class TP, typename T, int OWNER>
-MH_DEV bool zv_cols_pending(const ZvColRegs<TP, T, OWNER> &c)
+// (whatever arrives in this matrix from now on may be a late producer's: nothing of it is trusted until the host has refilled it)
+MH_DEV void zv_give_up(const ZvSync &sy)
 {
-   bool p = false;
-#pragma unroll
-   for (int i = 0; i < ZvColRegs<TP, T, OWNER>::count(); i++)
-      p = p || zv_is_sentinel(c.r[i]);
-   return p;
+   if ((threadIdx.x & 63) == 0)
+   {
+      __hip_atomic_store(sy.error, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sy.error + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(sy.flags + ZV_POISON_WORD, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+   }
 }
-// the limb columns of wave OWNER into its lanes' LDS rows, polled until they are all there; false: gave up (wall-clock limit, or the
-// context is poisoned)
+// One set of columns (OWNER 0-3: that wave's limbs'; -1: the trunk's) on its way from the matrix to the lane's LDS row, in three steps so
+// that other work can sit between them: issue (the loads, not waited for), settle (the first look; while a lane that holds a configuration
+// still reads the sentinel: sleep, load again, under the wall-clock limit -- false: gave up, the context is poisoned) and commit.
 template <class TP, typename T, int OWNER>
-MH_DEV bool zv_take_cols(const ZvSync &sy, const T *src, T *reset, lds_ptr<T> row, int lane, bool active, int poison)
+struct ZvColPoll
 {
    ZvColRegs<TP, T, OWNER> c;
-   bool ok = poison == 0;
-   if (ok)
+   MH_DEV bool pending(bool active) const
    {
-      c.issue(src, lane);
-      if (__builtin_amdgcn_ballot_w64(active && zv_cols_pending(c)) != 0)
+      bool p = false;
+#pragma unroll
+      for (int i = 0; i < ZvColRegs<TP, T, OWNER>::count(); i++)
+         p = p || zv_is_sentinel(c.r[i]);
+      return __builtin_amdgcn_ballot_w64(active && p) != 0; // (inactive lanes of a ragged group never count: nobody looks at what they loaded)
+   }
+   MH_DEV void issue(const T *src, int lane) { c.issue(src, lane); }
+   MH_DEV bool settle(const ZvSync &sy, const T *src, int lane, bool active)
+   {
+      if (pending(active))
       {
          const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
          for (;;)
          {
             __builtin_amdgcn_s_sleep(1);
             c.issue(src, lane);
-            if (__builtin_amdgcn_ballot_w64(active && zv_cols_pending(c)) == 0)
+            if (!pending(active))
                break;
             if (__builtin_amdgcn_s_memrealtime() - t0 > (unsigned long long)sy.wait_ticks)
             {
-               ok = false;
-               break;
+               zv_give_up(sy);
+               return false;
             }
          }
       }
+      return true;
    }
-   if (ok)
+   MH_DEV void commit(lds_ptr<T> row) const { c.commit(row); }
+};
+// the limb columns of wave OWNER into its lanes' LDS rows, the sentinel back into the matrix; false: gave up (wall-clock limit, or the
+// context is poisoned)
+template <class TP, typename T, int OWNER>
+MH_DEV bool zv_take_cols(const ZvSync &sy, const T *src, T *reset, lds_ptr<T> row, int lane, bool active, int poison)
+{
+   ZvColPoll<TP, T, OWNER> p;
+   if (poison != 0)
    {
-      c.commit(row);
-      c.reset(reset, lane);
+      zv_give_up(sy);
+      return false;
    }
-   else if ((threadIdx.x & 63) == 0)
-   { // (whatever arrives in this matrix from now on may be a late producer's: nothing of it is trusted until the host has refilled it)
-      __hip_atomic_store(sy.error, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(sy.error + 1, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-      __hip_atomic_store(sy.flags + ZV_POISON_WORD, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-   }
-   return ok;
+   p.issue(src, lane);
+   if (!p.settle(sy, src, lane, active))
+      return false;
+   p.commit(row);
+   p.c.reset(reset, lane);
+   return true;
 }
 // columns of this group's hand-off matrix from the lane's LDS row, write-through.  SHARE = -1: the trunk dofs' columns; 0..2: the limb dofs'
 // columns number % 3 == SHARE.  All LDS reads first, then all stores (read and stored one by one -- the columns picked by a run-time
@@ -1484,9 +1500,6 @@ MH_DEV void zv_bias_group2(const Args<T> &A, long k, lds_ptr<T> lds, T *taup, co
    const long cfg0 = k * 64;
    const int rows = (int)(A.B - cfg0 < 64 ? A.B - cfg0 : 64);
    const bool active = lane < rows;
-   __shared__ int zv_limb_waves; // waves 1-3 that have published their columns and seen them acknowledged
-   if (threadIdx.x == 0)
-      zv_limb_waves = 0;
    ZV_STAMP(0, 0);
    RowRegs<T, MH_ZV_TAU_LATE ? Tree<TP>::total_dofs() : 1, 256> rtau;
    if constexpr (MH_ZV_TAU_LATE)
@@ -1519,36 +1532,36 @@ MH_DEV void zv_bias_group2(const Args<T> &A, long k, lds_ptr<T> lds, T *taup, co
    __syncthreads(); // the limbs' entries of every row are final; the limbs' wrenches are parked for the trunk pass
    ZV_STAMP(0, 3);
    T *const dst = taup + k * 64 * nv;
-   int *const flags = sy.flags + k * ZV_SYNC_STRIDE;
    // (Storing tau - h of a joint to its column the moment it is formed -- no publishing pass at all -- was measured: the stores slow the
    // limbs' walks by 0.45 us, flag A comes 0.3 us earlier, flag B 0.4 later, the step takes as long: profiles/r04_zv_two_stage.txt.)
+   // Every column signals itself (see "The hand-off without flags" above): the waves store and are done -- no drain, no count, no flag.
    if (wave == 0)
    {
       if (active)
          rnea_trunk_roots<TP, T, CX>(cx);
       ZV_STAMP(0, 4);
+#ifndef MH_ZV_TEST_NO_FLAG // (tests/test_gpu_edge_cases.py builds ONE code object with this macro into a scratch directory: a producer that never
+                          // signals -- here, one that never publishes --, to see the consumer give up, write NaN rows and raise the error word)
       if constexpr (MH_ZV_TAU_LATE)
          ZvPublish<TP, T, -1>::run_minus(dst, lt + lane * nv, lx + lane * nv, lane);
       else
          ZvPublish<TP, T, -1>::run(dst, lx + lane * nv, lane);
+#endif
+      // (Nothing is waited for.  The marker keeps this wave's stores a tail of their own: hipcc 7.2 otherwise sinks the four waves' column
+      // stores into ONE tail whose addresses travel through selects and readfirstlane, and on the torso's tree wave 3 reached that tail
+      // with the address of its first column never set -- a store to a wild address, seen as an illegal memory access.)
+      asm volatile("; trunk columns stored" ::: "memory");
       ZV_STAMP(0, 5);
 #ifdef MH_ZV_TEST_FLAG_BEFORE_DRAIN // tests/test_handoff_isa.py compiles this ONCE, to ISA text only, to prove that its checks catch a flag
-                                    // that can overtake its columns; it is never linked into anything
+                                    // stored behind columns nobody has drained (one that can overtake them); it is never linked into anything
       if (lane == 0)
-         __hip_atomic_store(flags, sy.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+         __hip_atomic_store(sy.flags + k * ZV_SYNC_STRIDE, sy.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 #endif
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the columns have been acknowledged by memory ...
-      ZV_STAMP(0, 6);
-#if !defined(MH_ZV_TEST_FLAG_BEFORE_DRAIN) && !defined(MH_ZV_TEST_NO_FLAG)
-      if (lane == 0) // ... so flag B, stored by the wave that stored them, is never seen ahead of them
-         __hip_atomic_store(flags, sy.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-      ZV_STAMP(0, 7);
    }
    else
    {
       ZV_STAMP(0, 4);
-#if !(MH_ZV_SELF_SIGNAL && defined(MH_ZV_TEST_NO_FLAG)) // (the test build of a producer that never signals: here, one that never publishes)
+#ifndef MH_ZV_TEST_NO_FLAG
       if constexpr (MH_ZV_TAU_LATE)
       {
          if (wave == 1)
@@ -1566,20 +1579,9 @@ MH_DEV void zv_bias_group2(const Args<T> &A, long k, lds_ptr<T> lds, T *taup, co
          ZvPublish<TP, T, 2>::run(dst, lx + lane * nv, lane);
 #endif
       ZV_STAMP(0, 5);
-#if !MH_ZV_SELF_SIGNAL
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // this wave's columns have been acknowledged ...
-      ZV_STAMP(0, 6);
-      int before = 0;
-      if (lane == 0) // ... and the wave that learns it is the last of the three to say so stores flag A for all of them
-         before = __hip_atomic_fetch_add(&zv_limb_waves, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifndef MH_ZV_TEST_NO_FLAG // (tests/test_gpu_edge_cases.py builds ONE code object with this macro into a scratch directory: a producer that never
-                          // signals, to see the consumer give up, write NaN rows and raise the error word -- never shipped)
-      if (lane == 0 && before == 2)
-         __hip_atomic_store(flags + 1, sy.epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
-#endif // (self-signalling: the columns are their own flag -- nothing to wait for, nothing to count)
-      ZV_STAMP(0, 7);
    }
+   ZV_STAMP(0, 6); // (the slots of the drain and the flag this job no longer has: tools/exp_zv_probe.py prints them beside "copied")
+   ZV_STAMP(0, 7);
 }
 
 // bias job of group k: taup rows = tau - RNEA(q, qd, 0); A.in3 = tau
@@ -1766,25 +1768,6 @@ MH_DEV void zv_aba_group(const Args<T> &A, long k, lds_ptr<T> lds, const T *taup
    ZV_STAMP(1, 11);
 }
 
-// polls one word of the group's flag line until it holds this launch's epoch (see zv_wait): true when seen, false after the wall-clock limit
-MH_DEV bool zv_wait_word(const ZvSync &sy, const int *f)
-{
-   if (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == sy.epoch)
-      return true;
-   const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-   for (;;)
-   {
-      __builtin_amdgcn_s_sleep(1);
-      if (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == sy.epoch)
-         return true;
-      if (__builtin_amdgcn_s_memrealtime() - t0 > (unsigned long long)sy.wait_ticks)
-      {
-         if ((threadIdx.x & 63) == 0)
-            __hip_atomic_store(sy.error, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-         return false;
-      }
-   }
-}
 // inertia job of group k, two-stage hand-off (see zv_bias_group2)
 template <class TP, typename T, bool STEP>
 MH_DEV void zv_aba_group2(const Args<T> &A, long k, lds_ptr<T> lds, const T *taup, const ZvSync &sy)
@@ -1804,10 +1787,8 @@ MH_DEV void zv_aba_group2(const Args<T> &A, long k, lds_ptr<T> lds, const T *tau
    if (threadIdx.x == 0)
       zv_gave_up = 0;
    ZV_STAMP(1, 0);
-#if MH_ZV_SELF_SIGNAL
    // the context's poison word (see zv_take_cols), requested with the rows and long there when it is looked at
    const int poison = __hip_atomic_load(sy.flags + ZV_POISON_WORD, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#endif
    zv_stage_rows<T, Tree<TP>::total_cfgs(), 256>(lq, A.q + cfg0 * nq, rows);
    __syncthreads();
    ZV_STAMP(1, 1);
@@ -1837,84 +1818,47 @@ MH_DEV void zv_aba_group2(const Args<T> &A, long k, lds_ptr<T> lds, const T *tau
       rqd.issue(A.qd + cfg0 * nv, rows);
    // ---- stage one of the hand-off: the bias efforts of this wave's limbs, straight to its lanes' rows (nobody else reads those entries)
    const T *const src = taup + k * 64 * nv;
-   const int *const flags = sy.flags + k * ZV_SYNC_STRIDE;
+   T *const back = const_cast<T *>(src);
    const lds_ptr<T> row = lx + lane * nv;
-#if MH_ZV_SELF_SIGNAL
    bool seen;
-   {
-      T *const back = const_cast<T *>(src);
-      if (wave == 0)
-         seen = zv_take_cols<TP, T, 0>(sy, src, back, row, lane, active, poison);
-      else if (wave == 1)
-         seen = zv_take_cols<TP, T, 1>(sy, src, back, row, lane, active, poison);
-      else if (wave == 2)
-         seen = zv_take_cols<TP, T, 2>(sy, src, back, row, lane, active, poison);
-      else
-         seen = zv_take_cols<TP, T, 3>(sy, src, back, row, lane, active, poison);
-   }
-   ZV_STAMP(1, 5);
-#else
-   bool seen = zv_wait_word(sy, flags + 1);
-   ZV_STAMP(1, 5);
    if (wave == 0)
-   {
-      ZvColRegs<TP, T, 0> c;
-      c.issue(src, lane), c.commit(row);
-   }
+      seen = zv_take_cols<TP, T, 0>(sy, src, back, row, lane, active, poison);
    else if (wave == 1)
-   {
-      ZvColRegs<TP, T, 1> c;
-      c.issue(src, lane), c.commit(row);
-   }
+      seen = zv_take_cols<TP, T, 1>(sy, src, back, row, lane, active, poison);
    else if (wave == 2)
-   {
-      ZvColRegs<TP, T, 2> c;
-      c.issue(src, lane), c.commit(row);
-   }
+      seen = zv_take_cols<TP, T, 2>(sy, src, back, row, lane, active, poison);
    else
+      seen = zv_take_cols<TP, T, 3>(sy, src, back, row, lane, active, poison);
+   ZV_STAMP(1, 5);
+   // ---- stage two rides in the fold: the trunk's bias efforts, requested here (in flight during the early limbs' fold, across its LDS-only
+   // barriers: a look is a round trip to memory, 0.45-0.65 us on the stamps), looked at behind the early limbs' fold -- the same polling as
+   // stage one's, should they not be there yet -- and stored behind the late limbs'
+   struct TrunkTau : ZvNoHook
    {
-      ZvColRegs<TP, T, 3> c;
-      c.issue(src, lane), c.commit(row);
-   }
-#endif
-   // a first look at flag B, in flight during the early limbs' fold (a poll is a round trip to memory: 0.45 us on the stamps)
-   const int b_first = __hip_atomic_load(flags, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      mutable ZvColPoll<TP, T, -1> p;
+      const ZvSync &sy;
+      const T *src;
+      lds_ptr<T> row;
+      int lane;
+      bool &seen;
+      MH_DEV void after_early() const
+      { // (called by the lanes that hold a configuration only)
+         if (seen)
+            seen = p.settle(sy, src, lane, true);
+      }
+      MH_DEV void after_late() const { p.commit(row); } // (every wave stores the trunk's entries of its own lanes' rows: the same values four times)
+   };
+   const TrunkTau trunk{{}, {}, sy, src, row, lane, seen};
+   trunk.p.issue(src, lane);
    zv_lds_barrier(); // nobody reads the exchange area's inertias any more (the fold's records go over them)
    ZV_STAMP(1, 6);
    asm volatile("" ::: "memory");
-   // ---- stage two rides in the fold: the trunk's bias efforts, requested behind the early limbs' fold, stored behind the late limbs'
-   struct TrunkTau : ZvNoHook
-   {
-      mutable ZvColRegs<TP, T, -1> c;
-      const ZvSync &sy;
-      const int *flags;
-      const T *src;
-      lds_ptr<T> row;
-      int lane, b_first;
-      bool &seen;
-      MH_DEV void after_early() const
-      {
-         if (b_first != sy.epoch)
-            seen = zv_wait_word(sy, flags) && seen;
-         c.issue(src, lane);
-      }
-      MH_DEV void after_late() const { c.commit(row); } // (every wave stores the trunk's entries of its own lanes' rows: the same values four times)
-   };
-   const TrunkTau trunk{{}, {}, sy, flags, src, row, lane, b_first, seen};
    if (active) // (lane 0 of every wave is active: each wave reaches the barriers the fold carries in here)
       zv_fold_out<TP, 0, T, CX>(cx, trunk);
    ZV_STAMP(1, 10);
    if (!seen && lane == 0)
       zv_gave_up = 1;
    __syncthreads();
-   // The flags go back to zero once their columns have been consumed: a captured launch is replayed with the SAME epoch (hipGraph), and a flag
-   // left standing from the previous replay would let this job read the previous replay's columns.  (Stream order puts the reset before the
-   // next launch's bias job; every wave's polls and loads lie in front of the barrier above.)
-   if (threadIdx.x == 0)
-   {
-      __hip_atomic_store(const_cast<int *>(flags), 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      __hip_atomic_store(const_cast<int *>(flags) + 1, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-   }
    if (zv_gave_up)
    { // (the whole workgroup takes this branch) columns that never came: NaN instead of accelerations formed from whatever the scratch
      // matrix holds; the error word is set, the host reports MH_ERR_HIP at its next synchronisation point (mh_api.hip)
@@ -1927,8 +1871,13 @@ MH_DEV void zv_aba_group2(const Args<T> &A, long k, lds_ptr<T> lds, const T *tau
          for (int i = threadIdx.x; i < rows * nv; i += 256)
             reinterpret_cast<unsigned long long *>(A.qd_next)[cfg0 * nv + i] = 0x7ff8000000000000ull;
       }
-      return;
+      return; // (the sentinels are NOT written back: the host refills the whole matrix before it clears the poison word)
    }
+   // The sentinel goes back into the trunk's columns -- all 64 lanes of each, whatever the group's size -- now that all four waves have taken
+   // them: every wave's loads of them were waited for in front of the barrier above, and stream order puts these stores in front of the next
+   // launch's bias job (a replay of a captured launch included: there is no epoch in this hand-off).
+   if (wave == 0)
+      ZvColRegs<TP, T, -1>::reset(back, lane);
    if constexpr (STEP)
    { // fused simulation step (a kernel of its own, spec_zv_kernel<.., STEP = true>: the plain call's code stays as it is): q (lq) and the fresh accelerations (lres) of the 64 configurations sit in LDS, the velocities arrive in the
      // rows the bias efforts no longer need (lx) -- integrated in place (MultiBodySystemStateIntegrator.java:365-441, 503-575, 710-733)

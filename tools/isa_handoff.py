@@ -13,8 +13,8 @@ registered code object and checks the instruction stream itself:
   give-up    the wall-clock limit's error word is stored at system scope (sc0 sc1).
 
 Code objects with identity index maps run the hand-off in two stages (limb columns under flag A, trunk columns under flag B: see
-check_two_stage); the stream tells which form it is.  Round 5: stage one needs no flag -- the limb columns signal themselves (the matrix
-holds a signalling-NaN sentinel between launches, the consumer polls the columns): see check_self_signal.
+check_two_stage); the stream tells which form it is.  Since then both stages have lost their flags -- the columns signal themselves (the
+matrix holds a signalling-NaN sentinel between launches, the consumer polls the columns): see check_self_signal.
 
 usage: python tools/isa_handoff.py <libmecano_hip_topo_*.so | file.s> ...
 """
@@ -143,63 +143,82 @@ def is_self_signal(instrs) -> bool:
     return any(SENTINEL_HALF in a for _, a in instrs)
 
 
+def _column_store_runs(instrs):
+    """[first, last] of every run of consecutive scoped 8-byte stores (published columns, sentinels written back)"""
+    runs = []
+    for i, (op, a) in enumerate(instrs):
+        if op == "global_store_dwordx2" and scope(a) != "":
+            if runs and i - runs[-1][1] <= 3:
+                runs[-1][1] = i
+            else:
+                runs.append([i, i])
+    return runs
+
+
+def _flag_stores(instrs):
+    """Flag-sized stores of ANY scope (a compiler may re-scope a flag) that are not the give-up's three: the error word and the poison
+    word's host copy (sc0 sc1) and the device poison word right behind them"""
+    system = [i for i, (op, a) in enumerate(instrs) if op == "global_store_dword" and scope(a) == "sc0 sc1"]
+    return [i for i, (op, a) in enumerate(instrs) if op == "global_store_dword" and i not in system and not any(0 < i - s <= 4 for s in system)]
+
+
+def drained_and_flagged_runs(instrs) -> list:
+    """[(first, last, drain, flag)] of the runs of column stores that are followed by their wave's drain (`s_waitcnt vmcnt(0)` within 40
+    instructions) and then by a flag-sized store (within 120): the hand-off under a flag.  A two-stage kernel has none any more."""
+    drains = [i for i, (op, a) in enumerate(instrs) if op == "s_waitcnt" and re.search(r"vmcnt\(0\)", a)]
+    flags = _flag_stores(instrs)
+    out = []
+    for first, last in _column_store_runs(instrs):
+        nd = next((d for d in drains if last < d <= last + 40), None)
+        nf = None if nd is None else next((f for f in flags if nd < f <= nd + 120), None)
+        if nf is not None:
+            out.append((first, last, nd, nf))
+    return out
+
+
 def check_self_signal(instrs) -> list:
-    """Two-stage hand-off whose FIRST stage has no flag (mh_zv_kernels.h, "Stage one without a flag"):
-      producer   every published column store is write-through (global_store_dwordx2 sc1).  A run of column stores that is followed by its
-                 wave's drain (`s_waitcnt vmcnt(0)` within 40 instructions) is the trunk's (stage two, flag B): no flag-sized store between the
-                 run and the drain, an sc1 flag store within 120 instructions behind it; there is at least one such run.  The other runs are
-                 the limbs' self-signalling columns (and, in the consumer, the sentinels written back): no rule beyond sc1 -- each element is
-                 one aligned 8-byte store, valid by itself;
-      consumer   the limb columns are POLLED: per wave a loop with s_sleep, sc1 column loads and a comparison with the sentinel, under a
-                 wall-clock limit (s_memrealtime); flag B is polled with global_load_dword sc1 (a first look and a loop); every 8-byte
-                 load from the first polled column to the last column load is sc1;
+    """Two-stage hand-off WITHOUT flags (mh_zv_kernels.h, "The hand-off without flags"): the limbs' and the trunk's columns signal themselves.
+      producer   every published column store is write-through (global_store_dwordx2 sc1), and so is every sentinel written back -- each
+                 element is one aligned 8-byte store, valid by itself.  No flag-sized store of any scope behind a run of column stores: right
+                 behind it (no drain in between) such a store is a flag that can overtake its columns; behind the run's drain it is the
+                 flag form this kernel no longer has.  The only flag-sized stores are the give-up's;
+      consumer   the columns are POLLED: a loop with s_sleep, sc1 column loads, a comparison with the sentinel and the wall-clock limit
+                 (s_memrealtime) per wave and stage.  EIGHT loops: the four waves run different code in both stages -- in stage one each
+                 wave takes the columns of ITS limbs, and stage two sits in the bias fold, which is instantiated per wave (zv_fold_out<W>) --,
+                 so the compiler emits each wave's loop of each stage once.  The poison word is looked at with global_load_dword sc1;
+                 every 8-byte load from the first polled column to the last column load is sc1;
       give-up    error word and the poison word's host copy at system scope (sc0 sc1), the device poison word right behind them (sc1)."""
     bad = []
     idx = lambda pred: [i for i, (op, a) in enumerate(instrs) if pred(op, a)]
     drains = idx(lambda op, a: op == "s_waitcnt" and re.search(r"vmcnt\(0\)", a))
     small_stores = idx(lambda op, a: op == "global_store_dword")
-    flag_stores = [i for i in small_stores if scope(instrs[i][1]) == "sc1"]
+    flag_stores = _flag_stores(instrs)
     col_stores = idx(lambda op, a: op == "global_store_dwordx2" and scope(a) != "")
     col_loads = idx(lambda op, a: op == "global_load_dwordx2" and scope(a) == "sc1")
     polls = idx(lambda op, a: op == "global_load_dword" and scope(a) == "sc1")
     sleeps = idx(lambda op, a: op == "s_sleep")
     sentinels = idx(lambda op, a: SENTINEL_HALF in a)
-    # ---- producer
+    # ---- producer (and the sentinels the consumer writes back)
     if not col_stores:
         bad.append("producer: no scoped column store (global_store_dwordx2 sc1) found")
     for i in col_stores:
         if scope(instrs[i][1]) != "sc1":
             bad.append(f"producer: column store #{i} is {scope(instrs[i][1])}, not write-through (sc1)")
-    runs = []  # [first, last] of consecutive column stores
-    for i in col_stores:
-        if runs and i - runs[-1][1] <= 3:
-            runs[-1][1] = i
-        else:
-            runs.append([i, i])
-    flagged = 0
-    for first, last in runs:
+    for first, last in _column_store_runs(instrs):
         nd = next((d for d in drains if last < d <= last + 40), None)
-        nf = next((f for f in flag_stores if f > last), None)
-        if nd is None:
-            if nf is not None and nf - last <= 40:
-                bad.append(f"producer: flag-sized sc1 store #{nf} right behind the column stores #{first}..#{last} without a drain: the flag can overtake its columns")
-            continue
-        early = [f for f in small_stores if last < f < nd]
-        if early:
-            bad.append(f"producer: flag-sized store #{early[0]} sits between column store #{last} and its wave's drain #{nd}: the flag can overtake its columns")
-            continue
-        nf = next((f for f in flag_stores if f > nd), None)
-        if nf is not None and nf - nd <= 120:
-            flagged += 1
-    if not flagged:
-        bad.append("producer: no run of column stores that is drained and then flagged (stage two: the trunk's columns under flag B)")
+        nf = next((f for f in flag_stores if last < f <= last + 40), None)
+        if nf is not None and (nd is None or nf < nd):
+            bad.append(f"producer: flag-sized store #{nf} right behind the column stores #{first}..#{last} without a drain: the flag can overtake its columns")
+    for first, last, nd, nf in drained_and_flagged_runs(instrs):
+        bad.append(f"producer: the column stores #{first}..#{last} are drained (#{nd}) and then flagged (#{nf}): the columns of this form signal themselves")
     # ---- consumer
-    loops = [s for s in sleeps if [l for l in col_loads if s < l <= s + 30] and [c for c in sentinels if s < c <= s + 60]
+    # (the sentinel's literal: in the loop, or moved into a scalar register right in front of it -- the compiler does that in stage two)
+    loops = [s for s in sleeps if [l for l in col_loads if s < l <= s + 30] and [c for c in sentinels if s - 40 < c <= s + 60]
              and [i for i, (op, a) in enumerate(instrs) if s < i <= s + 90 and op == "s_memrealtime"]]
-    if len(loops) < 4:
-        bad.append(f"consumer: expected a polling loop (s_sleep, sc1 column loads, comparison with the sentinel, wall-clock limit) for each of the four waves, found {len(loops)}")
-    if len(polls) < 3:
-        bad.append(f"consumer: expected the poison word's load and a first look + polling loop on flag B (global_load_dword sc1), found {len(polls)}")
+    if len(loops) < 8:
+        bad.append(f"consumer: expected a polling loop (s_sleep, sc1 column loads, comparison with the sentinel, wall-clock limit) for each of the four waves in each of the two stages, found {len(loops)}")
+    if not polls:
+        bad.append("consumer: the poison word is not looked at (global_load_dword sc1)")
     if not col_loads:
         bad.append("consumer: no sc1 column load (global_load_dwordx2 sc1) found")
     else:
@@ -210,7 +229,7 @@ def check_self_signal(instrs) -> list:
     system = [f for f in small_stores if scope(instrs[f][1]) == "sc0 sc1"]
     if not system:
         bad.append("give-up: the error word is not stored at system scope (sc0 sc1)")
-    elif not [f for f in flag_stores if any(0 < f - s <= 4 for s in system)]:
+    elif not [f for f in small_stores if scope(instrs[f][1]) == "sc1" and any(0 < f - s <= 4 for s in system)]:
         bad.append("give-up: no device poison word (global_store_dword sc1) stored right behind the error word")
     return bad
 
