@@ -161,9 +161,8 @@ struct ContextState
    Workspace step;
    // mh_body_poses_* / mh_geometric_jacobian_*: the SoA form of AoS outputs, which a transposition then brings to the caller's rows
    Workspace kin;
-   // mh_aba_constrained_* / mh_constraint_impulse_* and their _between_ forms: W and its factor, the right-hand side, the per-body motions
-   // of the free launch, the wrenches of the second launch, a row of zeros; between two moving bodies also the per-body twists and the
-   // poses of the target frames in their bases (constraint_scratch_entries)
+   // mh_aba_constrained_* / mh_constraint_impulse_* / mh_contact_impulse_* and their _between_ forms: the blocks of con_scratch
+   // (mh_launch_plans.h)
    Workspace con;
    // bias-split forward dynamics (mh_zv_kernels.h): tau - h(q, qd) rows, one flag per 64 configurations (a launch stores its epoch there),
    // an error word in mapped host memory that a timed-out wait sets (read at the next call of the model)
@@ -1709,54 +1708,40 @@ mh_status gravity_gradient_impl(mh_model_t model, int64_t B, const T *q, const d
 // Inverse apparent inertia of K target bodies (MultiBodyResponseCalculator): run-time-topology kernel, which writes every entry of W --
 // no memset in front of it.  Targets and their frames travel as kernel arguments; which bodies the sweeps visit is decided on the device
 // from the model's Euler tour, so the call uploads nothing and allocates nothing beyond the workspace mh_reserve covers.
-static double rotation_error(const double *X)
-{
-   const double det = X[0] * (X[4] * X[8] - X[5] * X[7]) - X[1] * (X[3] * X[8] - X[5] * X[6]) + X[2] * (X[3] * X[7] - X[4] * X[6]);
-   double worst = std::fabs(det - 1.0);
-   for (int r = 0; r < 3; r++)
-      for (int s = 0; s < 3; s++)
-      {
-         double g = 0.0;
-         for (int t = 0; t < 3; t++)
-            g += X[3 * t + r] * X[3 * t + s];
-         worst = std::max(worst, std::fabs(g - (r == s ? 1.0 : 0.0)));
-      }
-   return worst; // (NaN where an entry is)
-}
-// The frame of a target in the canonical after-joint frame of its body: (body-fixed -> canonical) o (target frame -> body-fixed), where
-// X (NULL: the identity) is the caller's pose of the target frame in the body-fixed frame of engine body e; e = -1 is the root body,
-// whose body-fixed frame is the root frame itself.  False, with `off` set, where the 3 x 3 part of X is no rotation (a NaN fails too).
+// The launch: targets in range with their canonical frames (target_frame), opts resolved to its context (begin_call).
+// w_soa: W goes out as [entries][B] whatever the call's layout (scratch of the constrained dynamics)
 template <typename T>
-static bool target_frame(const mh_model *m, int e, const double *X, T pose[12], double &off)
+mh_status apparent_inertia_launch(mh_model *model, int64_t B, const T *q, int n_targets, const int32_t *joints, const double (*canon)[12], bool coupled,
+                                  const mh_options &opts, T *W_out, bool w_soa)
 {
-   static_assert(mh::MC_PF == mh::MC_RF + 9, "the body-fixed frame's rotation and translation are one pose of 12 numbers");
-   const double ident[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
-   if (!X)
-      X = ident;
-   off = rotation_error(X);
-   if (!(off <= 1.0e-9))
-      return false;
-   const double *c = e < 0 ? ident : &m->consts[(size_t)e * mh::MC_STRIDE + mh::MC_RF];
-   for (int r = 0; r < 3; r++)
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = launch_parts(model->cu_count, L, n_targets);
+   if (mh_status st = ensure_bytes(model->ws, lane_ws_bytes(model->resp_slots, L, parts, sizeof(T))); st != MH_OK)
+      return st;
+   mh::RespArgs<T> G{};
+   for (int k = 0; k < n_targets; k++)
    {
-      double p = c[9 + r];
-      for (int t = 0; t < 3; t++)
-         p += c[3 * r + t] * X[9 + t];
-      pose[9 + r] = (T)p;
-      for (int s = 0; s < 3; s++)
-      {
-         double v = 0.0;
-         for (int t = 0; t < 3; t++)
-            v += c[3 * r + t] * X[3 * t + s];
-         pose[3 * r + s] = (T)v;
-      }
+      G.tgt[k] = model->engine_of[joints[k]];
+      for (int r = 0; r < 12; r++)
+         G.pose[k][r] = (T)canon[k][r];
    }
-   return true;
+   mh::Args<T> &A = G.a;
+   A = make_args<T>(model, B, opts);
+   A.q = q, A.out = W_out;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = L.lanes;
+   set_strides(G.w_bs, G.w_es, w_soa || opts.layout == MH_LAYOUT_SOA, B, 36L * n_targets * (coupled ? n_targets : 1));
+   G.info = model->d_resp_info;
+   G.slots = model->resp_slots, G.a_base = model->resp_a_base, G.u_base = model->resp_u_base;
+   G.n_targets = n_targets, G.coupled = coupled;
+   hipLaunchKernelGGL((mh::apparent_inertia_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
 }
 template <typename T>
 mh_status apparent_inertia_impl(mh_model_t model, int64_t B, const T *q, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
-                                int32_t blocks, const mh_options *opts_in, T *W_out, bool w_soa = false)
-{ // w_soa: W goes out as [entries][B] whatever the call's layout (scratch of the constrained dynamics)
+                                int32_t blocks, const mh_options *opts_in, T *W_out)
+{
    mh_options opts;
    mh_status st = begin_call(model, B, opts_in, opts);
    if (st != MH_OK)
@@ -1767,47 +1752,27 @@ mh_status apparent_inertia_impl(mh_model_t model, int64_t B, const T *q, int32_t
       return fail(MH_ERR_INVALID_ARGUMENT, "unknown blocks value %d", blocks);
    if (!target_joints)
       return fail(MH_ERR_INVALID_ARGUMENT, "target_joints is NULL");
-   mh::RespArgs<T> G{};
+   double canon[MH_MAX_APPARENT_TARGETS][12];
    for (int k = 0; k < n_targets; k++)
    {
       const int i = target_joints[k];
       if (i < 0 || i >= model->n)
          return fail(MH_ERR_INVALID_ARGUMENT, "target %d names joint %d (the model has %d joints)", k, i, model->n);
-      const int e = model->engine_of[i];
-      G.tgt[k] = e;
-      double off;
-      if (!target_frame<T>(model, e, target_poses ? target_poses + 12 * k : nullptr, G.pose[k], off))
-         return fail(MH_ERR_INVALID_ARGUMENT, "target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", k, off);
+      if ((st = target_frame<double>(model, model->engine_of[i], target_poses ? target_poses + 12 * k : nullptr, canon[k], nullptr, k)) != MH_OK)
+         return st;
    }
    if (B == 0)
       return MH_OK;
    if (!q || !W_out)
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL configuration / output pointer");
    const bool coupled = blocks == MH_APPARENT_BLOCKS_COUPLED;
-   const long wsize = coupled ? 36L * n_targets * n_targets : 36L * n_targets;
    {
       const InRange in{"q", q, (size_t)B * model->nq * sizeof(T)};
-      const OutRange out{"W_out", W_out, (size_t)B * wsize * sizeof(T), 0u};
+      const OutRange out{"W_out", W_out, (size_t)B * 36 * n_targets * (coupled ? n_targets : 1) * sizeof(T), 0u};
       if ((st = check_aliasing("mh_apparent_inertia_inverse", &in, 1, &out, 1)) != MH_OK)
          return st;
    }
-   const Launch L = plan_launch(model->cu_count, B);
-   const int parts = launch_parts(model->cu_count, L, n_targets);
-   st = ensure_bytes(model->ws, lane_ws_bytes(model->resp_slots, L, parts, sizeof(T)));
-   if (st != MH_OK)
-      return st;
-   mh::Args<T> &A = G.a;
-   A = make_args<T>(model, B, opts);
-   A.q = q, A.out = W_out;
-   A.ws = (T *)model->ws.ptr;
-   A.ws_stride = L.lanes;
-   set_strides(G.w_bs, G.w_es, w_soa || opts.layout == MH_LAYOUT_SOA, B, wsize);
-   G.info = model->d_resp_info;
-   G.slots = model->resp_slots, G.a_base = model->resp_a_base, G.u_base = model->resp_u_base;
-   G.n_targets = n_targets, G.coupled = coupled;
-   hipLaunchKernelGGL((mh::apparent_inertia_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
-   HIP_TRY(hipGetLastError());
-   return MH_OK;
+   return apparent_inertia_launch<T>(model, B, q, n_targets, target_joints, canon, coupled, opts, W_out, false);
 }
 // Poses of frames fixed in bodies and geometric Jacobians between bodies (mh_kinematics_kernels.h): run-time-topology kernels, which write
 // every entry of their outputs -- no memset in front of them.  Targets, bases and frames travel as kernel arguments.  The kernels store
@@ -1851,9 +1816,8 @@ mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: base %d names joint %d (the model has %d joints; -1 is the root body)", call, k, ib, model->n);
       G.tgt[k] = i < 0 ? -1 : model->engine_of[i];
       G.base[k] = ib < 0 ? -1 : model->engine_of[ib];
-      double off;
-      if (!target_frame<T>(model, G.tgt[k], target_poses ? target_poses + 12 * k : nullptr, G.pose[k], off))
-         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", call, k, off);
+      if ((st = target_frame<T>(model, G.tgt[k], target_poses ? target_poses + 12 * k : nullptr, G.pose[k], call, k)) != MH_OK)
+         return st;
    }
    if (B == 0)
       return MH_OK;
@@ -1919,19 +1883,43 @@ mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int
    }
    return MH_OK;
 }
-// Forward dynamics under bilateral constraints on body frames, and its velocity-level twin (mh_constraint_kernels.h): launches composed
-// on the caller's stream -- the free forward dynamics with per-body accelerations (velocity form: the inverse dynamics with per-body
-// twists), the COUPLED inverse apparent inertia into SoA scratch, the constraint kernel (right-hand side, L D L^T in place, lambda, the
-// wrenches of the next launch), and forward dynamics again, whichever plan mh_aba_* takes.  Scratch per configuration, in elements of the
-// call's precision: (6 K)^2 for W, 6 K for the right-hand side, 6 n_joints each for the per-body motions and the wrenches, nv zeros.
-// The _between_ entry points with n_app = K + (non-root bases) frames in W: (6 n_app)^2 + 6 K + 18 n_joints + nv + 12 K -- the per-body
-// twists and the K relative poses come on top.  mh_reserve covers the rooted form at K = MH_MAX_CONSTRAINT_TARGETS; the first call of a
-// larger need grows the buffer (ensure_bytes), after which the calls only enqueue.
-static size_t constraint_scratch_entries(const mh_model *m, int K, int n_app = 0)
+// Forward dynamics under bilateral constraints on body frames, its velocity-level twin (mh_constraint_kernels.h) and the frictional contact
+// impulses (mh_contact_kernels.h): launches composed on the caller's stream -- the free forward dynamics with per-body accelerations
+// (velocity level: the inverse dynamics with per-body twists), the COUPLED inverse apparent inertia at the call's frames into SoA scratch,
+// the solve kernel, which leaves the wrenches of the next launch, and forward dynamics again, whichever plan mh_aba_* takes.  Frames and
+// scratch, rooted and _between_ alike: FrameList and con_scratch (mh_launch_plans.h); mh_reserve covers the rooted form at K = 8, the first
+// call of a larger need grows the buffer (ensure_bytes), then the calls only enqueue.
+static const double kNoGravity[3] = {0.0, 0.0, 0.0};
+template <class ARGS>
+void close_frames(const mh_model *m, FrameList &F, ARGS &G)
+{ // closes the list and hands it to a solve kernel's arguments: the targets' poses, relative to their body-fixed frames, in the call's precision
+   frame_list_close(*m, F);
+   std::copy_n(F.tgt, F.K, G.tgt), std::copy_n(F.ext, F.K, G.ext), std::copy_n(F.base, F.K, G.base), std::copy_n(F.bext, F.K, G.bext);
+   std::copy_n(F.bslot, F.K, G.bslot), std::copy_n(&F.pose[0][0], 12 * F.K, &G.pose[0][0]);
+   G.K = F.K, G.n_app = F.n_app;
+}
+// per-body twists of (q, qd): the inverse dynamics' outward sweep (its efforts go to qd_out, which the last launches overwrite)
+template <typename T>
+mh_status body_twists(mh_model_t model, int64_t B, const T *q, const T *qd, const mh_options &of, T *out, T *body)
 {
-   if (n_app > K)
-      return 36 * (size_t)n_app * n_app + 18 * (size_t)K + 18 * (size_t)m->n + (size_t)m->nv;
-   return 36 * (size_t)K * K + 6 * (size_t)K + 12 * (size_t)m->n + (size_t)m->nv;
+   return launch<T>(ALGO_RNEA, model, B, q, qd, qd, kNoGravity, nullptr, &of, out, body_outputs<T>(nullptr, body));
+}
+// the change of velocity: forward dynamics at rest, without gravity, under the impulses alone, into a cleared qd_out (it skips entries no
+// joint owns); then qd_out += qd
+template <typename T>
+mh_status impulses_to_qd(mh_model_t model, int64_t B, const T *q, const T *qd, const T *wrench, T *zeros, const mh_options &of, T *out)
+{
+   hipStream_t stream = (hipStream_t)of.stream;
+   const long n_out = (long)B * (long)model->nv;
+   HIP_TRY(hipMemsetAsync(zeros, 0, (size_t)n_out * sizeof(T), stream));
+   HIP_TRY(hipMemsetAsync(out, 0, (size_t)n_out * sizeof(T), stream));
+   const mh_status st = launch<T>(ALGO_ABA, model, B, q, zeros, zeros, kNoGravity, wrench, &of, out);
+   if (st != MH_OK || n_out == 0)
+      return st;
+   hipLaunchKernelGGL((mh::add_in_place_kernel<T>), dim3((int)std::min<long>((n_out + 255) / 256, (long)model->cu_count * 8)), dim3(256), 0, stream, out,
+                      qd, n_out);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
 }
 // between: the _between_ entry points (base_joints may still be NULL = every base the root: the rooted launches, bit for bit)
 template <typename T>
@@ -1959,85 +1947,47 @@ mh_status constrained_impl(bool velocity, mh_model_t model, int64_t B, const T *
       return fail(MH_ERR_INVALID_ARGUMENT, "%s: gravity is NULL and no root acceleration is set", call);
    mh::ConRelArgs<T> G{}; // (the rooted launch takes its ConArgs part)
    const int K = n_targets;
-   int rows_total = 0, n_app = K;
-   int32_t app_joints[MH_MAX_APPARENT_TARGETS];
-   double app_poses[MH_MAX_APPARENT_TARGETS][12];
+   FrameList F{K, K};
    for (int k = 0; k < K; k++)
    {
-      const int i = target_joints[k], rk = target_rows[k], ib = base_joints ? base_joints[k] : -1;
-      if (i < 0 || i >= model->n)
-         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d names joint %d (the model has %d joints; the root body is no target)", call, k, i, model->n);
-      if (ib < -1 || ib >= model->n)
-         return fail(MH_ERR_INVALID_ARGUMENT, "%s: base %d names joint %d (the model has %d joints; -1 is the root body)", call, k, ib, model->n);
-      if (ib == i)
-         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d is held against its own body (joint %d): the Jacobian is zero", call, k, i);
-      G.base[k] = ib < 0 ? -1 : model->engine_of[ib], G.bext[k] = ib, G.bslot[k] = -1;
-      app_joints[k] = i;
-      for (int r = 0; r < 12; r++)
-         app_poses[k][r] = target_poses ? target_poses[12 * k + r] : (r == 0 || r == 4 || r == 8 ? 1.0 : 0.0);
+      const int rk = target_rows[k];
+      if ((st = frame_target(*model, F, k, target_joints[k], base_joints ? base_joints[k] : -1, target_poses, call, false)) != MH_OK)
+         return st;
       if (rk < 0 || rk > 0x3f)
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: row mask 0x%x has bits beyond the six rows of a frame", call, k, (unsigned)rk);
-      double off;
-      T canonical[12]; // (validates the pose as mh_apparent_inertia_inverse_* does; the kernel takes it relative to the body-fixed frame)
-      if (!target_frame<T>(model, model->engine_of[i], target_poses ? target_poses + 12 * k : nullptr, canonical, off))
-         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", call, k, off);
-      G.tgt[k] = model->engine_of[i], G.ext[k] = i, G.rows[k] = rk;
-      for (int r = 0; r < 12; r++)
-         G.pose[k][r] = target_poses ? (T)target_poses[12 * k + r] : (T)(r == 0 || r == 4 || r == 8 ? 1 : 0);
+      if ((st = target_frame<double>(model, F.tgt[k], F.pose[k], F.app_canon[k], call, k)) != MH_OK)
+         return st;
+      G.rows[k] = rk;
       for (int r = 0; r < 6; r++)
          if ((rk >> r) & 1)
-            G.idx[rows_total++] = (signed char)(6 * k + r);
+            G.idx[G.rows_total++] = (signed char)(6 * k + r);
    }
-   if (rows_total == 0)
+   if (G.rows_total == 0)
       return fail(MH_ERR_INVALID_ARGUMENT, "%s: no row is constrained (every entry of target_rows is 0)", call);
-   for (int k = 0; k < K; k++)
-      if (G.base[k] >= 0)
-      { // one more frame of W per non-root base: its body-fixed frame
-         G.bslot[k] = n_app;
-         app_joints[n_app] = G.bext[k];
-         for (int r = 0; r < 12; r++)
-            app_poses[n_app][r] = r == 0 || r == 4 || r == 8 ? 1.0 : 0.0;
-         n_app++;
-      }
-   const bool rel = n_app > K;
-   G.n_app = n_app;
+   close_frames(model, F, G);
+   const bool rel = F.n_app > K;
    if (B == 0)
       return MH_OK;
    if (!q || !qd || (!velocity && !tau) || !out)
       return fail(MH_ERR_INVALID_ARGUMENT, "%s: NULL state / output pointer", call);
-   const size_t n6 = (size_t)model->n * 6, nv = (size_t)model->nv;
+   const size_t n6 = (size_t)model->n * 6;
    {
-      const size_t bv = (size_t)B * nv * sizeof(T), bd = (size_t)B * 6 * K * sizeof(T);
+      const size_t bv = (size_t)B * model->nv * sizeof(T), bd = (size_t)B * 6 * K * sizeof(T);
       const InRange ins[6] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"qd", qd, bv}, {"tau", tau, bv}, {"f_ext", f_ext, (size_t)B * n6 * sizeof(T)},
                               {"active", active, (size_t)B * K * sizeof(int32_t)}, {velocity ? "v_des" : "a_des", des, bd}};
       const OutRange outs[2] = {{velocity ? "qd_out" : "qdd_out", out, bv, 0u}, {velocity ? "impulse_out" : "lambda_out", lambda_out, bd, 0u}};
       if ((st = check_aliasing(call, ins, 6, outs, 2)) != MH_OK)
          return st;
    }
-   st = ensure_bytes(model->con, (size_t)B * constraint_scratch_entries(model, K, n_app) * sizeof(T));
-   if (st != MH_OK)
+   const ConScratch S = con_scratch(model->n, model->nv, K, F.n_app, true);
+   if ((st = ensure_bytes(model->con, (size_t)B * S.total * sizeof(T))) != MH_OK)
       return st;
-   T *W = (T *)model->con.ptr, *rhs = W + (size_t)B * 36 * n_app * n_app, *body = rhs + (size_t)B * 6 * K, *wrench = body + (size_t)B * n6,
-     *zeros = wrench + (size_t)B * n6;
-   T *twist = zeros + (size_t)B * nv, *zpose = twist + (size_t)B * n6; // (relative form only)
-   hipStream_t stream = (hipStream_t)o.stream;
-   const double no_gravity[3] = {0.0, 0.0, 0.0};
    mh_options of = o; // the launches below see the state as it is: both switches of the inverse dynamics on
-   of.consider_coriolis = 1, of.consider_accelerations = 1;
-   if (velocity)
-   { // per-body twists of (q, qd): the inverse dynamics' outward sweep (its efforts go to qd_out, which the last launches overwrite)
-      of.use_root_acceleration = 0;
-      st = launch<T>(ALGO_RNEA, model, B, q, qd, qd, no_gravity, nullptr, &of, out, body_outputs<T>(nullptr, body));
-   }
-   else
-      st = launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &of, out, body_outputs<T>(body, rel ? twist : nullptr));
-   if (st != MH_OK)
-      return st;
-   if (rel)
-      st = apparent_inertia_impl<T>(model, B, q, n_app, app_joints, &app_poses[0][0], MH_APPARENT_BLOCKS_COUPLED, &o, W, true);
-   else
-      st = apparent_inertia_impl<T>(model, B, q, K, target_joints, target_poses, MH_APPARENT_BLOCKS_COUPLED, &o, W, true);
-   if (st != MH_OK)
+   of.consider_coriolis = 1, of.consider_accelerations = 1, of.use_root_acceleration = velocity ? 0 : o.use_root_acceleration;
+   T *const con = (T *)model->con.ptr, *const W = con + B * S.W, *const body = con + B * S.body, *const wrench = con + B * S.wrench, *const twist = con + B * S.twist;
+   st = velocity ? body_twists<T>(model, B, q, qd, of, out, body)
+                 : launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &of, out, body_outputs<T>(body, rel ? twist : nullptr));
+   if (st != MH_OK || (st = apparent_inertia_launch<T>(model, B, q, F.n_app, F.app_joints, F.app_canon, true, o, W, true)) != MH_OK)
       return st;
    const bool soa = o.layout == MH_LAYOUT_SOA;
    G.m = dev_model<T>(model);
@@ -2046,7 +1996,7 @@ mh_status constrained_impl(bool velocity, mh_model_t model, int64_t B, const T *
    set_strides(G.q_bs, G.q_es, soa, B, model->nq);
    G.body = body, G.fext = velocity ? nullptr : f_ext, G.wrench = wrench;
    set_strides(G.f_bs, G.f_es, soa, B, (long)n6);
-   G.W = W, G.rhs = rhs;
+   G.W = W, G.rhs = con + B * S.rhs, G.twist = twist, G.zpose = con + B * S.zpose; // (rooted: two empty blocks, which its launch does not take)
    G.active = active;
    set_strides(G.a_bs, G.a_es, soa, B, K);
    G.des = des, G.lambda = lambda_out;
@@ -2054,34 +2004,18 @@ mh_status constrained_impl(bool velocity, mh_model_t model, int64_t B, const T *
    G.eps = (T)compliance;
    if (!velocity)
       set_root_acceleration(G, o, gravity);
-   G.K = K, G.rows_total = rows_total, G.velocity = velocity;
+   G.velocity = velocity;
    const int grid = (int)std::max<long>(1, std::min<long>(groups_of(B), (long)model->cu_count * 8));
-   G.twist = twist, G.zpose = zpose;
    if (rel)
-      hipLaunchKernelGGL((mh::constraint_solve_kernel<T, true>), dim3(grid), dim3(64), 0, stream, G);
+      hipLaunchKernelGGL((mh::constraint_solve_kernel<T, true>), dim3(grid), dim3(64), 0, (hipStream_t)o.stream, G);
    else
-      hipLaunchKernelGGL((mh::constraint_solve_kernel<T>), dim3(grid), dim3(64), 0, stream, static_cast<const mh::ConArgs<T> &>(G));
+      hipLaunchKernelGGL((mh::constraint_solve_kernel<T>), dim3(grid), dim3(64), 0, (hipStream_t)o.stream, static_cast<const mh::ConArgs<T> &>(G));
    HIP_TRY(hipGetLastError());
    if (!velocity)
       return launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, wrench, &of, out);
-   // the change of velocity: forward dynamics at rest, without gravity, with the impulses as the only wrenches; then qd_out += qd
-   // (entries of qd_out no joint owns are cleared first: forward dynamics does not write them)
-   HIP_TRY(hipMemsetAsync(zeros, 0, (size_t)B * nv * sizeof(T), stream));
-   HIP_TRY(hipMemsetAsync(out, 0, (size_t)B * nv * sizeof(T), stream));
-   st = launch<T>(ALGO_ABA, model, B, q, zeros, zeros, no_gravity, wrench, &of, out);
-   if (st != MH_OK || nv == 0)
-      return st;
-   const long n_out = (long)B * (long)nv;
-   hipLaunchKernelGGL((mh::add_in_place_kernel<T>), dim3((int)std::min<long>((n_out + 255) / 256, (long)model->cu_count * 8)), dim3(256), 0, stream, out,
-                      qd, n_out);
-   HIP_TRY(hipGetLastError());
-   return MH_OK;
+   return impulses_to_qd<T>(model, B, q, qd, wrench, con + B * S.zeros, of, out);
 }
-// Frictional contact impulses (mh_contact_kernels.h): the composition of the velocity form above with the contact solve between the
-// launches.  Scratch as the rooted form's: the 6 K rows behind W hold b and the normals in the target frames.
-// between: mh_contact_impulse_between_* (base_joints may still be NULL = every base the root: the rooted launches, bit for bit).  With
-// n_app = K + (non-root bases) frames in W the scratch is (6 n_app)^2 + 6 K + 12 n_joints + nv + 12 K per configuration: the K relative
-// poses come last.  mh_reserve covers the rooted form; the first call of a larger need grows the buffer (ensure_bytes).
+// Frictional contact impulses: the velocity form above with the contact solve between the launches; rhs holds b and the normals in the target frames
 template <typename T>
 mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
                        const double *mu, const T *normals, const int32_t *active, const T *v_normal, const T *impulse_init, const double &compliance,
@@ -2105,98 +2039,54 @@ mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int
       return fail(MH_ERR_INVALID_ARGUMENT, "%s: n_iterations = %d is outside 1 ... %d", call, n_iterations, MH_MAX_CONTACT_ITERATIONS);
    mh::ContactRelArgs<T> G{}; // (the rooted launch takes its ContactArgs part)
    const int K = n_targets;
-   int n_app = K;
-   int32_t app_joints[MH_MAX_APPARENT_TARGETS];
-   double app_poses[MH_MAX_APPARENT_TARGETS][12];
+   FrameList F{K, K};
    for (int k = 0; k < K; k++)
    {
-      const int i = target_joints[k], ib = base_joints ? base_joints[k] : -1;
-      if (i < 0 || i >= model->n)
-         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d names joint %d (the model has %d joints; the root body is no target)", call, k, i, model->n);
-      if (ib < -1 || ib >= model->n)
-         return fail(MH_ERR_INVALID_ARGUMENT, "%s: base %d names joint %d (the model has %d joints; -1 is the root body)", call, k, ib, model->n);
-      if (ib == i)
-         return fail(MH_ERR_INVALID_ARGUMENT, "%s: contact %d is between a body and itself (joint %d): the Jacobian is zero", call, k, i);
-      G.base[k] = ib < 0 ? -1 : model->engine_of[ib], G.bext[k] = ib, G.bslot[k] = -1;
-      app_joints[k] = i;
-      for (int r = 0; r < 12; r++)
-         app_poses[k][r] = target_poses ? target_poses[12 * k + r] : (r == 0 || r == 4 || r == 8 ? 1.0 : 0.0);
+      if ((st = frame_target(*model, F, k, target_joints[k], base_joints ? base_joints[k] : -1, target_poses, call, true)) != MH_OK)
+         return st;
       uint64_t mu_bits; // (read as bits: the translation unit is compiled with -ffinite-math-only)
       std::memcpy(&mu_bits, &mu[k], sizeof mu_bits);
       if (mu_bits >= 0x7ff0000000000000ull && mu_bits != 0x8000000000000000ull) // infinite, NaN or negative
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the friction coefficient must be finite and >= 0", call, k);
       if (mu[k] > (double)std::numeric_limits<T>::max()) // (finite in fp64, not in T)
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the friction coefficient %g is beyond the range of the call's precision", call, k, mu[k]);
-      double off;
-      T canonical[12];
-      if (!target_frame<T>(model, model->engine_of[i], target_poses ? target_poses + 12 * k : nullptr, canonical, off))
-         return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", call, k, off);
-      G.tgt[k] = model->engine_of[i], G.ext[k] = i;
+      if ((st = target_frame<double>(model, F.tgt[k], F.pose[k], F.app_canon[k], call, k)) != MH_OK)
+         return st;
       G.mu[k] = (T)(mu[k] > 1.0 ? 1.0 / mu[k] : mu[k]); // contact_project works a cone wider than 45 degrees with 1 / mu: no finite mu overflows
       G.wide |= mu[k] > 1.0 ? 1u << k : 0u;
-      for (int r = 0; r < 12; r++)
-         G.pose[k][r] = target_poses ? (T)target_poses[12 * k + r] : (T)(r == 0 || r == 4 || r == 8 ? 1 : 0);
    }
-   for (int k = 0; k < K; k++)
-      if (G.base[k] >= 0)
-      { // one more frame of W per non-root base: its body-fixed frame
-         G.bslot[k] = n_app;
-         app_joints[n_app] = G.bext[k];
-         for (int r = 0; r < 12; r++)
-            app_poses[n_app][r] = r == 0 || r == 4 || r == 8 ? 1.0 : 0.0;
-         n_app++;
-      }
-   const bool rel = n_app > K;
-   G.n_app = n_app;
+   close_frames(model, F, G);
+   const bool rel = F.n_app > K;
    if (B == 0)
       return MH_OK;
    if (!q || !qd || !out)
       return fail(MH_ERR_INVALID_ARGUMENT, "%s: NULL state / output pointer", call);
-   const size_t n6 = (size_t)model->n * 6, nv = (size_t)model->nv;
+   const size_t n6 = (size_t)model->n * 6;
    {
-      const size_t bv = (size_t)B * nv * sizeof(T), bk = (size_t)B * K * sizeof(T), bd = 6 * bk;
+      const size_t bv = (size_t)B * model->nv * sizeof(T), bk = (size_t)B * K * sizeof(T), bd = 6 * bk;
       const InRange ins[6] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"qd", qd, bv}, {"normals", normals, 3 * bk},
                               {"active", active, (size_t)B * K * sizeof(int32_t)}, {"v_normal", v_normal, bk}, {"impulse_init", impulse_init, bd}};
       const OutRange outs[3] = {{"qd_out", out, bv, 0u}, {"impulse_out", impulse_out, bd, 1u << 5}, {"residual_out", residual_out, (size_t)B * sizeof(T), 0u}};
       if ((st = check_aliasing(call, ins, 6, outs, 3)) != MH_OK)
          return st;
    }
-   // (the relative form: the 12 K relative poses behind the rooted layout at ld = 6 n_app)
-   const size_t entries = rel ? 36 * (size_t)n_app * n_app + 18 * (size_t)K + 2 * n6 + nv : constraint_scratch_entries(model, K);
-   st = ensure_bytes(model->con, (size_t)B * entries * sizeof(T));
-   if (st != MH_OK)
+   const ConScratch S = con_scratch(model->n, model->nv, K, F.n_app, false);
+   if ((st = ensure_bytes(model->con, (size_t)B * S.total * sizeof(T))) != MH_OK)
       return st;
    const ContactPlan P = contact_plan(K, sizeof(T), model->contact_path, model->cu_count, B);
-   const void *kern;
-   if (rel)
-   {
-      if (P.kmax == 4)
-         kern = P.resident ? (const void *)&mh::contact_solve_kernel<T, true, 4, true> : (const void *)&mh::contact_solve_kernel<T, false, 4, true>;
-      else
-         kern = P.resident ? (const void *)&mh::contact_solve_kernel<T, true, 8, true> : (const void *)&mh::contact_solve_kernel<T, false, 8, true>;
-   }
-   else if (P.kmax == 4)
-      kern = P.resident ? (const void *)&mh::contact_solve_kernel<T, true, 4> : (const void *)&mh::contact_solve_kernel<T, false, 4>;
-   else
-      kern = P.resident ? (const void *)&mh::contact_solve_kernel<T, true, 8> : (const void *)&mh::contact_solve_kernel<T, false, 8>;
+   static const void *const kernels[2][2][2] = { // [rel][kmax == 8][resident]
+      {{(const void *)&mh::contact_solve_kernel<T, false, 4>, (const void *)&mh::contact_solve_kernel<T, true, 4>},
+       {(const void *)&mh::contact_solve_kernel<T, false, 8>, (const void *)&mh::contact_solve_kernel<T, true, 8>}},
+      {{(const void *)&mh::contact_solve_kernel<T, false, 4, true>, (const void *)&mh::contact_solve_kernel<T, true, 4, true>},
+       {(const void *)&mh::contact_solve_kernel<T, false, 8, true>, (const void *)&mh::contact_solve_kernel<T, true, 8, true>}}};
+   const void *kern = kernels[rel][P.kmax == 8][P.resident];
    if ((st = raise_lds_limit(model, kern, (size_t)P.lds)) != MH_OK)
       return st;
-   T *W = (T *)model->con.ptr, *rhs = W + (size_t)B * 36 * n_app * n_app, *body = rhs + (size_t)B * 6 * K, *wrench = body + (size_t)B * n6,
-     *zeros = wrench + (size_t)B * n6;
-   T *zpose = zeros + (size_t)B * nv; // (relative form only)
-   hipStream_t stream = (hipStream_t)o.stream;
-   const double no_gravity[3] = {0.0, 0.0, 0.0};
    mh_options of = o;
    of.consider_coriolis = 1, of.consider_accelerations = 1, of.use_root_acceleration = 0;
-   // per-body twists of (q, qd): the inverse dynamics' outward sweep (its efforts go to qd_out, which the last launches overwrite)
-   st = launch<T>(ALGO_RNEA, model, B, q, qd, qd, no_gravity, nullptr, &of, out, body_outputs<T>(nullptr, body));
-   if (st != MH_OK)
-      return st;
-   if (rel)
-      st = apparent_inertia_impl<T>(model, B, q, n_app, app_joints, &app_poses[0][0], MH_APPARENT_BLOCKS_COUPLED, &o, W, true);
-   else
-      st = apparent_inertia_impl<T>(model, B, q, K, target_joints, target_poses, MH_APPARENT_BLOCKS_COUPLED, &o, W, true);
-   if (st != MH_OK)
+   T *const con = (T *)model->con.ptr, *const W = con + B * S.W, *const body = con + B * S.body, *const wrench = con + B * S.wrench;
+   st = body_twists<T>(model, B, q, qd, of, out, body);
+   if (st != MH_OK || (st = apparent_inertia_launch<T>(model, B, q, F.n_app, F.app_joints, F.app_canon, true, o, W, true)) != MH_OK)
       return st;
    const bool soa = o.layout == MH_LAYOUT_SOA;
    G.m = dev_model<T>(model);
@@ -2205,7 +2095,7 @@ mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int
    set_strides(G.q_bs, G.q_es, soa, B, model->nq);
    G.body = body, G.wrench = wrench;
    set_strides(G.f_bs, G.f_es, soa, B, (long)n6);
-   G.W = W, G.Wrel = W, G.zpose = zpose, G.bvec = rhs, G.nvec = rhs + (size_t)B * 3 * K;
+   G.W = W, G.Wrel = W, G.zpose = con + B * S.zpose, G.bvec = con + B * S.rhs, G.nvec = G.bvec + (size_t)B * 3 * K;
    G.active = active, G.v_normal = v_normal;
    set_strides(G.a_bs, G.a_es, soa, B, K);
    G.normals = normals;
@@ -2214,20 +2104,10 @@ mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int
    set_strides(G.d_bs, G.d_es, soa, B, 6L * K);
    G.residual = residual_out;
    G.eps = (T)compliance;
-   G.K = K, G.n_iter = n_iterations;
+   G.n_iter = n_iterations;
    void *args[] = {rel ? (void *)&G : (void *)static_cast<mh::ContactArgs<T> *>(&G)};
-   HIP_TRY(hipLaunchKernel(kern, dim3(P.grid), dim3(64), args, (size_t)P.lds, stream));
-   // the change of velocity: forward dynamics at rest, without gravity, with the impulses as the only wrenches; then qd_out += qd
-   HIP_TRY(hipMemsetAsync(zeros, 0, (size_t)B * nv * sizeof(T), stream));
-   HIP_TRY(hipMemsetAsync(out, 0, (size_t)B * nv * sizeof(T), stream));
-   st = launch<T>(ALGO_ABA, model, B, q, zeros, zeros, no_gravity, wrench, &of, out);
-   if (st != MH_OK || nv == 0)
-      return st;
-   const long n_out = (long)B * (long)nv;
-   hipLaunchKernelGGL((mh::add_in_place_kernel<T>), dim3((int)std::min<long>((n_out + 255) / 256, (long)model->cu_count * 8)), dim3(256), 0, stream, out,
-                      qd, n_out);
-   HIP_TRY(hipGetLastError());
-   return MH_OK;
+   HIP_TRY(hipLaunchKernel(kern, dim3(P.grid), dim3(64), args, (size_t)P.lds, (hipStream_t)o.stream));
+   return impulses_to_qd<T>(model, B, q, qd, wrench, con + B * S.zeros, of, out);
 }
 // Inverse of the joint-space inertia matrix, all columns or a list of them: run-time-topology kernel, which writes every entry of its
 // output -- no memset in front of it.  The listed columns travel as kernel arguments (resolved here to joint and place); the call
@@ -2722,6 +2602,8 @@ mh_status mh_internal_model_table(const mh_model_desc *desc, const char *name, v
 //   "split_rt_shape"   (cu_count, elem, algo 0 | 1 | 2, B, pair): k, mode, lds, grid (a model with a usable split only)
 //   "lane_ws"          (cu_count, B, want): block, grid, lanes of plan_launch; launch_parts; lane_ws_bytes and lane_ws_bound of one slot of
 //                      one byte (the bound with B and want as the largest batch and want)
+//   "constraint_frames" (K, K target joints, K base joints with -1 = the root body, twists wanted 0 | 1): the status of a refused list, or n_app,
+//                      tgt[K], base[K], bslot[K], app_joints[n_app] (FrameList), then the offsets W, rhs, body, wrench, zeros, zpose, twist, total (con_scratch)
 mh_status mh_internal_launch_plan(const mh_model_desc *desc, const char *plan, const int64_t *params, int32_t n_params, void *out, size_t capacity_bytes,
                                   size_t *bytes_out)
 {
@@ -2806,6 +2688,24 @@ mh_status mh_internal_launch_plan(const mh_model_desc *desc, const char *plan, c
          return fail(MH_ERR_INVALID_ARGUMENT, bad, plan);
       const ContactPlan c = contact_plan((int)params[0], (size_t)params[1], (int)params[2], (int)params[3], params[4]);
       w = {c.resident, (int)c.lds, c.per_cu, c.grid, c.kmax};
+   }
+   else if (name == "constraint_frames")
+   {
+      if (n_params < 1 || params[0] < 1 || params[0] > MH_MAX_CONSTRAINT_TARGETS || !takes(2 * (int)params[0] + 2) || !among(n_params - 1, {0, 1}))
+         return fail(MH_ERR_INVALID_ARGUMENT, bad, plan);
+      const int K = (int)params[0];
+      auto joint = [&](int i) { return (int)std::clamp<int64_t>(params[i], -2, INT32_MAX); }; // (what no int holds is no joint of any model)
+      FrameList F{K, K};
+      for (int k = 0; k < K; k++)
+         if ((st = frame_target(t, F, k, joint(1 + k), joint(1 + K + k), nullptr, plan, false)) != MH_OK)
+            return st;
+      frame_list_close(t, F);
+      const ConScratch s = con_scratch(t.n, t.nv, K, F.n_app, params[2 * K + 1] != 0);
+      w = {F.n_app};
+      w.insert(w.end(), F.tgt, F.tgt + K), w.insert(w.end(), F.base, F.base + K), w.insert(w.end(), F.bslot, F.bslot + K);
+      w.insert(w.end(), F.app_joints, F.app_joints + F.n_app);
+      for (size_t entry : {s.W, s.rhs, s.body, s.wrench, s.zeros, s.zpose, s.twist, s.total})
+         w.push_back((int)entry);
    }
    else if (name == "lane_ws")
    {
@@ -3266,7 +3166,7 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       if (st != MH_OK)
          return st;
       // mh_aba_constrained_* / mh_constraint_impulse_*: their scratch for the largest target list, under the same cap
-      const size_t con_bytes = (size_t)max_batch * constraint_scratch_entries(m, MH_MAX_CONSTRAINT_TARGETS) * sizeof(double);
+      const size_t con_bytes = (size_t)max_batch * con_scratch(m->n, m->nv, MH_MAX_CONSTRAINT_TARGETS, MH_MAX_CONSTRAINT_TARGETS, false).total * sizeof(double);
       if (con_bytes <= kDerivReserveCap && (st = ensure_bytes(m->con, con_bytes)) != MH_OK)
          return st;
    }

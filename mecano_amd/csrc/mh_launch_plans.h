@@ -12,6 +12,7 @@
 #include "mh_split_kernels.h"
 
 #include <algorithm>
+#include <cassert>
 #include <cstdint>
 #include <vector>
 
@@ -590,5 +591,103 @@ ContactPlan contact_plan(int K, size_t elem, int force, int cu_count, int64_t B)
    p.grid = (int)std::max<long>(1, std::min<long>(groups_of(B), (long)cu_count * p.per_cu));
    p.kmax = K <= 4 ? 4 : 8; // the kernel build: contacts the unrolled loops cover
    return p;
+}
+
+// ---- the constrained and the contact dynamics (mh_constraint_kernels.h, mh_contact_kernels.h), rooted and _between_ forms alike: the
+// frames their inverse apparent inertia W is taken at, and where the launches of one call keep their scratch
+constexpr double kIdentityPose[12] = {1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0}; // R row-major, then p
+double rotation_error(const double *X)
+{
+   const double det = X[0] * (X[4] * X[8] - X[5] * X[7]) - X[1] * (X[3] * X[8] - X[5] * X[6]) + X[2] * (X[3] * X[7] - X[4] * X[6]);
+   double worst = std::fabs(det - 1.0);
+   for (int r = 0; r < 3; r++)
+      for (int s = 0; s < 3; s++)
+      {
+         double g = 0.0;
+         for (int t = 0; t < 3; t++)
+            g += X[3 * t + r] * X[3 * t + s];
+         worst = std::max(worst, std::fabs(g - (r == s ? 1.0 : 0.0)));
+      }
+   return worst; // (NaN where an entry is)
+}
+// The frame of a target in the canonical after-joint frame of its body: (body-fixed -> canonical) o (target frame -> body-fixed), where
+// X (NULL: the identity) is the caller's pose of the target frame in the body-fixed frame of engine body e; e = -1 is the root body,
+// whose body-fixed frame is the root frame itself.  Refused, as target k of `call` (NULL: none named), where the 3 x 3 part of X is no rotation (NaN too).
+template <typename T>
+mh_status target_frame(const ModelTables *m, int e, const double *X, T pose[12], const char *call, int k)
+{
+   static_assert(mh::MC_PF == mh::MC_RF + 9, "the body-fixed frame's rotation and translation are one pose of 12 numbers");
+   if (!X)
+      X = kIdentityPose;
+   const double off = rotation_error(X);
+   if (!(off <= 1.0e-9))
+      return call ? fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", call, k, off)
+                  : fail(MH_ERR_INVALID_ARGUMENT, "target %d: the 3 x 3 part of its pose is not a rotation (off by %.3g > 1e-9)", k, off);
+   const double *c = e < 0 ? kIdentityPose : &m->consts[(size_t)e * mh::MC_STRIDE + mh::MC_RF];
+   for (int r = 0; r < 3; r++)
+   {
+      double p = c[9 + r];
+      for (int t = 0; t < 3; t++)
+         p += c[3 * r + t] * X[9 + t];
+      pose[9 + r] = (T)p;
+      for (int s = 0; s < 3; s++)
+      {
+         double v = 0.0;
+         for (int t = 0; t < 3; t++)
+            v += c[3 * r + t] * X[3 * t + s];
+         pose[3 * r + s] = (T)v;
+      }
+   }
+   return MH_OK;
+}
+// The frames of one call (FrameList F{K, K}): K targets, each held against a base; W's: the targets, then the body-fixed frame of every non-root base
+static_assert(MH_MAX_CONSTRAINT_TARGETS == MH_MAX_CONTACT_TARGETS && 2 * MH_MAX_CONSTRAINT_TARGETS <= MH_MAX_APPARENT_TARGETS, "one list serves both");
+struct FrameList
+{
+   static constexpr int N = MH_MAX_CONSTRAINT_TARGETS, M = MH_MAX_APPARENT_TARGETS;
+   int K, n_app;                                   // targets; frames of W
+   int tgt[N], ext[N], base[N], bext[N], bslot[N]; // per target, as ConRelArgs and ContactRelArgs hold them (mh_constraint_kernels.h),
+   double pose[N][12];                             // and its pose as the caller gave it
+   int32_t app_joints[M];                          // per frame of W: its joint in the caller's order,
+   double app_canon[M][12];                        // and its pose in the canonical frame of its body (target_frame)
+};
+// Target k < K of the list, by its joint and its base's in the caller's order; its pose from `poses` ([K][12], NULL: identities), which the
+// caller checks after its own checks of the target (target_frame of pose[k] into app_canon[k]).  contact: the noun of the own-body refusal.
+mh_status frame_target(const ModelTables &m, FrameList &F, int k, int joint, int base_joint, const double *poses, const char *call, bool contact)
+{
+   if (joint < 0 || joint >= m.n)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d names joint %d (the model has %d joints; the root body is no target)", call, k, joint, m.n);
+   if (base_joint < -1 || base_joint >= m.n)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: base %d names joint %d (the model has %d joints; -1 is the root body)", call, k, base_joint, m.n);
+   if (base_joint == joint)
+      return contact ? fail(MH_ERR_INVALID_ARGUMENT, "%s: contact %d is between a body and itself (joint %d): the Jacobian is zero", call, k, joint)
+                     : fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d is held against its own body (joint %d): the Jacobian is zero", call, k, joint);
+   F.tgt[k] = m.engine_of[joint], F.ext[k] = F.app_joints[k] = joint;
+   F.base[k] = base_joint < 0 ? -1 : m.engine_of[base_joint], F.bext[k] = base_joint, F.bslot[k] = -1;
+   std::copy_n(poses ? poses + 12 * k : kIdentityPose, 12, F.pose[k]);
+   return MH_OK;
+}
+// Closes a list whose K targets are resolved: one more frame of W per non-root base
+void frame_list_close(const ModelTables &m, FrameList &F)
+{
+   for (int k = 0; k < F.K; k++)
+      if (F.base[k] >= 0)
+      {
+         assert(F.n_app < MH_MAX_APPARENT_TARGETS); // K targets and at most one base each: n_app <= 2 K <= MH_MAX_APPARENT_TARGETS
+         F.app_joints[F.bslot[k] = F.n_app++] = F.bext[k];
+         target_frame<double>(&m, F.base[k], nullptr, F.app_canon[F.bslot[k]], nullptr, k);
+      }
+}
+// The scratch of one call (mh_model::con), blocks of [entries][B]: offsets and total per configuration, in elements, with the totals of
+// include/mecano_hip.h.  zpose and twist exist only with a base that is not the root (n_app > K), twist only where the call wants it.
+struct ConScratch
+{
+   size_t W, rhs, body, wrench, zeros, zpose, twist, total;
+};
+ConScratch con_scratch(int n_joints, int nv, int K, int n_app, bool wants_twists)
+{
+   const size_t n6 = 6 * (size_t)n_joints, rel = n_app > K;
+   const size_t rhs = 36 * (size_t)n_app * n_app, body = rhs + 6 * (size_t)K, zeros = body + 2 * n6, zpose = zeros + (size_t)nv, twist = zpose + rel * 12 * (size_t)K;
+   return {0, rhs, body, body + n6, zeros, zpose, twist, twist + (rel && wants_twists ? n6 : 0)};
 }
 } // namespace

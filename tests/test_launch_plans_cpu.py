@@ -1,5 +1,6 @@
 """The launch planners (mecano_amd/csrc/mh_launch_plans.h: dfs_frames, dfs_choose, dfs_geometry, split_rt_plan, split_rt_records,
-split_rt_shape, the lane-workspace arithmetic), read on the CPU through mh_internal_launch_plan: no device is needed, none is used.
+split_rt_shape, the lane-workspace arithmetic, the frame list and the scratch of the constrained and the contact dynamics), read on the CPU
+through mh_internal_launch_plan: no device is needed, none is used.
 
 PINNED: every plan below equals, word for word, what the statements of dfs_plan, split_rt_plan, split_rt_upload_meta, dfs_choose, dfs_setup
 and launch_split_rt produced before they moved out of mh_api.hip (tests/golden/launch_plans.json, written by
@@ -81,6 +82,8 @@ class Planner:
         self.meta.setflags(write=False)
         self.parent, self.type, self.nch = self.meta[:, MI_PARENT], self.meta[:, MI_TYPE], self.meta[:, MI_NCH]
         self.children = [[int(c) for c in np.flatnonzero(self.parent == e)] for e in range(self.n)]
+        st, self.engine_of = table_status(lib, self.d, "engine_of", np.int32)  # caller's joint -> engine index
+        assert st == 0
 
     def status(self, plan, *params):
         p = (ctypes.c_int64 * max(1, len(params)))(*params)
@@ -440,6 +443,119 @@ def test_batches_of_one_count_of_waves_per_cu_get_the_plans_of_their_largest(pla
                 for call in CHOICE_CALLS:
                     got, rep = choice(B, call), choice(representative, call)
                     assert np.array_equal(got[same], rep[same]) and got[grid] <= rep[grid], (name, cu, max_batch, B, call)
+
+
+# ------------------------------------------------------------------------------------------------ constraint and contact frames, their scratch
+FRAME_MODELS = ("humanoid30", "one_revolute", "every_kind_permuted")
+MAX_TARGETS = 8  # MH_MAX_CONSTRAINT_TARGETS = MH_MAX_CONTACT_TARGETS
+BLOCKS = ("W", "rhs", "body", "wrench", "zeros", "zpose", "twist")
+MIXED = ([6, 19, 12, 23], [12, 23, -1, 3])  # the lists of tests/test_gpu_contact_between.py
+
+
+def frames_status(P, targets, bases, twists):
+    K = len(targets)
+    st, w = P.status("constraint_frames", K, *targets, *bases, twists)
+    if st != 0:
+        return st, None
+    n_app = int(w[0])
+    at = np.cumsum([1, K, K, K, n_app, len(BLOCKS), 1])
+    assert at[-1] == len(w)
+    tgt, base, bslot, app_joints, offsets, total = (w[a:b] for a, b in zip(at[:-1], at[1:]))
+    return st, {"n_app": n_app, "tgt": tgt.tolist(), "base": base.tolist(), "bslot": bslot.tolist(), "app_joints": app_joints.tolist(),
+                "offsets": dict(zip(BLOCKS, (int(x) for x in offsets))), "total": int(total[0])}
+
+
+def frames(P, targets, bases, twists=0):
+    st, f = frames_status(P, targets, bases, twists)
+    assert st == 0, (P.name, targets, bases, P.lib.mh_last_error().decode())
+    return f
+
+
+def lists_of(P, K, nonroot):
+    """K targets of which the first `nonroot` are held against another joint's body; a 1-joint model has no other joint."""
+    if P.n == 1:
+        return ([0] * K, [-1] * K) if nonroot == 0 else None
+    targets = [1 + k % (P.n - 1) for k in range(K)]
+    return targets, [0] * nonroot + [-1] * (K - nonroot)
+
+
+def header_total(n, nv, K, n_app, twists):
+    """include/mecano_hip.h: the scratch per configuration of the rooted calls, of the relative constraints, of the relative contacts"""
+    if n_app == K:
+        return 36 * K * K + 6 * K + 12 * n + nv
+    return 36 * n_app * n_app + 18 * K + (18 if twists else 12) * n + nv
+
+
+def test_frame_lists_of_the_humanoid(planners):
+    P = planners["humanoid30"]
+    eng = lambda joints: [-1 if j < 0 else int(P.engine_of[j]) for j in joints]
+    f = frames(P, [19], [-1])
+    assert (f["n_app"], f["tgt"], f["base"], f["bslot"], f["app_joints"]) == (1, eng([19]), [-1], [-1], [19])
+    f = frames(P, [23], [19])
+    assert (f["n_app"], f["tgt"], f["base"], f["bslot"], f["app_joints"]) == (2, eng([23]), eng([19]), [1], [23, 19])
+    targets, others = list(range(3, 11)), list(range(13, 21))
+    f = frames(P, targets, [-1] * 8)
+    assert (f["n_app"], f["tgt"], f["base"], f["bslot"], f["app_joints"]) == (8, eng(targets), [-1] * 8, [-1] * 8, targets)
+    f = frames(P, targets, others)
+    assert (f["n_app"], f["tgt"], f["base"], f["bslot"], f["app_joints"]) == (16, eng(targets), eng(others), list(range(8, 16)), targets + others)
+    f = frames(P, *MIXED)
+    assert (f["n_app"], f["tgt"], f["base"], f["bslot"], f["app_joints"]) == (7, eng(MIXED[0]), eng(MIXED[1]), [4, 5, -1, 6], MIXED[0] + [12, 23, 3])
+    f = frames(P, [6] * 4 + [19] * 4, [12] * 4 + [23] * 4)  # a base that appears twice still gets a frame per appearance
+    assert f["n_app"] == 16 and f["bslot"] == list(range(8, 16)) and f["app_joints"][8:] == [12] * 4 + [23] * 4
+
+
+def test_frame_lists_hold_engine_indices(planners):
+    P = planners["every_kind_permuted"]
+    assert not np.array_equal(P.engine_of, np.arange(P.n))  # the model is here for its permuted engine order
+    targets = list(range(P.n))[:MAX_TARGETS]
+    bases = [(j + 1) % P.n if k % 2 else -1 for k, j in enumerate(targets)]
+    f = frames(P, targets, bases)
+    assert f["tgt"] == [int(P.engine_of[j]) for j in targets]
+    assert f["base"] == [-1 if b < 0 else int(P.engine_of[b]) for b in bases]
+    assert f["app_joints"] == targets + [b for b in bases if b >= 0]
+    assert [s for s in f["bslot"] if s >= 0] == list(range(len(targets), f["n_app"]))
+
+
+@pytest.mark.parametrize("name", FRAME_MODELS)
+def test_frame_lists_refuse_what_the_calls_refuse(planners, name):
+    P = planners[name]
+    for targets, bases in (([P.n], [-1]), ([-1], [-1]), ([0], [P.n]), ([0], [-2]), ([0], [0]), ([0, 0, 1 << 40], [-1] * 3), ([0, 0], [-1, -(1 << 40)])):
+        assert frames_status(P, targets, bases, 0)[0] == 1, (targets, bases)
+        assert "constraint_frames: " in P.lib.mh_last_error().decode()
+    assert frames_status(P, [0], [0], 1)[0] == 1 and "is held against its own body (joint 0)" in P.lib.mh_last_error().decode()
+    assert frames_status(P, [0], [-1], 0)[0] == 0
+    # the parameter list itself: K, K targets, K bases, the flag
+    for params in ((), (0, 0), (MAX_TARGETS + 1,) + (0,) * (2 * MAX_TARGETS + 3), (1, 0, -1), (1, 0, -1, 2), (1, 0, -1, 0, 0), (2, 0, -1, 0), (-1, 0, 0, 0)):
+        assert P.status("constraint_frames", *params)[0] == 1, params
+        assert "does not take these parameters" in P.lib.mh_last_error().decode()
+
+
+@pytest.mark.parametrize("name", FRAME_MODELS)
+def test_scratch_totals_are_the_headers_and_the_blocks_tile_them(planners, name):
+    P = planners[name]
+    n, nv = P.n, P.scalars["nv"]
+    rooted = {}
+    for K in range(1, MAX_TARGETS + 1):
+        for nonroot in range(K + 1):
+            lists = lists_of(P, K, nonroot)
+            if lists is None:
+                continue
+            for twists in (0, 1):
+                f = frames(P, *lists, twists)
+                n_app, rel, where = f["n_app"], nonroot > 0, (name, K, nonroot, twists)
+                assert n_app == K + nonroot, where
+                assert f["total"] == header_total(n, nv, K, n_app, twists), where
+                # the seven blocks: one behind the other from 0 to the total in some order, an unused one empty
+                size = {"W": 36 * n_app * n_app, "rhs": 6 * K, "body": 6 * n, "wrench": 6 * n, "zeros": nv, "zpose": 12 * K if rel else 0,
+                        "twist": 6 * n if rel and twists else 0}
+                spans = sorted((f["offsets"][b], f["offsets"][b] + size[b]) for b in BLOCKS)
+                assert spans[0][0] == 0 and spans[-1][1] == f["total"], where
+                assert all(a[1] <= b[0] for a, b in zip(spans, spans[1:])), where         # pairwise disjoint
+                assert sum(e - s for s, e in spans) == f["total"], where                  # ... and no gap
+                if nonroot == 0:
+                    rooted[K] = f["total"]
+    # mh_reserve sets the rooted form aside at the largest list: no shorter list needs more
+    assert all(rooted[K] <= rooted[MAX_TARGETS] for K in rooted)
 
 
 # ------------------------------------------------------------------------------------------------ the entry point's own arguments

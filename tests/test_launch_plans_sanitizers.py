@@ -1,9 +1,10 @@
-"""The launch planners (mecano_amd/csrc/mh_launch_plans.h) under AddressSanitizer + UndefinedBehaviorSanitizer: index arithmetic over the
-body records -- the knapsack's tables of n * (budget + 1) entries, the segment table of the tree split, the patches of the record sets.  A
-small stand-alone program includes the header, holds a few descriptions as plain C++ arrays (the stored ones of
-tests/golden/model_tables_models.json, the humanoid, and the 128-body tree, whose knapsack tables at 80 slots are the largest), runs every
-planner at the budgets, CU counts, batches and switches of tests/test_launch_plans_cpu.py and reads every result end to end (hipcc builds
-it here for the host; nothing touches a device and nothing is preloaded).  Exit status 0 and an empty stderr is the assertion."""
+"""The launch planners (mecano_amd/csrc/mh_launch_plans.h) under AddressSanitizer + UndefinedBehaviorSanitizer: index arithmetic over the body
+records -- the knapsack's tables of n * (budget + 1) entries, the segment table of the tree split, the patches of the record sets -- and
+the fixed arrays of the constraint and contact frame lists, indexed with the caller's joints.  A small stand-alone program includes the
+header, holds a few descriptions as plain C++ arrays (the stored ones of tests/golden/model_tables_models.json, the humanoid, and the
+128-body tree, whose knapsack tables at 80 slots are the largest), runs every planner at the budgets, CU counts, batches and switches of
+tests/test_launch_plans_cpu.py and reads every result end to end (hipcc builds it here for the host; nothing touches a device and nothing
+is preloaded).  Exit status 0 and an empty stderr is the assertion."""
 import os
 import shutil
 import subprocess
@@ -97,6 +98,60 @@ static int run(const char *name, const mh_model_desc &d)
             const int parts = launch_parts(cu, L, want);
             sum += (long)lane_ws_bytes(t.n_slots, L, parts, 8) + (long)lane_ws_bound(cu, t.n_slots, L, want, 8), plans++;
          }
+   // the frames and the scratch of the constrained and the contact dynamics: the lists of tests/test_launch_plans_cpu.py, refused ones too
+   const int n = t.n;
+   const int lists[][2][MH_MAX_CONSTRAINT_TARGETS + 1] = {
+      // K, then the targets; K again, then the bases
+      {{1, n - 1}, {1, -1}}, {{1, n - 1}, {1, 0}}, {{4, 6, 19, 12, 23}, {4, 12, 23, -1, 3}},
+      {{8, 3, 4, 5, 6, 7, 8, 9, 10}, {8, -1, -1, -1, -1, -1, -1, -1, -1}}, {{8, 3, 4, 5, 6, 7, 8, 9, 10}, {8, 13, 14, 15, 16, 17, 18, 19, 20}},
+      {{8, 0, 0, 0, 0, 0, 0, 0, 0}, {8, n - 1, n - 1, n - 1, n - 1, n - 1, n - 1, n - 1, n - 1}},
+      {{1, n}, {1, -1}}, {{1, -1}, {1, -1}}, {{1, 0}, {1, n}}, {{1, 0}, {1, -2}}, {{2, 0, 0}, {2, -1, 0}}};
+   const double turned[12] = {0, -1, 0, 1, 0, 0, 0, 0, 1, 0.1, -0.2, 0.3}, sheared[12] = {1, 0.5, 0, 0, 1, 0, 0, 0, 1, 0, 0, 0};
+   for (const auto &list : lists)
+      for (const double *pose : {(const double *)nullptr, turned, sheared})
+      {
+         const int K = list[0][0];
+         FrameList F{K, K};
+         double given[MH_MAX_CONSTRAINT_TARGETS][12];
+         for (int k = 0; k < K; k++)
+            std::copy_n(pose ? pose : turned, 12, given[k]);
+         mh_status refused = MH_OK;
+         for (int k = 0; k < K && refused == MH_OK; k++)
+            if ((refused = frame_target(t, F, k, list[0][1 + k], list[1][1 + k], pose ? &given[0][0] : nullptr, name, (k & 1) != 0)) == MH_OK)
+            { // the joints are accepted: a pose that is no rotation must be refused, as target k of this call, and no other pose may be
+               refused = target_frame<double>(&t, F.tgt[k], F.pose[k], F.app_canon[k], name, k);
+               char want[96];
+               snprintf(want, sizeof want, "%s: target %d: the 3 x 3 part of its pose is not a rotation", name, k);
+               if ((refused != MH_OK) != (pose == sheared) || (refused != MH_OK && (refused != MH_ERR_INVALID_ARGUMENT || !strstr(g_err, want))))
+               {
+                  printf("%s: target %d: pose check gave status %d -- %s\n", name, k, (int)refused, g_err);
+                  return 1;
+               }
+            }
+         plans++;
+         if (refused != MH_OK)
+         {
+            sum += (long)refused + (g_err[0] != 0);
+            continue;
+         }
+         frame_list_close(t, F);
+         sum += F.K + F.n_app;
+         for (int k = 0; k < F.K; k++)
+            sum += F.tgt[k] + F.ext[k] + F.base[k] + F.bext[k] + F.bslot[k];
+         double poses = 0.0;
+         for (int j = 0; j < F.n_app; j++)
+         {
+            sum += F.app_joints[j];
+            for (int r = 0; r < 12; r++)
+               poses += F.app_canon[j][r] + (j < F.K ? F.pose[j][r] : 0.0);
+         }
+         sum += (long)(1.0e3 * poses);
+         for (int twists = 0; twists < 2; twists++)
+         {
+            const ConScratch s = con_scratch(t.n, t.nv, F.K, F.n_app, twists != 0);
+            sum += (long)(s.W + s.rhs + s.body + s.wrench + s.zeros + s.zpose + s.twist + s.total);
+         }
+      }
    printf("%s: status 0 bodies %d split %d plans %ld checksum %ld\n", name, t.n, (int)S.usable, plans, sum);
    return 0;
 }
