@@ -873,6 +873,58 @@ mh_status mh_contact_impulse_between_f32(mh_model_t model, int64_t B, const floa
                                          float *residual_out);
 
 /*
+ * ---- joint limits: a knee that does not fold through itself.  The unilateral twin of the contact call in joint space ----
+ * L = n_limits rows, 1 ... MH_MAX_LIMIT_JOINTS.  limit_joints (HOST, [L]): positions in the model's joint list, as target_joints
+ * elsewhere; each listed joint must be revolute or prismatic and may be listed once only; the host resolves each to its DoF index d_i
+ * and configuration index c_i through the model's index maps.  lower, upper (HOST, [L]) may be -inf / +inf, lower <= upper; they, margin
+ * and erp are converted to the call's precision once.  Per configuration and per row i, in the call's precision:
+ *    gap_lo = q[c_i] - lower_i,  gap_hi = upper_i - q[c_i];
+ *    s_i = +1 if gap_lo <= gap_hi, else -1 (the nearer limit decides the side, the lower limit wins a tie);  gap_i = min(gap_lo, gap_hi);
+ *    row i is CLOSED where gap_i <= margin (margin >= 0, finite); every other row is open and keeps impulse 0.0 exactly;
+ *    b_i = s_i qd[d_i] + erp gap_i (erp >= 0, finite, in 1/s): a violated limit (gap < 0) is asked to recover at erp |gap|, a row inside
+ *          the margin may still approach at erp gap; with erp = 1 / dt this is exactly "do not cross in the next step";
+ *    S_ij = s_i s_j (H^-1)[d_i][d_j], read so that S is exactly symmetric: for j < i the entry in row d_i of column j as
+ *          mh_mass_matrix_inverse_* computed it, for j > i S_ji, the diagonal from column i.
+ * The call returns the iterate of
+ *    minimise 1/2 lambda^T (S + eps I) lambda + lambda^T b   subject to  lambda >= 0   (closed rows),
+ * the linear complementarity problem 0 <= lambda_i  _|_  s_i qd+[d_i] + eps lambda_i + erp gap_i >= 0: frictionless, so exact, with no
+ * relaxation artefact.  Start: lambda^0_i = max(0, s_i impulse_init_i) on closed rows (NULL = zeros), 0 on open rows: a stale warm start
+ * is safe.  Then n_iterations sweeps (1 ... MH_MAX_LIMIT_ITERATIONS), i = 0 ... L - 1 in list order with the newest lambda, closed rows only:
+ *    u = b_i + sum_j S_ij lambda_j + eps lambda_i,    lambda_i = max(0, lambda_i - rho_i u),    rho_i = 1 / (S_ii + eps).
+ * qd_out [B][nv] = qd + sum over the CLOSED rows, in list order, of (s_i lambda_i) (column d_i of H^-1); entries no joint owns hold those
+ * of qd; a configuration with no closed row returns the bits of qd.  impulse_out [B][L] (SoA [L][B]; may be NULL) = s_i lambda_i, the
+ * generalised impulse on joint i, positive pushing q up; open rows hold exactly 0.0; it may be impulse_init itself (in-place warm start),
+ * the only permitted overlap.  residual_out [B] (may be NULL): the largest |change of a lambda_i| in the last sweep.
+ * A configuration gets quiet NaN in all three outputs when q[c_i] of a listed joint is NaN (or infinite), when S_ii + eps of a closed row
+ * is not positive and finite, when b_i or impulse_init_i of a closed row is not finite, or when a lambda after the last sweep is not
+ * finite; no other configuration changes and no error is raised.
+ * Two launches on opts->stream: the listed columns of H^-1 (the kernel of mh_mass_matrix_inverse_*) into the context's scratch as
+ * [nv L][B], then the solve (one lane per configuration; S in LDS while (L (L + 1) / 2 + 3 L) 64 elements fit 160 KB -- L <= 22 in fp64,
+ * L <= 32 in fp32 -- otherwise streamed from the columns: the same bits either way), which also forms qd_out from those columns: no
+ * second forward-dynamics launch.  Scratch of the context: B * nv * L elements; mh_reserve / mh_context_reserve keep their size: a
+ * larger need is met by the first call at that batch; after reserve and one first call the entry point only enqueues work
+ * (graph-capturable).  Workspace: that of mh_mass_matrix_inverse_* with L columns, which mh_reserve covers.
+ * MH_ERR_INVALID_ARGUMENT, outputs untouched, checked before anything is launched: NULL model / q / qd / qd_out / limit_joints / lower /
+ * upper; L outside 1 ... MH_MAX_LIMIT_JOINTS; a joint outside 0 ... n_joints - 1, not revolute or prismatic, or listed twice;
+ * lower > upper or a NaN limit; margin, erp or compliance negative, NaN or infinite (compliance 0 is allowed); n_iterations outside
+ * 1 ... MH_MAX_LIMIT_ITERATIONS; MH_ACCELERATION_SOURCE joints in the model; any overlap of an output with an input or with another
+ * output other than impulse_out == impulse_init exactly.  B = 0 returns MH_OK and touches nothing.  Layouts, index maps, the stream and
+ * contexts are honoured as everywhere else.
+ * Beside contacts: the call solves the limits alone; the caller alternates it with mh_contact_impulse_*, each on the free velocity plus
+ * the other's change of velocity (block Gauss-Seidel on the joint dual problem, both blocks warm-started; examples/joint_limits_humanoid.py).
+ */
+#define MH_MAX_LIMIT_JOINTS 64 /* = MH_MAX_INVERSE_COLUMNS */
+#define MH_MAX_LIMIT_ITERATIONS 4096
+mh_status mh_joint_limit_impulse_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_limits, const int32_t *limit_joints,
+                                     const double *lower, const double *upper, double margin, double erp, const double *impulse_init,
+                                     double compliance, int32_t n_iterations, const mh_options *opts, double *qd_out, double *impulse_out,
+                                     double *residual_out);
+mh_status mh_joint_limit_impulse_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_limits, const int32_t *limit_joints,
+                                     const double *lower, const double *upper, double margin, double erp, const float *impulse_init,
+                                     double compliance, int32_t n_iterations, const mh_options *opts, float *qd_out, float *impulse_out,
+                                     float *residual_out);
+
+/*
  * ---- state integration (MultiBodySystemStateIntegrator.doubleIntegrateFromAcceleration, tools/MultiBodySystemStateIntegrator.java:365-441,
  *      503-575, 710-733): the step downstream of forward dynamics, so that a simulation loop never leaves the device ----
  * One explicit constant-acceleration step of size dt for every joint of every configuration: 1-DoF q' = q + dt qd + dt^2/2 qdd,

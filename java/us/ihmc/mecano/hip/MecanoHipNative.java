@@ -243,6 +243,19 @@ public final class MecanoHipNative
    static final MethodHandle CONTACT_IMPULSE_BETWEEN_F32 = handle("mh_contact_impulse_between_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
                                                                                                            ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, JAVA_DOUBLE,
                                                                                                            JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   static final int MAX_LIMIT_JOINTS = 64, MAX_LIMIT_ITERATIONS = 4096;
+   /**
+    * The velocity after joint limits have acted, for B configurations: (model, B, q, qd, n_limits, limit_joints (host int[]), lower (host
+    * double[n_limits]), upper (host double[n_limits]), margin, erp, impulse_init|NULL, compliance, n_iterations, opts|NULL, qd_out,
+    * impulse_out|NULL, residual_out|NULL); impulse_init / impulse_out [B][n_limits], the generalised impulse on each listed joint, residual_out [B].
+    */
+   static final MethodHandle JOINT_LIMIT_IMPULSE = handle("mh_joint_limit_impulse_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
+                                                                                               JAVA_DOUBLE, JAVA_DOUBLE, ADDRESS, JAVA_DOUBLE, JAVA_INT, ADDRESS, ADDRESS,
+                                                                                               ADDRESS, ADDRESS));
+   /** the same in fp32 (float state and impulses on the device; the limits, margin, erp and the compliance stay double) */
+   static final MethodHandle JOINT_LIMIT_IMPULSE_F32 = handle("mh_joint_limit_impulse_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
+                                                                                                   JAVA_DOUBLE, JAVA_DOUBLE, ADDRESS, JAVA_DOUBLE, JAVA_INT, ADDRESS, ADDRESS,
+                                                                                                   ADDRESS, ADDRESS));
    /** (model, B, dt, q, qd, qdd, opts, q_out, qd_out, qdd_out|NULL) */
    static final MethodHandle INTEGRATE = handle("mh_integrate_f64", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                            ADDRESS));

@@ -16,6 +16,7 @@
 #include "mh_step_kernels.h"
 #include "mh_constraint_kernels.h"
 #include "mh_contact_kernels.h"
+#include "mh_limit_kernels.h"
 #include "mh_model_tables.h"
 #include "mh_launch_plans.h"
 
@@ -2113,6 +2114,31 @@ mh_status contact_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int
 // output -- no memset in front of it.  The listed columns travel as kernel arguments (resolved here to joint and place); the call
 // uploads nothing and allocates nothing beyond the workspace mh_reserve covers.
 static int minv_groups(int n_columns) { return (n_columns + mh::MINV_GROUP - 1) / mh::MINV_GROUP; }
+// The launch: G.col filled where `listed`, opts resolved to its context (begin_call).  out_soa: Hinv_out is [nv n_columns][B] whatever
+// the call's layout (the scratch of mh_joint_limit_impulse_*); the strides of q stay those of the layout.
+template <typename T>
+mh_status minv_launch(mh_model_t model, int64_t B, const T *q, mh::MinvArgs<T> &G, int n_columns, bool listed, const mh_options &opts, T *Hinv_out,
+                      bool out_soa)
+{
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = launch_parts(model->cu_count, L, minv_groups(n_columns));
+   const mh_status st = ensure_bytes(model->ws, lane_ws_bytes(model->resp_slots, L, parts, sizeof(T)));
+   if (st != MH_OK)
+      return st;
+   mh::Args<T> &A = G.a;
+   A = make_args<T>(model, B, opts);
+   A.q = q, A.out = Hinv_out;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = L.lanes;
+   set_strides(G.h_bs, G.h_es, out_soa || opts.layout == MH_LAYOUT_SOA, B, (long)model->nv * n_columns);
+   G.info = model->d_resp_info, G.owner = model->d_minv_owner;
+   G.zero_ofs = model->d_grav_zero_ofs, G.zero_cols = model->d_grav_zero_cols;
+   G.slots = model->resp_slots, G.a_base = model->resp_a_base, G.u_base = model->resp_u_base;
+   G.n_columns = n_columns, G.listed = listed;
+   hipLaunchKernelGGL((mh::mass_matrix_inverse_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
 template <typename T>
 mh_status mass_matrix_inverse_impl(mh_model_t model, int64_t B, const T *q, int32_t n_columns, const int32_t *columns, const mh_options *opts_in,
                                    T *Hinv_out)
@@ -2146,23 +2172,88 @@ mh_status mass_matrix_inverse_impl(mh_model_t model, int64_t B, const T *q, int3
       if ((st = check_aliasing("mh_mass_matrix_inverse", &in, 1, &out, 1)) != MH_OK)
          return st;
    }
-   const Launch L = plan_launch(model->cu_count, B);
-   const int parts = launch_parts(model->cu_count, L, minv_groups(n_columns));
-   st = ensure_bytes(model->ws, lane_ws_bytes(model->resp_slots, L, parts, sizeof(T)));
+   return minv_launch<T>(model, B, q, G, n_columns, columns != nullptr, opts, Hinv_out, false);
+}
+// Joint-limit impulses: the listed columns of H^-1 at the DoFs of the limited joints into SoA scratch (the launch above), then the solve
+// kernel (mh_limit_kernels.h), which also forms qd_out from those columns.  Two launches on the caller's stream; the first call of a
+// batch grows the scratch (ensure_bytes), then the calls only enqueue.
+template <typename T>
+mh_status limit_impl(mh_model_t model, int64_t B, const T *q, const T *qd, int32_t n_limits, const int32_t *limit_joints, const double *lower,
+                     const double *upper, const double &margin, const double &erp, const T *impulse_init, const double &compliance,
+                     int32_t n_iterations, const mh_options *opts_in, T *out, T *impulse_out, T *residual_out)
+{
+   const char *call = "mh_joint_limit_impulse";
+   mh_options o;
+   mh_status st = begin_call(model, B, opts_in, o);
    if (st != MH_OK)
       return st;
-   mh::Args<T> &A = G.a;
-   A = make_args<T>(model, B, opts);
-   A.q = q, A.out = Hinv_out;
-   A.ws = (T *)model->ws.ptr;
-   A.ws_stride = L.lanes;
-   set_strides(G.h_bs, G.h_es, opts.layout == MH_LAYOUT_SOA, B, hsize);
-   G.info = model->d_resp_info, G.owner = model->d_minv_owner;
-   G.zero_ofs = model->d_grav_zero_ofs, G.zero_cols = model->d_grav_zero_cols;
-   G.slots = model->resp_slots, G.a_base = model->resp_a_base, G.u_base = model->resp_u_base;
-   G.n_columns = n_columns, G.listed = columns != nullptr;
-   hipLaunchKernelGGL((mh::mass_matrix_inverse_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
-   HIP_TRY(hipGetLastError());
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: %d joint(s) are acceleration sources: the joint-limit solve takes none", call, model->n_locked);
+   if (n_limits < 1 || n_limits > MH_MAX_LIMIT_JOINTS)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: n_limits = %d is outside 1 ... %d", call, n_limits, MH_MAX_LIMIT_JOINTS);
+   if (!limit_joints || !lower || !upper)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: %s is NULL", call, !limit_joints ? "limit_joints" : (!lower ? "lower" : "upper"));
+   auto finite_nonneg = [](const double &x) { return !nonfinite_bits(x) && x >= 0.0; }; // (bits: -ffinite-math-only)
+   if (!finite_nonneg(margin))
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: margin must be finite and >= 0", call);
+   if (!finite_nonneg(erp))
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: erp must be finite and >= 0", call);
+   if (!finite_nonneg(compliance))
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: compliance must be finite and >= 0", call);
+   if (n_iterations < 1 || n_iterations > MH_MAX_LIMIT_ITERATIONS)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: n_iterations = %d is outside 1 ... %d", call, n_iterations, MH_MAX_LIMIT_ITERATIONS);
+   const int L = n_limits;
+   mh::LimitArgs<T> G{};
+   mh::MinvArgs<T> M{};
+   for (int i = 0; i < L; i++)
+   {
+      const int joint = limit_joints[i];
+      if (joint < 0 || joint >= model->n)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: limit_joints[%d] names joint %d (the model has %d joints)", call, i, joint, model->n);
+      const int *mi = &model->meta[(size_t)model->engine_of[joint] * mh::MI_STRIDE];
+      if (mi[mh::MI_TYPE] != mh::JT_REVOLUTE && mi[mh::MI_TYPE] != mh::JT_PRISMATIC)
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: limit_joints[%d]: joint %d is neither revolute nor prismatic", call, i, joint);
+      for (int k = 0; k < i; k++)
+         if (limit_joints[k] == joint)
+            return fail(MH_ERR_INVALID_ARGUMENT, "%s: limit_joints[%d]: joint %d is listed twice", call, i, joint);
+      if (nan_bits(lower[i]) || nan_bits(upper[i]))
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: lower / upper of limit %d is NaN", call, i);
+      if (lower[i] > upper[i])
+         return fail(MH_ERR_INVALID_ARGUMENT, "%s: limit %d: lower %g > upper %g", call, i, lower[i], upper[i]);
+      G.dof[i] = model->dof_map[mi[mh::MI_DOF]], G.cfg[i] = model->cfg_map[mi[mh::MI_CFG]];
+      G.lower[i] = (T)lower[i], G.upper[i] = (T)upper[i];
+      M.col[i] = model->minv_owner[G.dof[i]];
+   }
+   if (B == 0)
+      return MH_OK;
+   if (!q || !qd || !out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: %s is NULL", call, !q ? "q" : (!qd ? "qd" : "qd_out"));
+   {
+      const size_t bv = (size_t)B * model->nv * sizeof(T), bl = (size_t)B * L * sizeof(T);
+      const InRange ins[3] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"qd", qd, bv}, {"impulse_init", impulse_init, bl}};
+      const OutRange outs[3] = {{"qd_out", out, bv, 0u}, {"impulse_out", impulse_out, bl, 1u << 2}, {"residual_out", residual_out, (size_t)B * sizeof(T), 0u}};
+      if ((st = check_aliasing(call, ins, 3, outs, 3)) != MH_OK)
+         return st;
+   }
+   if ((st = ensure_bytes(model->con, (size_t)B * model->nv * L * sizeof(T))) != MH_OK)
+      return st;
+   const LimitPlan P = limit_plan(L, sizeof(T), model->limit_path, model->cu_count, B);
+   const void *kern = P.resident ? (const void *)&mh::limit_solve_kernel<T, true> : (const void *)&mh::limit_solve_kernel<T, false>;
+   if ((st = raise_lds_limit(model, kern, (size_t)P.lds)) != MH_OK)
+      return st;
+   T *const Hinv = (T *)model->con.ptr;
+   if ((st = minv_launch<T>(model, B, q, M, L, true, o, Hinv, true)) != MH_OK)
+      return st;
+   const bool soa = o.layout == MH_LAYOUT_SOA;
+   G.B = B, G.nv = model->nv, G.L = L, G.n_iter = n_iterations;
+   G.q = q, G.qd = qd, G.out = out;
+   set_strides(G.q_bs, G.q_es, soa, B, model->nq);
+   set_strides(G.v_bs, G.v_es, soa, B, model->nv);
+   G.Hinv = Hinv, G.init = impulse_init, G.impulse = impulse_out, G.residual = residual_out;
+   set_strides(G.d_bs, G.d_es, soa, B, L);
+   G.eps = (T)compliance, G.margin = (T)margin, G.erp = (T)erp;
+   void *args[] = {(void *)&G};
+   HIP_TRY(hipLaunchKernel(kern, dim3(P.grid), dim3(64), args, (size_t)P.lds, (hipStream_t)o.stream));
    return MH_OK;
 }
 // Inverse / forward dynamics with the inertial parameters of every configuration in the batch (mh_params_kernels.h): run-time-topology
@@ -2688,6 +2779,14 @@ mh_status mh_internal_launch_plan(const mh_model_desc *desc, const char *plan, c
          return fail(MH_ERR_INVALID_ARGUMENT, bad, plan);
       const ContactPlan c = contact_plan((int)params[0], (size_t)params[1], (int)params[2], (int)params[3], params[4]);
       w = {c.resident, (int)c.lds, c.per_cu, c.grid, c.kmax};
+   }
+   else if (name == "limit_solve")
+   { // (L, bytes per element, force, CUs, batch)
+      if (!takes(5) || params[0] < 1 || params[0] > MH_MAX_LIMIT_JOINTS || !among(1, {4, 8}) || !among(2, {-1, 0, 1}) || params[3] < 1
+          || params[3] > (1 << 20) || params[4] < 0)
+         return fail(MH_ERR_INVALID_ARGUMENT, bad, plan);
+      const LimitPlan c = limit_plan((int)params[0], (size_t)params[1], (int)params[2], (int)params[3], params[4]);
+      w = {c.resident, (int)c.lds, c.per_cu, c.grid};
    }
    else if (name == "constraint_frames")
    {
@@ -3931,6 +4030,31 @@ mh_status mh_internal_contact_path(mh_model_t model, int32_t path)
    if (!model || path < -1 || path > 1)
       return fail(MH_ERR_INVALID_ARGUMENT, "mh_internal_contact_path: model is NULL, or path is outside -1 ... 1");
    model->contact_path = path;
+   return MH_OK;
+}
+mh_status mh_joint_limit_impulse_f64(mh_model_t model, int64_t B, const double *q, const double *qd, int32_t n_limits, const int32_t *limit_joints,
+                                     const double *lower, const double *upper, double margin, double erp, const double *impulse_init,
+                                     double compliance, int32_t n_iterations, const mh_options *opts, double *qd_out, double *impulse_out,
+                                     double *residual_out)
+{
+   return limit_impl<double>(model, B, q, qd, n_limits, limit_joints, lower, upper, margin, erp, impulse_init, compliance, n_iterations, opts, qd_out,
+                             impulse_out, residual_out);
+}
+mh_status mh_joint_limit_impulse_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_limits, const int32_t *limit_joints,
+                                     const double *lower, const double *upper, double margin, double erp, const float *impulse_init,
+                                     double compliance, int32_t n_iterations, const mh_options *opts, float *qd_out, float *impulse_out,
+                                     float *residual_out)
+{
+   return limit_impl<float>(model, B, q, qd, n_limits, limit_joints, lower, upper, margin, erp, impulse_init, compliance, n_iterations, opts, qd_out,
+                            impulse_out, residual_out);
+}
+// not in include/mecano_hip.h: where the joint-limit solve of this model (or context) reads S from now on -- -1 = limit_plan chooses,
+// 0 = streamed, 1 = LDS-resident where it fits (tests/test_gpu_joint_limits.py holds the two to the same bits)
+mh_status mh_internal_limit_path(mh_model_t model, int32_t path)
+{
+   if (!model || path < -1 || path > 1)
+      return fail(MH_ERR_INVALID_ARGUMENT, "mh_internal_limit_path: model is NULL, or path is outside -1 ... 1");
+   model->limit_path = path;
    return MH_OK;
 }
 mh_status mh_configuration_add_f64(mh_model_t model, int64_t B, const double *q, const double *dq, const mh_options *opts, double *q_out)

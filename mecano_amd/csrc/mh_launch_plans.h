@@ -45,6 +45,7 @@ struct Switches
    int zv_same_l2 = 0;    // MH_ZV_SAME_L2=1 (experiment, off by default; one-stage hand-off only: the two-stage form of identity index maps is write-through): bias rows and flag of a group whose two jobs prove to sit behind the same L2
                           // stay in that L2 (workgroup-scope stores) -- cache behaviour the memory model does not promise, for no measured gain
    int contact_path = -1; // no variable of the environment: mh_internal_contact_path (tests, measurements) forces the streamed (0) or the LDS-resident (1) contact solve
+   int limit_path = -1;   // likewise mh_internal_limit_path: the streamed (0) or the LDS-resident (1) joint-limit solve
    unsigned zv_wait_ticks = 200000000u; // MH_ZV_WAIT_MS: how long an inertia job waits for its bias rows (100 MHz ticks; default 2 s)
 };
 
@@ -590,6 +591,28 @@ ContactPlan contact_plan(int K, size_t elem, int force, int cu_count, int64_t B)
    p.per_cu = p.resident ? (int)std::max<long>(1, std::min<long>(kWavesPerCu, 160 * 1024 / bytes)) : kWavesPerCu;
    p.grid = (int)std::max<long>(1, std::min<long>(groups_of(B), (long)cu_count * p.per_cu));
    p.kmax = K <= 4 ? 4 : 8; // the kernel build: contacts the unrolled loops cover
+   return p;
+}
+
+// ---- joint-limit solve (mh_limit_kernels.h): a wave (one workgroup) keeps t, c and rho of its L rows in LDS, 3 L entries per lane, and
+// the lower triangle of the listed block of H^-1, L (L + 1) / 2 entries per lane, behind them while both fit the 160 KB of a CU -- up to
+// L = 22 in fp64 (163 328 bytes; L = 23 takes 176 640), up to L = 32 in fp32 -- and otherwise streams the triangle from the columns in
+// the SoA scratch.  force: -1 = choose, 0 = stream, 1 = resident where it fits (tests and measurements: both forms give the same bits).
+// The grid: the waves of the batch, capped at the workgroups whose LDS a CU holds, eight at most.
+struct LimitPlan
+{
+   bool resident;
+   long lds;
+   int per_cu, grid;
+};
+LimitPlan limit_plan(int L, size_t elem, int force, int cu_count, int64_t B)
+{
+   LimitPlan p{};
+   const long state = 3L * L * 64 * (long)elem, full = state + (long)L * (L + 1) / 2 * 64 * (long)elem;
+   p.resident = force != 0 && full <= 160 * 1024;
+   p.lds = p.resident ? full : state;
+   p.per_cu = (int)std::max<long>(1, std::min<long>(kWavesPerCu, 160 * 1024 / p.lds));
+   p.grid = (int)std::max<long>(1, std::min<long>(groups_of(B), (long)cu_count * p.per_cu));
    return p;
 }
 

@@ -803,6 +803,39 @@ class HipModel:
             ptr(active), ptr(v_normal), ptr(init), float(compliance), int(iterations), ctypes.byref(opts), qd_next.data_ptr(), ptr(imp), ptr(res)))
         return qd_next, imp, res
 
+    def joint_limit_impulse(self, q, qd, joints, lower, upper, margin=0.0, erp=0.0, compliance=0.0, iterations=50, init=None,
+                            layout=_lib.LAYOUT_AOS, out=None):
+        """The velocity after joint limits have acted: (qd_next [B, nv], impulse [B, L], residual [B]).  ``joints``: 1 to 64 positions in
+        the joint list, revolute or prismatic, each once; ``lower`` / ``upper`` one range per listed joint (-inf / +inf allowed).  A row is
+        closed where its joint is within ``margin`` of the nearer limit (or beyond it); closed rows get impulses lam >= 0 towards the
+        inside of the range that solve 0 <= lam  _|_  s qd_next + compliance lam + erp gap >= 0 (include/mecano_hip.h,
+        mh_joint_limit_impulse_*) by ``iterations`` projected Gauss-Seidel sweeps from ``init`` (an impulse of an earlier call, None:
+        zeros; it may be the impulse output itself).  impulse[:, i] is the generalised impulse on joint i, positive pushing q up; open
+        rows hold 0.  residual: the largest change of an impulse in the last sweep.  SoA: [nv, B], [L, B], [B].  ``out``: a
+        (qd_next, impulse, residual) triple to write into; the last two may be None."""
+        B, dt, sfx, stream = self._device_inputs([q, qd], layout)
+        jnt = np.ascontiguousarray(np.asarray(joints, dtype=np.int32).reshape(-1))
+        lo = np.ascontiguousarray(np.asarray(lower, dtype=np.float64).reshape(-1))
+        hi = np.ascontiguousarray(np.asarray(upper, dtype=np.float64).reshape(-1))
+        L = int(jnt.shape[0])
+        if lo.shape[0] != L or hi.shape[0] != L:
+            raise _lib.MecanoHipError(2, f"lower and upper must hold one limit per listed joint ({L}), got {lo.shape[0]} and {hi.shape[0]}")
+        aos = layout == _lib.LAYOUT_AOS
+        row_shape = (B, L) if aos else (L, B)
+        if init is not None:
+            self._device_tensor(init, dt)
+            if tuple(init.shape) != row_shape:
+                raise _lib.MecanoHipError(2, f"init has shape {tuple(init.shape)}, expected {row_shape}")
+        qd_next, imp, res = self._outputs(out, ((B, self.nv) if aos else (self.nv, B), row_shape, (B,)), ("qd_next", "impulse", "residual"), dt, q.device)
+        if qd_next is None:
+            raise _lib.MecanoHipError(1, "the qd_next output is None")
+        ptr = lambda t: None if t is None else t.data_ptr()
+        opts = self._options(layout, stream=stream)
+        _lib.check(getattr(_lib.load(), f"mh_joint_limit_impulse_{sfx}")(
+            self._h, B, q.data_ptr(), qd.data_ptr(), L, jnt.ctypes.data, lo.ctypes.data, hi.ctypes.data, float(margin), float(erp), ptr(init),
+            float(compliance), int(iterations), ctypes.byref(opts), qd_next.data_ptr(), ptr(imp), ptr(res)))
+        return qd_next, imp, res
+
     def rnea_derivatives(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, consider_coriolis=True,
                          consider_accelerations=True, out=None):
         """Inverse dynamics and its first-order derivatives at a moving state, one analytic launch: (tau [B, nv], dtau_dq [B, nv, nv],
