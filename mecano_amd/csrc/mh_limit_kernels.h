@@ -111,8 +111,10 @@ __global__ void __launch_bounds__(64) limit_solve_kernel(LimitArgs<T> G)
          closed |= on ? (mask_t)1 << i : 0, side |= low ? (mask_t)1 << i : 0;
          wave |= __ballot(on) != 0 ? (mask_t)1 << i : 0;
       }
-      // `wave` is made a scalar: the rows and columns below are walked bit by bit on the scalar unit
-      wave = (mask_t)__builtin_amdgcn_readfirstlane((unsigned)(wave >> 32)) << 32 | (mask_t)__builtin_amdgcn_readfirstlane((unsigned)wave);
+      // `wave` is made a scalar: the rows and columns below are walked bit by bit on the scalar unit.  readfirstlane returns an int: each
+      // half goes through unsigned before it is widened, or a closed row 31 would set bits 32 ... 63 and the walks would take rows past L
+      wave = (mask_t)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)(wave >> 32)) << 32 |
+             (mask_t)(unsigned)__builtin_amdgcn_readfirstlane((unsigned)wave);
       if constexpr (RESIDENT)
       { // the lower triangle of the listed block into LDS, the entries the sweeps read: rows and columns closed in some lane (one wave per
         // workgroup: the lane's own column, no barrier)

@@ -6,6 +6,8 @@ import pytest
 
 import joint_limits_check as jl
 from helpers import U32, close_aba
+from mecano_amd import random_tools as rt
+from mecano_amd.multibody import MultiBodySystem, RigidBody
 from oracle.cpu_oracle import OracleModel
 from test_kinematics_cpu import make_case, states
 
@@ -15,9 +17,30 @@ B_CPU = 64
 _MODELS = {}
 
 
+COMB_CHAINS, COMB_DEPTH, COMB_SEED = 16, 4, 77
+
+
+def comb16x4():
+    """A fixed root body carrying 16 chains of 4 one-DoF joints, every fifth joint (in the order they are made, chain by chain) prismatic:
+    64 rows that couple within a chain only, so that the stick system stays well conditioned at the cap of the list length
+    (tests/test_joint_limits_wide_cpu.py pins how well).  The joint list is chain by chain: joint 4 c + k is joint k of chain c."""
+    rng = np.random.default_rng(COMB_SEED)
+    root = RigidBody("combBase")
+    for c in range(COMB_CHAINS):
+        body = root
+        for k in range(COMB_DEPTH):
+            make = rt.nextPrismaticJoint if (COMB_DEPTH * c + k) % 5 == 4 else rt.nextRevoluteJoint
+            body = rt.nextRigidBody(rng, f"chain{c}Body{k}", make(rng, f"chain{c}Joint{k}", body))
+    return MultiBodySystem.toMultiBodySystemInput(root)
+
+
 def model_of(name):
     if name not in _MODELS:
-        sys_, desc = make_case(name)
+        if name == "comb16x4":
+            sys_ = comb16x4()
+            desc = sys_.toModelDesc()
+        else:
+            sys_, desc = make_case(name)
         _MODELS[name] = (sys_, desc, OracleModel(desc))
     return _MODELS[name]
 
