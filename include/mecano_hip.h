@@ -600,6 +600,38 @@ mh_status mh_aba_derivatives_f32(mh_model_t model, int64_t B, const float *q, co
                                  float *Hinv_out);
 
 /*
+ * ---- reverse-mode gradients (vector-Jacobian products) of the inverse and the forward dynamics: what backpropagation through the dynamics
+ *      needs, without any of the matrices above (no calculator of the reference) ----
+ * mh_rnea_vjp_*: for a cotangent u [B][nv] of the efforts, gq_out[j] = sum_i u_i d tau_i / d q_j, gqd_out[j] = sum_i u_i d tau_i / d qd_j and
+ * gqdd_out = H(q) u, each [B][nv] (MH_LAYOUT_SOA: [nv][B]) and each optional -- at least one (MH_ERR_INVALID_ARGUMENT otherwise).  The
+ * matrices are exactly those of mh_rnea_derivatives_*: dq is a velocity-space step, the COMPONENTS of qd and qdd are held fixed, every
+ * external wrench is held constant IN THE WORLD.  opts->consider_coriolis = 0 evaluates at qd = 0 (qd may then be NULL) and writes gqd_out
+ * as zeros; opts->consider_accelerations = 0 evaluates at qdd = 0 (qdd may then be NULL); opts->use_root_acceleration / root_acceleration
+ * are honoured (gravity may then be NULL).  u = 0 gives zeros.  Every entry of the outputs given is written once, zeros at DoF indices no
+ * joint owns included (no memset needed), nothing outside them.  Analytic, O(n) per configuration, 3 nv numbers written instead of
+ * 2 nv^2: ONE launch of a run-time-topology kernel for every model; after mh_reserve the call allocates nothing.
+ * mh_aba_vjp_*: for a cotangent w [B][nv] of qdd = mh_aba_*(q, qd, tau): gtau_out = mu = H^-1 w, gq_out = -(d tau / d q)^T mu and
+ * gqd_out = -(d tau / d qd)^T mu at that qdd, i.e. w^T d qdd / d (q, qd, tau) with the matrices of mh_aba_derivatives_*; at least one of
+ * the three (MH_ERR_INVALID_ARGUMENT otherwise).  qdd_out [B][nv] may be NULL.  Launches composed on opts->stream: forward dynamics
+ * (whichever plan mh_aba_* takes), forward dynamics again at rest without root acceleration and wrenches for H^-1 w, the kernel above.
+ * No nv x nv matrix is read, written or reserved: the scratch is 2 B nv elements of the context (qdd and mu where the caller takes
+ * neither), set aside by mh_reserve / mh_context_reserve, after which the call only enqueues work (graph-capturable).
+ * Both: a model with MH_ACCELERATION_SOURCE joints is refused (MH_ERR_INVALID_ARGUMENT).  The outputs must not overlap the inputs (u / w
+ * included) or each other.  B = 0 or nv = 0 returns MH_OK and touches nothing.  Device pointers, asynchronous on opts->stream, layouts,
+ * index maps and contexts honoured.
+ */
+mh_status mh_rnea_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double gravity[3],
+                          const double *f_ext, const double *u, const mh_options *opts, double *gq_out, double *gqd_out, double *gqdd_out);
+mh_status mh_rnea_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const double gravity[3],
+                          const float *f_ext, const float *u, const mh_options *opts, float *gq_out, float *gqd_out, float *gqdd_out);
+mh_status mh_aba_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
+                         const double *f_ext, const double *w, const mh_options *opts, double *qdd_out, double *gq_out, double *gqd_out,
+                         double *gtau_out);
+mh_status mh_aba_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const double gravity[3],
+                         const float *f_ext, const float *w, const mh_options *opts, float *qdd_out, float *gq_out, float *gqd_out,
+                         float *gtau_out);
+
+/*
  * ---- the chart of the velocity-space derivatives, and the linearisation of the simulation step ----
  * mh_configuration_add_*: q_out [B][nq] = q (+) dq, dq [B][nv]: the pure configuration step every gradient above is defined in --
  * MultiBodySystemStateIntegrator.integrateFromVelocity with dt = 1 and twist dq (tools/MultiBodySystemStateIntegrator.java:164-243), per

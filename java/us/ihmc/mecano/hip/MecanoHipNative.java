@@ -140,6 +140,24 @@ public final class MecanoHipNative
    /** the same in fp32 */
    static final MethodHandle ABA_DERIVATIVES_F32 = handle("mh_aba_derivatives_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                                            ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * Reverse-mode gradients of the inverse dynamics for a cotangent u of the efforts: (model, B, q, qd, qdd, gravity[3] (host), f_ext|NULL, u,
+    * opts|NULL, gq_out|NULL, gqd_out|NULL, gqdd_out|NULL), vectors [B][nv]; not all three NULL.
+    */
+   static final MethodHandle RNEA_VJP = handle("mh_rnea_vjp_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                         ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle RNEA_VJP_F32 = handle("mh_rnea_vjp_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                             ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * Reverse-mode gradients of the forward dynamics for a cotangent w of qdd: (model, B, q, qd, tau, gravity[3] (host), f_ext|NULL, w, opts|NULL,
+    * qdd_out|NULL, gq_out|NULL, gqd_out|NULL, gtau_out|NULL), vectors [B][nv]; not all three gradients NULL.
+    */
+   static final MethodHandle ABA_VJP = handle("mh_aba_vjp_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                       ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle ABA_VJP_F32 = handle("mh_aba_vjp_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                           ADDRESS, ADDRESS, ADDRESS, ADDRESS));
    /** q_out = q (+) dq, the pure configuration step of the velocity-space derivatives: (model, B, q, dq, opts|NULL, q_out); q_out may be q. */
    static final MethodHandle CONFIGURATION_ADD = handle("mh_configuration_add_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
    /** the same in fp32 */

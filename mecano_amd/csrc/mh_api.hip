@@ -158,6 +158,8 @@ struct ContextState
    FreshOnCopy<std::vector<int>> pairs_host;
    // mh_rnea_derivatives_* / mh_aba_derivatives_*: scratch of the forward form (Hinv and qdd the caller did not ask for)
    Workspace deriv;
+   // mh_aba_vjp_*: qdd and H^-1 w the caller did not ask for, B nv entries each
+   Workspace vjp;
    // mh_aba_integrate_derivatives_*: d qdd / d q and d qdd / d qd of the call (Hinv and qdd go to `deriv`)
    Workspace step;
    // mh_body_poses_* / mh_geometric_jacobian_*: the SoA form of AoS outputs, which a transposition then brings to the caller's rows
@@ -177,7 +179,7 @@ struct ContextState
 };
 void free_scratch(ContextState &c)
 {
-   for (Workspace *w : {&c.ws, &c.ws_pair, &c.stage, &c.tr, &c.tr_pair, &c.aux, &c.pairs, &c.deriv, &c.step, &c.kin, &c.con, &c.zv_tau, &c.zv_flags, &c.zv_cols, &c.zvb_cs})
+   for (Workspace *w : {&c.ws, &c.ws_pair, &c.stage, &c.tr, &c.tr_pair, &c.aux, &c.pairs, &c.deriv, &c.vjp, &c.step, &c.kin, &c.con, &c.zv_tau, &c.zv_flags, &c.zv_cols, &c.zvb_cs})
       (void)hipFree(w->ptr);
    if (c.zv_error_host)
    {
@@ -214,6 +216,7 @@ struct DeviceTables
    int *d_resp_info = nullptr;
    int *d_minv_owner = nullptr;
    int *d_deriv_slot = nullptr;
+   int *d_vjp_slot = nullptr;
 };
 
 // The switches of the environment (struct Switches: mh_launch_plans.h, whose planners read some of them).
@@ -315,6 +318,9 @@ struct mh_model : ModelTables, DeviceTables, Switches, ContextState
    int n_contexts = 0; // live contexts of this model (guarded by g_context_mutex)
    bool destroy_pending = false; // mh_model_destroy was called while contexts were alive: the last mh_context_destroy releases the model
    int n_locked = 0;        // joints in MH_ACCELERATION_SOURCE mode (mh_model_set_joint_source_modes)
+   // mh_rnea_vjp_* / mh_aba_vjp_*: first workspace slot of every body in that kernel's own plan (vjp_slot_plan, mh_launch_plans.h)
+   std::vector<int> vjp_slot;
+   int vjp_slots = 0;
    SpecLib spec;
    bool spec_minimal = false; // the loaded code object is a minimal (fast) build
    std::string variant = "generic";
@@ -363,7 +369,7 @@ std::vector<DeviceRow> device_rows(mh_model *m, const std::vector<float> &consts
            device_row(m->d_prog_seq, m->prog_seq), device_row(m->d_consts64, m->consts), device_row(m->d_consts32, consts32),
            device_row(m->d_sub_mass64, m->sub_mass), device_row(m->d_sub_mass32, sub_mass32), device_row(m->d_grav_zero_ofs, m->grav_zero_ofs),
            device_row(m->d_grav_zero_cols, m->grav_zero_cols), device_row(m->d_resp_info, m->resp_info),
-           device_row(m->d_minv_owner, m->minv_owner), device_row(m->d_deriv_slot, m->deriv_slot)};
+           device_row(m->d_minv_owner, m->minv_owner), device_row(m->d_deriv_slot, m->deriv_slot), device_row(m->d_vjp_slot, m->vjp_slot)};
 }
 mh_status ensure_bytes(Workspace &w, size_t bytes)
 {
@@ -2434,6 +2440,116 @@ mh_status aba_derivatives_impl(mh_model_t model, int64_t B, const T *q, const T 
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
+// Reverse-mode gradients of the inverse dynamics (mh_rnea_vjp_kernels.h): one launch of a run-time-topology kernel in a slot plan of its
+// own, which writes every entry of the outputs it is given.  negate: -gq and -gqd (the forward form below).
+static size_t vjp_scratch_bytes(const mh_model *m, int64_t B, size_t elem) { return (size_t)B * 2 * (size_t)m->nv * elem; }
+template <typename T>
+mh_status rnea_vjp_launch(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const double *gravity, const T *f_ext, const T *u,
+                          const mh_options &opts, bool negate, T *gq_out, T *gqd_out, T *gqdd_out)
+{
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
+   mh_status st = ensure_bytes(model->ws, lane_ws_bytes(model->vjp_slots, L, parts, sizeof(T)));
+   if (st != MH_OK)
+      return st;
+   mh::VjpArgs<T> G{};
+   mh::Args<T> &A = G.a;
+   A = make_args<T>(model, B, opts, gravity);
+   A.q = q, A.qd = qd, A.in3 = qdd, A.fext = f_ext, A.out = nullptr;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = L.lanes;
+   G.u = u, G.gq = gq_out, G.gqd = gqd_out, G.gqdd = gqdd_out;
+   G.slot = model->d_vjp_slot, G.slots = model->vjp_slots;
+   G.negate = negate;
+   G.unowned = model->d_grav_zero_cols + model->grav_zero_ofs[model->n];
+   G.n_unowned = model->grav_zero_ofs[model->n + 1] - model->grav_zero_ofs[model->n];
+   hipLaunchKernelGGL((mh::rnea_vjp_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
+template <typename T>
+mh_status rnea_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const double *gravity, const T *f_ext, const T *u,
+                        const mh_options *opts_in, T *gq_out, T *gqd_out, T *gqdd_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: the gradients of the dynamics take none", model->n_locked);
+   if (!gravity && !opts.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (!gq_out && !gqd_out && !gqdd_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gq_out, gqd_out and gqdd_out are all NULL");
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!q || !u || (opts.consider_coriolis && !qd) || (opts.consider_accelerations && !qdd))
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / cotangent pointer (qd may be NULL with consider_coriolis = 0, qdd with consider_accelerations = 0)");
+   {
+      const size_t nq = (size_t)B * model->nq * sizeof(T), nvb = (size_t)B * model->nv * sizeof(T), nf = (size_t)B * model->n * 6 * sizeof(T);
+      const InRange ins[5] = {{"q", q, nq}, {"qd", opts.consider_coriolis ? qd : nullptr, nvb}, {"qdd", opts.consider_accelerations ? qdd : nullptr, nvb},
+                              {"f_ext", f_ext, nf}, {"u", u, nvb}};
+      const OutRange outs[3] = {{"gq_out", gq_out, nvb, 0u}, {"gqd_out", gqd_out, nvb, 0u}, {"gqdd_out", gqdd_out, nvb, 0u}};
+      if ((st = check_aliasing("mh_rnea_vjp", ins, 5, outs, 3)) != MH_OK)
+         return st;
+   }
+   return rnea_vjp_launch<T>(model, B, q, qd, qdd, gravity, f_ext, u, opts, false, gq_out, gqd_out, gqdd_out);
+}
+// Reverse-mode gradients of the forward dynamics: three launches (and one memset) composed on the caller's stream -- forward dynamics
+// (whichever plan mh_aba_* takes) for qdd; forward dynamics again at rest, without root acceleration and wrenches, with tau = w, which is
+// mu = H^-1 w (its qd is the output itself, zeroed first: the in-place form of mh_aba_*, so the scratch stays at two vectors); the
+// kernel above at that qdd with u = mu, negated.  No matrix anywhere.
+template <typename T>
+mh_status aba_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const double *gravity, const T *f_ext, const T *w,
+                       const mh_options *opts_in, T *qdd_out, T *gq_out, T *gqd_out, T *gtau_out)
+{
+   mh_options o;
+   mh_status st = begin_call(model, B, opts_in, o);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: the gradients of the dynamics take none", model->n_locked);
+   if (!gravity && !o.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (!gq_out && !gqd_out && !gtau_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gq_out, gqd_out and gtau_out are all NULL");
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!q || !qd || !tau || !w)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / cotangent pointer");
+   const size_t nvb = (size_t)B * model->nv * sizeof(T);
+   {
+      const InRange ins[5] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"qd", qd, nvb}, {"tau", tau, nvb}, {"f_ext", f_ext, (size_t)B * model->n * 6 * sizeof(T)},
+                              {"w", w, nvb}};
+      const OutRange outs[4] = {{"qdd_out", qdd_out, nvb, 0u}, {"gq_out", gq_out, nvb, 0u}, {"gqd_out", gqd_out, nvb, 0u}, {"gtau_out", gtau_out, nvb, 0u}};
+      if ((st = check_aliasing("mh_aba_vjp", ins, 5, outs, 4)) != MH_OK)
+         return st;
+   }
+   T *qdd = qdd_out, *mu = gtau_out;
+   if (!qdd || !mu)
+   {
+      if ((st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T)))) != MH_OK)
+         return st;
+      if (!qdd)
+         qdd = (T *)model->vjp.ptr;
+      if (!mu)
+         mu = (T *)model->vjp.ptr + (size_t)B * model->nv;
+   }
+   if (qdd_out || gq_out || gqd_out) // (gtau_out alone needs no qdd)
+      if ((st = launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &o, qdd)) != MH_OK)
+         return st;
+   mh_options rest = o; // H^-1 w: nothing moves, nothing pulls
+   rest.use_root_acceleration = 1;
+   for (double &x : rest.root_acceleration)
+      x = 0.0;
+   HIP_TRY(hipMemsetAsync(mu, 0, nvb, (hipStream_t)o.stream));
+   st = launch<T>(ALGO_ABA, model, B, q, mu, w, nullptr, nullptr, &rest, mu);
+   if (st != MH_OK || (!gq_out && !gqd_out))
+      return st;
+   mh_options od = o; // the inverse dynamics at the state forward dynamics saw: both switches on
+   od.consider_coriolis = 1, od.consider_accelerations = 1;
+   return rnea_vjp_launch<T>(model, B, q, qd, qdd, gravity, f_ext, mu, od, true, gq_out, gqd_out, nullptr);
+}
 template <typename T>
 mh_status integrate_impl(mh_model_t model, int64_t B, double dt, const T *q, const T *qd, const T *qdd, const mh_options *opts_in, T *q_out,
                                 T *qd_out, T *qdd_out)
@@ -2885,6 +3001,7 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
          m->cu_count = prop.multiProcessorCount;
    }
    m->device = dev;
+   m->vjp_slots = vjp_slot_plan(m->meta, m->n, m->vjp_slot);
    const std::vector<float> c32(m->consts.begin(), m->consts.end()), sm32(m->sub_mass.begin(), m->sub_mass.end());
    for (const DeviceRow &r : device_rows(m, c32, sm32))
    {
@@ -3238,12 +3355,13 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
    { // the lane-workspace kernels: (slots per lane, the most waves per group of configurations a call may want), bounded over every
       // batch up to max_batch (lane_ws_bound; swept by tests/test_launch_plans_cpu.py)
       const Launch L = plan_launch(m->cu_count, max_batch);
-      const long lane_plans[4][2] = {
+      const long lane_plans[5][2] = {
          {m->n_slots, std::min(8, m->n)}, // mh_regressor_*, mh_crba_coriolis_*, mh_centroidal_*, mh_gravity_gradient_*, the mass matrix
          // mh_apparent_inertia_inverse_*: its own slots behind the model's, up to one wave per target; mh_mass_matrix_inverse_* works in
          // the same slots with up to one wave per group of six columns
          {m->resp_slots, std::max<long>(MH_MAX_APPARENT_TARGETS, minv_groups(std::max<int>(m->nv, MH_MAX_INVERSE_COLUMNS)))},
          {m->deriv_slots, std::min(8, m->n)}, // mh_rnea_derivatives_* / mh_aba_derivatives_*: the kernel's own slot plan
+         {m->vjp_slots, std::min(8, m->n)},   // mh_rnea_vjp_* / mh_aba_vjp_*: likewise
          // mh_body_poses_* / mh_geometric_jacobian_*: pose and twist of every body per lane, up to one wave per target
          {(long)m->n * mh::KIN_SLOTS, MH_MAX_KINEMATIC_TARGETS}};
       for (const auto &plan : lane_plans)
@@ -3252,6 +3370,9 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       // mh_aba_derivatives_*: the scratch of the forward form
       if (m->nv > 0 && deriv_scratch_bytes(m, max_batch, sizeof(double)) <= kDerivReserveCap)
          st = ensure_bytes(m->deriv, deriv_scratch_bytes(m, max_batch, sizeof(double)));
+      // mh_aba_vjp_*: qdd and H^-1 w, should the caller take neither
+      if (st == MH_OK && m->nv > 0)
+         st = ensure_bytes(m->vjp, vjp_scratch_bytes(m, max_batch, sizeof(double)));
       // mh_aba_integrate_derivatives_*: the two derivative matrices beside them, under the same cap
       if (st == MH_OK && m->nv > 0 && deriv_scratch_bytes(m, max_batch, sizeof(double)) + step_scratch_bytes(m, max_batch, sizeof(double)) <= kDerivReserveCap)
          st = ensure_bytes(m->step, step_scratch_bytes(m, max_batch, sizeof(double)));
@@ -4072,6 +4193,27 @@ mh_status mh_configuration_difference_f64(mh_model_t model, int64_t B, const dou
 mh_status mh_configuration_difference_f32(mh_model_t model, int64_t B, const float *q0, const float *q1, const mh_options *opts, float *dq_out)
 {
    return configuration_difference_impl<float>(model, B, q0, q1, opts, dq_out);
+}
+mh_status mh_rnea_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double gravity[3],
+                          const double *f_ext, const double *u, const mh_options *opts, double *gq_out, double *gqd_out, double *gqdd_out)
+{
+   return rnea_vjp_impl<double>(model, B, q, qd, qdd, gravity, f_ext, u, opts, gq_out, gqd_out, gqdd_out);
+}
+mh_status mh_rnea_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const double gravity[3],
+                          const float *f_ext, const float *u, const mh_options *opts, float *gq_out, float *gqd_out, float *gqdd_out)
+{
+   return rnea_vjp_impl<float>(model, B, q, qd, qdd, gravity, f_ext, u, opts, gq_out, gqd_out, gqdd_out);
+}
+mh_status mh_aba_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
+                         const double *f_ext, const double *w, const mh_options *opts, double *qdd_out, double *gq_out, double *gqd_out,
+                         double *gtau_out)
+{
+   return aba_vjp_impl<double>(model, B, q, qd, tau, gravity, f_ext, w, opts, qdd_out, gq_out, gqd_out, gtau_out);
+}
+mh_status mh_aba_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const double gravity[3],
+                         const float *f_ext, const float *w, const mh_options *opts, float *qdd_out, float *gq_out, float *gqd_out, float *gtau_out)
+{
+   return aba_vjp_impl<float>(model, B, q, qd, tau, gravity, f_ext, w, opts, qdd_out, gq_out, gqd_out, gtau_out);
 }
 mh_status mh_aba_integrate_derivatives_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *tau,
                                            const double gravity[3], const double *f_ext, const mh_options *opts, double *qdd_out,

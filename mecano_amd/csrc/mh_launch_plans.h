@@ -10,6 +10,7 @@
 #include "mh_model_tables.h"
 #include "mh_dfs_kernels.h"
 #include "mh_split_kernels.h"
+#include "mh_rnea_vjp_kernels.h"
 
 #include <algorithm>
 #include <cassert>
@@ -100,6 +101,20 @@ size_t lane_ws_bound(int cu_count, long slots, const Launch &L, long max_want, s
 {
    const long waves = std::max<long>(L.grid, std::min<long>(max_want * L.grid, (long)cu_count * 4));
    return (size_t)slots * (size_t)waves * (size_t)L.block * elem;
+}
+
+// ---- reverse-mode gradients of the dynamics (mh_rnea_vjp_kernels.h): that kernel's own slot plan -- the first workspace slot of every
+// body, VS_BODY slots each and VS_BRANCH for a body with a child that does not directly follow it; returns the slots per lane
+int vjp_slot_plan(const std::vector<int> &meta, int n, std::vector<int> &slot)
+{
+   slot.assign((size_t)std::max(1, n), 0);
+   int slots = 0;
+   for (int e = 0; e < n; e++)
+   {
+      slot[e] = slots;
+      slots += (meta[(size_t)e * mh::MI_STRIDE + mh::MI_FLAGS] & mh::MF_STORE_VA) ? mh::VS_BRANCH : mh::VS_BODY;
+   }
+   return std::max(slots, 1);
 }
 
 // Depth-first run-time-topology kernels (mh_dfs_kernels.h): homes of the stack frames, where ABA's hand-over lives, grid.

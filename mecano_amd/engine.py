@@ -885,6 +885,61 @@ class HipModel:
             self._h, B, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), g, ptr(f_ext), ctypes.byref(opts), ptr(qdd), ptr(dq), ptr(dqd), ptr(Hinv)))
         return qdd, dq, dqd, Hinv
 
+    def rnea_vjp(self, q, qd, qdd, u, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, consider_coriolis=True,
+                 consider_accelerations=True, out=None):
+        """Reverse-mode gradients of the inverse dynamics, one O(n) launch and no matrix: for a cotangent ``u`` [B, nv] of the efforts,
+        (gq, gqd, gqdd) [B, nv] each with gq = u^T d tau / d q, gqd = u^T d tau / d qd (the matrices of ``rnea_derivatives``: velocity-space
+        steps, wrenches held in the world) and gqdd = H(q) u.  ``chart_pullback`` turns gq into the gradient with respect to the raw
+        coordinates.  SoA: [nv, B].  ``qdd`` may be None with ``consider_accelerations=False``, ``qd`` with ``consider_coriolis=False``
+        (gqd is then zeros).  ``out``: a (gq, gqd, gqdd) tuple to write into; any may be None (not computed), not all three."""
+        given = [t for t in (q, qd if consider_coriolis else None, qdd if consider_accelerations else None, u) if t is not None]
+        B, dt, sfx, stream = self._device_inputs(given, layout)
+        if u is None or (consider_coriolis and qd is None) or (consider_accelerations and qdd is None):
+            raise _lib.MecanoHipError(1, "u is needed; qd / qdd may be None only with their switch off")
+        if f_ext is not None:
+            self._device_tensor(f_ext, dt)
+        self._check_f_ext(f_ext, B, layout)
+        vec = (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B)
+        gq, gqd, gqdd = self._outputs(out, (vec, vec, vec), ("gq", "gqd", "gqdd"), dt, q.device)
+        if gq is None and gqd is None and gqdd is None:
+            raise _lib.MecanoHipError(1, "all three outputs are None")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, consider_coriolis, consider_accelerations, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_rnea_vjp_{sfx}")(
+            self._h, B, q.data_ptr(), ptr(qd) if consider_coriolis else None, ptr(qdd) if consider_accelerations else None, g, ptr(f_ext),
+            u.data_ptr(), ctypes.byref(opts), ptr(gq), ptr(gqd), ptr(gqdd)))
+        return gq, gqd, gqdd
+
+    def aba_vjp(self, q, qd, tau, w, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Reverse-mode gradients of the forward dynamics, no matrix: for a cotangent ``w`` [B, nv] of qdd = aba(q, qd, tau),
+        (qdd, gq, gqd, gtau) [B, nv] each with gtau = H^-1 w, gq = w^T d qdd / d q and gqd = w^T d qdd / d qd (the matrices of
+        ``aba_derivatives``).  Two forward-dynamics launches and the kernel of ``rnea_vjp``.  ``out``: a (qdd, gq, gqd, gtau) tuple to write
+        into; any may be None, not all three gradients.  A model with acceleration-source joints is refused."""
+        B, dt, sfx, stream = self._device_inputs([q, qd, tau, w], layout)
+        if f_ext is not None:
+            self._device_tensor(f_ext, dt)
+        self._check_f_ext(f_ext, B, layout)
+        vec = (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B)
+        qdd, gq, gqd, gtau = self._outputs(out, (vec, vec, vec, vec), ("qdd", "gq", "gqd", "gtau"), dt, q.device)
+        if gq is None and gqd is None and gtau is None:
+            raise _lib.MecanoHipError(1, "all three gradients are None")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, True, True, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_aba_vjp_{sfx}")(
+            self._h, B, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), g, ptr(f_ext), w.data_ptr(), ctypes.byref(opts), ptr(qdd), ptr(gq), ptr(gqd),
+            ptr(gtau)))
+        return qdd, gq, gqd, gtau
+
+    def chart_pullback(self, q, g):
+        """The gradient with respect to the raw coordinates q [B, nq] from a velocity-space gradient g [B, nv] (gq of ``rnea_vjp`` /
+        ``aba_vjp``): ``mecano_amd.autograd.chart_pullback`` on this model's index maps.  Plain torch operations, AoS, any device."""
+        from . import autograd
+        if getattr(self, "_chart_index", None) is None:
+            self._chart_index = autograd.chart_maps(self.desc)
+        return autograd.chart_pullback(self.desc, q, g, self._chart_index)
+
     def _chart_call(self, name, a, b, b_cols, out_cols, layout, out):
         B, dt, sfx, stream = self._device_inputs([a], layout)
         aos = layout == _lib.LAYOUT_AOS
