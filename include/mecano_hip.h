@@ -674,6 +674,42 @@ mh_status mh_aba_integrate_derivatives_f32(mh_model_t model, int64_t B, double d
                                            float *q_next, float *qd_next, float *A_out, float *B_out);
 
 /*
+ * ---- reverse-mode gradients of the integrator and of the simulation step: what backpropagation through a rollout needs, without the
+ *      matrices A and B above (no calculator of the reference) ----
+ * mh_integrate_vjp_*: for cotangents gq_next, gqd_next [B][nv] of (dq', dqd') of mh_integrate_*(q, qd, qdd) with step dt, the gradients
+ * gq_out, gqd_out, gqdd_out [B][nv] with respect to (dq, dqd, dqdd): the transpose of the integrator's per-joint tangent map, in the
+ * conventions of mh_aba_integrate_derivatives_* -- dq and dq' are velocity-space steps of (+), dqd and dqd' component increments, qd_next
+ * of a SixDoF joint in the NEW frame.  Neither q nor the joints' poses appear.  The cotangent of the integrator's optional re-expressed
+ * qdd_out is not an input: it is taken as zero.  ONE launch of an elementwise run-time-topology kernel, no workspace; joint source modes
+ * play no part.
+ * mh_aba_integrate_vjp_*: the same for the step mh_aba_* followed by mh_integrate_*: gq_out = A^T g', gqd_out likewise and
+ * gtau_out = B^T g' with g' = (gq_next, gqd_next) and the (A, B) of mh_aba_integrate_derivatives_*, external wrenches held IN THE WORLD.
+ * qdd_out [B][nv] may be NULL.  Launches composed on opts->stream: forward dynamics (whichever plan mh_aba_* takes), the kernel of
+ * mh_integrate_vjp_* (the integrator's own share of gq and gqd, and w = the cotangent of qdd), forward dynamics at rest for H^-1 w, and the
+ * adjoint sweep of mh_aba_vjp_*, which adds its share to gq_out and gqd_out -- one launch more than mh_aba_vjp_*; the sweep is dropped where
+ * gq_out and gqd_out are both NULL.  No nv x nv matrix is read, written or reserved: the scratch is at most 3 B nv elements of the context
+ * (qdd, w and H^-1 w where the caller takes neither qdd_out nor gtau_out), set aside by mh_reserve / mh_context_reserve.  A model with
+ * MH_ACCELERATION_SOURCE joints is refused (MH_ERR_INVALID_ARGUMENT), as is gravity == NULL without a root acceleration.
+ * Both: every cotangent and gradient is [B][nv] (MH_LAYOUT_SOA: [nv][B]).  Either cotangent may be NULL and is then taken as zero; both
+ * NULL is refused.  At least one gradient output must be given (MH_ERR_INVALID_ARGUMENT otherwise).  Every entry of an output given is
+ * written once, zeros at DoF indices no joint owns included (cotangent entries there are not read), nothing outside the outputs.  The
+ * outputs overlap neither the inputs nor each other.  dt may be 0 (gq_out = gq_next, gqd_out = gqd_next, gqdd_out / gtau_out = 0, exactly)
+ * or negative; a dt that is not finite is MH_ERR_INVALID_ARGUMENT.  B = 0 or nv = 0 returns MH_OK and touches nothing.  Device pointers,
+ * asynchronous on opts->stream, layouts, index maps and contexts honoured; after mh_reserve / mh_context_reserve the calls only enqueue
+ * work (graph-capturable).
+ */
+mh_status mh_integrate_vjp_f64(mh_model_t model, int64_t B, double dt, const double *qd, const double *qdd, const double *gq_next,
+                               const double *gqd_next, const mh_options *opts, double *gq_out, double *gqd_out, double *gqdd_out);
+mh_status mh_integrate_vjp_f32(mh_model_t model, int64_t B, double dt, const float *qd, const float *qdd, const float *gq_next,
+                               const float *gqd_next, const mh_options *opts, float *gq_out, float *gqd_out, float *gqdd_out);
+mh_status mh_aba_integrate_vjp_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *tau,
+                                   const double gravity[3], const double *f_ext, const double *gq_next, const double *gqd_next,
+                                   const mh_options *opts, double *qdd_out, double *gq_out, double *gqd_out, double *gtau_out);
+mh_status mh_aba_integrate_vjp_f32(mh_model_t model, int64_t B, double dt, const float *q, const float *qd, const float *tau,
+                                   const double gravity[3], const float *f_ext, const float *gq_next, const float *gqd_next,
+                                   const mh_options *opts, float *qdd_out, float *gq_out, float *gqd_out, float *gtau_out);
+
+/*
  * ---- inverse and forward dynamics with per-configuration inertial parameters: B different robots of one topology and geometry
  *      (domain randomisation, identification by simulation error, payload sweeps; no calculator of the reference evaluates a batch) ----
  * pi (DEVICE) is [B][n_joints][10], MH_LAYOUT_SOA: [10 n_joints][B] (opts->layout, as for every other matrix of the call).  The ten

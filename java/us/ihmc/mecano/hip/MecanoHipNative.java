@@ -175,6 +175,24 @@ public final class MecanoHipNative
    /** the same in fp32 */
    static final MethodHandle ABA_INTEGRATE_DERIVATIVES_F32 = handle("mh_aba_integrate_derivatives_f32", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                                                                ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * Reverse-mode gradients of the integrator: (model, B, dt, qd, qdd, gq_next|NULL, gqd_next|NULL, opts|NULL, gq_out|NULL, gqd_out|NULL,
+    * gqdd_out|NULL), vectors [B][nv]; not both cotangents NULL, not all three gradients NULL.
+    */
+   static final MethodHandle INTEGRATE_VJP = handle("mh_integrate_vjp_f64", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                   ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle INTEGRATE_VJP_F32 = handle("mh_integrate_vjp_f32", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                       ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * Reverse-mode gradients of the simulation step: (model, B, dt, q, qd, tau, gravity[3] (host), f_ext|NULL, gq_next|NULL, gqd_next|NULL,
+    * opts|NULL, qdd_out|NULL, gq_out|NULL, gqd_out|NULL, gtau_out|NULL), vectors [B][nv]; not both cotangents NULL, not all three gradients NULL.
+    */
+   static final MethodHandle ABA_INTEGRATE_VJP = handle("mh_aba_integrate_vjp_f64", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                           ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle ABA_INTEGRATE_VJP_F32 = handle("mh_aba_integrate_vjp_f32", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                               ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
    /** The model's own inertial parameters: (model, pi_out (host double[n_joints][10])), the layout of a row of pi below. */
    static final MethodHandle MODEL_INERTIAL_PARAMETERS = handle("mh_model_inertial_parameters", status(ADDRESS, ADDRESS));
    /**

@@ -1,8 +1,10 @@
-"""torch.autograd through the batched dynamics: ``rnea`` and ``aba`` as differentiable functions of (q, qd, qdd | tau), and the pullback
-from velocity-space gradients to the raw coordinates.
+"""torch.autograd through the batched dynamics: ``rnea`` and ``aba`` as differentiable functions of (q, qd, qdd | tau), ``integrate`` and
+``step`` (forward dynamics, then the integrator) as differentiable functions of the state, and the maps between velocity-space gradients
+and the raw coordinates.
 
-The forward passes are ``HipModel.rnea`` / ``HipModel.aba`` unchanged; a backward pass is ONE call of ``HipModel.rnea_vjp`` /
-``HipModel.aba_vjp`` (the O(n) adjoint sweep of mh_rnea_vjp_kernels.h: no nv x nv matrix is formed) plus ``chart_pullback`` for q.
+The forward passes are ``HipModel.rnea`` / ``HipModel.aba`` / ``HipModel.integrate`` / ``HipModel.step`` unchanged; a backward pass is ONE
+call of ``HipModel.rnea_vjp`` / ``HipModel.aba_vjp`` / ``HipModel.integrate_vjp`` / ``HipModel.step_vjp`` (no nv x nv matrix is formed)
+plus ``chart_pullback`` for q, and ``chart_cotangent`` at the new configuration for the two steps.
 AoS device tensors, fp64 or fp32.  gravity and f_ext are not differentiated.  Once differentiable: the backward pass is not itself a
 graph of torch operations, and a second backward raises.
 """
@@ -76,6 +78,53 @@ def chart_pullback(desc, q, g, maps=None):
     return out
 
 
+def chart_cotangent(desc, q, g_raw, maps=None):
+    """The velocity-space cotangent [B, nv] at q [B, nq] from a gradient g_raw [B, nq] with respect to the raw coordinates: the transpose
+    of the tangent map of q (+) dq at dq = 0, the other direction of ``chart_pullback``.  Plain torch operations (AoS, any device):
+      1-DoF joints and the planar pitch       pass through;
+      a quaternion Q = (x, y, z, s), raw      vec(conj(Q) o g_Q) / 2 -- Q' = Q exp(dth) moves the raw Q by Q o (dth, 0) / 2, not normalised;
+      SixDoF translations                     R(Q)^T g_p -- the step moves p by R(Q) dp, R of the normalised Q;
+      planar translations                     (c g_x - s g_z, s g_x + c g_z), c and s of the pitch;
+      DoF entries no joint owns               0."""
+    nq, nv = int(desc.nq), int(desc.nv)
+    if q.ndim != 2 or g_raw.ndim != 2 or q.shape[1] != nq or tuple(g_raw.shape) != tuple(q.shape):
+        raise ValueError(f"expected q and g_raw [B, {nq}], got {tuple(q.shape)} and {tuple(g_raw.shape)}")
+    m = chart_maps(desc) if maps is None else maps
+    idx = lambda rows: torch.as_tensor(rows, dtype=torch.long, device=q.device)
+    out = torch.zeros((q.shape[0], nv), dtype=q.dtype, device=q.device)
+    if m["one_q"]:
+        out[:, idx(m["one_v"])] = g_raw[:, idx(m["one_q"])]
+    if m["quat_q"]:
+        Q, gQ = q[:, idx(m["quat_q"])], g_raw[:, idx(m["quat_q"])]  # [B, J, 4] each
+        v, s, gv, gs = Q[..., :3], Q[..., 3:], gQ[..., :3], gQ[..., 3:]
+        out[:, idx(m["quat_v"])] = 0.5 * (s * gv - gs * v - torch.cross(v, gv, dim=-1))
+        if m["lin_q"]:
+            x, y, z, s = (Q / Q.norm(dim=-1, keepdim=True))[:, idx(m["lin_quat"])].unbind(-1)
+            R = torch.stack([1 - 2 * (y * y + z * z), 2 * (x * y - z * s), 2 * (x * z + y * s),
+                             2 * (x * y + z * s), 1 - 2 * (x * x + z * z), 2 * (y * z - x * s),
+                             2 * (x * z - y * s), 2 * (y * z + x * s), 1 - 2 * (x * x + y * y)], dim=-1).reshape(*x.shape, 3, 3)
+            out[:, idx(m["lin_v"])] = (R.transpose(-1, -2) @ g_raw[:, idx(m["lin_q"])].unsqueeze(-1)).squeeze(-1)
+    if m["pl_q"]:
+        P, gp = q[:, idx(m["pl_q"])], g_raw[:, idx(m["pl_q"])]  # (pitch, x, z) each
+        c, s = torch.cos(P[..., 0]), torch.sin(P[..., 0])
+        out[:, idx(m["pl_v"])] = torch.stack([gp[..., 0], c * gp[..., 1] - s * gp[..., 2], s * gp[..., 1] + c * gp[..., 2]], dim=-1)
+    return out
+
+
+def radial_passthrough(desc, q, q_next, g_raw_next, maps=None):
+    """What the raw quaternions of q receive through their LENGTH from a gradient g_raw_next [B, nq] with respect to the raw q_next of
+    ``integrate`` / ``step``, [B, nq]: the integrator forms Q' = Q exp(r) from the raw Q without normalising while everything else reads
+    Q / |Q|, so scaling Q scales Q' and nothing else, which is (g_Q' . Q') Q / |Q|^2.  Zero everywhere but the quaternions; orthogonal to
+    what ``chart_pullback`` returns there."""
+    m = chart_maps(desc) if maps is None else maps
+    out = torch.zeros_like(q)
+    if m["quat_q"]:
+        at = torch.as_tensor(m["quat_q"], dtype=torch.long, device=q.device)
+        Q = q[:, at]
+        out[:, at] = (g_raw_next[:, at] * q_next[:, at]).sum(-1, keepdim=True) * Q / (Q * Q).sum(-1, keepdim=True)
+    return out
+
+
 def _wanted(ctx, first, like):
     """One new output tensor per input of ctx.needs_input_grad[first : first + 3] that wants a gradient, None for the others."""
     return tuple(torch.empty_like(like) if need else None for need in ctx.needs_input_grad[first:first + 3])
@@ -109,6 +158,62 @@ class _Aba(torch.autograd.Function):
         q, qd, tau = ctx.saved_tensors
         _, gq, gqd, gtau = ctx.model.aba_vjp(q, qd, tau, w.contiguous(), ctx.gravity, ctx.f_ext, out=(None,) + _wanted(ctx, 1, qd))
         return None, (None if gq is None else ctx.model.chart_pullback(q, gq)), gqd, gtau, None, None
+
+
+def _raw_gradient(model, q, q_next, gq, g_raw_next):
+    """chart_pullback at q plus the quaternions' radial pass-through: the gradient of the raw map q -> (q_next, qd_next)."""
+    if gq is None:
+        return None
+    return model.chart_pullback(q, gq) + radial_passthrough(model.desc, q, q_next, g_raw_next, getattr(model, "_chart_index", None))
+
+
+class _Integrate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, dt, q, qd, qdd):
+        q_next, qd_next = model.integrate(dt, q, qd, qdd)[:2]
+        ctx.model, ctx.dt = model, dt
+        ctx.save_for_backward(q, qd, qdd, q_next)
+        return q_next, qd_next
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_q_next, g_qd_next):
+        q, qd, qdd, q_next = ctx.saved_tensors
+        gth = ctx.model.chart_cotangent(q_next, g_q_next)
+        gq, gqd, gqdd = ctx.model.integrate_vjp(ctx.dt, qd, qdd, gth, g_qd_next.contiguous(), out=_wanted(ctx, 2, qd))
+        return None, None, _raw_gradient(ctx.model, q, q_next, gq, g_q_next), gqd, gqdd
+
+
+class _Step(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, dt, q, qd, tau, gravity, f_ext):
+        if q.dtype == torch.float64:
+            q_next, qd_next, _ = model.step(dt, q, qd, tau, gravity, f_ext)
+        else:  # (the fused entry point is fp64 only)
+            q_next, qd_next = model.integrate(dt, q, qd, model.aba(q, qd, tau, gravity, f_ext))[:2]
+        ctx.model, ctx.dt, ctx.gravity, ctx.f_ext = model, dt, gravity, f_ext
+        ctx.save_for_backward(q, qd, tau, q_next)
+        return q_next, qd_next
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_q_next, g_qd_next):
+        q, qd, tau, q_next = ctx.saved_tensors
+        gth = ctx.model.chart_cotangent(q_next, g_q_next)
+        _, gq, gqd, gtau = ctx.model.step_vjp(ctx.dt, q, qd, tau, gth, g_qd_next.contiguous(), ctx.gravity, ctx.f_ext,
+                                              out=(None,) + _wanted(ctx, 2, qd))
+        return None, None, _raw_gradient(ctx.model, q, q_next, gq, g_q_next), gqd, gtau, None, None
+
+
+def integrate(model, dt, q, qd, qdd):
+    """(q_next, qd_next) = ``model.integrate(dt, q, qd, qdd)``, differentiable with respect to q (raw coordinates), qd and qdd."""
+    return _Integrate.apply(model, dt, q, qd, qdd)
+
+
+def step(model, dt, q, qd, tau, gravity=(0.0, 0.0, -9.81), f_ext=None):
+    """(q_next, qd_next) of one simulation step, ``model.aba`` then ``model.integrate`` with step ``dt`` (fp64: ``model.step``),
+    differentiable with respect to q (raw coordinates), qd and tau: the backward pass is ONE ``model.step_vjp``."""
+    return _Step.apply(model, dt, q, qd, tau, gravity, f_ext)
 
 
 def rnea(model, q, qd, qdd, gravity=(0.0, 0.0, -9.81), f_ext=None):

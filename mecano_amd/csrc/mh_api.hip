@@ -2441,11 +2441,13 @@ mh_status aba_derivatives_impl(mh_model_t model, int64_t B, const T *q, const T 
    return MH_OK;
 }
 // Reverse-mode gradients of the inverse dynamics (mh_rnea_vjp_kernels.h): one launch of a run-time-topology kernel in a slot plan of its
-// own, which writes every entry of the outputs it is given.  negate: -gq and -gqd (the forward form below).
-static size_t vjp_scratch_bytes(const mh_model *m, int64_t B, size_t elem) { return (size_t)B * 2 * (size_t)m->nv * elem; }
+// own, which writes every entry of the outputs it is given.  negate: -gq and -gqd (the forward form below).  accumulate: gq and gqd are
+// added to what the outputs hold and entries no joint owns are left alone (mh_aba_integrate_vjp_*).
+// The scratch of the forward forms: qdd and H^-1 w for mh_aba_vjp_*, which is given w; qdd, w and H^-1 w for mh_aba_integrate_vjp_*.
+static size_t vjp_scratch_bytes(const mh_model *m, int64_t B, size_t elem, int vectors = 3) { return (size_t)B * vectors * (size_t)m->nv * elem; }
 template <typename T>
 mh_status rnea_vjp_launch(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const double *gravity, const T *f_ext, const T *u,
-                          const mh_options &opts, bool negate, T *gq_out, T *gqd_out, T *gqdd_out)
+                          const mh_options &opts, bool negate, T *gq_out, T *gqd_out, T *gqdd_out, bool accumulate = false)
 {
    const Launch L = plan_launch(model->cu_count, B);
    const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
@@ -2460,7 +2462,7 @@ mh_status rnea_vjp_launch(mh_model_t model, int64_t B, const T *q, const T *qd, 
    A.ws_stride = L.lanes;
    G.u = u, G.gq = gq_out, G.gqd = gqd_out, G.gqdd = gqdd_out;
    G.slot = model->d_vjp_slot, G.slots = model->vjp_slots;
-   G.negate = negate;
+   G.negate = negate, G.accumulate = accumulate;
    G.unowned = model->d_grav_zero_cols + model->grav_zero_ofs[model->n];
    G.n_unowned = model->grav_zero_ofs[model->n + 1] - model->grav_zero_ofs[model->n];
    hipLaunchKernelGGL((mh::rnea_vjp_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
@@ -2528,7 +2530,7 @@ mh_status aba_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, con
    T *qdd = qdd_out, *mu = gtau_out;
    if (!qdd || !mu)
    {
-      if ((st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T)))) != MH_OK)
+      if ((st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T), 2))) != MH_OK)
          return st;
       if (!qdd)
          qdd = (T *)model->vjp.ptr;
@@ -2729,6 +2731,125 @@ mh_status step_derivatives_impl(mh_model_t model, int64_t B, const double &dt, c
    if (q_next)
       return integrate_impl<T>(model, B, dt, q, qd, S.qdd, &o, q_next, qd_next, nullptr);
    return MH_OK;
+}
+// Reverse mode of the integrator (mh_step_kernels.h: integrate_vjp_*_kernel): one elementwise launch in the integrator's own launch
+// shape, no workspace.  Every entry of the outputs given is written once.
+template <typename T>
+mh_status integrate_vjp_launch(mh_model_t model, int64_t B, double dt, const T *qd, const T *qdd, const T *gq_next, const T *gqd_next,
+                               const mh_options &opts, T *gq_out, T *gqd_out, T *gqdd_out)
+{
+   mh::StepVjpArgs<T> A{};
+   A.m = dev_model<T>(model);
+   A.B = B, A.dt = (T)dt;
+   A.qd = qd, A.qdd = qdd, A.gqn = gq_next, A.gqdn = gqd_next;
+   A.gq = gq_out, A.gqd = gqd_out, A.gqdd = gqdd_out;
+   A.unowned = model->d_grav_zero_cols + model->grav_zero_ofs[model->n];
+   A.n_unowned = model->grav_zero_ofs[model->n + 1] - model->grav_zero_ofs[model->n];
+   const bool soa = opts.layout == MH_LAYOUT_SOA;
+   set_strides(A.v_bs, A.v_es, soa, B, model->nv);
+   const int block = 256;
+   if (soa)
+   {
+      const int grid = (int)std::max<long>(1, std::min<long>((B + block - 1) / block, (long)model->cu_count * 8));
+      hipLaunchKernelGGL((mh::integrate_vjp_soa_kernel<T>), dim3(grid), dim3(block), 0, (hipStream_t)opts.stream, A);
+   }
+   else
+   { // the integrator's tiles: enough workgroups to cover the device at small B, up to 256 configurations each at large B
+      const int tile = (int)std::max<long>(16, std::min<long>(256, B / ((long)model->cu_count * 4)));
+      const int grid = (int)std::max<long>(1, std::min<long>((B + tile - 1) / tile, (long)model->cu_count * 8));
+      hipLaunchKernelGGL((mh::integrate_vjp_aos_kernel<T>), dim3(grid), dim3(block), ((size_t)model->n * 2 + 2) * sizeof(int), (hipStream_t)opts.stream, A,
+                         tile);
+   }
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
+template <typename T>
+mh_status integrate_vjp_impl(mh_model_t model, int64_t B, double dt, const T *qd, const T *qdd, const T *gq_next, const T *gqd_next,
+                             const mh_options *opts_in, T *gq_out, T *gqd_out, T *gqdd_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   if (nonfinite_bits(dt))
+      return fail(MH_ERR_INVALID_ARGUMENT, "dt is not finite");
+   if (!gq_out && !gqd_out && !gqdd_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gq_out, gqd_out and gqdd_out are all NULL");
+   if (!gq_next && !gqd_next)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gq_next and gqd_next are both NULL");
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!qd || !qdd)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state pointer");
+   {
+      const size_t bv = (size_t)B * model->nv * sizeof(T);
+      const InRange ins[4] = {{"qd", qd, bv}, {"qdd", qdd, bv}, {"gq_next", gq_next, bv}, {"gqd_next", gqd_next, bv}};
+      const OutRange outs[3] = {{"gq_out", gq_out, bv, 0u}, {"gqd_out", gqd_out, bv, 0u}, {"gqdd_out", gqdd_out, bv, 0u}};
+      if ((st = check_aliasing("mh_integrate_vjp", ins, 4, outs, 3)) != MH_OK)
+         return st;
+   }
+   return integrate_vjp_launch<T>(model, B, dt, qd, qdd, gq_next, gqd_next, opts, gq_out, gqd_out, gqdd_out);
+}
+// Reverse mode of the step x' = integrate(q, qd, aba(q, qd, tau)): four launches (and one memset) composed on the caller's stream --
+// forward dynamics for qdd; the kernel above, which writes the integrator's own share of gq and gqd into the outputs and
+// w = the cotangent of qdd into scratch; forward dynamics at rest with tau = w, which is mu = H^-1 w = gtau (as in aba_vjp_impl); the
+// adjoint sweep at that qdd with u = mu, negated, ADDING its gq and gqd to what the outputs hold (VjpArgs::accumulate).
+template <typename T>
+mh_status step_vjp_impl(mh_model_t model, int64_t B, double dt, const T *q, const T *qd, const T *tau, const double *gravity, const T *f_ext,
+                        const T *gq_next, const T *gqd_next, const mh_options *opts_in, T *qdd_out, T *gq_out, T *gqd_out, T *gtau_out)
+{
+   mh_options o;
+   mh_status st = begin_call(model, B, opts_in, o);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: the gradients of the step take none", model->n_locked);
+   if (nonfinite_bits(dt))
+      return fail(MH_ERR_INVALID_ARGUMENT, "dt is not finite");
+   if (!gravity && !o.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (!gq_out && !gqd_out && !gtau_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gq_out, gqd_out and gtau_out are all NULL");
+   if (!gq_next && !gqd_next)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gq_next and gqd_next are both NULL");
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!q || !qd || !tau)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state pointer");
+   const size_t nvb = (size_t)B * model->nv * sizeof(T);
+   {
+      const InRange ins[6] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"qd", qd, nvb}, {"tau", tau, nvb}, {"f_ext", f_ext, (size_t)B * model->n * 6 * sizeof(T)},
+                              {"gq_next", gq_next, nvb}, {"gqd_next", gqd_next, nvb}};
+      const OutRange outs[4] = {{"qdd_out", qdd_out, nvb, 0u}, {"gq_out", gq_out, nvb, 0u}, {"gqd_out", gqd_out, nvb, 0u}, {"gtau_out", gtau_out, nvb, 0u}};
+      if ((st = check_aliasing("mh_aba_integrate_vjp", ins, 6, outs, 4)) != MH_OK)
+         return st;
+   }
+   // scratch: w always, qdd and mu where the caller takes neither
+   if ((st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T), 1 + !qdd_out + !gtau_out))) != MH_OK)
+      return st;
+   const size_t bn = (size_t)B * model->nv;
+   T *next = (T *)model->vjp.ptr;
+   T *const w = next;
+   next += bn;
+   T *const qdd = qdd_out ? qdd_out : next;
+   if (!qdd_out)
+      next += bn;
+   T *const mu = gtau_out ? gtau_out : next;
+   if ((st = launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &o, qdd)) != MH_OK) // (w needs qdd wherever dt != 0)
+      return st;
+   if ((st = integrate_vjp_launch<T>(model, B, dt, qd, qdd, gq_next, gqd_next, o, gq_out, gqd_out, w)) != MH_OK)
+      return st;
+   mh_options rest = o; // H^-1 w: nothing moves, nothing pulls
+   rest.use_root_acceleration = 1;
+   for (double &x : rest.root_acceleration)
+      x = 0.0;
+   HIP_TRY(hipMemsetAsync(mu, 0, nvb, (hipStream_t)o.stream));
+   st = launch<T>(ALGO_ABA, model, B, q, mu, w, nullptr, nullptr, &rest, mu);
+   if (st != MH_OK || (!gq_out && !gqd_out))
+      return st;
+   mh_options od = o; // the inverse dynamics at the state forward dynamics saw: both switches on
+   od.consider_coriolis = 1, od.consider_accelerations = 1;
+   return rnea_vjp_launch<T>(model, B, q, qd, qdd, gravity, f_ext, mu, od, true, gq_out, gqd_out, nullptr, true);
 }
 } // namespace
 
@@ -3370,7 +3491,7 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       // mh_aba_derivatives_*: the scratch of the forward form
       if (m->nv > 0 && deriv_scratch_bytes(m, max_batch, sizeof(double)) <= kDerivReserveCap)
          st = ensure_bytes(m->deriv, deriv_scratch_bytes(m, max_batch, sizeof(double)));
-      // mh_aba_vjp_*: qdd and H^-1 w, should the caller take neither
+      // mh_aba_vjp_* / mh_aba_integrate_vjp_*: qdd, w and H^-1 w, should the caller take neither qdd nor gtau
       if (st == MH_OK && m->nv > 0)
          st = ensure_bytes(m->vjp, vjp_scratch_bytes(m, max_batch, sizeof(double)));
       // mh_aba_integrate_derivatives_*: the two derivative matrices beside them, under the same cap
@@ -4226,6 +4347,28 @@ mh_status mh_aba_integrate_derivatives_f32(mh_model_t model, int64_t B, double d
                                            float *q_next, float *qd_next, float *A_out, float *B_out)
 {
    return step_derivatives_impl<float>(model, B, dt, q, qd, tau, gravity, f_ext, opts, qdd_out, q_next, qd_next, A_out, B_out);
+}
+mh_status mh_integrate_vjp_f64(mh_model_t model, int64_t B, double dt, const double *qd, const double *qdd, const double *gq_next,
+                               const double *gqd_next, const mh_options *opts, double *gq_out, double *gqd_out, double *gqdd_out)
+{
+   return integrate_vjp_impl<double>(model, B, dt, qd, qdd, gq_next, gqd_next, opts, gq_out, gqd_out, gqdd_out);
+}
+mh_status mh_integrate_vjp_f32(mh_model_t model, int64_t B, double dt, const float *qd, const float *qdd, const float *gq_next,
+                               const float *gqd_next, const mh_options *opts, float *gq_out, float *gqd_out, float *gqdd_out)
+{
+   return integrate_vjp_impl<float>(model, B, dt, qd, qdd, gq_next, gqd_next, opts, gq_out, gqd_out, gqdd_out);
+}
+mh_status mh_aba_integrate_vjp_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *tau,
+                                   const double gravity[3], const double *f_ext, const double *gq_next, const double *gqd_next,
+                                   const mh_options *opts, double *qdd_out, double *gq_out, double *gqd_out, double *gtau_out)
+{
+   return step_vjp_impl<double>(model, B, dt, q, qd, tau, gravity, f_ext, gq_next, gqd_next, opts, qdd_out, gq_out, gqd_out, gtau_out);
+}
+mh_status mh_aba_integrate_vjp_f32(mh_model_t model, int64_t B, double dt, const float *q, const float *qd, const float *tau,
+                                   const double gravity[3], const float *f_ext, const float *gq_next, const float *gqd_next,
+                                   const mh_options *opts, float *qdd_out, float *gq_out, float *gqd_out, float *gtau_out)
+{
+   return step_vjp_impl<float>(model, B, dt, q, qd, tau, gravity, f_ext, gq_next, gqd_next, opts, qdd_out, gq_out, gqd_out, gtau_out);
 }
 mh_status mh_rnea_parameters_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double *pi,
                                  const double gravity[3], const double *f_ext, const mh_options *opts, double *tau_out)

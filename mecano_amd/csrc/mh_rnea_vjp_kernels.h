@@ -62,6 +62,7 @@ struct VjpArgs
    const int *slot;     // [n] first workspace slot of every body
    int slots;           // workspace slots per lane
    int negate;          // store -gq and -gqd (the forward form: u = H^-1 w)
+   int accumulate;      // gq and gqd are added to what the outputs hold (mh_aba_integrate_vjp_*); unowned entries are left alone
    const int *unowned;  // DoF indices no joint owns: zeros
    int n_unowned;
 };
@@ -85,6 +86,7 @@ __global__ void __launch_bounds__(256) rnea_vjp_kernel(VjpArgs<T> G)
    const SV<T> Z6{Z, Z};
    const bool with_ext = A.fext != nullptr, with_gq = G.gq != nullptr, with_gqd = G.gqd != nullptr, with_gqdd = G.gqdd != nullptr;
    const T sign = G.negate ? T(-1) : T(1);
+   const bool acc = G.accumulate != 0;
 
    for (long cfg = lane; cfg < A.B; cfg += nlanes)
    {
@@ -204,7 +206,11 @@ __global__ void __launch_bounds__(256) rnea_vjp_kernel(VjpArgs<T> G)
                {
                   const SV<T> Gv = X4 - crf(vl + vj, X1);
                   for (int k = 0; k < nd; k++)
-                     gqd[(long)dj[k] * A.v_es] = sign * comp(Gv, dof_comp(type, k));
+                  {
+                     T *at = gqd + (long)dj[k] * A.v_es;
+                     const T val = sign * comp(Gv, dof_comp(type, k));
+                     *at = acc ? *at + val : val;
+                  }
                }
                if (with_gq)
                {
@@ -214,7 +220,11 @@ __global__ void __launch_bounds__(256) rnea_vjp_kernel(VjpArgs<T> G)
                      X5 = X5 - crf(nu, W);
                   const SV<T> Gq = X5 - crf(vl, X4 - crf(vl, X1)) - crf(al, X1);
                   for (int k = 0; k < nd; k++)
-                     gq[(long)dj[k] * A.v_es] = sign * comp(Gq, dof_comp(type, k));
+                  {
+                     T *at = gq + (long)dj[k] * A.v_es;
+                     const T val = sign * comp(Gq, dof_comp(type, k));
+                     *at = acc ? *at + val : val;
+                  }
                }
             }
          }
@@ -271,7 +281,7 @@ __global__ void __launch_bounds__(256) rnea_vjp_kernel(VjpArgs<T> G)
          }
       }
       // entries no joint owns
-      if (part == 0)
+      if (part == 0 && !acc)
          for (int z = 0; z < G.n_unowned; z++)
          {
             const long at = (long)unowned[z] * A.v_es;

@@ -5,6 +5,8 @@
 //   configuration_difference_kernel  the dq with q0 (+) dq = q1, rotations in their shortest form
 //   step_assemble_aos_kernel /       A [2nv][2nv] and B [2nv][nv] of x' = (q_next, qd_next) of "forward dynamics, then integrate_joint with
 //   step_assemble_soa_kernel         step dt" from d qdd / d q, d qdd / d qd and H^-1 (mh_aba_derivatives_*)
+//   integrate_vjp_aos_kernel /       the transpose of integrate_joint's tangent map applied to cotangents of (dq', dqd'): gq, gqd, gqdd
+//   integrate_vjp_soa_kernel         (mh_integrate_vjp_*, and the integrator's share of mh_aba_integrate_vjp_*)
 //
 // The step of one joint, in joint-local components (pose (R, p), twist (w, v), acceleration (al, a) from forward dynamics; integrate_sixdof):
 //   a_o = a + w x v,  r = dt w + dt^2/2 al,  E = exp(r),  d = dt v + dt^2/2 a_o,  c = v + dt a_o
@@ -262,6 +264,194 @@ __global__ void __launch_bounds__(256) step_assemble_soa_kernel(StepArgs<T> S)
             step_lin_of_joint<T, const int *>(type, di, S.qd + cfg * S.v_bs, S.qdd + cfg * S.v_bs, S.v_es, dt, hdd, L);
          for (int c = 0; c < w3; c++)
             step_item<T>(S, cfg, type, k, dof, L, c, dt, hdd);
+      }
+   }
+}
+
+// ------------------------------------------------------------------------------------------------ the transpose of the step
+// Reverse mode of integrate_joint: cotangents (gth', gp', gw', gv') of a joint's (dth', dp', dw', dv') give, with the E, J_r, d, v, w, v'
+// of step_lin,
+//   P = E gp',  V = E gv',  s = J_r^T (gth' + gv' x v'),  g_ao = dt^2/2 P + dt V
+//   gq   (dth, dp) : E gth' + d x P,            P
+//   gqd  (dw,  dv) : gw' + dt s + v x g_ao,     dt P + V + g_ao x w
+//   gqdd (dal, da) : dt gw' + dt^2/2 s,         g_ao
+// which is step_apply transposed term by term.  A spherical joint is the rotational half, a planar joint the restriction to
+// (w_y, v_x, v_z) as step_column embeds it, a 1-DoF joint gq = gq', gqd = dt gq' + gqd', gqdd = dt^2/2 gq' + dt gqd'.  Neither q nor the
+// joint's pose appears.  At dt = 0 E and J_r are the identity and gq = gq', gqd = gqd', gqdd = 0 come out exactly.
+template <typename T>
+MH_DEV void step_apply_t(const StepLin<T> &L, T dt, T hdd, V3<T> gth, V3<T> gp, V3<T> gw, V3<T> gv, V3<T> &oth, V3<T> &op, V3<T> &ow, V3<T> &ov,
+                         V3<T> &oal, V3<T> &oa)
+{
+   const V3<T> P = mul(L.E, gp), V = mul(L.E, gv);
+   const V3<T> s = tmul(L.Jr, gth + cross(gv, L.vn));
+   const V3<T> gao = hdd * P + dt * V;
+   oth = mul(L.E, gth) + cross(L.d, P);
+   op = P;
+   ow = gw + dt * s + cross(L.v, gao);
+   ov = dt * P + V + cross(gao, L.w);
+   oal = dt * gw + hdd * s;
+   oa = gao;
+}
+template <typename T>
+struct StepVjpArgs
+{
+   DevModel m;
+   long B;
+   T dt;
+   const T *qd, *qdd;       // [B][nv] in the call's layout (v_bs, v_es)
+   const T *gqn, *gqdn;     // cotangents of (dq', dqd'); either may be NULL (zero)
+   T *gq, *gqd, *gqdd;      // any may be NULL
+   const int *unowned;      // DoF indices no joint owns: zeros
+   int n_unowned;
+   long v_bs, v_es;
+};
+// One multi-DoF joint of one configuration (rows at `at`, element stride es).  di: the joint's entries of the DoF index map.
+template <typename T, class IP>
+MH_DEV void integrate_vjp_joint(int type, IP di, const StepVjpArgs<T> &A, long at, T dt, T hdd)
+{
+   const long es = A.v_es;
+   const V3<T> z{T(0), T(0), T(0)};
+   StepLin<T> L;
+   step_lin_of_joint<T, IP>(type, di, A.qd + at, A.qdd + at, es, dt, hdd, L);
+   const T *a = A.gqn ? A.gqn + at : nullptr, *b = A.gqdn ? A.gqdn + at : nullptr;
+   const int k = dof_count(type);
+   T ga[6], gb[6];
+#pragma unroll
+   for (int i = 0; i < 6; i++)
+   {
+      ga[i] = a && i < k ? a[di[i] * es] : T(0);
+      gb[i] = b && i < k ? b[di[i] * es] : T(0);
+   }
+   V3<T> o0, o1, o2, o3, o4, o5;
+   T oq[6], ov[6], oa[6];
+   if (type == JT_SIXDOF)
+   {
+      step_apply_t<T>(L, dt, hdd, V3<T>{ga[0], ga[1], ga[2]}, V3<T>{ga[3], ga[4], ga[5]}, V3<T>{gb[0], gb[1], gb[2]}, V3<T>{gb[3], gb[4], gb[5]}, o0, o1,
+                      o2, o3, o4, o5);
+      oq[0] = o0.x, oq[1] = o0.y, oq[2] = o0.z, oq[3] = o1.x, oq[4] = o1.y, oq[5] = o1.z;
+      ov[0] = o2.x, ov[1] = o2.y, ov[2] = o2.z, ov[3] = o3.x, ov[4] = o3.y, ov[5] = o3.z;
+      oa[0] = o4.x, oa[1] = o4.y, oa[2] = o4.z, oa[3] = o5.x, oa[4] = o5.y, oa[5] = o5.z;
+   }
+   else if (type == JT_SPHERICAL)
+   {
+      step_apply_t<T>(L, dt, hdd, V3<T>{ga[0], ga[1], ga[2]}, z, V3<T>{gb[0], gb[1], gb[2]}, z, o0, o1, o2, o3, o4, o5);
+      oq[0] = o0.x, oq[1] = o0.y, oq[2] = o0.z;
+      ov[0] = o2.x, ov[1] = o2.y, ov[2] = o2.z;
+      oa[0] = o4.x, oa[1] = o4.y, oa[2] = o4.z;
+   }
+   else
+   { // planar (w_y, v_x, v_z): the restriction of the 6-DoF map to the XZ plane
+      step_apply_t<T>(L, dt, hdd, V3<T>{T(0), ga[0], T(0)}, V3<T>{ga[1], T(0), ga[2]}, V3<T>{T(0), gb[0], T(0)}, V3<T>{gb[1], T(0), gb[2]}, o0, o1, o2, o3,
+                      o4, o5);
+      oq[0] = o0.y, oq[1] = o1.x, oq[2] = o1.z;
+      ov[0] = o2.y, ov[1] = o3.x, ov[2] = o3.z;
+      oa[0] = o4.y, oa[1] = o5.x, oa[2] = o5.z;
+   }
+#pragma unroll
+   for (int i = 0; i < 6; i++)
+      if (i < k)
+      {
+         const long e = at + di[i] * es;
+         if (A.gq)
+            A.gq[e] = oq[i];
+         if (A.gqd)
+            A.gqd[e] = ov[i];
+         if (A.gqdd)
+            A.gqdd[e] = oa[i];
+      }
+}
+// a 1-DoF joint: entry e of every vector
+template <typename T>
+MH_DEV void integrate_vjp_one(const StepVjpArgs<T> &A, long e, T dt, T hdd)
+{
+   const T a = A.gqn ? A.gqn[e] : T(0), b = A.gqdn ? A.gqdn[e] : T(0);
+   if (A.gq)
+      A.gq[e] = a;
+   if (A.gqd)
+      A.gqd[e] = dt * a + b;
+   if (A.gqdd)
+      A.gqdd[e] = hdd * a + dt * b;
+}
+template <typename T>
+MH_DEV void integrate_vjp_zero(const StepVjpArgs<T> &A, long at)
+{
+   for (int z = 0; z < A.n_unowned; z++)
+   {
+      const long e = at + A.unowned[z] * A.v_es;
+      if (A.gq)
+         A.gq[e] = T(0);
+      if (A.gqd)
+         A.gqd[e] = T(0);
+      if (A.gqdd)
+         A.gqdd[e] = T(0);
+   }
+}
+// SoA: lane = configuration, joints looped, the joint's small matrices in registers.
+template <typename T>
+__global__ void __launch_bounds__(256) integrate_vjp_soa_kernel(StepVjpArgs<T> A)
+{
+   const DevModel &m = A.m;
+   const ciptr meta = as_const(m.meta), dof_map = as_const(m.dof_map);
+   const long nlanes = (long)gridDim.x * blockDim.x;
+   const T dt = A.dt, hdd = T(0.5) * A.dt * A.dt;
+   for (long cfg = (long)blockIdx.x * blockDim.x + threadIdx.x; cfg < A.B; cfg += nlanes)
+   {
+      const long at = cfg * A.v_bs;
+      integrate_vjp_zero<T>(A, at);
+      for (int j = 0; j < m.n; j++)
+      {
+         ciptr mi = meta + j * MI_STRIDE;
+         const int type = mi[MI_TYPE];
+         if (type == JT_REVOLUTE || type == JT_PRISMATIC)
+            integrate_vjp_one<T>(A, at + dof_map[mi[MI_DOF]] * A.v_es, dt, hdd);
+         else if (type != JT_FIXED)
+            integrate_vjp_joint<T, ciptr>(type, dof_map + mi[MI_DOF], A, at, dt, hdd);
+      }
+   }
+}
+// AoS: the thread mapping of integrate_aos_kernel.  A workgroup takes tiles of `tile` configurations; pass A: thread = (configuration,
+// 1-DoF joint), the joint running fastest; pass B: thread = (configuration, multi-DoF joint).  The two joint lists are built once per
+// workgroup in LDS; the unowned entries of a configuration are zeroed by one thread.
+template <typename T>
+__global__ void __launch_bounds__(256) integrate_vjp_aos_kernel(StepVjpArgs<T> A, int tile)
+{
+   extern __shared__ int lds_meta[]; // [n] v index of the 1-DoF joints ; [n] engine index of the others ; counts
+   const DevModel &m = A.m;
+   int *l1_v = lds_meta, *lm = lds_meta + m.n, *cnt = lds_meta + 2 * m.n;
+   if (threadIdx.x == 0)
+   {
+      int n1 = 0, nm = 0;
+      for (int j = 0; j < m.n; j++)
+      {
+         const int type = m.meta[j * MI_STRIDE + MI_TYPE];
+         if (type == JT_REVOLUTE || type == JT_PRISMATIC)
+            l1_v[n1++] = m.dof_map[m.meta[j * MI_STRIDE + MI_DOF]];
+         else if (type != JT_FIXED)
+            lm[nm++] = j;
+      }
+      cnt[0] = n1, cnt[1] = nm;
+   }
+   __syncthreads();
+   const unsigned n1 = (unsigned)cnt[0], nm = (unsigned)cnt[1];
+   const T dt = A.dt, hdd = T(0.5) * A.dt * A.dt;
+   const long ntiles = (A.B + tile - 1) / tile;
+   for (long t = blockIdx.x; t < ntiles; t += gridDim.x)
+   {
+      const long cfg0 = t * tile;
+      const unsigned rows = (unsigned)(A.B - cfg0 < (long)tile ? A.B - cfg0 : (long)tile);
+      if (A.n_unowned > 0)
+         for (unsigned u = threadIdx.x; u < rows; u += blockDim.x)
+            integrate_vjp_zero<T>(A, (cfg0 + u) * A.v_bs);
+      for (unsigned u = threadIdx.x; u < rows * n1; u += blockDim.x)
+      {
+         const unsigned lc = u / n1, k = u - lc * n1;
+         integrate_vjp_one<T>(A, (cfg0 + lc) * A.v_bs + l1_v[k], dt, hdd);
+      }
+      for (unsigned u = threadIdx.x; u < rows * nm; u += blockDim.x)
+      {
+         const unsigned lc = u / nm, j = (unsigned)lm[u - lc * nm];
+         const int *mi = m.meta + j * MI_STRIDE;
+         integrate_vjp_joint<T, const int *>(mi[MI_TYPE], m.dof_map + mi[MI_DOF], A, (cfg0 + lc) * A.v_bs, dt, hdd);
       }
    }
 }

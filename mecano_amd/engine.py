@@ -940,6 +940,74 @@ class HipModel:
             self._chart_index = autograd.chart_maps(self.desc)
         return autograd.chart_pullback(self.desc, q, g, self._chart_index)
 
+    def chart_cotangent(self, q, g_raw):
+        """The velocity-space cotangent [B, nv] at q from a gradient with respect to the raw coordinates g_raw [B, nq]:
+        ``mecano_amd.autograd.chart_cotangent`` on this model's index maps.  Plain torch operations, AoS, any device."""
+        from . import autograd
+        if getattr(self, "_chart_index", None) is None:
+            self._chart_index = autograd.chart_maps(self.desc)
+        return autograd.chart_cotangent(self.desc, q, g_raw, self._chart_index)
+
+    def _cotangents(self, gq_next, gqd_next, vec, dt):
+        """The two cotangents of a step: either may be None (zero), not both; shapes and dtype as the state vectors."""
+        if gq_next is None and gqd_next is None:
+            raise _lib.MecanoHipError(1, "gq_next and gqd_next are both None")
+        for t in (gq_next, gqd_next):
+            if t is not None:
+                self._device_tensor(t, dt)
+                if tuple(t.shape) != vec:
+                    raise _lib.MecanoHipError(2, f"cotangent has shape {tuple(t.shape)}, expected {vec}")
+
+    def integrate_vjp(self, dt, qd, qdd, gq_next, gqd_next, layout=_lib.LAYOUT_AOS, out=None):
+        """Reverse-mode gradients of ``integrate``, one elementwise launch: for cotangents ``gq_next``, ``gqd_next`` [B, nv] of the new
+        state (q_next as a velocity-space step, qd_next by components; either may be None for zero), (gq, gqd, gqdd) [B, nv] each: the
+        transpose of the integrator's tangent map in the conventions of ``step_derivatives``.  The configuration does not appear.
+        SoA: [nv, B].  fp64 / fp32.  ``out``: a (gq, gqd, gqdd) tuple to write into; any may be None (not computed), not all three."""
+        import torch
+        dtp = qd.dtype
+        if dtp not in (torch.float64, torch.float32):
+            raise TypeError("state tensors must be float64 or float32")
+        for t in (qd, qdd):
+            self._device_tensor(t, dtp)
+        B = self._batch(qd, self.nv, layout)
+        if self._batch(qdd, self.nv, layout) != B:
+            raise _lib.MecanoHipError(2, "batch sizes of the state matrices differ")
+        vec = (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B)
+        self._cotangents(gq_next, gqd_next, vec, dtp)
+        gq, gqd, gqdd = self._outputs(out, (vec, vec, vec), ("gq", "gqd", "gqdd"), dtp, qd.device)
+        if gq is None and gqd is None and gqdd is None:
+            raise _lib.MecanoHipError(1, "all three outputs are None")
+        opts = self._options(layout, True, True, torch.cuda.current_stream(qd.device).cuda_stream)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        sfx = "f64" if dtp == torch.float64 else "f32"
+        _lib.check(getattr(_lib.load(), f"mh_integrate_vjp_{sfx}")(
+            self._h, B, float(dt), qd.data_ptr(), qdd.data_ptr(), ptr(gq_next), ptr(gqd_next), ctypes.byref(opts), ptr(gq), ptr(gqd), ptr(gqdd)))
+        return gq, gqd, gqdd
+
+    def step_vjp(self, dt, q, qd, tau, gq_next, gqd_next, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Reverse-mode gradients of the simulation step ``aba`` then ``integrate`` with step ``dt``, no matrix: for cotangents
+        ``gq_next``, ``gqd_next`` [B, nv] of the new state (either may be None for zero), (qdd, gq, gqd, gtau) [B, nv] each with
+        (gq, gqd) = A^T g' and gtau = B^T g' for the (A, B) of ``step_derivatives``.  ``chart_cotangent`` makes gq_next from a gradient
+        with respect to raw coordinates, ``chart_pullback`` turns gq into one.  Two forward-dynamics launches, the kernel of
+        ``integrate_vjp`` and that of ``rnea_vjp``.  SoA: [nv, B].  fp64 / fp32.  ``out``: a (qdd, gq, gqd, gtau) tuple to write into; any
+        may be None, not all three gradients.  A model with acceleration-source joints is refused."""
+        B, dtp, sfx, stream = self._device_inputs([q, qd, tau], layout)
+        if f_ext is not None:
+            self._device_tensor(f_ext, dtp)
+        self._check_f_ext(f_ext, B, layout)
+        vec = (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B)
+        self._cotangents(gq_next, gqd_next, vec, dtp)
+        qdd, gq, gqd, gtau = self._outputs(out, (vec, vec, vec, vec), ("qdd", "gq", "gqd", "gtau"), dtp, q.device)
+        if gq is None and gqd is None and gtau is None:
+            raise _lib.MecanoHipError(1, "all three gradients are None")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, True, True, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_aba_integrate_vjp_{sfx}")(
+            self._h, B, float(dt), q.data_ptr(), qd.data_ptr(), tau.data_ptr(), g, ptr(f_ext), ptr(gq_next), ptr(gqd_next), ctypes.byref(opts),
+            ptr(qdd), ptr(gq), ptr(gqd), ptr(gtau)))
+        return qdd, gq, gqd, gtau
+
     def _chart_call(self, name, a, b, b_cols, out_cols, layout, out):
         B, dt, sfx, stream = self._device_inputs([a], layout)
         aos = layout == _lib.LAYOUT_AOS
