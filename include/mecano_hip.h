@@ -739,6 +739,41 @@ mh_status mh_aba_parameters_f32(mh_model_t model, int64_t B, const float *q, con
                                 const double gravity[3], const float *f_ext, const mh_options *opts, float *qdd_out);
 
 /*
+ * ---- reverse-mode gradients of the two calls above with respect to the inertial parameters: what a descent on pi needs (identification
+ *      by simulation error, fitting a payload, a learned residual inertia), without the regressor (no calculator of the reference) ----
+ * mh_rnea_parameters_vjp_*: for a cotangent u [B][nv] of the efforts of mh_rnea_parameters_*(q, qd, qdd, pi),
+ * gpi_out[r][j][k] = sum_i u_i d tau_i / d pi[r][j][k], laid out like pi ([B][n_joints][10], MH_LAYOUT_SOA: [10 n_joints][B]), with respect
+ * to the ten numbers themselves (mass, com, J) -- not to (m, m c, J): the call applies the chain rule with the row's pi, the only use it
+ * makes of pi.  opts->consider_coriolis = 0 evaluates at qd = 0 (qd may then be NULL), opts->consider_accelerations = 0 at qdd = 0 (qdd
+ * may then be NULL); opts->use_root_acceleration / root_acceleration are honoured (gravity may then be NULL).  External wrenches do not
+ * enter: tau is affine in them.  u = 0 gives zeros, and the block of a body outside the subtrees of the joints where u is not zero is
+ * zero.  Every entry of gpi_out is written once (no memset needed), fixed joints' blocks included, nothing outside it.  Analytic, O(n) per
+ * configuration, one outward sweep and no inward one, 10 n_joints numbers written where mh_regressor_* writes nv 10 n_joints: ONE launch
+ * of a run-time-topology kernel for every model (mh_params_vjp_kernels.h) in the model's own workspace plan.  Joint source modes play
+ * no part.
+ * mh_aba_parameters_vjp_*: for a cotangent w [B][nv] of qdd = mh_aba_parameters_*(q, qd, tau, pi): gtau_out = mu = H(pi)^-1 w and
+ * gpi_out = w^T d qdd / d pi = -mu^T d tau / d pi at that qdd (the kernel above with u = mu, negated).  qdd_out and gtau_out [B][nv] may be
+ * NULL.  Launches composed on opts->stream: mh_aba_parameters_* for qdd, again at rest without root acceleration and wrenches with
+ * tau = w for mu, the kernel above.  The scratch is 2 B nv elements of the context (qdd and mu where the caller takes neither), set
+ * aside by mh_reserve / mh_context_reserve.  A model with MH_ACCELERATION_SOURCE joints is refused (MH_ERR_INVALID_ARGUMENT).
+ * Both: pi, u / w or gpi_out = NULL is MH_ERR_INVALID_ARGUMENT, as is an output that overlaps an input (u / w and pi included) or another
+ * output.  B = 0 returns MH_OK and touches nothing.  A pi row that is no physical inertia or not finite is not diagnosed: it shows as
+ * inf / nan in that row's outputs only.  The state gradients of mh_rnea_vjp_* / mh_aba_vjp_* at per-configuration parameters are not
+ * provided.  Device pointers, asynchronous on opts->stream, layouts, index maps and contexts honoured; after mh_reserve /
+ * mh_context_reserve the calls only enqueue work (graph-capturable).
+ */
+mh_status mh_rnea_parameters_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double *pi,
+                                     const double gravity[3], const double *u, const mh_options *opts, double *gpi_out);
+mh_status mh_rnea_parameters_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const float *pi,
+                                     const double gravity[3], const float *u, const mh_options *opts, float *gpi_out);
+mh_status mh_aba_parameters_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double *pi,
+                                    const double gravity[3], const double *f_ext, const double *w, const mh_options *opts, double *qdd_out,
+                                    double *gtau_out, double *gpi_out);
+mh_status mh_aba_parameters_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const float *pi,
+                                    const double gravity[3], const float *f_ext, const float *w, const mh_options *opts, float *qdd_out,
+                                    float *gtau_out, float *gpi_out);
+
+/*
  * ---- forward dynamics under bilateral constraints on body frames, and the velocity-level twin for touch-down (the consumer of the
  *      apparent inertias: MultiBodyResponseCalculator's applyRigidBodyWrench / propagateImpulse are the pieces, the reference has no
  *      calculator that solves for the wrench; algorithms/MultiBodyResponseCalculator.java:39-41, 608-627, 640, 836) ----

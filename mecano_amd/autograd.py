@@ -5,6 +5,9 @@ and the raw coordinates.
 The forward passes are ``HipModel.rnea`` / ``HipModel.aba`` / ``HipModel.integrate`` / ``HipModel.step`` unchanged; a backward pass is ONE
 call of ``HipModel.rnea_vjp`` / ``HipModel.aba_vjp`` / ``HipModel.integrate_vjp`` / ``HipModel.step_vjp`` (no nv x nv matrix is formed)
 plus ``chart_pullback`` for q, and ``chart_cotangent`` at the new configuration for the two steps.
+``rnea_parameters`` and ``aba_parameters`` are the per-configuration-parameter calls as differentiable functions of **pi**: their backward
+is ONE call of ``HipModel.rnea_parameters_vjp`` / ``HipModel.aba_parameters_vjp`` (no regressor is formed).  They are not differentiable
+with respect to the state: a q, qd, qdd or tau that requires grad raises NotImplementedError.
 AoS device tensors, fp64 or fp32.  gravity and f_ext are not differentiated.  Once differentiable: the backward pass is not itself a
 graph of torch operations, and a second backward raises.
 """
@@ -160,6 +163,35 @@ class _Aba(torch.autograd.Function):
         return None, (None if gq is None else ctx.model.chart_pullback(q, gq)), gqd, gtau, None, None
 
 
+class _RneaParameters(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, q, qd, qdd, pi, gravity, f_ext):
+        ctx.model, ctx.gravity = model, gravity
+        ctx.save_for_backward(q, qd, qdd, pi)
+        return model.rnea_parameters(q, qd, qdd, pi, gravity, f_ext)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, u):
+        q, qd, qdd, pi = ctx.saved_tensors
+        return None, None, None, None, ctx.model.rnea_parameters_vjp(q, qd, qdd, pi, u.contiguous(), ctx.gravity), None, None
+
+
+class _AbaParameters(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, q, qd, tau, pi, gravity, f_ext):
+        ctx.model, ctx.gravity, ctx.f_ext = model, gravity, f_ext
+        ctx.save_for_backward(q, qd, tau, pi)
+        return model.aba_parameters(q, qd, tau, pi, gravity, f_ext)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, w):
+        q, qd, tau, pi = ctx.saved_tensors
+        gpi = ctx.model.aba_parameters_vjp(q, qd, tau, pi, w.contiguous(), ctx.gravity, ctx.f_ext, out=(None, None, torch.empty_like(pi)))[2]
+        return None, None, None, None, gpi, None, None
+
+
 def _raw_gradient(model, q, q_next, gq, g_raw_next):
     """chart_pullback at q plus the quaternions' radial pass-through: the gradient of the raw map q -> (q_next, qd_next)."""
     if gq is None:
@@ -224,3 +256,25 @@ def rnea(model, q, qd, qdd, gravity=(0.0, 0.0, -9.81), f_ext=None):
 def aba(model, q, qd, tau, gravity=(0.0, 0.0, -9.81), f_ext=None):
     """qdd = ``model.aba(q, qd, tau, gravity, f_ext)``, differentiable with respect to q (raw coordinates), qd and tau."""
     return _Aba.apply(model, q, qd, tau, gravity, f_ext)
+
+
+def _state_is_constant(call, **state):
+    for name, t in state.items():
+        if t.requires_grad:
+            raise NotImplementedError(f"{call} is differentiable with respect to pi only: {name} requires grad (the state gradients at "
+                                      "per-configuration parameters are not provided)")
+
+
+def rnea_parameters(model, q, qd, qdd, pi, gravity=(0.0, 0.0, -9.81), f_ext=None):
+    """tau = ``model.rnea_parameters(q, qd, qdd, pi, gravity, f_ext)``, differentiable with respect to pi ([B, n_joints, 10] or
+    [B, 10 n_joints]) and to nothing else: a q, qd or qdd that requires grad raises NotImplementedError.  A pi made by
+    ``shared.expand(B, n, 10).contiguous()`` hands the sum over the batch to ``shared`` through torch's own expand backward."""
+    _state_is_constant("rnea_parameters", q=q, qd=qd, qdd=qdd)
+    return _RneaParameters.apply(model, q, qd, qdd, pi, gravity, f_ext)
+
+
+def aba_parameters(model, q, qd, tau, pi, gravity=(0.0, 0.0, -9.81), f_ext=None):
+    """qdd = ``model.aba_parameters(q, qd, tau, pi, gravity, f_ext)``, differentiable with respect to pi as ``rnea_parameters`` is: a q,
+    qd or tau that requires grad raises NotImplementedError."""
+    _state_is_constant("aba_parameters", q=q, qd=qd, tau=tau)
+    return _AbaParameters.apply(model, q, qd, tau, pi, gravity, f_ext)

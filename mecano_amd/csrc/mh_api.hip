@@ -13,6 +13,7 @@
 #include "mh_kinematics_kernels.h"
 #include "mh_rnea_deriv_kernels.h"
 #include "mh_params_kernels.h"
+#include "mh_params_vjp_kernels.h"
 #include "mh_step_kernels.h"
 #include "mh_constraint_kernels.h"
 #include "mh_contact_kernels.h"
@@ -2552,6 +2553,134 @@ mh_status aba_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, con
    od.consider_coriolis = 1, od.consider_accelerations = 1;
    return rnea_vjp_launch<T>(model, B, q, qd, qdd, gravity, f_ext, mu, od, true, gq_out, gqd_out, nullptr);
 }
+// Reverse-mode gradient of the inverse dynamics with respect to the per-configuration inertial parameters (mh_params_vjp_kernels.h): one
+// launch of a run-time-topology kernel in the model's own workspace plan, up to min(8, n) waves per group of configurations on small
+// batches (the first row of mh_reserve's lane plans), which writes every entry of gpi_out.  negate: -gpi (the forward form below).  Big AoS
+// batches of wide state matrices go through the transposed scratch copies, as in parameters_impl; pi and gpi are staged by the kernel.
+template <typename T>
+mh_status parameters_vjp_launch(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const T *pi, const double *gravity, const T *u,
+                                const mh_options &opts, bool negate, T *gpi_out)
+{
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
+   mh_status st = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T)));
+   if (st != MH_OK)
+      return st;
+   hipStream_t stream = (hipStream_t)opts.stream;
+   const bool soa = opts.layout == MH_LAYOUT_SOA;
+   mh::ParamVjpArgs<T> G{};
+   mh::Args<T> &A = G.p.a;
+   A = make_args<T>(model, B, opts, gravity);
+   A.q = q, A.qd = qd, A.in3 = qdd, A.fext = nullptr, A.out = nullptr;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = L.lanes;
+   G.p.pi = pi, G.u = u, G.gpi = gpi_out, G.negate = negate;
+   set_strides(G.p.p_bs, G.p.p_es, soa, B, (long)model->n * mh::PARAMS_PER_BODY);
+   if (!soa && transposes(model, B))
+   {
+      const size_t nq = model->nq, nv = model->nv;
+      st = ensure_bytes(model->tr, (size_t)B * (nq + 3 * nv) * sizeof(T));
+      if (st != MH_OK)
+         return st;
+      T *t_q = (T *)model->tr.ptr, *t_qd = t_q + (size_t)B * nq, *t_qdd = t_qd + (size_t)B * nv, *t_u = t_qdd + (size_t)B * nv;
+      mh::transpose_rows<T>(q, t_q, (long)B, (long)nq, true, stream);
+      if (opts.consider_coriolis)
+         mh::transpose_rows<T>(qd, t_qd, (long)B, (long)nv, true, stream);
+      if (opts.consider_accelerations)
+         mh::transpose_rows<T>(qdd, t_qdd, (long)B, (long)nv, true, stream);
+      mh::transpose_rows<T>(u, t_u, (long)B, (long)nv, true, stream);
+      A.q = t_q, A.qd = t_qd, A.in3 = t_qdd, G.u = t_u;
+      A.q_bs = 1, A.q_es = B, A.v_bs = 1, A.v_es = B;
+   }
+   hipLaunchKernelGGL((mh::rnea_parameters_vjp_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, stream, G);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
+template <typename T>
+mh_status rnea_parameters_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const T *pi, const double *gravity, const T *u,
+                                   const mh_options *opts_in, T *gpi_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   if (!pi || !u || !gpi_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s is NULL", !pi ? "pi" : (!u ? "u" : "gpi_out"));
+   if (B == 0)
+      return MH_OK;
+   if (!gravity && !opts.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (!q || (opts.consider_coriolis && !qd) || (opts.consider_accelerations && !qdd))
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state pointer (qd may be NULL with consider_coriolis = 0, qdd with consider_accelerations = 0)");
+   {
+      const size_t nq = (size_t)B * model->nq * sizeof(T), nvb = (size_t)B * model->nv * sizeof(T);
+      const size_t np = (size_t)B * model->n * mh::PARAMS_PER_BODY * sizeof(T);
+      const InRange ins[5] = {{"q", q, nq}, {"qd", opts.consider_coriolis ? qd : nullptr, nvb}, {"qdd", opts.consider_accelerations ? qdd : nullptr, nvb},
+                              {"pi", pi, np}, {"u", u, nvb}};
+      const OutRange out = {"gpi_out", gpi_out, np, 0u};
+      if ((st = check_aliasing("mh_rnea_parameters_vjp", ins, 5, &out, 1)) != MH_OK)
+         return st;
+   }
+   return parameters_vjp_launch<T>(model, B, q, qd, qdd, pi, gravity, u, opts, false, gpi_out);
+}
+// ... and of the forward dynamics: three launches (and one memset) composed on the caller's stream, as in aba_vjp_impl with the
+// per-configuration kernels -- aba_parameters_kernel for qdd; again at rest, without root acceleration and wrenches, with tau = w, which is
+// mu = H(pi)^-1 w (its qd is the output itself, zeroed first); the kernel above at that qdd with u = mu, negated.  External wrenches enter
+// the first launch only: tau is affine in them.  The scratch: qdd and mu where the caller takes neither (two of the three vectors
+// mh_reserve sets aside for the state gradients).
+template <typename T>
+mh_status aba_parameters_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const T *pi, const double *gravity, const T *f_ext,
+                                  const T *w, const mh_options *opts_in, T *qdd_out, T *gtau_out, T *gpi_out)
+{
+   mh_options o;
+   mh_status st = begin_call(model, B, opts_in, o);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: forward dynamics with inertial parameters takes none", model->n_locked);
+   if (!pi || !w || !gpi_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s is NULL", !pi ? "pi" : (!w ? "w" : "gpi_out"));
+   if (B == 0)
+      return MH_OK;
+   if (!gravity && !o.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (!q || !qd || !tau)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state pointer");
+   const size_t nvb = (size_t)B * model->nv * sizeof(T);
+   {
+      const size_t bj = (size_t)B * model->n * sizeof(T);
+      const InRange ins[6] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"qd", qd, nvb}, {"tau", tau, nvb}, {"pi", pi, mh::PARAMS_PER_BODY * bj},
+                              {"f_ext", f_ext, 6 * bj}, {"w", w, nvb}};
+      const OutRange outs[3] = {{"qdd_out", qdd_out, nvb, 0u}, {"gtau_out", gtau_out, nvb, 0u}, {"gpi_out", gpi_out, mh::PARAMS_PER_BODY * bj, 0u}};
+      if ((st = check_aliasing("mh_aba_parameters_vjp", ins, 6, outs, 3)) != MH_OK)
+         return st;
+   }
+   T *qdd = qdd_out, *mu = gtau_out;
+   if ((!qdd || !mu) && model->nv > 0)
+   {
+      if ((st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T), 2))) != MH_OK)
+         return st;
+      if (!qdd)
+         qdd = (T *)model->vjp.ptr;
+      if (!mu)
+         mu = (T *)model->vjp.ptr + (size_t)B * model->nv;
+   }
+   mh_options od = o; // forward dynamics, and the inverse dynamics at the state it saw: both switches on
+   od.consider_coriolis = 1, od.consider_accelerations = 1;
+   mh_options rest = od; // H^-1 w: nothing moves, nothing pulls
+   rest.use_root_acceleration = 1;
+   for (double &x : rest.root_acceleration)
+      x = 0.0;
+   if (model->nv > 0)
+   {
+      if ((st = parameters_impl<T>(ALGO_ABA, model, B, q, qd, tau, pi, gravity, f_ext, &od, qdd)) != MH_OK)
+         return st;
+      HIP_TRY(hipMemsetAsync(mu, 0, nvb, (hipStream_t)o.stream));
+      if ((st = parameters_impl<T>(ALGO_ABA, model, B, q, mu, w, pi, nullptr, nullptr, &rest, mu)) != MH_OK)
+         return st;
+   }
+   return parameters_vjp_launch<T>(model, B, q, qd, qdd, pi, gravity, mu, od, true, gpi_out);
+}
 template <typename T>
 mh_status integrate_impl(mh_model_t model, int64_t B, double dt, const T *q, const T *qd, const T *qdd, const mh_options *opts_in, T *q_out,
                                 T *qd_out, T *qdd_out)
@@ -3477,7 +3606,9 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       // batch up to max_batch (lane_ws_bound; swept by tests/test_launch_plans_cpu.py)
       const Launch L = plan_launch(m->cu_count, max_batch);
       const long lane_plans[5][2] = {
-         {m->n_slots, std::min(8, m->n)}, // mh_regressor_*, mh_crba_coriolis_*, mh_centroidal_*, mh_gravity_gradient_*, the mass matrix
+         // mh_regressor_*, mh_crba_coriolis_*, mh_centroidal_*, mh_gravity_gradient_*, the mass matrix, mh_rnea_parameters_vjp_* /
+         // mh_aba_parameters_vjp_* (the model's own slots: a branching body parks nu where the inverse dynamics parks its force)
+         {m->n_slots, std::min(8, m->n)},
          // mh_apparent_inertia_inverse_*: its own slots behind the model's, up to one wave per target; mh_mass_matrix_inverse_* works in
          // the same slots with up to one wave per group of six columns
          {m->resp_slots, std::max<long>(MH_MAX_APPARENT_TARGETS, minv_groups(std::max<int>(m->nv, MH_MAX_INVERSE_COLUMNS)))},
@@ -3491,7 +3622,8 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       // mh_aba_derivatives_*: the scratch of the forward form
       if (m->nv > 0 && deriv_scratch_bytes(m, max_batch, sizeof(double)) <= kDerivReserveCap)
          st = ensure_bytes(m->deriv, deriv_scratch_bytes(m, max_batch, sizeof(double)));
-      // mh_aba_vjp_* / mh_aba_integrate_vjp_*: qdd, w and H^-1 w, should the caller take neither qdd nor gtau
+      // mh_aba_vjp_* / mh_aba_integrate_vjp_*: qdd, w and H^-1 w, should the caller take neither qdd nor gtau (mh_aba_parameters_vjp_*: the
+      // first two of the three)
       if (st == MH_OK && m->nv > 0)
          st = ensure_bytes(m->vjp, vjp_scratch_bytes(m, max_batch, sizeof(double)));
       // mh_aba_integrate_derivatives_*: the two derivative matrices beside them, under the same cap
@@ -4384,6 +4516,28 @@ mh_status mh_aba_parameters_f64(mh_model_t model, int64_t B, const double *q, co
                                 const double gravity[3], const double *f_ext, const mh_options *opts, double *qdd_out)
 {
    return parameters_impl<double>(ALGO_ABA, model, B, q, qd, tau, pi, gravity, f_ext, opts, qdd_out);
+}
+mh_status mh_rnea_parameters_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double *pi,
+                                     const double gravity[3], const double *u, const mh_options *opts, double *gpi_out)
+{
+   return rnea_parameters_vjp_impl<double>(model, B, q, qd, qdd, pi, gravity, u, opts, gpi_out);
+}
+mh_status mh_rnea_parameters_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const float *pi,
+                                     const double gravity[3], const float *u, const mh_options *opts, float *gpi_out)
+{
+   return rnea_parameters_vjp_impl<float>(model, B, q, qd, qdd, pi, gravity, u, opts, gpi_out);
+}
+mh_status mh_aba_parameters_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double *pi,
+                                    const double gravity[3], const double *f_ext, const double *w, const mh_options *opts, double *qdd_out,
+                                    double *gtau_out, double *gpi_out)
+{
+   return aba_parameters_vjp_impl<double>(model, B, q, qd, tau, pi, gravity, f_ext, w, opts, qdd_out, gtau_out, gpi_out);
+}
+mh_status mh_aba_parameters_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const float *pi,
+                                    const double gravity[3], const float *f_ext, const float *w, const mh_options *opts, float *qdd_out,
+                                    float *gtau_out, float *gpi_out)
+{
+   return aba_parameters_vjp_impl<float>(model, B, q, qd, tau, pi, gravity, f_ext, w, opts, qdd_out, gtau_out, gpi_out);
 }
 mh_status mh_aba_parameters_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const float *pi,
                                 const double gravity[3], const float *f_ext, const mh_options *opts, float *qdd_out)

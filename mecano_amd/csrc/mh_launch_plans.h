@@ -82,7 +82,8 @@ Launch plan_launch(int cu_count, int64_t B)
 
 // The lane-workspace kernels, small batches: `parts` waves per group of 64 configurations (the grid's y), each with a workspace block of
 // its own -- as many as the call wants while they keep one wave per SIMD.  Kernels whose per-body columns are independent (mass matrix,
-// Coriolis matrix, centroidal momentum matrix, joint torque regressor, gravity gradient, dynamics derivatives) want min(8, n), each wave
+// Coriolis matrix, centroidal momentum matrix, joint torque regressor, gravity gradient, dynamics derivatives, the gradient with respect
+// to the inertial parameters -- mh_params_vjp_kernels.h, in the model's own n_slots per lane --) want min(8, n), each wave
 // taking every parts-th body (mh_kernels.h; measured: profiles/r02_regressor_rates.txt, profiles/r02_column_parts.txt); the kernels that
 // work through a list want one wave per target or per group of columns.
 int launch_parts(int cu_count, const Launch &L, long want)

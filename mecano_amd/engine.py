@@ -1112,6 +1112,58 @@ class HipModel:
         A model with acceleration-source joints is refused."""
         return self._parameters_call("aba", q, qd, tau, pi, gravity, f_ext, layout, True, True, out)
 
+    def _parameter_tensor(self, pi, B, dt, layout, name="pi"):
+        """``pi`` checked as a device tensor of the parameters' shape; returns that shape as given."""
+        if pi is None:
+            raise _lib.MecanoHipError(1, f"{name} is None")
+        self._device_tensor(pi, dt)
+        want = ((B, self.n_joints, 10), (B, self.n_joints * 10)) if layout == _lib.LAYOUT_AOS else ((self.n_joints * 10, B),)
+        if tuple(pi.shape) not in want:
+            raise _lib.MecanoHipError(2, f"{name} has shape {tuple(pi.shape)}, expected {want[0]}")
+        return tuple(pi.shape)
+
+    def rnea_parameters_vjp(self, q, qd, qdd, pi, u, gravity=(0.0, 0.0, -9.81), layout=_lib.LAYOUT_AOS, consider_coriolis=True,
+                            consider_accelerations=True, out=None):
+        """Reverse-mode gradient of ``rnea_parameters`` with respect to the inertial parameters, one O(n) launch and no regressor: for a
+        cotangent ``u`` [B, nv] of the efforts, gpi = u^T d tau / d pi in the shape of ``pi`` ([B, n_joints, 10]; SoA: [10 n_joints, B]),
+        with respect to the ten numbers (mass, com, J) themselves.  ``qdd`` may be None with ``consider_accelerations=False``, ``qd`` with
+        ``consider_coriolis=False``.  External wrenches do not enter (the efforts are affine in them).  Device tensors, fp64 / fp32;
+        ``out``: a device tensor of pi's shape to write into."""
+        given = [t for t in (q, qd if consider_coriolis else None, qdd if consider_accelerations else None, u) if t is not None]
+        B, dt, sfx, stream = self._device_inputs(given, layout)
+        if u is None or (consider_coriolis and qd is None) or (consider_accelerations and qdd is None):
+            raise _lib.MecanoHipError(1, "u is needed; qd / qdd may be None only with their switch off")
+        gpi = self._output(out, self._parameter_tensor(pi, B, dt, layout), dt, q.device, "gpi")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, consider_coriolis, consider_accelerations, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_rnea_parameters_vjp_{sfx}")(
+            self._h, B, q.data_ptr(), ptr(qd) if consider_coriolis else None, ptr(qdd) if consider_accelerations else None, pi.data_ptr(), g,
+            u.data_ptr(), ctypes.byref(opts), gpi.data_ptr()))
+        return gpi
+
+    def aba_parameters_vjp(self, q, qd, tau, pi, w, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Reverse-mode gradient of ``aba_parameters`` with respect to the inertial parameters: for a cotangent ``w`` [B, nv] of
+        qdd = aba_parameters(q, qd, tau, pi), (qdd, gtau, gpi) with gtau = H(pi)^-1 w [B, nv] and gpi = w^T d qdd / d pi in the shape of
+        ``pi``.  Two forward-dynamics launches and the kernel of ``rnea_parameters_vjp``.  ``out``: a (qdd, gtau, gpi) tuple to write into;
+        qdd and gtau may be None (they then go to scratch of the model and None is returned in their place), gpi not.  A model with
+        acceleration-source joints is refused."""
+        B, dt, sfx, stream = self._device_inputs([q, qd, tau, w], layout)
+        if f_ext is not None:
+            self._device_tensor(f_ext, dt)
+        self._check_f_ext(f_ext, B, layout)
+        vec = (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B)
+        qdd, gtau, gpi = self._outputs(out, (vec, vec, self._parameter_tensor(pi, B, dt, layout)), ("qdd", "gtau", "gpi"), dt, q.device)
+        if gpi is None:
+            raise _lib.MecanoHipError(1, "the gpi output is None")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, True, True, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_aba_parameters_vjp_{sfx}")(
+            self._h, B, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), pi.data_ptr(), g, ptr(f_ext), w.data_ptr(), ctypes.byref(opts), ptr(qdd),
+            ptr(gtau), gpi.data_ptr()))
+        return qdd, gtau, gpi
+
     def regressor(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), layout=_lib.LAYOUT_AOS, consider_coriolis=True, consider_accelerations=True,
                   first_moment_columns=False):
         """Joint torque regressor (JointTorqueRegressorCalculator.compute, JointTorqueRegressorCalculator.java:173-190): Y [B, nv, 10 n_joints]
