@@ -264,8 +264,9 @@ mh_status mh_model_check(mh_model_t model, mh_context_t ctx, void *stream);
  * Memory: beside the workspaces, the scratch matrices of the derivative calls and of the AoS form of mh_body_poses_* /
  * mh_geometric_jacobian_* are set aside here for every model and every context, used or not, each while it stays within 4 GiB at
  * max_batch (a larger need is met by the first call that has it).  The kinematics scratch holds the largest target list:
- * max_batch * max(6 * 16 * (nv + 1), 12 * max(16, n_joints)) doubles -- 23.8 KB per configuration for a 30-DoF model, 97 MB at
- * max_batch = 4096, 3.1 GB at 131 072; from 180 400 configurations on it is left to the first AoS call. */
+ * max_batch * max(6 * 16 * (nv + 1), 12 * max(16, n_joints) + nv) doubles (the second: the cotangents and the result of
+ * mh_body_poses_vjp_*, more than the first only for a model with many fixed joints) -- 23.8 KB per configuration for a 30-DoF model,
+ * 97 MB at max_batch = 4096, 3.1 GB at 131 072; from 180 400 configurations on it is left to the first AoS call. */
 mh_status mh_reserve(mh_model_t model, int64_t max_batch);
 
 /*
@@ -538,6 +539,43 @@ mh_status mh_geometric_jacobian_f64(mh_model_t model, int64_t B, const double *q
 mh_status mh_geometric_jacobian_f32(mh_model_t model, int64_t B, const float *q, const float *qd, int32_t n_targets,
                                     const int32_t *base_joints, const int32_t *target_joints, const double *target_poses,
                                     const mh_options *opts, float *J_out, float *conv_out);
+
+/*
+ * ---- reverse mode of the kinematics: the gradient of a loss on body poses with respect to q, and J^T w without forming J
+ *      (GeometricJacobianCalculator.getJointTorques, algorithms/GeometricJacobianCalculator.java:477-484, is J^T w through the matrix) ----
+ * target_joints, base_joints, target_poses, layouts, index maps, contexts and quaternion normalisation: the conventions of mh_body_poses_*
+ * and mh_geometric_jacobian_* above, word for word.  One outward sweep for the poses and one inward sweep that adds the wrenches up towards
+ * the root and reads each joint's share as S^T f: nv numbers per configuration are written, no 6 K x nv matrix.
+ *
+ * mh_body_poses_vjp_*: g_pose [B][n_targets][12] (MH_LAYOUT_SOA: [12 n_targets][B]) is the cotangent of pose_out of mh_body_poses_* for the
+ * same targets and poses, entry for entry (9 for R row-major, then 3 for p); the nine need not be tangent to the rotations.  gq_out [B][nv]
+ * (MH_LAYOUT_SOA: [nv][B]), indexed like tau:  gq_out[j] = sum_k sum_e g_pose[k][e] d pose_out[k][e] / d q_j, a step of q being the
+ * velocity-space step of mh_configuration_add_* (the chart of every other derivative of the library).  In closed form, with (R_k, p_k) the
+ * pose of target k, M = R_k^T G_R, n_k = (M32 - M23, M13 - M31, M21 - M12) and f_k = R_k^T g_p:  gq = sum_k J_k^T (n_k; f_k), J_k the
+ * rooted Jacobian of mh_geometric_jacobian_* for that target and pose.  target_joints = NULL with n_targets = n_joints (and target_poses =
+ * NULL): the cotangents of the body-fixed frames of every body, in joint order.  The root body as a target contributes nothing.
+ *
+ * mh_jacobian_transpose_*: wrench [B][n_targets][6] (MH_LAYOUT_SOA: [6 n_targets][B]), moment then force, in the target frame at its
+ * origin.  tau_out [B][nv] (MH_LAYOUT_SOA: [nv][B]) = sum_k J_k^T w_k, J_k exactly the block mh_geometric_jacobian_* returns for
+ * (base_joints[k], target_joints[k], pose k); base_joints = NULL: every base is the root body.  With a moving base w_k acts on the target
+ * body and its opposite on the base body: joints above their common ancestor receive nothing.  target_joints = NULL is refused.
+ *
+ * Both: every entry of the output is written exactly once -- exact zeros for joints on no chain and for DoF indices no joint owns -- and
+ * nothing outside it.  Joint source modes play no part.  Rows are independent: a non-finite q or cotangent spoils its own row only.
+ * B = 0 or nv = 0 returns MH_OK and touches nothing.  MH_ERR_INVALID_ARGUMENT: the argument errors of the forward calls, NULL g_pose /
+ * wrench / output with B > 0, any overlap of the output with an input.  Device pointers, asynchronous on opts->stream; after mh_reserve /
+ * mh_context_reserve the calls allocate nothing and can be captured in a graph.
+ */
+mh_status mh_body_poses_vjp_f64(mh_model_t model, int64_t B, const double *q, int32_t n_targets, const int32_t *target_joints,
+                                const double *target_poses, const double *g_pose, const mh_options *opts, double *gq_out);
+mh_status mh_body_poses_vjp_f32(mh_model_t model, int64_t B, const float *q, int32_t n_targets, const int32_t *target_joints,
+                                const double *target_poses, const float *g_pose, const mh_options *opts, float *gq_out);
+mh_status mh_jacobian_transpose_f64(mh_model_t model, int64_t B, const double *q, int32_t n_targets, const int32_t *base_joints,
+                                    const int32_t *target_joints, const double *target_poses, const double *wrench,
+                                    const mh_options *opts, double *tau_out);
+mh_status mh_jacobian_transpose_f32(mh_model_t model, int64_t B, const float *q, int32_t n_targets, const int32_t *base_joints,
+                                    const int32_t *target_joints, const double *target_poses, const float *wrench,
+                                    const mh_options *opts, float *tau_out);
 
 /*
  * ---- inverse of the joint-space inertia matrix (columns of H^-1: MultiBodyResponseCalculator.applyJointWrench and the recursion behind

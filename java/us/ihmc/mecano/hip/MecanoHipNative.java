@@ -261,6 +261,26 @@ public final class MecanoHipNative
    /** the same in fp32 (float q / qd / J_out / conv_out on the device; the poses stay double) */
    static final MethodHandle GEOMETRIC_JACOBIAN_F32 = handle("mh_geometric_jacobian_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, JAVA_INT, ADDRESS, ADDRESS,
                                                                                                    ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * The gradient of a loss on body poses with respect to q for B configurations, one launch: (model, B, q, n_targets, target_joints (host
+    * int[], -1 = the root body)|NULL = every body, target_poses (host double[n_targets][12])|NULL, g_pose, opts|NULL, gq_out), g_pose
+    * [B][n_targets][12] the cotangent of BODY_POSES' pose_out, gq_out [B][nv] in the chart of mh_configuration_add.
+    */
+   static final MethodHandle BODY_POSES_VJP = handle("mh_body_poses_vjp_f64", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                       ADDRESS));
+   /** the same in fp32 (float q / g_pose / gq_out on the device; the poses stay double) */
+   static final MethodHandle BODY_POSES_VJP_F32 = handle("mh_body_poses_vjp_f32", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                           ADDRESS));
+   /**
+    * GeometricJacobianCalculator.getJointTorques summed over up to 16 kinematic chains without forming J, one launch: (model, B, q, n_targets,
+    * base_joints (host int[])|NULL = the root body, target_joints (host int[]), target_poses (host double[n_targets][12])|NULL, wrench,
+    * opts|NULL, tau_out), wrench [B][n_targets][6] (moment, force) in the target frames, tau_out [B][nv].
+    */
+   static final MethodHandle JACOBIAN_TRANSPOSE = handle("mh_jacobian_transpose_f64", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
+                                                                                               ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 (float q / wrench / tau_out on the device; the poses stay double) */
+   static final MethodHandle JACOBIAN_TRANSPOSE_F32 = handle("mh_jacobian_transpose_f32", status(ADDRESS, JAVA_LONG, ADDRESS, JAVA_INT, ADDRESS, ADDRESS, ADDRESS,
+                                                                                                   ADDRESS, ADDRESS, ADDRESS));
    /** mh_mass_matrix_inverse_*: at most this many listed columns per call */
    static final int MAX_INVERSE_COLUMNS = 64;
    /**

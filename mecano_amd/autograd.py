@@ -8,6 +8,8 @@ plus ``chart_pullback`` for q, and ``chart_cotangent`` at the new configuration 
 ``rnea_parameters`` and ``aba_parameters`` are the per-configuration-parameter calls as differentiable functions of **pi**: their backward
 is ONE call of ``HipModel.rnea_parameters_vjp`` / ``HipModel.aba_parameters_vjp`` (no regressor is formed).  They are not differentiable
 with respect to the state: a q, qd, qdd or tau that requires grad raises NotImplementedError.
+``body_poses`` carries gradients from where the bodies are back to q: the forward pass is ``HipModel.body_poses`` unchanged, the backward
+pass ONE call of ``HipModel.body_poses_vjp`` (no 6 K x nv Jacobian is formed) plus ``chart_pullback``.
 AoS device tensors, fp64 or fp32.  gravity and f_ext are not differentiated.  Once differentiable: the backward pass is not itself a
 graph of torch operations, and a second backward raises.
 """
@@ -163,6 +165,21 @@ class _Aba(torch.autograd.Function):
         return None, (None if gq is None else ctx.model.chart_pullback(q, gq)), gqd, gtau, None, None
 
 
+class _BodyPoses(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, q, targets, poses):
+        ctx.model, ctx.targets, ctx.poses = model, targets, poses
+        ctx.save_for_backward(q)
+        return model.body_poses(q, targets, poses)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_pose):
+        q, = ctx.saved_tensors
+        gq = ctx.model.body_poses_vjp(q, g_pose.contiguous(), ctx.targets, ctx.poses)
+        return None, ctx.model.chart_pullback(q, gq), None, None
+
+
 class _RneaParameters(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, q, qd, qdd, pi, gravity, f_ext):
@@ -256,6 +273,12 @@ def rnea(model, q, qd, qdd, gravity=(0.0, 0.0, -9.81), f_ext=None):
 def aba(model, q, qd, tau, gravity=(0.0, 0.0, -9.81), f_ext=None):
     """qdd = ``model.aba(q, qd, tau, gravity, f_ext)``, differentiable with respect to q (raw coordinates), qd and tau."""
     return _Aba.apply(model, q, qd, tau, gravity, f_ext)
+
+
+def body_poses(model, q, targets=None, poses=None):
+    """[B, K, 12] = ``model.body_poses(q, targets, poses)``, differentiable with respect to q (raw coordinates): the backward pass is ONE
+    ``model.body_poses_vjp`` (no Jacobian is formed) plus ``chart_pullback``.  Every task-space loss lives on this output."""
+    return _BodyPoses.apply(model, q, targets, poses)
 
 
 def _state_is_constant(call, **state):

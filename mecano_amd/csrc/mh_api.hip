@@ -11,6 +11,7 @@
 #include "mh_response_kernels.h"
 #include "mh_minv_kernels.h"
 #include "mh_kinematics_kernels.h"
+#include "mh_kinematics_vjp_kernels.h"
 #include "mh_rnea_deriv_kernels.h"
 #include "mh_params_kernels.h"
 #include "mh_params_vjp_kernels.h"
@@ -164,6 +165,7 @@ struct ContextState
    // mh_aba_integrate_derivatives_*: d qdd / d q and d qdd / d qd of the call (Hinv and qdd go to `deriv`)
    Workspace step;
    // mh_body_poses_* / mh_geometric_jacobian_*: the SoA form of AoS outputs, which a transposition then brings to the caller's rows
+   // (mh_body_poses_vjp_* / mh_jacobian_transpose_*: the SoA form of their AoS cotangents too)
    Workspace kin;
    // mh_aba_constrained_* / mh_constraint_impulse_* / mh_contact_impulse_* and their _between_ forms: the blocks of con_scratch
    // (mh_launch_plans.h)
@@ -1790,16 +1792,14 @@ static size_t kin_scratch_entries(const mh_model *m, int n_targets, bool jacobia
 {
    return jacobian ? 6 * (size_t)n_targets * (size_t)m->nv + (conv ? 6 * (size_t)n_targets : 0) : 12 * (size_t)n_targets;
 }
+// The target list of a kinematics call, forward or reverse: counts and indices checked, targets and bases as engine indices, each target
+// frame in the canonical frame of its body (target_frame).  with_all_bodies: target_joints = NULL names every body (all_bodies is set).
 template <typename T>
-mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int64_t B, const T *q, const T *qd, int32_t n_targets,
-                          const int32_t *base_joints, const int32_t *target_joints, const double *target_poses, const mh_options *opts_in,
-                          T *pose_out, T *J_out, T *conv_out)
+mh_status kin_targets(const char *call, bool with_all_bodies, mh_model_t model, int32_t n_targets, const int32_t *base_joints,
+                      const int32_t *target_joints, const double *target_poses, int *tgt, int *base, T (*pose)[12], bool &all_bodies)
 {
-   mh_options opts;
-   mh_status st = begin_call(model, B, opts_in, opts);
-   if (st != MH_OK)
-      return st;
-   const bool all_bodies = !jacobian && !target_joints;
+   mh_status st = MH_OK;
+   all_bodies = with_all_bodies && !target_joints;
    if (all_bodies)
    {
       if (n_targets != model->n)
@@ -1814,7 +1814,6 @@ mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int
       if (n_targets < 1 || n_targets > MH_MAX_KINEMATIC_TARGETS)
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: n_targets = %d is outside 1 ... %d", call, n_targets, MH_MAX_KINEMATIC_TARGETS);
    }
-   mh::KinArgs<T> G{};
    for (int k = 0; k < (all_bodies ? 0 : n_targets); k++)
    {
       const int i = target_joints[k], ib = base_joints ? base_joints[k] : -1;
@@ -1822,11 +1821,26 @@ mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: target %d names joint %d (the model has %d joints; -1 is the root body)", call, k, i, model->n);
       if (ib < -1 || ib >= model->n)
          return fail(MH_ERR_INVALID_ARGUMENT, "%s: base %d names joint %d (the model has %d joints; -1 is the root body)", call, k, ib, model->n);
-      G.tgt[k] = i < 0 ? -1 : model->engine_of[i];
-      G.base[k] = ib < 0 ? -1 : model->engine_of[ib];
-      if ((st = target_frame<T>(model, G.tgt[k], target_poses ? target_poses + 12 * k : nullptr, G.pose[k], call, k)) != MH_OK)
+      tgt[k] = i < 0 ? -1 : model->engine_of[i];
+      base[k] = ib < 0 ? -1 : model->engine_of[ib];
+      if ((st = target_frame<T>(model, tgt[k], target_poses ? target_poses + 12 * k : nullptr, pose[k], call, k)) != MH_OK)
          return st;
    }
+   return MH_OK;
+}
+template <typename T>
+mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int64_t B, const T *q, const T *qd, int32_t n_targets,
+                          const int32_t *base_joints, const int32_t *target_joints, const double *target_poses, const mh_options *opts_in,
+                          T *pose_out, T *J_out, T *conv_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   mh::KinArgs<T> G{};
+   bool all_bodies = false;
+   if ((st = kin_targets<T>(call, !jacobian, model, n_targets, base_joints, target_joints, target_poses, G.tgt, G.base, G.pose, all_bodies)) != MH_OK)
+      return st;
    if (B == 0)
       return MH_OK;
    if (!q || (jacobian ? !J_out : !pose_out))
@@ -1887,6 +1901,75 @@ mh_status kinematics_impl(const char *call, bool jacobian, mh_model_t model, int
          if (conv_out)
             mh::transpose_rows<T>(conv_dst, conv_out, (long)B, (long)n_conv, false, stream);
       }
+      HIP_TRY(hipGetLastError());
+   }
+   return MH_OK;
+}
+// Reverse mode of the kinematics (mh_kinematics_vjp_kernels.h): the gradient of a loss on body poses with respect to q (g = the cotangent
+// of pose_out, 12 per target) and, wrench = true, J^T w of up to sixteen chains (g = the wrenches, 6 per target).  One kernel in the
+// workspace plan of the forward calls (parts = 1), which reads and writes SoA always: an AoS batch has its cotangents transposed into the
+// context's kin scratch, the kernel writes the nv entries behind them, and a second transposition brings those to the caller's rows.
+static size_t kin_vjp_scratch_entries(const mh_model *m, int n_targets, bool wrench) { return (wrench ? 6 : 12) * (size_t)n_targets + (size_t)m->nv; }
+template <typename T>
+mh_status kinematics_vjp_impl(const char *call, bool wrench, mh_model_t model, int64_t B, const T *q, int32_t n_targets, const int32_t *base_joints,
+                              const int32_t *target_joints, const double *target_poses, const T *g, const mh_options *opts_in, T *out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   mh::KinVjpArgs<T> G{};
+   bool all_bodies = false;
+   if ((st = kin_targets<T>(call, !wrench, model, n_targets, base_joints, target_joints, target_poses, G.tgt, G.base, G.pose, all_bodies)) != MH_OK)
+      return st;
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!q || !g || !out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%s: NULL configuration / %s / output pointer", call, wrench ? "wrench" : "cotangent");
+   const size_t n_g = (wrench ? 6 : 12) * (size_t)n_targets, nv = (size_t)model->nv;
+   {
+      const InRange ins[2] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {wrench ? "wrench" : "g_pose", g, (size_t)B * n_g * sizeof(T)}};
+      const OutRange outs[1] = {{wrench ? "tau_out" : "gq_out", out, (size_t)B * nv * sizeof(T), 0u}};
+      if ((st = check_aliasing(call, ins, 2, outs, 1)) != MH_OK)
+         return st;
+   }
+   const Launch L = plan_launch(model->cu_count, B);
+   st = ensure_bytes(model->ws, lane_ws_bytes((long)model->n * mh::KIN_SLOTS, L, 1, sizeof(T)));
+   if (st != MH_OK)
+      return st;
+   // B = 1: the two layouts are the same memory
+   const bool staged = opts.layout != MH_LAYOUT_SOA && B > 1;
+   const T *g_src = g;
+   T *out_dst = out;
+   hipStream_t stream = (hipStream_t)opts.stream;
+   if (staged)
+   {
+      st = ensure_bytes(model->kin, (size_t)B * kin_vjp_scratch_entries(model, n_targets, wrench) * sizeof(T));
+      if (st != MH_OK)
+         return st;
+      T *t_g = (T *)model->kin.ptr;
+      mh::transpose_rows<T>(g, t_g, (long)B, (long)n_g, true, stream);
+      HIP_TRY(hipGetLastError());
+      g_src = t_g, out_dst = t_g + (size_t)B * n_g;
+   }
+   mh::Args<T> &A = G.a;
+   A = make_args<T>(model, B, opts);
+   A.q = q;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = L.lanes;
+   G.g = g_src, G.out = out_dst;
+   G.g_bs = G.o_bs = 1, G.g_es = G.o_es = (long)B;
+   G.info = model->d_resp_info;
+   G.zero_ofs = model->d_grav_zero_ofs, G.zero_cols = model->d_grav_zero_cols;
+   G.n_targets = n_targets, G.all_bodies = all_bodies;
+   if (wrench)
+      hipLaunchKernelGGL((mh::kinematics_vjp_kernel<T, true>), dim3(L.grid), dim3(L.block), 0, stream, G);
+   else
+      hipLaunchKernelGGL((mh::kinematics_vjp_kernel<T, false>), dim3(L.grid), dim3(L.block), 0, stream, G);
+   HIP_TRY(hipGetLastError());
+   if (staged)
+   {
+      mh::transpose_rows<T>(out_dst, out, (long)B, (long)nv, false, stream);
       HIP_TRY(hipGetLastError());
    }
    return MH_OK;
@@ -3633,7 +3716,10 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
          return st;
       // mh_body_poses_* / mh_geometric_jacobian_*: the SoA form of their AoS outputs for the largest target list, while it stays within
       // the cap of the scratch above
-      const size_t kin_entries = std::max(kin_scratch_entries(m, MH_MAX_KINEMATIC_TARGETS, true, true), kin_scratch_entries(m, std::max(m->n, MH_MAX_KINEMATIC_TARGETS), false, false));
+      // (mh_body_poses_vjp_* / mh_jacobian_transpose_*: the cotangents of that many poses and nv entries behind them -- more than the
+      // above only for a model with many fixed joints)
+      const size_t kin_entries = std::max({kin_scratch_entries(m, MH_MAX_KINEMATIC_TARGETS, true, true), kin_scratch_entries(m, std::max(m->n, MH_MAX_KINEMATIC_TARGETS), false, false),
+                                           kin_vjp_scratch_entries(m, std::max(m->n, MH_MAX_KINEMATIC_TARGETS), false)});
       if ((size_t)max_batch * kin_entries * sizeof(double) <= kDerivReserveCap)
          st = ensure_bytes(m->kin, (size_t)max_batch * kin_entries * sizeof(double));
       if (st != MH_OK)
@@ -3786,6 +3872,26 @@ mh_status mh_geometric_jacobian_f32(mh_model_t model, int64_t B, const float *q,
 {
    return kinematics_impl<float>("mh_geometric_jacobian_f32", true, model, B, q, qd, n_targets, base_joints, target_joints, target_poses, opts, nullptr, J_out,
                                  conv_out);
+}
+mh_status mh_body_poses_vjp_f64(mh_model_t model, int64_t B, const double *q, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
+                                const double *g_pose, const mh_options *opts, double *gq_out)
+{
+   return kinematics_vjp_impl<double>("mh_body_poses_vjp_f64", false, model, B, q, n_targets, nullptr, target_joints, target_poses, g_pose, opts, gq_out);
+}
+mh_status mh_body_poses_vjp_f32(mh_model_t model, int64_t B, const float *q, int32_t n_targets, const int32_t *target_joints, const double *target_poses,
+                                const float *g_pose, const mh_options *opts, float *gq_out)
+{
+   return kinematics_vjp_impl<float>("mh_body_poses_vjp_f32", false, model, B, q, n_targets, nullptr, target_joints, target_poses, g_pose, opts, gq_out);
+}
+mh_status mh_jacobian_transpose_f64(mh_model_t model, int64_t B, const double *q, int32_t n_targets, const int32_t *base_joints, const int32_t *target_joints,
+                                    const double *target_poses, const double *wrench, const mh_options *opts, double *tau_out)
+{
+   return kinematics_vjp_impl<double>("mh_jacobian_transpose_f64", true, model, B, q, n_targets, base_joints, target_joints, target_poses, wrench, opts, tau_out);
+}
+mh_status mh_jacobian_transpose_f32(mh_model_t model, int64_t B, const float *q, int32_t n_targets, const int32_t *base_joints, const int32_t *target_joints,
+                                    const double *target_poses, const float *wrench, const mh_options *opts, float *tau_out)
+{
+   return kinematics_vjp_impl<float>("mh_jacobian_transpose_f32", true, model, B, q, n_targets, base_joints, target_joints, target_poses, wrench, opts, tau_out);
 }
 mh_status mh_apparent_inertia_inverse_f64(mh_model_t model, int64_t B, const double *q, int32_t n_targets, const int32_t *target_joints,
                                           const double *target_poses, int32_t blocks, const mh_options *opts, double *W_out)

@@ -661,6 +661,61 @@ class HipModel:
             None if poses is None else poses.ctypes.data, ctypes.byref(opts), J.data_ptr(), None if c is None else c.data_ptr()))
         return (J, c) if convective else J
 
+    def _kinematic_cotangent(self, g, B, K, per_target, layout, dt, name):
+        """``g`` checked as [B, K, per_target] (SoA: [per_target K, B]) beside q."""
+        self._device_tensor(g, dt)
+        shape = (B, K, per_target) if layout == _lib.LAYOUT_AOS else (per_target * K, B)
+        if tuple(g.shape) != shape:
+            raise _lib.MecanoHipError(2, f"{name} has shape {tuple(g.shape)}, expected {shape}")
+
+    def body_poses_vjp(self, q, g_pose, targets=None, poses=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Reverse mode of ``body_poses``, one launch that writes nv numbers per configuration: for a cotangent ``g_pose`` [B, K, 12] of
+        the poses (entry for entry: 9 for R row-major, 3 for p; the nine need not be tangent to the rotations) of the same ``targets`` /
+        ``poses``, gq [B, nv] = sum g_pose d pose / d q, a step of q being the velocity-space step of ``configuration_add`` (the chart of
+        ``rnea_vjp`` / ``aba_vjp``; ``chart_pullback`` brings it to the raw coordinates).  ``targets=None``: the cotangents of every
+        body-fixed frame, in joint order.  SoA: [12 K, B] in, [nv, B] out.  numpy in -> numpy out (fp64); device tensors (fp64 / fp32)
+        stay on the device, and ``out`` is a device tensor to write into."""
+        import torch
+        if not self._is_torch(q):
+            dev = [torch.tensor(_np(x, np.float64), device="cuda") for x in (q, g_pose)]
+            return self.body_poses_vjp(dev[0], dev[1], targets, poses, layout).cpu().numpy()
+        B, dt, sfx, stream = self._device_inputs([q], layout)
+        if targets is None:
+            if poses is not None:
+                raise _lib.MecanoHipError(1, "poses need targets: every body comes with the identity pose")
+            tgt, K = None, self.n_joints
+        else:
+            tgt, K, _, poses = self._kinematic_targets(targets, None, poses)
+        self._kinematic_cotangent(g_pose, B, K, 12, layout, dt, "g_pose")
+        out = self._output(out, (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B), dt, q.device, "gq")
+        opts = self._options(layout, stream=stream)
+        _lib.check(getattr(_lib.load(), f"mh_body_poses_vjp_{sfx}")(
+            self._h, B, q.data_ptr(), K, None if tgt is None else tgt.ctypes.data, None if poses is None else poses.ctypes.data,
+            g_pose.data_ptr(), ctypes.byref(opts), out.data_ptr()))
+        return out
+
+    def jacobian_transpose(self, q, wrench, targets, bases=None, poses=None, layout=_lib.LAYOUT_AOS, out=None):
+        """sum_k J_k^T w_k without forming J (GeometricJacobianCalculator.getJointTorques, GeometricJacobianCalculator.java:477-484, summed
+        over K chains), one launch: ``wrench`` [B, K, 6] (moment, then force) in the target frames at their origins, J_k exactly the block
+        ``geometric_jacobian`` returns for (``bases[k]``, ``targets[k]``, ``poses[k]``); tau [B, nv], indexed like tau.  With a moving
+        base the wrench acts on the target body and its opposite on the base body.  SoA: [6 K, B] in, [nv, B] out.  numpy in -> numpy
+        out (fp64); device tensors (fp64 / fp32) stay on the device, and ``out`` is a device tensor to write into."""
+        import torch
+        if targets is None:
+            raise _lib.MecanoHipError(1, "jacobian_transpose needs targets: there is no all-bodies form")
+        if not self._is_torch(q):
+            dev = [torch.tensor(_np(x, np.float64), device="cuda") for x in (q, wrench)]
+            return self.jacobian_transpose(dev[0], dev[1], targets, bases, poses, layout).cpu().numpy()
+        B, dt, sfx, stream = self._device_inputs([q], layout)
+        tgt, K, bases, poses = self._kinematic_targets(targets, bases, poses)
+        self._kinematic_cotangent(wrench, B, K, 6, layout, dt, "wrench")
+        out = self._output(out, (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B), dt, q.device, "tau")
+        opts = self._options(layout, stream=stream)
+        _lib.check(getattr(_lib.load(), f"mh_jacobian_transpose_{sfx}")(
+            self._h, B, q.data_ptr(), K, None if bases is None else bases.ctypes.data, tgt.ctypes.data,
+            None if poses is None else poses.ctypes.data, wrench.data_ptr(), ctypes.byref(opts), out.data_ptr()))
+        return out
+
     def mass_matrix_inverse(self, q, columns=None, layout=_lib.LAYOUT_AOS, out=None):
         """Inverse of the joint-space inertia matrix, H^-1 = d qdd / d tau, from the articulated-body recursion in one launch
         (MultiBodyResponseCalculator.applyJointWrench and its recursion, MultiBodyResponseCalculator.java:685-735, 1206-1338; H is not
