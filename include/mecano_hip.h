@@ -796,9 +796,9 @@ mh_status mh_aba_parameters_f32(mh_model_t model, int64_t B, const float *q, con
  * aside by mh_reserve / mh_context_reserve.  A model with MH_ACCELERATION_SOURCE joints is refused (MH_ERR_INVALID_ARGUMENT).
  * Both: pi, u / w or gpi_out = NULL is MH_ERR_INVALID_ARGUMENT, as is an output that overlaps an input (u / w and pi included) or another
  * output.  B = 0 returns MH_OK and touches nothing.  A pi row that is no physical inertia or not finite is not diagnosed: it shows as
- * inf / nan in that row's outputs only.  The state gradients of mh_rnea_vjp_* / mh_aba_vjp_* at per-configuration parameters are not
- * provided.  Device pointers, asynchronous on opts->stream, layouts, index maps and contexts honoured; after mh_reserve /
- * mh_context_reserve the calls only enqueue work (graph-capturable).
+ * inf / nan in that row's outputs only.  The state gradients of mh_rnea_vjp_* / mh_aba_vjp_* at per-configuration parameters are those
+ * of mh_rnea_parameters_state_vjp_* / mh_aba_parameters_state_vjp_* below.  Device pointers, asynchronous on opts->stream, layouts, index
+ * maps and contexts honoured; after mh_reserve / mh_context_reserve the calls only enqueue work (graph-capturable).
  */
 mh_status mh_rnea_parameters_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double *pi,
                                      const double gravity[3], const double *u, const mh_options *opts, double *gpi_out);
@@ -810,6 +810,51 @@ mh_status mh_aba_parameters_vjp_f64(mh_model_t model, int64_t B, const double *q
 mh_status mh_aba_parameters_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const float *pi,
                                     const double gravity[3], const float *f_ext, const float *w, const mh_options *opts, float *qdd_out,
                                     float *gtau_out, float *gpi_out);
+
+/*
+ * ---- reverse-mode gradients of the same two calls with respect to the state AND the inertial parameters in one call: what
+ *      backpropagation through a rollout of a robot whose parameters are being learned needs (fitting pi from measured trajectories, a
+ *      policy over randomised robots, a payload and a controller optimised together; no calculator of the reference) ----
+ * The contract is the union of mh_rnea_vjp_* / mh_aba_vjp_* and mh_rnea_parameters_vjp_* / mh_aba_parameters_vjp_*.
+ * mh_rnea_parameters_state_vjp_*: for a cotangent u [B][nv] of the efforts of mh_rnea_parameters_*(q, qd, qdd, pi): gq_out = u^T d tau / d q,
+ * gqd_out = u^T d tau / d qd, gqdd_out = H(pi) u, each [B][nv] (MH_LAYOUT_SOA: [nv][B]), and gpi_out[r][j][k] = sum_i u_i d tau_i / d pi[r][j][k],
+ * laid out like pi ([B][n_joints][10], MH_LAYOUT_SOA: [10 n_joints][B]) and taken with respect to the ten numbers themselves.  The matrices
+ * contracted are those of mh_rnea_derivatives_*, evaluated with the inertias of row r -- the velocity-space chart, the components of qd and
+ * qdd fixed, external wrenches held IN THE WORLD --, none of them formed.  opts->consider_coriolis = 0 evaluates at qd = 0 (qd may then be
+ * NULL; gqd_out is exact zeros), opts->consider_accelerations = 0 at qdd = 0 (qdd may then be NULL); opts->use_root_acceleration is
+ * honoured (gravity may then be NULL).  u = 0 gives exact zeros in every output.  ONE launch of a run-time-topology kernel for every model
+ * (mh_params_state_vjp_kernels.h): the two sweeps of mh_rnea_vjp_* in that call's workspace plan, with every body's inertia read from the
+ * row's pi in both, and the ten derivatives of a body formed in the outward one -- where mh_rnea_vjp_* beside mh_rnea_parameters_vjp_*
+ * runs two outward sweeps and one inward.  No scratch.
+ * mh_aba_parameters_state_vjp_*: for a cotangent w [B][nv] of qdd = mh_aba_parameters_*(q, qd, tau, pi): gtau_out = mu = H(pi)^-1 w,
+ * gq_out = -mu^T d tau / d q, gqd_out = -mu^T d tau / d qd and gpi_out = -mu^T d tau / d pi at that qdd (the kernel above with u = mu, negated),
+ * which are w^T d qdd / d q, w^T d qdd / d qd, w^T d qdd / d tau and w^T d qdd / d pi with the matrices of mh_aba_derivatives_* at H(pi_r).
+ * qdd_out [B][nv] may be NULL; it is written as mh_aba_parameters_* writes it (entries at DoF indices no joint owns are left alone).
+ * Launches composed on opts->stream: mh_aba_parameters_* for qdd, again at rest without root acceleration and wrenches with tau = w for mu
+ * (behind one memset), the kernel above -- three launches where mh_aba_vjp_* beside mh_aba_parameters_vjp_*
+ * takes six; the sweep is dropped where only gtau_out is asked for.  The scratch is 2 B nv elements of the context (qdd and mu where the
+ * caller takes neither), set aside by mh_reserve / mh_context_reserve.
+ * Both: each gradient output may be NULL and is then neither formed nor written; at least one of gq_out, gqd_out, gqdd_out / gtau_out and
+ * gpi_out must be given (MH_ERR_INVALID_ARGUMENT otherwise).  Every entry of an output given is written once (no memset needed), zeros at
+ * DoF indices no joint owns and the blocks of fixed joints included, nothing outside the outputs.  pi == NULL is
+ * MH_ERR_INVALID_ARGUMENT, as are MH_ACCELERATION_SOURCE joints in the model, gravity == NULL without a root acceleration, and an output
+ * that overlaps an input (u / w and pi included) or another output.  B = 0 or nv = 0 returns MH_OK and touches nothing.  A pi row that is
+ * no physical inertia or not finite is not diagnosed: it shows as inf / nan in that row's outputs only.  Device pointers, asynchronous on
+ * opts->stream, layouts, index maps and contexts honoured; after mh_reserve / mh_context_reserve the calls only enqueue work
+ * (graph-capturable).
+ */
+mh_status mh_rnea_parameters_state_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double *pi,
+                                           const double gravity[3], const double *f_ext, const double *u, const mh_options *opts, double *gq_out,
+                                           double *gqd_out, double *gqdd_out, double *gpi_out);
+mh_status mh_rnea_parameters_state_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const float *pi,
+                                           const double gravity[3], const float *f_ext, const float *u, const mh_options *opts, float *gq_out,
+                                           float *gqd_out, float *gqdd_out, float *gpi_out);
+mh_status mh_aba_parameters_state_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double *pi,
+                                          const double gravity[3], const double *f_ext, const double *w, const mh_options *opts, double *qdd_out,
+                                          double *gq_out, double *gqd_out, double *gtau_out, double *gpi_out);
+mh_status mh_aba_parameters_state_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const float *pi,
+                                          const double gravity[3], const float *f_ext, const float *w, const mh_options *opts, float *qdd_out,
+                                          float *gq_out, float *gqd_out, float *gtau_out, float *gpi_out);
 
 /*
  * ---- forward dynamics under bilateral constraints on body frames, and the velocity-level twin for touch-down (the consumer of the

@@ -228,6 +228,25 @@ public final class MecanoHipNative
    /** the same in fp32 */
    static final MethodHandle ABA_PARAMETERS_VJP_F32 = handle("mh_aba_parameters_vjp_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                                                  ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * Reverse-mode gradients of the inverse dynamics at per-configuration inertial parameters with respect to the state AND the parameters,
+    * one launch: (model, B, q, qd, qdd, pi, gravity[3] (host), f_ext|NULL, u, opts|NULL, gq_out|NULL, gqd_out|NULL, gqdd_out|NULL,
+    * gpi_out|NULL), not all four NULL; gpi_out laid out like pi, gqdd_out = H(pi) u.
+    */
+   static final MethodHandle RNEA_PARAMETERS_STATE_VJP = handle("mh_rnea_parameters_state_vjp_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                                           ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle RNEA_PARAMETERS_STATE_VJP_F32 = handle("mh_rnea_parameters_state_vjp_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                                               ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * The same of the forward dynamics, for a cotangent w of qdd: (model, B, q, qd, tau, pi, gravity[3] (host), f_ext|NULL, w, opts|NULL,
+    * qdd_out|NULL, gq_out|NULL, gqd_out|NULL, gtau_out|NULL, gpi_out|NULL), not all four gradients NULL; gtau_out = H(pi)^-1 w.
+    */
+   static final MethodHandle ABA_PARAMETERS_STATE_VJP = handle("mh_aba_parameters_state_vjp_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                                         ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle ABA_PARAMETERS_STATE_VJP_F32 = handle("mh_aba_parameters_state_vjp_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                                             ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
    /** mh_apparent_inertia_inverse_*: the targets' own 6 x 6 blocks, or the coupled 6K x 6K matrix; at most this many targets per call */
    static final int APPARENT_BLOCKS_DIAGONAL = 0, APPARENT_BLOCKS_COUPLED = 1;
    static final int MAX_APPARENT_TARGETS = 16;

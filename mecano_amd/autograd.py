@@ -8,6 +8,10 @@ plus ``chart_pullback`` for q, and ``chart_cotangent`` at the new configuration 
 ``rnea_parameters`` and ``aba_parameters`` are the per-configuration-parameter calls as differentiable functions of **pi**: their backward
 is ONE call of ``HipModel.rnea_parameters_vjp`` / ``HipModel.aba_parameters_vjp`` (no regressor is formed).  They are not differentiable
 with respect to the state: a q, qd, qdd or tau that requires grad raises NotImplementedError.
+``rnea_parameters_state``, ``aba_parameters_state`` and ``step_parameters`` are the same calls as differentiable functions of the state
+AND pi: their backward is ONE call of ``HipModel.rnea_parameters_state_vjp`` / ``HipModel.aba_parameters_state_vjp`` that asks for exactly
+the gradients needed, plus ``chart_pullback`` for q.  Use them where the state requires grad -- a rollout of robots whose parameters
+are being learned.
 ``body_poses`` carries gradients from where the bodies are back to q: the forward pass is ``HipModel.body_poses`` unchanged, the backward
 pass ONE call of ``HipModel.body_poses_vjp`` (no 6 K x nv Jacobian is formed) plus ``chart_pullback``.
 AoS device tensors, fp64 or fp32.  gravity and f_ext are not differentiated.  Once differentiable: the backward pass is not itself a
@@ -209,6 +213,43 @@ class _AbaParameters(torch.autograd.Function):
         return None, None, None, None, gpi, None, None
 
 
+def _wanted_with_pi(ctx, first, like, pi):
+    """``_wanted`` for three state inputs, and one more tensor like pi where pi wants a gradient."""
+    return _wanted(ctx, first, like) + (torch.empty_like(pi) if ctx.needs_input_grad[first + 3] else None,)
+
+
+class _RneaParametersState(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, q, qd, qdd, pi, gravity, f_ext):
+        ctx.model, ctx.gravity, ctx.f_ext = model, gravity, f_ext
+        ctx.save_for_backward(q, qd, qdd, pi)
+        return model.rnea_parameters(q, qd, qdd, pi, gravity, f_ext)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, u):
+        q, qd, qdd, pi = ctx.saved_tensors
+        gq, gqd, gqdd, gpi = ctx.model.rnea_parameters_state_vjp(q, qd, qdd, pi, u.contiguous(), ctx.gravity, ctx.f_ext,
+                                                                 out=_wanted_with_pi(ctx, 1, qd, pi))
+        return None, (None if gq is None else ctx.model.chart_pullback(q, gq)), gqd, gqdd, gpi, None, None
+
+
+class _AbaParametersState(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, model, q, qd, tau, pi, gravity, f_ext):
+        ctx.model, ctx.gravity, ctx.f_ext = model, gravity, f_ext
+        ctx.save_for_backward(q, qd, tau, pi)
+        return model.aba_parameters(q, qd, tau, pi, gravity, f_ext)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, w):
+        q, qd, tau, pi = ctx.saved_tensors
+        _, gq, gqd, gtau, gpi = ctx.model.aba_parameters_state_vjp(q, qd, tau, pi, w.contiguous(), ctx.gravity, ctx.f_ext,
+                                                                   out=(None,) + _wanted_with_pi(ctx, 1, qd, pi))
+        return None, (None if gq is None else ctx.model.chart_pullback(q, gq)), gqd, gtau, gpi, None, None
+
+
 def _raw_gradient(model, q, q_next, gq, g_raw_next):
     """chart_pullback at q plus the quaternions' radial pass-through: the gradient of the raw map q -> (q_next, qd_next)."""
     if gq is None:
@@ -301,3 +342,21 @@ def aba_parameters(model, q, qd, tau, pi, gravity=(0.0, 0.0, -9.81), f_ext=None)
     qd or tau that requires grad raises NotImplementedError."""
     _state_is_constant("aba_parameters", q=q, qd=qd, tau=tau)
     return _AbaParameters.apply(model, q, qd, tau, pi, gravity, f_ext)
+
+
+def rnea_parameters_state(model, q, qd, qdd, pi, gravity=(0.0, 0.0, -9.81), f_ext=None):
+    """tau = ``model.rnea_parameters(q, qd, qdd, pi, gravity, f_ext)``, differentiable with respect to q (raw coordinates), qd, qdd AND pi
+    in one backward call: ONE ``model.rnea_parameters_state_vjp`` that forms only the gradients ``needs_input_grad`` asks for."""
+    return _RneaParametersState.apply(model, q, qd, qdd, pi, gravity, f_ext)
+
+
+def aba_parameters_state(model, q, qd, tau, pi, gravity=(0.0, 0.0, -9.81), f_ext=None):
+    """qdd = ``model.aba_parameters(q, qd, tau, pi, gravity, f_ext)``, differentiable with respect to q (raw coordinates), qd, tau AND pi
+    in one backward call: ONE ``model.aba_parameters_state_vjp``."""
+    return _AbaParametersState.apply(model, q, qd, tau, pi, gravity, f_ext)
+
+
+def step_parameters(model, dt, q, qd, tau, pi, gravity=(0.0, 0.0, -9.81), f_ext=None):
+    """(q_next, qd_next) of one simulation step of B different robots: ``aba_parameters_state`` then ``integrate`` with step ``dt``,
+    differentiable with respect to q (raw coordinates), qd, tau and pi, so that rollouts chain across quaternions."""
+    return integrate(model, dt, q, qd, aba_parameters_state(model, q, qd, tau, pi, gravity, f_ext))

@@ -15,6 +15,7 @@
 #include "mh_rnea_deriv_kernels.h"
 #include "mh_params_kernels.h"
 #include "mh_params_vjp_kernels.h"
+#include "mh_params_state_vjp_kernels.h"
 #include "mh_step_kernels.h"
 #include "mh_constraint_kernels.h"
 #include "mh_contact_kernels.h"
@@ -160,7 +161,7 @@ struct ContextState
    FreshOnCopy<std::vector<int>> pairs_host;
    // mh_rnea_derivatives_* / mh_aba_derivatives_*: scratch of the forward form (Hinv and qdd the caller did not ask for)
    Workspace deriv;
-   // mh_aba_vjp_*: qdd and H^-1 w the caller did not ask for, B nv entries each
+   // mh_aba_vjp_* / mh_aba_parameters_vjp_* / mh_aba_parameters_state_vjp_*: qdd and H^-1 w the caller did not ask for, B nv entries each
    Workspace vjp;
    // mh_aba_integrate_derivatives_*: d qdd / d q and d qdd / d qd of the call (Hinv and qdd go to `deriv`)
    Workspace step;
@@ -2764,6 +2765,127 @@ mh_status aba_parameters_vjp_impl(mh_model_t model, int64_t B, const T *q, const
    }
    return parameters_vjp_launch<T>(model, B, q, qd, qdd, pi, gravity, mu, od, true, gpi_out);
 }
+// State AND parameter gradients of the inverse dynamics at per-configuration parameters (mh_params_state_vjp_kernels.h): one launch of
+// the adjoint sweep of rnea_vjp_launch with every body's inertia read from the row's pi, in that kernel's slot plan (vjp_slots: the fourth
+// row of mh_reserve's lane plans) and with its parts; it writes every entry of the outputs it is given, the ten derivatives per body in
+// its outward sweep when gpi_out is given.  The state matrices are read in place in both layouts, as rnea_vjp_launch reads them; pi and
+// gpi are staged by the kernel.  negate: -gq, -gqd and -gpi (the forward form below).
+template <typename T>
+mh_status parameters_state_vjp_launch(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const T *pi, const double *gravity,
+                                      const T *f_ext, const T *u, const mh_options &opts, bool negate, T *gq_out, T *gqd_out, T *gqdd_out, T *gpi_out)
+{
+   const Launch L = plan_launch(model->cu_count, B);
+   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
+   mh_status st = ensure_bytes(model->ws, lane_ws_bytes(model->vjp_slots, L, parts, sizeof(T)));
+   if (st != MH_OK)
+      return st;
+   mh::ParamStateVjpArgs<T> G{};
+   mh::Args<T> &A = G.pv.p.a;
+   A = make_args<T>(model, B, opts, gravity);
+   A.q = q, A.qd = qd, A.in3 = qdd, A.fext = f_ext, A.out = nullptr;
+   A.ws = (T *)model->ws.ptr;
+   A.ws_stride = L.lanes;
+   G.pv.p.pi = pi, G.pv.u = u, G.pv.gpi = gpi_out, G.pv.negate = negate;
+   set_strides(G.pv.p.p_bs, G.pv.p.p_es, opts.layout == MH_LAYOUT_SOA, B, (long)model->n * mh::PARAMS_PER_BODY);
+   G.gq = gq_out, G.gqd = gqd_out, G.gqdd = gqdd_out;
+   G.slot = model->d_vjp_slot, G.slots = model->vjp_slots;
+   G.unowned = model->d_grav_zero_cols + model->grav_zero_ofs[model->n];
+   G.n_unowned = model->grav_zero_ofs[model->n + 1] - model->grav_zero_ofs[model->n];
+   hipLaunchKernelGGL((mh::rnea_parameters_state_vjp_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
+template <typename T>
+mh_status rnea_parameters_state_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const T *pi, const double *gravity,
+                                         const T *f_ext, const T *u, const mh_options *opts_in, T *gq_out, T *gqd_out, T *gqdd_out, T *gpi_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: the gradients of the dynamics take none", model->n_locked);
+   if (!pi)
+      return fail(MH_ERR_INVALID_ARGUMENT, "pi is NULL");
+   if (!gravity && !opts.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (!gq_out && !gqd_out && !gqdd_out && !gpi_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gq_out, gqd_out, gqdd_out and gpi_out are all NULL");
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!q || !u || (opts.consider_coriolis && !qd) || (opts.consider_accelerations && !qdd))
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / cotangent pointer (qd may be NULL with consider_coriolis = 0, qdd with consider_accelerations = 0)");
+   {
+      const size_t nq = (size_t)B * model->nq * sizeof(T), nvb = (size_t)B * model->nv * sizeof(T), bj = (size_t)B * model->n * sizeof(T);
+      const InRange ins[6] = {{"q", q, nq}, {"qd", opts.consider_coriolis ? qd : nullptr, nvb}, {"qdd", opts.consider_accelerations ? qdd : nullptr, nvb},
+                              {"pi", pi, mh::PARAMS_PER_BODY * bj}, {"f_ext", f_ext, 6 * bj}, {"u", u, nvb}};
+      const OutRange outs[4] = {{"gq_out", gq_out, nvb, 0u}, {"gqd_out", gqd_out, nvb, 0u}, {"gqdd_out", gqdd_out, nvb, 0u},
+                                {"gpi_out", gpi_out, mh::PARAMS_PER_BODY * bj, 0u}};
+      if ((st = check_aliasing("mh_rnea_parameters_state_vjp", ins, 6, outs, 4)) != MH_OK)
+         return st;
+   }
+   return parameters_state_vjp_launch<T>(model, B, q, qd, qdd, pi, gravity, f_ext, u, opts, false, gq_out, gqd_out, gqdd_out, gpi_out);
+}
+// ... and of the forward dynamics: three launches (and one memset) composed on the caller's stream, exactly as in
+// aba_parameters_vjp_impl -- aba_parameters_kernel for qdd; again at rest, without root acceleration and wrenches, with tau = w, which is
+// mu = H(pi)^-1 w = gtau (its qd is the output itself, zeroed first); the kernel above at that qdd with u = mu, negated, which gives gq,
+// gqd and gpi together.  The scratch: qdd and mu where the caller takes neither (two of the three vectors mh_reserve sets aside).
+template <typename T>
+mh_status aba_parameters_state_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const T *pi, const double *gravity,
+                                        const T *f_ext, const T *w, const mh_options *opts_in, T *qdd_out, T *gq_out, T *gqd_out, T *gtau_out,
+                                        T *gpi_out)
+{
+   mh_options o;
+   mh_status st = begin_call(model, B, opts_in, o);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: the gradients of the dynamics take none", model->n_locked);
+   if (!pi)
+      return fail(MH_ERR_INVALID_ARGUMENT, "pi is NULL");
+   if (!gravity && !o.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (!gq_out && !gqd_out && !gtau_out && !gpi_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gq_out, gqd_out, gtau_out and gpi_out are all NULL");
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!q || !qd || !tau || !w)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / cotangent pointer");
+   const size_t nvb = (size_t)B * model->nv * sizeof(T);
+   {
+      const size_t bj = (size_t)B * model->n * sizeof(T);
+      const InRange ins[6] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"qd", qd, nvb}, {"tau", tau, nvb}, {"pi", pi, mh::PARAMS_PER_BODY * bj},
+                              {"f_ext", f_ext, 6 * bj}, {"w", w, nvb}};
+      const OutRange outs[5] = {{"qdd_out", qdd_out, nvb, 0u}, {"gq_out", gq_out, nvb, 0u}, {"gqd_out", gqd_out, nvb, 0u}, {"gtau_out", gtau_out, nvb, 0u},
+                                {"gpi_out", gpi_out, mh::PARAMS_PER_BODY * bj, 0u}};
+      if ((st = check_aliasing("mh_aba_parameters_state_vjp", ins, 6, outs, 5)) != MH_OK)
+         return st;
+   }
+   T *qdd = qdd_out, *mu = gtau_out;
+   if (!qdd || !mu)
+   {
+      if ((st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T), 2))) != MH_OK)
+         return st;
+      if (!qdd)
+         qdd = (T *)model->vjp.ptr;
+      if (!mu)
+         mu = (T *)model->vjp.ptr + (size_t)B * model->nv;
+   }
+   mh_options od = o; // forward dynamics, and the inverse dynamics at the state it saw: both switches on
+   od.consider_coriolis = 1, od.consider_accelerations = 1;
+   mh_options rest = od; // H^-1 w: nothing moves, nothing pulls
+   rest.use_root_acceleration = 1;
+   for (double &x : rest.root_acceleration)
+      x = 0.0;
+   if (qdd_out || gq_out || gqd_out || gpi_out) // (gtau_out alone needs no qdd)
+      if ((st = parameters_impl<T>(ALGO_ABA, model, B, q, qd, tau, pi, gravity, f_ext, &od, qdd)) != MH_OK)
+         return st;
+   HIP_TRY(hipMemsetAsync(mu, 0, nvb, (hipStream_t)o.stream));
+   st = parameters_impl<T>(ALGO_ABA, model, B, q, mu, w, pi, nullptr, nullptr, &rest, mu);
+   if (st != MH_OK || (!gq_out && !gqd_out && !gpi_out))
+      return st;
+   return parameters_state_vjp_launch<T>(model, B, q, qd, qdd, pi, gravity, f_ext, mu, od, true, gq_out, gqd_out, nullptr, gpi_out);
+}
 template <typename T>
 mh_status integrate_impl(mh_model_t model, int64_t B, double dt, const T *q, const T *qd, const T *qdd, const mh_options *opts_in, T *q_out,
                                 T *qd_out, T *qdd_out)
@@ -3696,7 +3818,8 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
          // the same slots with up to one wave per group of six columns
          {m->resp_slots, std::max<long>(MH_MAX_APPARENT_TARGETS, minv_groups(std::max<int>(m->nv, MH_MAX_INVERSE_COLUMNS)))},
          {m->deriv_slots, std::min(8, m->n)}, // mh_rnea_derivatives_* / mh_aba_derivatives_*: the kernel's own slot plan
-         {m->vjp_slots, std::min(8, m->n)},   // mh_rnea_vjp_* / mh_aba_vjp_*: likewise
+         // mh_rnea_vjp_* / mh_aba_vjp_*: likewise; mh_rnea_parameters_state_vjp_* / mh_aba_parameters_state_vjp_* work in the same plan
+         {m->vjp_slots, std::min(8, m->n)},
          // mh_body_poses_* / mh_geometric_jacobian_*: pose and twist of every body per lane, up to one wave per target
          {(long)m->n * mh::KIN_SLOTS, MH_MAX_KINEMATIC_TARGETS}};
       for (const auto &plan : lane_plans)
@@ -3705,8 +3828,8 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
       // mh_aba_derivatives_*: the scratch of the forward form
       if (m->nv > 0 && deriv_scratch_bytes(m, max_batch, sizeof(double)) <= kDerivReserveCap)
          st = ensure_bytes(m->deriv, deriv_scratch_bytes(m, max_batch, sizeof(double)));
-      // mh_aba_vjp_* / mh_aba_integrate_vjp_*: qdd, w and H^-1 w, should the caller take neither qdd nor gtau (mh_aba_parameters_vjp_*: the
-      // first two of the three)
+      // mh_aba_vjp_* / mh_aba_integrate_vjp_*: qdd, w and H^-1 w, should the caller take neither qdd nor gtau (mh_aba_parameters_vjp_* /
+      // mh_aba_parameters_state_vjp_*: the first two of the three)
       if (st == MH_OK && m->nv > 0)
          st = ensure_bytes(m->vjp, vjp_scratch_bytes(m, max_batch, sizeof(double)));
       // mh_aba_integrate_derivatives_*: the two derivative matrices beside them, under the same cap
@@ -4644,6 +4767,30 @@ mh_status mh_aba_parameters_vjp_f32(mh_model_t model, int64_t B, const float *q,
                                     float *gtau_out, float *gpi_out)
 {
    return aba_parameters_vjp_impl<float>(model, B, q, qd, tau, pi, gravity, f_ext, w, opts, qdd_out, gtau_out, gpi_out);
+}
+mh_status mh_rnea_parameters_state_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double *pi,
+                                           const double gravity[3], const double *f_ext, const double *u, const mh_options *opts, double *gq_out,
+                                           double *gqd_out, double *gqdd_out, double *gpi_out)
+{
+   return rnea_parameters_state_vjp_impl<double>(model, B, q, qd, qdd, pi, gravity, f_ext, u, opts, gq_out, gqd_out, gqdd_out, gpi_out);
+}
+mh_status mh_rnea_parameters_state_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const float *pi,
+                                           const double gravity[3], const float *f_ext, const float *u, const mh_options *opts, float *gq_out,
+                                           float *gqd_out, float *gqdd_out, float *gpi_out)
+{
+   return rnea_parameters_state_vjp_impl<float>(model, B, q, qd, qdd, pi, gravity, f_ext, u, opts, gq_out, gqd_out, gqdd_out, gpi_out);
+}
+mh_status mh_aba_parameters_state_vjp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double *pi,
+                                          const double gravity[3], const double *f_ext, const double *w, const mh_options *opts, double *qdd_out,
+                                          double *gq_out, double *gqd_out, double *gtau_out, double *gpi_out)
+{
+   return aba_parameters_state_vjp_impl<double>(model, B, q, qd, tau, pi, gravity, f_ext, w, opts, qdd_out, gq_out, gqd_out, gtau_out, gpi_out);
+}
+mh_status mh_aba_parameters_state_vjp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const float *pi,
+                                          const double gravity[3], const float *f_ext, const float *w, const mh_options *opts, float *qdd_out,
+                                          float *gq_out, float *gqd_out, float *gtau_out, float *gpi_out)
+{
+   return aba_parameters_state_vjp_impl<float>(model, B, q, qd, tau, pi, gravity, f_ext, w, opts, qdd_out, gq_out, gqd_out, gtau_out, gpi_out);
 }
 mh_status mh_aba_parameters_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const float *pi,
                                 const double gravity[3], const float *f_ext, const mh_options *opts, float *qdd_out)

@@ -1219,6 +1219,55 @@ class HipModel:
             ptr(gtau), gpi.data_ptr()))
         return qdd, gtau, gpi
 
+    def rnea_parameters_state_vjp(self, q, qd, qdd, pi, u, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, consider_coriolis=True,
+                                  consider_accelerations=True, out=None):
+        """Reverse-mode gradients of ``rnea_parameters`` with respect to the state AND the inertial parameters, one O(n) launch: for a
+        cotangent ``u`` [B, nv] of the efforts, (gq, gqd, gqdd, gpi) -- what ``rnea_vjp`` gives, with the inertias of row r taken from
+        ``pi[r]`` (gqdd = H(pi) u), and what ``rnea_parameters_vjp`` gives, from one pair of sweeps.  Shapes, layouts, ``chart_pullback``
+        and the two switches as in those two.  ``out``: a (gq, gqd, gqdd, gpi) tuple to write into; any may be None (not computed), not all
+        four.  A model with acceleration-source joints is refused."""
+        given = [t for t in (q, qd if consider_coriolis else None, qdd if consider_accelerations else None, u) if t is not None]
+        B, dt, sfx, stream = self._device_inputs(given, layout)
+        if u is None or (consider_coriolis and qd is None) or (consider_accelerations and qdd is None):
+            raise _lib.MecanoHipError(1, "u is needed; qd / qdd may be None only with their switch off")
+        if f_ext is not None:
+            self._device_tensor(f_ext, dt)
+        self._check_f_ext(f_ext, B, layout)
+        vec = (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B)
+        gq, gqd, gqdd, gpi = self._outputs(out, (vec, vec, vec, self._parameter_tensor(pi, B, dt, layout)), ("gq", "gqd", "gqdd", "gpi"), dt, q.device)
+        if gq is None and gqd is None and gqdd is None and gpi is None:
+            raise _lib.MecanoHipError(1, "all four outputs are None")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, consider_coriolis, consider_accelerations, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_rnea_parameters_state_vjp_{sfx}")(
+            self._h, B, q.data_ptr(), ptr(qd) if consider_coriolis else None, ptr(qdd) if consider_accelerations else None, pi.data_ptr(), g,
+            ptr(f_ext), u.data_ptr(), ctypes.byref(opts), ptr(gq), ptr(gqd), ptr(gqdd), ptr(gpi)))
+        return gq, gqd, gqdd, gpi
+
+    def aba_parameters_state_vjp(self, q, qd, tau, pi, w, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Reverse-mode gradients of ``aba_parameters`` with respect to the state AND the inertial parameters: for a cotangent ``w``
+        [B, nv] of qdd = aba_parameters(q, qd, tau, pi), (qdd, gq, gqd, gtau, gpi) -- what ``aba_vjp`` gives at H(pi_r) and the inertias of
+        row r, and the gpi of ``aba_parameters_vjp``.  Two forward-dynamics launches and the kernel of ``rnea_parameters_state_vjp``.
+        ``out``: a (qdd, gq, gqd, gtau, gpi) tuple to write into; any may be None, not all four gradients.  A model with
+        acceleration-source joints is refused."""
+        B, dt, sfx, stream = self._device_inputs([q, qd, tau, w], layout)
+        if f_ext is not None:
+            self._device_tensor(f_ext, dt)
+        self._check_f_ext(f_ext, B, layout)
+        vec = (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B)
+        qdd, gq, gqd, gtau, gpi = self._outputs(out, (vec, vec, vec, vec, self._parameter_tensor(pi, B, dt, layout)),
+                                                ("qdd", "gq", "gqd", "gtau", "gpi"), dt, q.device)
+        if gq is None and gqd is None and gtau is None and gpi is None:
+            raise _lib.MecanoHipError(1, "all four gradients are None")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, True, True, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_aba_parameters_state_vjp_{sfx}")(
+            self._h, B, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), pi.data_ptr(), g, ptr(f_ext), w.data_ptr(), ctypes.byref(opts), ptr(qdd),
+            ptr(gq), ptr(gqd), ptr(gtau), ptr(gpi)))
+        return qdd, gq, gqd, gtau, gpi
+
     def regressor(self, q, qd, qdd, gravity=(0.0, 0.0, -9.81), layout=_lib.LAYOUT_AOS, consider_coriolis=True, consider_accelerations=True,
                   first_moment_columns=False):
         """Joint torque regressor (JointTorqueRegressorCalculator.compute, JointTorqueRegressorCalculator.java:173-190): Y [B, nv, 10 n_joints]
