@@ -536,6 +536,33 @@ mh::Args<T> make_args(const mh_model *m, int64_t B, const mh_options &o, const d
    A.coriolis = o.consider_coriolis, A.accel = o.consider_accelerations;
    return A;
 }
+// The set-up of a lane sweep whose bodies up to min(8, n) waves per group of configurations share: the launch shape, the workspace of
+// `slots` entries per lane on every such wave, and the kernel's common arguments with the workspace in them.
+template <typename T>
+struct LaneSweep
+{
+   Launch L;
+   int parts;
+   mh::Args<T> A;
+};
+template <typename T>
+mh_status plan_lane_sweep(mh_model *model, int64_t B, const mh_options &opts, const double *gravity, long slots, LaneSweep<T> &S)
+{
+   S.L = plan_launch(model->cu_count, B);
+   S.parts = launch_parts(model->cu_count, S.L, std::min(8, model->n));
+   if (const mh_status st = ensure_bytes(model->ws, lane_ws_bytes(slots, S.L, S.parts, sizeof(T))); st != MH_OK)
+      return st;
+   S.A = make_args<T>(model, B, opts, gravity);
+   S.A.ws = (T *)model->ws.ptr;
+   S.A.ws_stride = S.L.lanes;
+   return MH_OK;
+}
+// the DoF indices no joint owns (the last row of the gravity gradient's zero table): entries the kernels fill with zeros
+static void set_unowned(const mh_model *model, const int *&unowned, int &n_unowned)
+{
+   unowned = model->d_grav_zero_cols + model->grav_zero_ofs[model->n];
+   n_unowned = model->grav_zero_ofs[model->n + 1] - model->grav_zero_ofs[model->n];
+}
 
 // A code object's launcher returns 0 when it launched, hipErrorNotSupported when the plan is not in the object (the caller goes on to
 // its next plan) and anything else on failure.  True: the call is over, with status st.
@@ -1598,16 +1625,12 @@ mh_status regressor_impl(mh_model_t model, int64_t B, const T *q, const T *qd, c
       return MH_OK;
    if (!q || !qd || !qdd || !Y_out)
       return fail(MH_ERR_INVALID_ARGUMENT, "NULL state / output pointer");
-   const Launch L = plan_launch(model->cu_count, B);
-   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
-   st = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T)));
-   if (st != MH_OK)
+   LaneSweep<T> S;
+   if ((st = plan_lane_sweep<T>(model, B, opts, gravity, model->n_slots, S)) != MH_OK)
       return st;
    hipStream_t stream = (hipStream_t)opts.stream;
-   mh::Args<T> A = make_args<T>(model, B, opts, gravity);
+   mh::Args<T> &A = S.A;
    A.q = q, A.qd = qd, A.in3 = qdd, A.out = Y_out;
-   A.ws = (T *)model->ws.ptr;
-   A.ws_stride = L.lanes;
    const long ysize = (long)model->nv * model->n * 10;
    set_strides(A.f_bs, A.f_es, opts.layout == MH_LAYOUT_SOA, B, ysize); // strides of Y
    // entries of joints that do not support a body are zero, and so are the reference's centre-of-mass columns (mh_kernels.h)
@@ -1615,11 +1638,11 @@ mh_status regressor_impl(mh_model_t model, int64_t B, const T *q, const T *qd, c
    // the centre-of-mass columns: d tau / d (m c) on request; else the reference's -- zero, or e x a once the twist is switched off
    const int mode = first_moment_columns ? 1 : (opts.consider_coriolis ? 0 : 2);
    if (mode == 0)
-      hipLaunchKernelGGL((mh::regressor_kernel<T, 0>), dim3(L.grid, parts), dim3(L.block), 0, stream, A);
+      hipLaunchKernelGGL((mh::regressor_kernel<T, 0>), dim3(S.L.grid, S.parts), dim3(S.L.block), 0, stream, A);
    else if (mode == 1)
-      hipLaunchKernelGGL((mh::regressor_kernel<T, 1>), dim3(L.grid, parts), dim3(L.block), 0, stream, A);
+      hipLaunchKernelGGL((mh::regressor_kernel<T, 1>), dim3(S.L.grid, S.parts), dim3(S.L.block), 0, stream, A);
    else
-      hipLaunchKernelGGL((mh::regressor_kernel<T, 2>), dim3(L.grid, parts), dim3(L.block), 0, stream, A);
+      hipLaunchKernelGGL((mh::regressor_kernel<T, 2>), dim3(S.L.grid, S.parts), dim3(S.L.block), 0, stream, A);
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
@@ -2444,22 +2467,17 @@ mh_status rnea_derivatives_impl(mh_model_t model, int64_t B, const T *q, const T
       if ((st = check_aliasing("mh_rnea_derivatives", ins, 4, outs, 3)) != MH_OK)
          return st;
    }
-   const Launch L = plan_launch(model->cu_count, B);
-   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
-   st = ensure_bytes(model->ws, lane_ws_bytes(model->deriv_slots, L, parts, sizeof(T)));
-   if (st != MH_OK)
+   LaneSweep<T> S;
+   if ((st = plan_lane_sweep<T>(model, B, opts, gravity, model->deriv_slots, S)) != MH_OK)
       return st;
    mh::DerivArgs<T> G{};
-   mh::Args<T> &A = G.a;
-   A = make_args<T>(model, B, opts, gravity);
+   mh::Args<T> &A = G.a = S.A;
    A.q = q, A.qd = qd, A.in3 = qdd, A.fext = f_ext, A.out = tau_out;
-   A.ws = (T *)model->ws.ptr;
-   A.ws_stride = L.lanes;
    G.dq = dq_out, G.dqd = dqd_out;
    set_strides(G.g_bs, G.g_es, opts.layout == MH_LAYOUT_SOA, B, (long)model->nv * model->nv);
    G.slot = model->d_deriv_slot, G.slots = model->deriv_slots;
    G.zero_ofs = model->d_grav_zero_ofs, G.zero_cols = model->d_grav_zero_cols;
-   hipLaunchKernelGGL((mh::rnea_derivatives_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
+   hipLaunchKernelGGL((mh::rnea_derivatives_kernel<T>), dim3(S.L.grid, S.parts), dim3(S.L.block), 0, (hipStream_t)opts.stream, G);
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
@@ -2534,23 +2552,17 @@ template <typename T>
 mh_status rnea_vjp_launch(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const double *gravity, const T *f_ext, const T *u,
                           const mh_options &opts, bool negate, T *gq_out, T *gqd_out, T *gqdd_out, bool accumulate = false)
 {
-   const Launch L = plan_launch(model->cu_count, B);
-   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
-   mh_status st = ensure_bytes(model->ws, lane_ws_bytes(model->vjp_slots, L, parts, sizeof(T)));
-   if (st != MH_OK)
+   LaneSweep<T> S;
+   if (const mh_status st = plan_lane_sweep<T>(model, B, opts, gravity, model->vjp_slots, S); st != MH_OK)
       return st;
    mh::VjpArgs<T> G{};
-   mh::Args<T> &A = G.a;
-   A = make_args<T>(model, B, opts, gravity);
+   mh::Args<T> &A = G.a = S.A;
    A.q = q, A.qd = qd, A.in3 = qdd, A.fext = f_ext, A.out = nullptr;
-   A.ws = (T *)model->ws.ptr;
-   A.ws_stride = L.lanes;
    G.u = u, G.gq = gq_out, G.gqd = gqd_out, G.gqdd = gqdd_out;
    G.slot = model->d_vjp_slot, G.slots = model->vjp_slots;
    G.negate = negate, G.accumulate = accumulate;
-   G.unowned = model->d_grav_zero_cols + model->grav_zero_ofs[model->n];
-   G.n_unowned = model->grav_zero_ofs[model->n + 1] - model->grav_zero_ofs[model->n];
-   hipLaunchKernelGGL((mh::rnea_vjp_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
+   set_unowned(model, G.unowned, G.n_unowned);
+   hipLaunchKernelGGL((mh::rnea_vjp_kernel<T>), dim3(S.L.grid, S.parts), dim3(S.L.block), 0, (hipStream_t)opts.stream, G);
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
@@ -2582,10 +2594,85 @@ mh_status rnea_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, co
    }
    return rnea_vjp_launch<T>(model, B, q, qd, qdd, gravity, f_ext, u, opts, false, gq_out, gqd_out, gqdd_out);
 }
-// Reverse-mode gradients of the forward dynamics: three launches (and one memset) composed on the caller's stream -- forward dynamics
-// (whichever plan mh_aba_* takes) for qdd; forward dynamics again at rest, without root acceleration and wrenches, with tau = w, which is
-// mu = H^-1 w (its qd is the output itself, zeroed first: the in-place form of mh_aba_*, so the scratch stays at two vectors); the
-// kernel above at that qdd with u = mu, negated.  No matrix anywhere.
+// ---- The forward form, shared by mh_aba_vjp_*, mh_aba_parameters_vjp_*, mh_aba_parameters_state_vjp_* and mh_aba_integrate_vjp_*: with
+// tau = H qdd + b, the cotangent w of qdd gives gtau = mu = H^-1 w and the adjoint sweep of the inverse dynamics at (q, qd, qdd) with
+// u = mu, negated, gives the rest.  Every such call resolves qdd and mu, runs forward_form and then its own adjoint launch.
+//
+// the options of the inverse dynamics at the state forward dynamics saw (and of the per-row forms' forward dynamics): both switches on
+static mh_options both_switches_on(mh_options o)
+{
+   o.consider_coriolis = 1, o.consider_accelerations = 1;
+   return o;
+}
+// qdd and mu: the caller's outputs, or two vectors of the context's vjp scratch -- qdd at 0 and mu at B nv, whichever is missing
+template <typename T>
+mh_status forward_form_scratch(mh_model *model, int64_t B, T *qdd_out, T *gtau_out, T *&qdd, T *&mu)
+{
+   qdd = qdd_out, mu = gtau_out;
+   if (qdd && mu)
+      return MH_OK;
+   if (const mh_status st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T), 2)); st != MH_OK)
+      return st;
+   if (!qdd)
+      qdd = (T *)model->vjp.ptr;
+   if (!mu)
+      mu = (T *)model->vjp.ptr + (size_t)B * model->nv;
+   return MH_OK;
+}
+// ... for the step, whose w is scratch as well: w first, then qdd and mu where the caller takes neither, 1 + !qdd_out + !gtau_out vectors
+template <typename T>
+mh_status step_form_scratch(mh_model *model, int64_t B, T *qdd_out, T *gtau_out, T *&w, T *&qdd, T *&mu)
+{
+   if (const mh_status st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T), 1 + !qdd_out + !gtau_out)); st != MH_OK)
+      return st;
+   const size_t bn = (size_t)B * model->nv;
+   w = (T *)model->vjp.ptr;
+   qdd = qdd_out ? qdd_out : w + bn;
+   mu = gtau_out ? gtau_out : (qdd_out ? w + bn : w + 2 * bn);
+   return MH_OK;
+}
+// the forward dynamics of a call, as forward_form runs it: (qd, tau, gravity, f_ext, options, out) -> status, everything else bound.
+// Fixed parameters: whichever plan mh_aba_* takes.  (The per-row forms bind parameters_impl and pi.)
+template <typename T>
+auto fixed_forward_dynamics(mh_model_t model, int64_t B, const T *q)
+{
+   return [=](const T *qd, const T *tau, const double *gravity, const T *f_ext, const mh_options &o, T *out) {
+      return launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &o, out);
+   };
+}
+template <typename T>
+auto per_row_forward_dynamics(mh_model_t model, int64_t B, const T *q, const T *pi)
+{
+   return [=](const T *qd, const T *tau, const double *gravity, const T *f_ext, const mh_options &o, T *out) {
+      return parameters_impl<T>(ALGO_ABA, model, B, q, qd, tau, pi, gravity, f_ext, &o, out);
+   };
+}
+static mh_status nothing_between() { return MH_OK; }
+// The launches, composed on the caller's stream:
+//   fd(qd, tau, gravity, f_ext) -> qdd with the options `first` -- the caller's, or both_switches_on (the per-row forms) -- unless
+//                                  !run_first (only gtau is asked for, which needs no qdd);
+//   between()                      the step's integrator launch, which forms w from that qdd; nothing elsewhere;
+//   memset(mu), then fd IN PLACE at rest: qd = mu (zeroed first, so the scratch stays at two vectors), tau = w, out = mu, no gravity
+//                                  pointer, a zero root acceleration in `first`'s options and no wrenches: mu = H^-1 w.
+template <typename T, class FD, class Between>
+mh_status forward_form(mh_model *model, int64_t B, const T *qd, const T *tau, const double *gravity, const T *f_ext, const T *w, const mh_options &first,
+                       bool run_first, T *qdd, T *mu, FD fd, Between between)
+{
+   mh_status st;
+   if (run_first)
+      if ((st = fd(qd, tau, gravity, f_ext, first, qdd)) != MH_OK)
+         return st;
+   if ((st = between()) != MH_OK)
+      return st;
+   mh_options rest = first; // H^-1 w: nothing moves, nothing pulls
+   rest.use_root_acceleration = 1;
+   for (double &x : rest.root_acceleration)
+      x = 0.0;
+   HIP_TRY(hipMemsetAsync(mu, 0, (size_t)B * model->nv * sizeof(T), (hipStream_t)first.stream));
+   return fd(mu, w, nullptr, nullptr, rest, mu);
+}
+// Reverse-mode gradients of the forward dynamics: three launches (and one memset) on the caller's stream -- forward_form with the
+// fixed-parameter forward dynamics and the caller's options, then the kernel above at that qdd with u = mu, negated.  No matrix anywhere.
 template <typename T>
 mh_status aba_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const double *gravity, const T *f_ext, const T *w,
                        const mh_options *opts_in, T *qdd_out, T *gq_out, T *gqd_out, T *gtau_out)
@@ -2612,30 +2699,14 @@ mh_status aba_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, con
       if ((st = check_aliasing("mh_aba_vjp", ins, 5, outs, 4)) != MH_OK)
          return st;
    }
-   T *qdd = qdd_out, *mu = gtau_out;
-   if (!qdd || !mu)
-   {
-      if ((st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T), 2))) != MH_OK)
-         return st;
-      if (!qdd)
-         qdd = (T *)model->vjp.ptr;
-      if (!mu)
-         mu = (T *)model->vjp.ptr + (size_t)B * model->nv;
-   }
-   if (qdd_out || gq_out || gqd_out) // (gtau_out alone needs no qdd)
-      if ((st = launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &o, qdd)) != MH_OK)
-         return st;
-   mh_options rest = o; // H^-1 w: nothing moves, nothing pulls
-   rest.use_root_acceleration = 1;
-   for (double &x : rest.root_acceleration)
-      x = 0.0;
-   HIP_TRY(hipMemsetAsync(mu, 0, nvb, (hipStream_t)o.stream));
-   st = launch<T>(ALGO_ABA, model, B, q, mu, w, nullptr, nullptr, &rest, mu);
+   T *qdd, *mu;
+   if ((st = forward_form_scratch<T>(model, B, qdd_out, gtau_out, qdd, mu)) != MH_OK)
+      return st;
+   const bool need_qdd = qdd_out || gq_out || gqd_out; // (gtau_out alone needs no qdd)
+   st = forward_form<T>(model, B, qd, tau, gravity, f_ext, w, o, need_qdd, qdd, mu, fixed_forward_dynamics<T>(model, B, q), nothing_between);
    if (st != MH_OK || (!gq_out && !gqd_out))
       return st;
-   mh_options od = o; // the inverse dynamics at the state forward dynamics saw: both switches on
-   od.consider_coriolis = 1, od.consider_accelerations = 1;
-   return rnea_vjp_launch<T>(model, B, q, qd, qdd, gravity, f_ext, mu, od, true, gq_out, gqd_out, nullptr);
+   return rnea_vjp_launch<T>(model, B, q, qd, qdd, gravity, f_ext, mu, both_switches_on(o), true, gq_out, gqd_out, nullptr);
 }
 // Reverse-mode gradient of the inverse dynamics with respect to the per-configuration inertial parameters (mh_params_vjp_kernels.h): one
 // launch of a run-time-topology kernel in the model's own workspace plan, up to min(8, n) waves per group of configurations on small
@@ -2645,19 +2716,15 @@ template <typename T>
 mh_status parameters_vjp_launch(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const T *pi, const double *gravity, const T *u,
                                 const mh_options &opts, bool negate, T *gpi_out)
 {
-   const Launch L = plan_launch(model->cu_count, B);
-   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
-   mh_status st = ensure_bytes(model->ws, lane_ws_bytes(model->n_slots, L, parts, sizeof(T)));
+   LaneSweep<T> S;
+   mh_status st = plan_lane_sweep<T>(model, B, opts, gravity, model->n_slots, S);
    if (st != MH_OK)
       return st;
    hipStream_t stream = (hipStream_t)opts.stream;
    const bool soa = opts.layout == MH_LAYOUT_SOA;
    mh::ParamVjpArgs<T> G{};
-   mh::Args<T> &A = G.p.a;
-   A = make_args<T>(model, B, opts, gravity);
+   mh::Args<T> &A = G.p.a = S.A;
    A.q = q, A.qd = qd, A.in3 = qdd, A.fext = nullptr, A.out = nullptr;
-   A.ws = (T *)model->ws.ptr;
-   A.ws_stride = L.lanes;
    G.p.pi = pi, G.u = u, G.gpi = gpi_out, G.negate = negate;
    set_strides(G.p.p_bs, G.p.p_es, soa, B, (long)model->n * mh::PARAMS_PER_BODY);
    if (!soa && transposes(model, B))
@@ -2676,7 +2743,7 @@ mh_status parameters_vjp_launch(mh_model_t model, int64_t B, const T *q, const T
       A.q = t_q, A.qd = t_qd, A.in3 = t_qdd, G.u = t_u;
       A.q_bs = 1, A.q_es = B, A.v_bs = 1, A.v_es = B;
    }
-   hipLaunchKernelGGL((mh::rnea_parameters_vjp_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, stream, G);
+   hipLaunchKernelGGL((mh::rnea_parameters_vjp_kernel<T>), dim3(S.L.grid, S.parts), dim3(S.L.block), 0, stream, G);
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
@@ -2707,11 +2774,10 @@ mh_status rnea_parameters_vjp_impl(mh_model_t model, int64_t B, const T *q, cons
    }
    return parameters_vjp_launch<T>(model, B, q, qd, qdd, pi, gravity, u, opts, false, gpi_out);
 }
-// ... and of the forward dynamics: three launches (and one memset) composed on the caller's stream, as in aba_vjp_impl with the
-// per-configuration kernels -- aba_parameters_kernel for qdd; again at rest, without root acceleration and wrenches, with tau = w, which is
-// mu = H(pi)^-1 w (its qd is the output itself, zeroed first); the kernel above at that qdd with u = mu, negated.  External wrenches enter
-// the first launch only: tau is affine in them.  The scratch: qdd and mu where the caller takes neither (two of the three vectors
-// mh_reserve sets aside for the state gradients).
+// ... and of the forward dynamics: forward_form with the per-configuration forward dynamics (aba_parameters_kernel) and both switches
+// on, which never skips its first launch here (gpi needs qdd), then the kernel above at that qdd with u = mu = H(pi)^-1 w, negated.
+// External wrenches enter the first launch only: tau is affine in them.  The scratch: qdd and mu where the caller takes neither (two of
+// the three vectors mh_reserve sets aside for the state gradients).  Unlike its neighbours the call goes on at nv = 0.
 template <typename T>
 mh_status aba_parameters_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const T *pi, const double *gravity, const T *f_ext,
                                   const T *w, const mh_options *opts_in, T *qdd_out, T *gtau_out, T *gpi_out)
@@ -2739,28 +2805,13 @@ mh_status aba_parameters_vjp_impl(mh_model_t model, int64_t B, const T *q, const
       if ((st = check_aliasing("mh_aba_parameters_vjp", ins, 6, outs, 3)) != MH_OK)
          return st;
    }
+   const mh_options od = both_switches_on(o); // forward dynamics, and the inverse dynamics at the state it saw
    T *qdd = qdd_out, *mu = gtau_out;
-   if ((!qdd || !mu) && model->nv > 0)
+   if (model->nv > 0) // (a model without DoFs has parameters all the same: no forward dynamics, and the kernel below writes its zeros)
    {
-      if ((st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T), 2))) != MH_OK)
+      if ((st = forward_form_scratch<T>(model, B, qdd_out, gtau_out, qdd, mu)) != MH_OK)
          return st;
-      if (!qdd)
-         qdd = (T *)model->vjp.ptr;
-      if (!mu)
-         mu = (T *)model->vjp.ptr + (size_t)B * model->nv;
-   }
-   mh_options od = o; // forward dynamics, and the inverse dynamics at the state it saw: both switches on
-   od.consider_coriolis = 1, od.consider_accelerations = 1;
-   mh_options rest = od; // H^-1 w: nothing moves, nothing pulls
-   rest.use_root_acceleration = 1;
-   for (double &x : rest.root_acceleration)
-      x = 0.0;
-   if (model->nv > 0)
-   {
-      if ((st = parameters_impl<T>(ALGO_ABA, model, B, q, qd, tau, pi, gravity, f_ext, &od, qdd)) != MH_OK)
-         return st;
-      HIP_TRY(hipMemsetAsync(mu, 0, nvb, (hipStream_t)o.stream));
-      if ((st = parameters_impl<T>(ALGO_ABA, model, B, q, mu, w, pi, nullptr, nullptr, &rest, mu)) != MH_OK)
+      if ((st = forward_form<T>(model, B, qd, tau, gravity, f_ext, w, od, true, qdd, mu, per_row_forward_dynamics<T>(model, B, q, pi), nothing_between)) != MH_OK)
          return st;
    }
    return parameters_vjp_launch<T>(model, B, q, qd, qdd, pi, gravity, mu, od, true, gpi_out);
@@ -2774,24 +2825,18 @@ template <typename T>
 mh_status parameters_state_vjp_launch(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const T *pi, const double *gravity,
                                       const T *f_ext, const T *u, const mh_options &opts, bool negate, T *gq_out, T *gqd_out, T *gqdd_out, T *gpi_out)
 {
-   const Launch L = plan_launch(model->cu_count, B);
-   const int parts = launch_parts(model->cu_count, L, std::min(8, model->n));
-   mh_status st = ensure_bytes(model->ws, lane_ws_bytes(model->vjp_slots, L, parts, sizeof(T)));
-   if (st != MH_OK)
+   LaneSweep<T> S;
+   if (const mh_status st = plan_lane_sweep<T>(model, B, opts, gravity, model->vjp_slots, S); st != MH_OK)
       return st;
    mh::ParamStateVjpArgs<T> G{};
-   mh::Args<T> &A = G.pv.p.a;
-   A = make_args<T>(model, B, opts, gravity);
+   mh::Args<T> &A = G.pv.p.a = S.A;
    A.q = q, A.qd = qd, A.in3 = qdd, A.fext = f_ext, A.out = nullptr;
-   A.ws = (T *)model->ws.ptr;
-   A.ws_stride = L.lanes;
    G.pv.p.pi = pi, G.pv.u = u, G.pv.gpi = gpi_out, G.pv.negate = negate;
    set_strides(G.pv.p.p_bs, G.pv.p.p_es, opts.layout == MH_LAYOUT_SOA, B, (long)model->n * mh::PARAMS_PER_BODY);
    G.gq = gq_out, G.gqd = gqd_out, G.gqdd = gqdd_out;
    G.slot = model->d_vjp_slot, G.slots = model->vjp_slots;
-   G.unowned = model->d_grav_zero_cols + model->grav_zero_ofs[model->n];
-   G.n_unowned = model->grav_zero_ofs[model->n + 1] - model->grav_zero_ofs[model->n];
-   hipLaunchKernelGGL((mh::rnea_parameters_state_vjp_kernel<T>), dim3(L.grid, parts), dim3(L.block), 0, (hipStream_t)opts.stream, G);
+   set_unowned(model, G.unowned, G.n_unowned);
+   hipLaunchKernelGGL((mh::rnea_parameters_state_vjp_kernel<T>), dim3(S.L.grid, S.parts), dim3(S.L.block), 0, (hipStream_t)opts.stream, G);
    HIP_TRY(hipGetLastError());
    return MH_OK;
 }
@@ -2826,10 +2871,9 @@ mh_status rnea_parameters_state_vjp_impl(mh_model_t model, int64_t B, const T *q
    }
    return parameters_state_vjp_launch<T>(model, B, q, qd, qdd, pi, gravity, f_ext, u, opts, false, gq_out, gqd_out, gqdd_out, gpi_out);
 }
-// ... and of the forward dynamics: three launches (and one memset) composed on the caller's stream, exactly as in
-// aba_parameters_vjp_impl -- aba_parameters_kernel for qdd; again at rest, without root acceleration and wrenches, with tau = w, which is
-// mu = H(pi)^-1 w = gtau (its qd is the output itself, zeroed first); the kernel above at that qdd with u = mu, negated, which gives gq,
-// gqd and gpi together.  The scratch: qdd and mu where the caller takes neither (two of the three vectors mh_reserve sets aside).
+// ... and of the forward dynamics: forward_form with the per-configuration forward dynamics and both switches on, as in
+// aba_parameters_vjp_impl, then the kernel above at that qdd with u = mu = H(pi)^-1 w = gtau, negated, which gives gq, gqd and gpi
+// together.  The scratch: qdd and mu where the caller takes neither (two of the three vectors mh_reserve sets aside).
 template <typename T>
 mh_status aba_parameters_state_vjp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const T *pi, const double *gravity,
                                         const T *f_ext, const T *w, const mh_options *opts_in, T *qdd_out, T *gq_out, T *gqd_out, T *gtau_out,
@@ -2861,27 +2905,12 @@ mh_status aba_parameters_state_vjp_impl(mh_model_t model, int64_t B, const T *q,
       if ((st = check_aliasing("mh_aba_parameters_state_vjp", ins, 6, outs, 5)) != MH_OK)
          return st;
    }
-   T *qdd = qdd_out, *mu = gtau_out;
-   if (!qdd || !mu)
-   {
-      if ((st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T), 2))) != MH_OK)
-         return st;
-      if (!qdd)
-         qdd = (T *)model->vjp.ptr;
-      if (!mu)
-         mu = (T *)model->vjp.ptr + (size_t)B * model->nv;
-   }
-   mh_options od = o; // forward dynamics, and the inverse dynamics at the state it saw: both switches on
-   od.consider_coriolis = 1, od.consider_accelerations = 1;
-   mh_options rest = od; // H^-1 w: nothing moves, nothing pulls
-   rest.use_root_acceleration = 1;
-   for (double &x : rest.root_acceleration)
-      x = 0.0;
-   if (qdd_out || gq_out || gqd_out || gpi_out) // (gtau_out alone needs no qdd)
-      if ((st = parameters_impl<T>(ALGO_ABA, model, B, q, qd, tau, pi, gravity, f_ext, &od, qdd)) != MH_OK)
-         return st;
-   HIP_TRY(hipMemsetAsync(mu, 0, nvb, (hipStream_t)o.stream));
-   st = parameters_impl<T>(ALGO_ABA, model, B, q, mu, w, pi, nullptr, nullptr, &rest, mu);
+   T *qdd, *mu;
+   if ((st = forward_form_scratch<T>(model, B, qdd_out, gtau_out, qdd, mu)) != MH_OK)
+      return st;
+   const mh_options od = both_switches_on(o); // forward dynamics, and the inverse dynamics at the state it saw
+   const bool need_qdd = qdd_out || gq_out || gqd_out || gpi_out; // (gtau_out alone needs no qdd)
+   st = forward_form<T>(model, B, qd, tau, gravity, f_ext, w, od, need_qdd, qdd, mu, per_row_forward_dynamics<T>(model, B, q, pi), nothing_between);
    if (st != MH_OK || (!gq_out && !gqd_out && !gpi_out))
       return st;
    return parameters_state_vjp_launch<T>(model, B, q, qd, qdd, pi, gravity, f_ext, mu, od, true, gq_out, gqd_out, nullptr, gpi_out);
@@ -2941,8 +2970,7 @@ mh::ChartArgs<T> chart_args(const mh_model *model, int64_t B, const mh_options &
    A.soa = opts.layout == MH_LAYOUT_SOA;
    set_strides(A.q_bs, A.q_es, A.soa, B, model->nq);
    set_strides(A.v_bs, A.v_es, A.soa, B, model->nv);
-   A.unowned = model->d_grav_zero_cols + model->grav_zero_ofs[model->n];
-   A.n_unowned = model->grav_zero_ofs[model->n + 1] - model->grav_zero_ofs[model->n];
+   set_unowned(model, A.unowned, A.n_unowned);
    return A;
 }
 static int chart_grid(const mh_model *model, int64_t B)
@@ -3045,8 +3073,7 @@ mh_status step_derivatives_impl(mh_model_t model, int64_t B, const double &dt, c
    S.qd = qd, S.qdd = qdd_out ? qdd_out : (T *)model->deriv.ptr + (size_t)B * nv * nv;
    S.Dq = Dq, S.Dv = Dv, S.Hinv = (const T *)model->deriv.ptr;
    S.A = A_out, S.Bm = B_out;
-   S.unowned = model->d_grav_zero_cols + model->grav_zero_ofs[model->n];
-   S.n_unowned = model->grav_zero_ofs[model->n + 1] - model->grav_zero_ofs[model->n];
+   set_unowned(model, S.unowned, S.n_unowned);
    set_strides(S.v_bs, S.v_es, soa, B, (long)nv);
    set_strides(S.d_bs, S.d_es, soa, B, (long)(nv * nv));
    set_strides(S.a_bs, S.a_es, soa, B, (long)(4 * nv * nv));
@@ -3077,8 +3104,7 @@ mh_status integrate_vjp_launch(mh_model_t model, int64_t B, double dt, const T *
    A.B = B, A.dt = (T)dt;
    A.qd = qd, A.qdd = qdd, A.gqn = gq_next, A.gqdn = gqd_next;
    A.gq = gq_out, A.gqd = gqd_out, A.gqdd = gqdd_out;
-   A.unowned = model->d_grav_zero_cols + model->grav_zero_ofs[model->n];
-   A.n_unowned = model->grav_zero_ofs[model->n + 1] - model->grav_zero_ofs[model->n];
+   set_unowned(model, A.unowned, A.n_unowned);
    const bool soa = opts.layout == MH_LAYOUT_SOA;
    set_strides(A.v_bs, A.v_es, soa, B, model->nv);
    const int block = 256;
@@ -3125,9 +3151,9 @@ mh_status integrate_vjp_impl(mh_model_t model, int64_t B, double dt, const T *qd
    return integrate_vjp_launch<T>(model, B, dt, qd, qdd, gq_next, gqd_next, opts, gq_out, gqd_out, gqdd_out);
 }
 // Reverse mode of the step x' = integrate(q, qd, aba(q, qd, tau)): four launches (and one memset) composed on the caller's stream --
-// forward dynamics for qdd; the kernel above, which writes the integrator's own share of gq and gqd into the outputs and
-// w = the cotangent of qdd into scratch; forward dynamics at rest with tau = w, which is mu = H^-1 w = gtau (as in aba_vjp_impl); the
-// adjoint sweep at that qdd with u = mu, negated, ADDING its gq and gqd to what the outputs hold (VjpArgs::accumulate).
+// forward_form as in aba_vjp_impl, with the kernel above between its two launches, which writes the integrator's own share of gq and
+// gqd into the outputs and w = the cotangent of qdd into scratch; then the adjoint sweep at that qdd with u = mu = H^-1 w = gtau,
+// negated, ADDING its gq and gqd to what the outputs hold (VjpArgs::accumulate).
 template <typename T>
 mh_status step_vjp_impl(mh_model_t model, int64_t B, double dt, const T *q, const T *qd, const T *tau, const double *gravity, const T *f_ext,
                         const T *gq_next, const T *gqd_next, const mh_options *opts_in, T *qdd_out, T *gq_out, T *gqd_out, T *gtau_out)
@@ -3158,32 +3184,15 @@ mh_status step_vjp_impl(mh_model_t model, int64_t B, double dt, const T *q, cons
       if ((st = check_aliasing("mh_aba_integrate_vjp", ins, 6, outs, 4)) != MH_OK)
          return st;
    }
-   // scratch: w always, qdd and mu where the caller takes neither
-   if ((st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T), 1 + !qdd_out + !gtau_out))) != MH_OK)
+   T *w, *qdd, *mu;
+   if ((st = step_form_scratch<T>(model, B, qdd_out, gtau_out, w, qdd, mu)) != MH_OK)
       return st;
-   const size_t bn = (size_t)B * model->nv;
-   T *next = (T *)model->vjp.ptr;
-   T *const w = next;
-   next += bn;
-   T *const qdd = qdd_out ? qdd_out : next;
-   if (!qdd_out)
-      next += bn;
-   T *const mu = gtau_out ? gtau_out : next;
-   if ((st = launch<T>(ALGO_ABA, model, B, q, qd, tau, gravity, f_ext, &o, qdd)) != MH_OK) // (w needs qdd wherever dt != 0)
-      return st;
-   if ((st = integrate_vjp_launch<T>(model, B, dt, qd, qdd, gq_next, gqd_next, o, gq_out, gqd_out, w)) != MH_OK)
-      return st;
-   mh_options rest = o; // H^-1 w: nothing moves, nothing pulls
-   rest.use_root_acceleration = 1;
-   for (double &x : rest.root_acceleration)
-      x = 0.0;
-   HIP_TRY(hipMemsetAsync(mu, 0, nvb, (hipStream_t)o.stream));
-   st = launch<T>(ALGO_ABA, model, B, q, mu, w, nullptr, nullptr, &rest, mu);
+   // the first launch always runs (w needs qdd wherever dt != 0); the integrator's own launch sits between the two
+   const auto integrator = [&] { return integrate_vjp_launch<T>(model, B, dt, qd, qdd, gq_next, gqd_next, o, gq_out, gqd_out, w); };
+   st = forward_form<T>(model, B, qd, tau, gravity, f_ext, (const T *)w, o, true, qdd, mu, fixed_forward_dynamics<T>(model, B, q), integrator);
    if (st != MH_OK || (!gq_out && !gqd_out))
       return st;
-   mh_options od = o; // the inverse dynamics at the state forward dynamics saw: both switches on
-   od.consider_coriolis = 1, od.consider_accelerations = 1;
-   return rnea_vjp_launch<T>(model, B, q, qd, qdd, gravity, f_ext, mu, od, true, gq_out, gqd_out, nullptr, true);
+   return rnea_vjp_launch<T>(model, B, q, qd, qdd, gravity, f_ext, mu, both_switches_on(o), true, gq_out, gqd_out, nullptr, true);
 }
 } // namespace
 

@@ -63,10 +63,22 @@ MH_DEV void wave_lds_fence()
    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 }
 
-// the ten numbers of body `ext` (mh_model_desc order) of this lane's configuration.  first = configuration of the wave's lane 0, cfg =
-// this lane's; every lane of the wave that is still in the loop over the batch calls this together.
+// The lane index for load_parameters / store_parameters, formed anew at every call.  With threadIdx.x & 63 passed in, the ten (row, number)
+// pairs of a lane and the addresses made of them do not depend on the body, so the compiler keeps them in registers across the sweeps:
+// about 50 in rnea_parameters_state_vjp_kernel, which has none to spare (fp32: 266 registers and one wave per SIMD with them, against 211
+// and two for rnea_vjp_kernel).  An empty asm on the lane index makes them a dozen integer operations per body instead.
+MH_DEV int staging_lane()
+{
+   int l = threadIdx.x & 63;
+   asm volatile("" : "+v"(l));
+   return l;
+}
+
+// the ten numbers of body `ext` (mh_model_desc order) of this lane's configuration.  l = the lane's index in its wave (threadIdx.x & 63,
+// or staging_lane()), first = configuration of the wave's lane 0, cfg = this lane's; every lane of the wave that is still in the loop
+// over the batch calls this together.
 template <typename T>
-MH_DEV void load_parameters(const ParamArgs<T> &G, T *stage, long first, long cfg, int ext, T (&p)[PARAMS_PER_BODY])
+MH_DEV void load_parameters(const ParamArgs<T> &G, T *stage, int l, long first, long cfg, int ext, T (&p)[PARAMS_PER_BODY])
 {
    if (G.p_es != 1)
    { // lanes are neighbours in memory
@@ -76,7 +88,6 @@ MH_DEV void load_parameters(const ParamArgs<T> &G, T *stage, long first, long cf
          p[k] = row[k * G.p_es];
       return;
    }
-   const int l = threadIdx.x & 63;
    const long left = G.a.B - first;
    const int rows = left < 64 ? (int)left : 64; // lanes 0 .. rows - 1 are in the loop, the others have left it
    wave_lds_fence(); // every lane has taken the previous body's numbers
@@ -125,7 +136,7 @@ __global__ void __launch_bounds__(256) rnea_parameters_kernel(ParamArgs<T> G)
          const int parent = mi[MI_PARENT], type = mi[MI_TYPE], flags = mi[MI_FLAGS];
          const CRef<T> c{CB + j * MC_STRIDE};
          T par[PARAMS_PER_BODY];
-         load_parameters(G, stage, first, cfg, mi[MI_EXT], par);
+         load_parameters(G, stage, threadIdx.x & 63, first, cfg, mi[MI_EXT], par);
          SV<T> vp, ap;
          if (parent < 0)
          {
@@ -239,7 +250,7 @@ __global__ void __launch_bounds__(256) aba_parameters_kernel(ParamArgs<T> G)
          const int parent = mi[MI_PARENT], type_rt = mi[MI_TYPE], flags = mi[MI_FLAGS];
          const CRef<T> c{CB + j * MC_STRIDE};
          T par[PARAMS_PER_BODY];
-         load_parameters(G, stage, first, cfg, mi[MI_EXT], par);
+         load_parameters(G, stage, threadIdx.x & 63, first, cfg, mi[MI_EXT], par);
          auto body = [&](auto kind) { // one dispatch on the joint kind per body, straight-line code per kind (as in aba_kernel)
             const int type = kind;
             SV<T> vp;
@@ -297,7 +308,7 @@ __global__ void __launch_bounds__(256) aba_parameters_kernel(ParamArgs<T> G)
          const int parent = mi[MI_PARENT], type_rt = mi[MI_TYPE], flags = mi[MI_FLAGS];
          const CRef<T> c{CB + j * MC_STRIDE};
          T par[PARAMS_PER_BODY];
-         load_parameters(G, stage, first, cfg, mi[MI_EXT], par);
+         load_parameters(G, stage, threadIdx.x & 63, first, cfg, mi[MI_EXT], par);
          auto body = [&](auto kind) {
             const int type = kind;
             ABI<T> IA = abi_from_rigid(inertia_from_parameters<T>(c, par));

@@ -8,7 +8,11 @@
 // (mh_params_vjp_kernels.h): the two pairings nu . (I a) + y . (I v) in the body-fixed frame and the chain to (m, c, J).  That kernel
 // runs an outward sweep of its own only to have (nu, v, a) of a body in registers; the outward sweep of the state gradients has all
 // three, so the ten derivatives are formed there, after the body's force and motions are parked -- nothing of them is live while the
-// block is formed and leaves.
+// block is formed and leaves.  The block (parameter_gradient) and the staged read and store of the ten numbers (load_parameters,
+// store_parameters, here with staging_lane() for the lane index) are the functions of mh_params_vjp_kernels.h and mh_params_kernels.h.
+// The two sweeps are a COPY of rnea_vjp_kernel's, kept in step by hand: written once as function templates over the inertia's source
+// they compiled to other register counts and, by other fused multiply-adds, to other last bits -- a change to
+// a sweep there is made here too.
 //
 // The inertia is needed in both sweeps (I a + v x* I v going out, Ic and the factorised inertia coming in).  It is formed twice from pi,
 // as aba_parameters_kernel forms it, and not parked: parking costs ten stores and ten loads per body and a slot plan of its own; reading
@@ -36,70 +40,6 @@ struct ParamStateVjpArgs
    const int *unowned;  // DoF indices no joint owns: zeros
    int n_unowned;
 };
-
-// load_parameters / store_parameters with the lane's staging indices formed anew at every call.  In those two the ten (row, number)
-// pairs of a lane and the addresses made of them do not depend on the body, so the compiler keeps them in registers across both sweeps:
-// about 50 in this kernel, which has none to spare (fp32: 266 registers and one wave per SIMD with them, against 211 and two for
-// rnea_vjp_kernel).  An empty asm on the lane index makes them a dozen integer operations per body instead.
-MH_DEV int staging_lane()
-{
-   int l = threadIdx.x & 63;
-   asm volatile("" : "+v"(l));
-   return l;
-}
-template <typename T>
-MH_DEV void load_parameters_fresh(const ParamArgs<T> &G, T *stage, long first, long cfg, int ext, T (&p)[PARAMS_PER_BODY])
-{
-   if (G.p_es != 1)
-   { // lanes are neighbours in memory
-      const T *row = G.pi + cfg * G.p_bs + (long)ext * PARAMS_PER_BODY * G.p_es;
-#pragma unroll
-      for (int k = 0; k < PARAMS_PER_BODY; k++)
-         p[k] = row[k * G.p_es];
-      return;
-   }
-   const int l = staging_lane();
-   const long left = G.a.B - first;
-   const int rows = left < 64 ? (int)left : 64; // lanes 0 .. rows - 1 are in the loop, the others have left it
-   wave_lds_fence(); // every lane has taken what was staged before
-#pragma unroll
-   for (int i = 0; i < PARAMS_PER_BODY; i++)
-   {
-      const int idx = l + rows * i, r = idx / PARAMS_PER_BODY, k = idx - PARAMS_PER_BODY * r;
-      stage[k * PARAMS_STAGE_PITCH + r] = G.pi[(first + r) * G.p_bs + (long)ext * PARAMS_PER_BODY + k];
-   }
-   wave_lds_fence();
-#pragma unroll
-   for (int k = 0; k < PARAMS_PER_BODY; k++)
-      p[k] = stage[k * PARAMS_STAGE_PITCH + l];
-}
-template <typename T>
-MH_DEV void store_parameters_fresh(const ParamVjpArgs<T> &G, T *stage, long first, long cfg, int ext, const T (&g)[PARAMS_PER_BODY])
-{
-   const long p_bs = G.p.p_bs, p_es = G.p.p_es;
-   if (p_es != 1)
-   { // lanes are neighbours in memory
-      T *row = G.gpi + cfg * p_bs + (long)ext * PARAMS_PER_BODY * p_es;
-#pragma unroll
-      for (int k = 0; k < PARAMS_PER_BODY; k++)
-         row[k * p_es] = g[k];
-      return;
-   }
-   const int l = staging_lane();
-   const long left = G.p.a.B - first;
-   const int rows = left < 64 ? (int)left : 64;
-   wave_lds_fence(); // every lane has taken what was staged before
-#pragma unroll
-   for (int k = 0; k < PARAMS_PER_BODY; k++)
-      stage[k * PARAMS_STAGE_PITCH + l] = g[k];
-   wave_lds_fence();
-#pragma unroll
-   for (int i = 0; i < PARAMS_PER_BODY; i++)
-   {
-      const int idx = l + rows * i, r = idx / PARAMS_PER_BODY, k = idx - PARAMS_PER_BODY * r;
-      G.gpi[(first + r) * p_bs + (long)ext * PARAMS_PER_BODY + k] = stage[k * PARAMS_STAGE_PITCH + r];
-   }
-}
 
 template <typename T>
 __global__ void __launch_bounds__(256) rnea_parameters_state_vjp_kernel(ParamStateVjpArgs<T> G)
@@ -166,7 +106,7 @@ __global__ void __launch_bounds__(256) rnea_parameters_state_vjp_kernel(ParamSta
          const SV<T> nu = nul + Su;
          // (read here and not at the top of the body: the ten numbers are not live across the kinematics)
          T par[PARAMS_PER_BODY];
-         load_parameters_fresh(G.pv.p, stage, first, cfg, mi[MI_EXT], par);
+         load_parameters(G.pv.p, stage, staging_lane(), first, cfg, mi[MI_EXT], par);
          if (with_state)
          {
             const RI<T> I = inertia_from_parameters<T>(c, par);
@@ -194,26 +134,13 @@ __global__ void __launch_bounds__(256) rnea_parameters_state_vjp_kernel(ParamSta
             ws_store6(ws, ws_stride, s + VS_T5, Z6);
          }
          v_prev = v, a_prev = a, nu_prev = nu;
-         // ---- the parameter block of this body (rnea_parameters_vjp_kernel's, statement for statement); store_parameters is wave-wide
-         //      like load_parameters, and the condition is the wave's
+         // ---- the parameter block of this body (parameter_gradient of mh_params_vjp_kernels.h, as in rnea_parameters_vjp_kernel);
+         //      store_parameters is wave-wide like load_parameters, and the condition is the wave's
          if (with_gpi && j % parts == part)
          {
-            XF<T> Xf;
-            Xf.R = M3<T>{c[MC_RF + 0], c[MC_RF + 1], c[MC_RF + 2], c[MC_RF + 3], c[MC_RF + 4], c[MC_RF + 5], c[MC_RF + 6], c[MC_RF + 7], c[MC_RF + 8]};
-            Xf.p = V3<T>{c[MC_PF + 0], c[MC_PF + 1], c[MC_PF + 2]};
-            const SV<T> nb = motion_to_child(Xf, nu), vb = motion_to_child(Xf, v), ab = motion_to_child(Xf, a);
-            const SV<T> y = crm(nb, vb); // = -(v xm nu)
-            T gh[PARAMS_PER_BODY] = {T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0)};
-            pairing_gradient(nb, ab, gh);
-            pairing_gradient(y, vb, gh);
             T g[PARAMS_PER_BODY];
-            g[0] = sign * (gh[0] + (par[1] * gh[1] + par[2] * gh[2] + par[3] * gh[3]));
-            const T sm = sign * par[0];
-            g[1] = sm * gh[1], g[2] = sm * gh[2], g[3] = sm * gh[3];
-#pragma unroll
-            for (int k = 4; k < PARAMS_PER_BODY; k++)
-               g[k] = sign * gh[k];
-            store_parameters_fresh(G.pv, stage, first, cfg, mi[MI_EXT], g);
+            parameter_gradient<T>(c, nu, v, a, par, sign, g);
+            store_parameters(G.pv, stage, staging_lane(), first, cfg, mi[MI_EXT], g);
          }
       }
       if (!with_state) // (wave-uniform: the inward sweep has nothing to store)
@@ -229,7 +156,7 @@ __global__ void __launch_bounds__(256) rnea_parameters_state_vjp_kernel(ParamSta
          const CRef<T> c{CB + j * MC_STRIDE};
          const int s = slot[j];
          T par[PARAMS_PER_BODY];
-         load_parameters_fresh(G.pv.p, stage, first, cfg, mi[MI_EXT], par);
+         load_parameters(G.pv.p, stage, staging_lane(), first, cfg, mi[MI_EXT], par);
          const SV<T> vj = ws_load6(ws, ws_stride, s + VS_V);
          RI<T> Ic = inertia_from_parameters<T>(c, par);
          FB<T> Bc = fb_from_rigid(Ic, vj);

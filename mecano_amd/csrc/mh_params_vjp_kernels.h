@@ -22,6 +22,9 @@
 //
 // gridDim.y waves may share a group of 64 configurations (small batches), as in rnea_vjp_kernel: each runs the sweep -- there is nothing
 // else to run -- and forms and stores the blocks of every gridDim.y-th body.
+//
+// The block of a body (parameter_gradient) and its way out (store_parameters) are also what rnea_parameters_state_vjp_kernel
+// (mh_params_state_vjp_kernels.h) calls from the outward sweep of the state gradients.
 #pragma once
 #include "mh_params_kernels.h"
 
@@ -36,10 +39,10 @@ struct ParamVjpArgs
    int negate;     // store -gpi (the forward form: u = H^-1 w)
 };
 
-// the ten numbers g of body `ext` of this lane's configuration into gpi: load_parameters run backwards.  Every lane of the wave that is
-// still in the loop over the batch calls this together.
+// the ten numbers g of body `ext` of this lane's configuration into gpi: load_parameters run backwards, with its lane index l.  Every lane
+// of the wave that is still in the loop over the batch calls this together.
 template <typename T>
-MH_DEV void store_parameters(const ParamVjpArgs<T> &G, T *stage, long first, long cfg, int ext, const T (&g)[PARAMS_PER_BODY])
+MH_DEV void store_parameters(const ParamVjpArgs<T> &G, T *stage, int l, long first, long cfg, int ext, const T (&g)[PARAMS_PER_BODY])
 {
    const long p_bs = G.p.p_bs, p_es = G.p.p_es;
    if (p_es != 1)
@@ -50,7 +53,6 @@ MH_DEV void store_parameters(const ParamVjpArgs<T> &G, T *stage, long first, lon
          row[k * p_es] = g[k];
       return;
    }
-   const int l = threadIdx.x & 63;
    const long left = G.p.a.B - first;
    const int rows = left < 64 ? (int)left : 64; // lanes 0 .. rows - 1 are in the loop, the others have left it
    wave_lds_fence(); // every lane has taken what was staged before
@@ -79,6 +81,28 @@ MH_DEV void pairing_gradient(const SV<T> &y, const SV<T> &x, T (&g)[PARAMS_PER_B
    g[7] += y.a.y * x.a.y;
    g[8] += y.a.y * x.a.z + y.a.z * x.a.y;
    g[9] += y.a.z * x.a.z;
+}
+
+// the parameter block of a body: g = sign * d (nu . f) / d (m, c, J) from the body's (nu, v, a) in its canonical frame, its constants c
+// (MC_RF, MC_PF) and its ten numbers par.  rnea_parameters_vjp_kernel and rnea_parameters_state_vjp_kernel both form it here.
+template <typename T, class CR>
+MH_DEV void parameter_gradient(const CR &c, const SV<T> &nu, const SV<T> &v, const SV<T> &a, const T (&par)[PARAMS_PER_BODY], T sign,
+                               T (&g)[PARAMS_PER_BODY])
+{
+   XF<T> Xf;
+   Xf.R = M3<T>{c[MC_RF + 0], c[MC_RF + 1], c[MC_RF + 2], c[MC_RF + 3], c[MC_RF + 4], c[MC_RF + 5], c[MC_RF + 6], c[MC_RF + 7], c[MC_RF + 8]};
+   Xf.p = V3<T>{c[MC_PF + 0], c[MC_PF + 1], c[MC_PF + 2]};
+   const SV<T> nb = motion_to_child(Xf, nu), vb = motion_to_child(Xf, v), ab = motion_to_child(Xf, a);
+   const SV<T> y = crm(nb, vb); // = -(v xm nu)
+   T gh[PARAMS_PER_BODY] = {T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0)};
+   pairing_gradient(nb, ab, gh);
+   pairing_gradient(y, vb, gh);
+   g[0] = sign * (gh[0] + (par[1] * gh[1] + par[2] * gh[2] + par[3] * gh[3]));
+   const T sm = sign * par[0];
+   g[1] = sm * gh[1], g[2] = sm * gh[2], g[3] = sm * gh[3];
+#pragma unroll
+   for (int k = 4; k < PARAMS_PER_BODY; k++)
+      g[k] = sign * gh[k];
 }
 
 template <typename T>
@@ -145,24 +169,10 @@ __global__ void __launch_bounds__(256) rnea_parameters_vjp_kernel(ParamVjpArgs<T
          if (j % parts != part)
             continue;
          // ---- the block of this body
-         XF<T> Xf;
-         Xf.R = M3<T>{c[MC_RF + 0], c[MC_RF + 1], c[MC_RF + 2], c[MC_RF + 3], c[MC_RF + 4], c[MC_RF + 5], c[MC_RF + 6], c[MC_RF + 7], c[MC_RF + 8]};
-         Xf.p = V3<T>{c[MC_PF + 0], c[MC_PF + 1], c[MC_PF + 2]};
-         const SV<T> nb = motion_to_child(Xf, nu), vb = motion_to_child(Xf, v), ab = motion_to_child(Xf, a);
-         const SV<T> y = crm(nb, vb); // = -(v xm nu)
-         T gh[PARAMS_PER_BODY] = {T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0), T(0)};
-         pairing_gradient(nb, ab, gh);
-         pairing_gradient(y, vb, gh);
-         T par[PARAMS_PER_BODY];
-         load_parameters(G.p, stage, first, cfg, mi[MI_EXT], par);
-         T g[PARAMS_PER_BODY];
-         g[0] = sign * (gh[0] + (par[1] * gh[1] + par[2] * gh[2] + par[3] * gh[3]));
-         const T sm = sign * par[0];
-         g[1] = sm * gh[1], g[2] = sm * gh[2], g[3] = sm * gh[3];
-#pragma unroll
-         for (int k = 4; k < PARAMS_PER_BODY; k++)
-            g[k] = sign * gh[k];
-         store_parameters(G, stage, first, cfg, mi[MI_EXT], g);
+         T par[PARAMS_PER_BODY], g[PARAMS_PER_BODY];
+         load_parameters(G.p, stage, threadIdx.x & 63, first, cfg, mi[MI_EXT], par);
+         parameter_gradient<T>(c, nu, v, a, par, sign, g);
+         store_parameters(G, stage, threadIdx.x & 63, first, cfg, mi[MI_EXT], g);
       }
    }
 }

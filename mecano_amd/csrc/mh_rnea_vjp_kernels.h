@@ -24,6 +24,8 @@
 //   gq [jk] = s . (X5 - vl x* (X4 - vl x* X1) - al x* X1),   gqd[jk] = s . (X4 - (vl + v) x* X1),   gqdd[jk] = s . X1
 // Two sweeps, O(n), no loop over DoF pairs; every output entry is written once, by the wave that owns the body (j % parts == part), no
 // atomics.  u = 0 gives exact zeros, qd = 0 (consider_coriolis = 0) exact zeros in gqd.
+// rnea_parameters_state_vjp_kernel (mh_params_state_vjp_kernels.h) holds a copy of both sweeps with the inertia taken from the lane's own
+// parameters: a change to a sweep here is made there too.
 #pragma once
 #include "mh_rnea_deriv_kernels.h"
 #include "mh_response_kernels.h" // dot6

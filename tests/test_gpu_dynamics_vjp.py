@@ -277,7 +277,7 @@ def _cover_case(torch, sys_, desc, B, grid, layout, with_f, skip=None, forward=F
     f = dev(torch, f_host)[period].contiguous() if with_f else None
     outs, guards = [], []
     for k in range(4 if forward else 3):
-        if k == skip:
+        if k in (skip if isinstance(skip, tuple) else (skip,)):
             outs.append(None), guards.append(None)
             continue
         o, g = poisoned(torch, B, (nv,), torch.float64) if layout == AOS else poisoned(torch, nv, (B,), torch.float64)
@@ -338,6 +338,77 @@ def test_each_output_null_in_turn(torch_cuda, skip, layout):
 def test_forward_each_output_null_in_turn(torch_cuda, skip, layout):
     sys_, desc = make_case("humanoid30")
     _cover_case(torch_cuda, sys_, desc, 64 * 5 + 3, None, layout, with_f=True, skip=skip, forward=True)
+
+
+@pytest.mark.parametrize("skip", [(0, 1, 2), (1, 2), (0, 3)])
+@pytest.mark.parametrize("case,B", [("arm7", 1), ("arm7", 65), ("humanoid30", 197)])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+def test_forward_outputs_null_together(torch_cuda, skip, case, B, layout):
+    """gtau alone (no qdd is needed: the first forward-dynamics launch is skipped), qdd and gtau without gq and gqd (no adjoint launch),
+    and gq and gqd with qdd and H^-1 w both in the context's scratch."""
+    sys_, desc = make_case(case)
+    _cover_case(torch_cuda, sys_, desc, B, None, layout, with_f=True, skip=skip, forward=True)
+
+
+@pytest.mark.parametrize("case,B", [("arm7", 1), ("arm7", 65), ("humanoid30", 197)])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+def test_forward_fp32_outputs_null_together(torch_cuda, case, B, layout):
+    """The same selections in fp32: what is asked for has the bits of the call that asks for everything, which
+    test_fp32_matches_checker holds to the checker."""
+    from mecano_amd.engine import HipModel
+    torch = torch_cuda
+    sys_, desc = make_case(case)
+    hm = HipModel(desc)
+    put = lambda x: dev(torch, x.reshape(B, -1), torch.float32) if layout == AOS else soa(dev(torch, x.reshape(B, -1), torch.float32))
+    q, qd, _, tau = (put(x) for x in state(sys_, B))
+    w, f = put(cotangent(B, desc.nv, 9)), put(random_wrenches(np.random.default_rng(31), B, desc.n_joints))
+    full = hm.aba_vjp(q, qd, tau, w, GRAVITY, f, layout)
+    assert all(torch.isfinite(t).all() for t in full)
+    for keep in ((3,), (0, 3), (1, 2)):  # of (qdd, gq, gqd, gtau)
+        outs = tuple(torch.full_like(t, float("nan")) if k in keep else None for k, t in enumerate(full))
+        res = hm.aba_vjp(q, qd, tau, w, GRAVITY, f, layout, out=outs)
+        torch.cuda.synchronize()
+        assert all((r is None) if k not in keep else torch.equal(r, full[k]) for k, r in enumerate(res)), keep
+
+
+@pytest.mark.parametrize("case,B", [("arm7", 65), ("humanoid30", 197)])
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+def test_forward_form_hands_the_callers_switches_to_forward_dynamics_only(torch_cuda, case, B, dtype_name, layout):
+    """mh_aba_vjp_* handed consider_coriolis = 0 through the C ABI (the engine never does).  The first launch is mh_aba_* with the
+    caller's options: qdd_out has the bits of mh_aba_* with the same options.  gtau is H^-1 w, within the bounds of the call with the
+    switch on.  The adjoint sweep runs with both switches on at that qdd: gq and gqd have the bits of -mh_rnea_vjp_*(q, qd, qdd_out,
+    u = gtau) with the switches on, and gqd is not the zeros a sweep with the switch off stores."""
+    import ctypes
+
+    from mecano_amd import _lib
+    from mecano_amd.engine import HipModel
+    torch = torch_cuda
+    dtype, unit, sfx = (torch.float64, U64, "f64") if dtype_name == "float64" else (torch.float32, U32, "f32")
+    sys_, desc = make_case(case)
+    hm = HipModel(desc)
+    q, qd, _, tau = (x.astype(dtype_name) for x in state(sys_, B))
+    w = cotangent(B, desc.nv, 9).astype(dtype_name)
+    f = random_wrenches(np.random.default_rng(31), B, desc.n_joints).astype(dtype_name)
+    put = lambda x: dev(torch, x.reshape(B, -1), dtype) if layout == AOS else soa(dev(torch, x.reshape(B, -1), dtype))
+    tq, tqd, ttau, tf, tw = (put(x) for x in (q, qd, tau, f, w))
+    qdd, gq, gqd, gtau, qdd_aba = (torch.full_like(tw, float("nan")) for _ in range(5))
+    g, ra = hm._root(GRAVITY)
+    opts = hm._options(layout, False, True, torch.cuda.current_stream().cuda_stream, root_acceleration=ra)
+    lib = _lib.load()
+    _lib.check(getattr(lib, "mh_aba_vjp_" + sfx)(hm._h, B, tq.data_ptr(), tqd.data_ptr(), ttau.data_ptr(), g, tf.data_ptr(), tw.data_ptr(),
+                                                 ctypes.byref(opts), qdd.data_ptr(), gq.data_ptr(), gqd.data_ptr(), gtau.data_ptr()))
+    _lib.check(getattr(lib, "mh_aba_" + sfx)(hm._h, B, tq.data_ptr(), tqd.data_ptr(), ttau.data_ptr(), g, tf.data_ptr(), ctypes.byref(opts),
+                                             qdd_aba.data_ptr()))
+    torch.cuda.synchronize()
+    assert torch.isfinite(qdd).all() and torch.equal(qdd, qdd_aba)
+    ref = hm.rnea_vjp(tq, tqd, qdd, gtau, GRAVITY, tf, layout)
+    torch.cuda.synchronize()
+    assert torch.equal(gq, -ref[0]) and torch.equal(gqd, -ref[1]) and gqd.any()
+    q64, qd64, tau64, w64, f64 = (x.astype(np.float64) for x in (q, qd, tau, w, f))
+    conds = conds_of(desc, q64)
+    mu_ref = np.linalg.solve(OracleModel(desc).crba(q64), w64[:, :, None])[:, :, 0]
+    close_aba(host(gtau, layout), mu_ref, None, desc.n_joints, unit, label="switch off: gtau", conds=conds)
 
 
 # ------------------------------------------------------------------------------------------------ plumbing

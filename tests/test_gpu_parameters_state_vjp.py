@@ -314,6 +314,62 @@ def test_each_output_null_in_turn_leaves_the_others_bit_for_bit(torch_cuda, layo
             method(Q, QD, x3, PI, U, GRAVITY, F, layout, out=(torch.empty_like(full[0]),) + (None,) * 4 if count == 5 else (None,) * 4)
 
 
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("case,B", [("arm7", 1), ("arm7", 65), ("humanoid30", 197)])
+def test_forward_outputs_null_together_leave_the_others_bit_for_bit(torch_cuda, case, B, layout, dtype_name):
+    """The forward form with several outputs None at once: gtau alone (no qdd is needed: the first forward-dynamics launch is skipped),
+    qdd and gtau (no adjoint launch), gpi alone and gq, gqd, gpi (qdd and H^-1 w both in the context's scratch) -- what is asked for has
+    the bits of the call that asks for everything."""
+    torch = torch_cuda
+    dtype = getattr(torch, dtype_name)
+    sys_, desc = make_case(case)
+    hm, n, nv = model_of(desc), desc.n_joints, desc.nv
+    q, qd, _, tau = state(sys_, B)
+    pi, w = parameters(desc, POOL)[np.arange(B) % POOL], cotangent(B, nv, 9)
+    f = random_wrenches(np.random.default_rng(27), B, n)
+    put = lambda x: dev(torch, x.reshape(len(x), -1), dtype) if layout == AOS else soa(dev(torch, x.reshape(len(x), -1), dtype))
+    Q, QD, TAU, PI, W, F = (put(x) for x in (q, qd, tau, pi, w, f))
+    full = hm.aba_parameters_state_vjp(Q, QD, TAU, PI, W, GRAVITY, F, layout)
+    assert all(torch.isfinite(t).all() for t in full)
+    for keep in ((3,), (0, 3), (4,), (1, 2, 4)):  # of (qdd, gq, gqd, gtau, gpi)
+        outs = [torch.full_like(t, float("nan")) if k in keep else None for k, t in enumerate(full)]
+        res = hm.aba_parameters_state_vjp(Q, QD, TAU, PI, W, GRAVITY, F, layout, out=tuple(outs))
+        torch.cuda.synchronize()
+        assert all((r is None) if k not in keep else torch.equal(r, full[k]) for k, r in enumerate(res)), keep
+
+
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("case,B", [("arm7", 65), ("humanoid30", 197)])
+def test_forward_form_turns_both_switches_on(torch_cuda, case, B, layout, dtype_name):
+    """mh_aba_parameters_state_vjp_* handed consider_coriolis = 0 and consider_accelerations = 0 through the C ABI (the engine never
+    does): the per-row form runs forward dynamics and the adjoint sweep with both switches on whatever the caller sets -- every output
+    has the bits of the engine's call."""
+    import ctypes
+
+    from mecano_amd import _lib
+    torch = torch_cuda
+    dtype = getattr(torch, dtype_name)
+    sys_, desc = make_case(case)
+    hm, n, nv = model_of(desc), desc.n_joints, desc.nv
+    q, qd, _, tau = state(sys_, B)
+    pi, w = parameters(desc, POOL)[np.arange(B) % POOL], cotangent(B, nv, 9)
+    f = random_wrenches(np.random.default_rng(27), B, n)
+    put = lambda x: dev(torch, x.reshape(len(x), -1), dtype) if layout == AOS else soa(dev(torch, x.reshape(len(x), -1), dtype))
+    Q, QD, TAU, PI, W, F = (put(x) for x in (q, qd, tau, pi, w, f))
+    full = hm.aba_parameters_state_vjp(Q, QD, TAU, PI, W, GRAVITY, F, layout)
+    outs = [torch.full_like(t, float("nan")) for t in full]
+    g, ra = hm._root(GRAVITY)
+    opts = hm._options(layout, False, False, torch.cuda.current_stream().cuda_stream, root_acceleration=ra)
+    _lib.check(getattr(_lib.load(), "mh_aba_parameters_state_vjp_" + ("f64" if dtype_name == "float64" else "f32"))(
+        hm._h, B, Q.data_ptr(), QD.data_ptr(), TAU.data_ptr(), PI.data_ptr(), g, F.data_ptr(), W.data_ptr(), ctypes.byref(opts),
+        *(o.data_ptr() for o in outs)))
+    torch.cuda.synchronize()
+    assert all(torch.isfinite(t).all() for t in full) and full[2].any()
+    assert all(torch.equal(a, b) for a, b in zip(outs, full))
+
+
 # ------------------------------------------------------------------------------------------------ exact cases
 @pytest.mark.parametrize("layout", [AOS, SOA])
 def test_exact_zeros(torch_cuda, layout):

@@ -369,6 +369,70 @@ def test_fixed_joints_bodies_get_a_block(torch_cuda):
     assert np.abs(ref[:, fixed]).max() > 1e-3 and np.abs(got[:, fixed]).max() > 1e-3
 
 
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+def test_a_model_without_dofs_gets_exact_zero_blocks(torch_cuda, layout, dtype_name):
+    """Fixed joints only, nv = 0, through the C ABI (the state matrices are empty; the call wants pointers all the same): the forward
+    form has no forward dynamics to run and does not return early -- it writes gpi, a zero block for every body (qdd does not depend
+    on pi), over what the output held, with qdd_out and gtau_out NULL."""
+    import ctypes
+
+    from mecano_amd import _lib
+    from mecano_amd.multibody import MultiBodySystem
+    torch = torch_cuda
+    dtype = getattr(torch, dtype_name)
+    joints = rt.nextJointTree(np.random.default_rng(3), 3, ("fixed",))
+    desc = MultiBodySystem.toMultiBodySystemInput(joints[0].getPredecessor()).toModelDesc()
+    assert desc.nv == 0 and desc.nq == 0
+    hm, B, n = model_of(desc), 65, desc.n_joints
+    pi = dev(torch, parameters(desc, B).reshape(B, -1), dtype)
+    gpi = torch.full((B, 10 * n), float("nan"), dtype=dtype, device="cuda")
+    if layout == SOA:
+        pi, gpi = soa(pi), soa(gpi)
+    q, qd, tau, w = (torch.zeros(8, dtype=dtype, device="cuda") for _ in range(4))  # somewhere to point: nothing of them is read
+    g, ra = hm._root(GRAVITY)
+    opts = hm._options(layout, True, True, torch.cuda.current_stream().cuda_stream, root_acceleration=ra)
+    _lib.check(getattr(_lib.load(), "mh_aba_parameters_vjp_" + ("f64" if dtype_name == "float64" else "f32"))(
+        hm._h, B, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), pi.data_ptr(), g, None, w.data_ptr(), ctypes.byref(opts), None, None, gpi.data_ptr()))
+    torch.cuda.synchronize()
+    assert not torch.isnan(gpi).any() and not gpi.any()
+
+
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("case,B", [("arm7", 1), ("arm7", 65), ("humanoid30", 197)])
+def test_forward_form_outputs_in_scratch_and_both_switches_on(torch_cuda, case, B, layout, dtype_name):
+    """qdd and gtau None (both in the context's scratch), each alone, and the call through the C ABI with consider_coriolis = 0 and
+    consider_accelerations = 0 (the per-row form runs everything with both switches on): gpi has the bits of the full call."""
+    import ctypes
+
+    from mecano_amd import _lib
+    torch = torch_cuda
+    dtype = getattr(torch, dtype_name)
+    sys_, desc = make_case(case)
+    hm, n, nv = model_of(desc), desc.n_joints, desc.nv
+    q, qd, _, tau = state(sys_, B)
+    pi, w = parameters(desc, B), cotangent(B, nv, 9)
+    f = random_wrenches(np.random.default_rng(21), B, n)
+    put = lambda x: dev(torch, x.reshape(B, -1), dtype) if layout == AOS else soa(dev(torch, x.reshape(B, -1), dtype))
+    Q, QD, TAU, PI, W, F = (put(x) for x in (q, qd, tau, pi, w, f))
+    full = hm.aba_parameters_vjp(Q, QD, TAU, PI, W, GRAVITY, F, layout)
+    assert all(torch.isfinite(t).all() for t in full) and full[2].any()
+    for keep in ((2,), (0, 2), (1, 2)):  # of (qdd, gtau, gpi)
+        outs = tuple(torch.full_like(t, float("nan")) if k in keep else None for k, t in enumerate(full))
+        res = hm.aba_parameters_vjp(Q, QD, TAU, PI, W, GRAVITY, F, layout, out=outs)
+        torch.cuda.synchronize()
+        assert all((r is None) if k not in keep else torch.equal(r, full[k]) for k, r in enumerate(res)), keep
+    outs = [torch.full_like(t, float("nan")) for t in full]
+    g, ra = hm._root(GRAVITY)
+    opts = hm._options(layout, False, False, torch.cuda.current_stream().cuda_stream, root_acceleration=ra)
+    _lib.check(getattr(_lib.load(), "mh_aba_parameters_vjp_" + ("f64" if dtype_name == "float64" else "f32"))(
+        hm._h, B, Q.data_ptr(), QD.data_ptr(), TAU.data_ptr(), PI.data_ptr(), g, F.data_ptr(), W.data_ptr(), ctypes.byref(opts),
+        *(o.data_ptr() for o in outs)))
+    torch.cuda.synchronize()
+    assert all(torch.equal(a, b) for a, b in zip(outs, full))
+
+
 def test_switches_and_root_acceleration(torch_cuda):
     """consider_coriolis = False gives the bits of qd = 0 and needs no qd; consider_accelerations = False those of qdd = 0; a root
     acceleration (0, -g) gives the bits of the gravity vector g.  The checker agrees with each."""

@@ -301,8 +301,9 @@ def cover_reference(case, B, grid, dt, group=64, step_rows=None):
 
 
 def cover_case(torch, case, B, grid, layout, which, skip=None, dt=0.02, group=64, step_rows=None):
-    """B distinct rows, poisoned outputs with a guard row behind them, every row group checked; `skip`: index of the output passed as
-    NULL.  which: "integrate" or "step"."""
+    """B distinct rows, poisoned outputs with a guard row behind them, every row group checked; `skip`: index (or tuple of indices) of
+    the outputs passed as NULL.  which: "integrate" or "step"."""
+    skips = skip if isinstance(skip, tuple) else (skip,)
     _, desc, hm = model_of(case)
     rows, idx, sidx, ga64, gb64, f64, ref_i, ref_s, conds = cover_reference(case, B, grid, dt, group, step_rows)
     nv = desc.nv
@@ -311,7 +312,7 @@ def cover_case(torch, case, B, grid, layout, which, skip=None, dt=0.02, group=64
     ga, gb, f = (dev(torch, x)[period].contiguous() for x in (ga64, gb64, f64))
     outs, guards = [], []
     for k in range(3 if which == "integrate" else 4):
-        o, g = (None, None) if k == skip else (poisoned(torch, B, (nv,), torch.float64) if layout == AOS else poisoned(torch, nv, (B,), torch.float64))
+        o, g = (None, None) if k in skips else (poisoned(torch, B, (nv,), torch.float64) if layout == AOS else poisoned(torch, nv, (B,), torch.float64))
         outs.append(o), guards.append(g)
     L = lambda t: lay(t, layout)
     if which == "integrate":
@@ -347,6 +348,38 @@ def test_integrate_vjp_each_output_null_in_turn(torch_cuda, skip, layout):
 @pytest.mark.parametrize("layout", [AOS, SOA])
 def test_step_vjp_each_output_null_in_turn(torch_cuda, skip, layout):
     cover_case(torch_cuda, "humanoid30", 64 * 5 + 3, None, layout, "step", skip)
+
+
+@pytest.mark.parametrize("skip", [(0, 1, 2), (1, 2), (0, 3)])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+def test_step_vjp_outputs_null_together(torch_cuda, skip, layout):
+    """gtau alone (the first forward-dynamics launch still runs: the cotangent of qdd needs qdd wherever dt != 0), qdd and gtau without
+    gq and gqd (no adjoint launch), and gq and gqd with qdd and gtau both in the context's scratch behind w."""
+    cover_case(torch_cuda, "humanoid30", 64 * 5 + 3, None, layout, "step", skip)
+
+
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("case,B", [("arm7", 1), ("arm7", 65), ("humanoid30", 197)])
+def test_step_vjp_outputs_null_together_leave_the_others_bit_for_bit(torch_cuda, case, B, layout, dtype_name):
+    """Small batches (one lane, a ragged second wave, several waves per group), both precisions: gtau alone, qdd and gtau, gq and gqd
+    (qdd and gtau in the context's scratch behind w), qdd without gtau and gtau without qdd -- what is asked for has the bits of the
+    call that asks for everything, which the tests above hold to the checker."""
+    torch = torch_cuda
+    dtype = getattr(torch, dtype_name)
+    sys_, desc, hm = model_of(case)
+    q, qd, _, tau = state(sys_, B)
+    ga, gb = cotangents(B, desc.nv)
+    f = random_wrenches(np.random.default_rng(24), B, desc.n_joints)
+    put = lambda x: lay(dev(torch, x.reshape(B, -1), dtype), layout)
+    Q, QD, TAU, GA, GB, F = (put(x) for x in (q, qd, tau, ga, gb, f))
+    full = hm.step_vjp(0.02, Q, QD, TAU, GA, GB, GRAVITY, F, layout)
+    assert all(torch.isfinite(t).all() for t in full)
+    for keep in ((3,), (0, 3), (1, 2), (0, 1, 2), (1, 2, 3)):  # of (qdd, gq, gqd, gtau)
+        outs = tuple(torch.full_like(t, float("nan")) if k in keep else None for k, t in enumerate(full))
+        res = hm.step_vjp(0.02, Q, QD, TAU, GA, GB, GRAVITY, F, layout, out=outs)
+        torch.cuda.synchronize()
+        assert all((r is None) if k not in keep else torch.equal(r, full[k]) for k, r in enumerate(res)), keep
 
 
 @pytest.mark.parametrize("layout", [AOS, SOA])
