@@ -227,6 +227,215 @@ def check_cover(out, guard, idx, ref, tol=1.0e-10, absolute=False, label=None, r
     return err
 
 
+# ---- scattered index maps.  A model's dof_indices / cfg_indices may send every DoF and every configuration entry to any row of the caller's
+# matrices, entry by entry, and nv / nq may be wider than what the joints own.  On identity maps a kernel that ignores a map, or applies the
+# DoF map where the configuration map belongs, computes the right numbers: these builders make descriptions on which it does not, and move
+# inputs and outputs between the identity description's index space (where the CPU checkers give the reference) and the scattered one.
+UNOWNED = 7.0  # what the unowned entries of a moved input hold: finite, and nothing a state holds
+
+
+def _scatter(rng, n, holes):
+    """An injection range(n) -> range(n + holes) without a fixed point (n >= 2), the holes at random positions"""
+    while True:
+        perm = rng.permutation(n + holes)[:n].astype(np.int32)
+        if n < 2 or not np.any(perm == np.arange(n)):
+            return perm
+
+
+def scattered_maps(desc, rng, holes=0):
+    """(a copy of `desc` on scattered maps, perm_v, perm_q): entry k of the DoF space of `desc` lives at perm_v[k] of the copy's, entry k of
+    its configuration space at perm_q[k], drawn independently (the parts of a quaternion part company) and without a fixed point; with
+    `holes` the copy's nv and nq are that much wider, and the extra indices -- owned by no joint -- sit at random positions."""
+    import copy
+    d = copy.copy(desc)
+    perm_v, perm_q = _scatter(rng, int(desc.nv), holes), _scatter(rng, int(desc.nq), holes)
+    d.dof_indices = perm_v[np.asarray(desc.dof_indices, dtype=np.int64)].astype(np.int32)
+    d.cfg_indices = perm_q[np.asarray(desc.cfg_indices, dtype=np.int64)].astype(np.int32)
+    d.nv, d.nq = int(desc.nv) + holes, int(desc.nq) + holes
+    return d, perm_v, perm_q
+
+
+def unowned(perm, n):
+    """The indices of range(n) that `perm` sends nothing to, ascending"""
+    return np.setdiff1d(np.arange(n), perm)
+
+
+def to_v(x, perm, n=None, fill=UNOWNED):
+    """[B, len(perm)] in the identity description's space -> [B, n] in the scattered one (n: its nv or nq; unowned entries hold `fill`)"""
+    x = np.asarray(x)
+    y = np.full(x.shape[:-1] + (len(perm) if n is None else int(n),), fill, dtype=x.dtype)
+    y[..., perm] = x
+    return y
+
+
+to_q = to_v  # (the same move, with perm_q and nq)
+
+
+def from_v(y, perm):
+    """[..., n] of the scattered space -> ([..., len(perm)] back in the identity space, the unowned entries)"""
+    y = np.asarray(y)
+    return y[..., perm], y[..., unowned(perm, y.shape[-1])]
+
+
+from_cols = from_v  # (a Jacobian's columns: the last index alone)
+
+
+def from_vv(Y, perm):
+    """[B, n, n] with both indices in the scattered DoF space -> (moved back, the unowned rows [B, h, n], the unowned columns [B, n, h])"""
+    Y = np.asarray(Y)
+    free = unowned(perm, Y.shape[-1])
+    return Y[..., perm, :][..., perm], Y[..., free, :], Y[..., free]
+
+
+def from_step(M, perm):
+    """A [B, 2 n, 2 n] or B [B, 2 n, n] of the step's linearisation: index i and index n + i both follow perm"""
+    M = np.asarray(M)
+    n = M.shape[-2] // 2
+    free = unowned(perm, n)
+    rows, free_rows = np.concatenate([perm, n + perm]), np.concatenate([free, n + free])
+    cols, free_cols = (rows, free_rows) if M.shape[-1] == 2 * n else (perm, free)
+    return M[..., rows, :][..., cols], M[..., free_rows, :], M[..., free_cols]
+
+
+def keep_order(y, perm, axes=(-1,)):
+    """`y` of the scattered space with the unowned entries of `axes` dropped and the others left where they are: what a caller reads who
+    ignores the map (for the tests' own proof that they tell the maps apart)"""
+    y = np.asarray(y)
+    for ax in axes:
+        y = np.delete(y, unowned(perm, y.shape[ax]), axis=ax)
+    return y
+
+
+def keep_order_step(M, perm, rows=True, cols=True):
+    """from_step with the rows, the columns or both left in the scattered order (unowned ones dropped)"""
+    M = np.asarray(M)
+    n = M.shape[-2] // 2
+    free = unowned(perm, n)
+    stay = np.delete(np.arange(n), free)
+    wide = M.shape[-1] == 2 * n
+    r = np.concatenate([stay, n + stay]) if rows else np.concatenate([perm, n + perm])
+    c = (np.concatenate([stay, n + stay]) if wide else stay) if cols else (np.concatenate([perm, n + perm]) if wide else perm)
+    return M[..., r, :][..., c]
+
+
+def assert_misses(unmoved, ref, label=""):
+    """The proof that a comparison tells the maps apart: outputs read without moving them back miss the reference by more than
+    1e-3 max(1, |ref|_inf)."""
+    unmoved, ref = np.asarray(unmoved, dtype=np.float64), np.asarray(ref, dtype=np.float64)
+    assert unmoved.shape == ref.shape, (label, unmoved.shape, ref.shape)
+    miss, floor = float(np.abs(unmoved - ref).max()), 1.0e-3 * max(1.0, float(np.abs(ref).max()))
+    assert not miss <= floor, f"{label}: passes with the maps ignored (miss {miss:.3e} <= {floor:.3e})"  # (a NaN misses too)
+
+
+def relisted(desc, rng):
+    """(the description with its joints listed in another order -- parents possibly after their children -- on the same index maps, order):
+    joint k of the copy is joint order[k] of `desc`; a joint index j of `desc` is np.argsort(order)[j] of the copy."""
+    from mecano_amd.multibody import ModelDesc
+    n = int(desc.n_joints)
+    order = rng.permutation(n)
+    inv = np.argsort(order)
+    types = [int(t) for t in desc.joint_type]
+    nd, nc = {0: 1, 1: 1, 2: 6, 3: 0, 4: 3, 5: 3}, {0: 1, 1: 1, 2: 7, 3: 0, 4: 3, 5: 4}
+    dofs = np.concatenate([[0], np.cumsum([nd[t] for t in types])])
+    cfgs = np.concatenate([[0], np.cumsum([nc[t] for t in types])])
+    r = lambda a, w: np.asarray(a).reshape(n, w)[order].reshape(-1)
+    pick = lambda a, ofs: np.concatenate([np.asarray(a).reshape(-1)[ofs[o]:ofs[o + 1]] for o in order]).astype(np.int32)
+    parent = np.array([(-1 if desc.parent[o] < 0 else inv[desc.parent[o]]) for o in order], dtype=np.int32)
+    d = ModelDesc(n, int(desc.nq), int(desc.nv), parent, np.asarray(desc.joint_type)[order].astype(np.int32), r(desc.axis, 3), r(desc.X_before, 12),
+                  r(desc.X_com, 12), r(desc.inertia_J, 9), np.asarray(desc.inertia_mass)[order], r(desc.inertia_com, 3),
+                  pick(desc.dof_indices, dofs), pick(desc.cfg_indices, cfgs))
+    return d, order
+
+
+def maps_flags(desc):
+    """(ident_maps, dense_maps) as the engine's own model compiler sets them for `desc` (mh_model_tables.h): what turns the tree-split code
+    object's identity build, the bias-split hand-off, the LDS row windows, the one-launch step and the dense row staging on and off."""
+    import ctypes
+    from mecano_amd import _lib
+    lib = _lib.load()
+    keep, d = [], _lib.MhModelDesc()
+    d.n_joints, d.nq, d.nv = int(desc.n_joints), int(desc.nq), int(desc.nv)
+    for k, dt in (("parent", np.int32), ("joint_type", np.int32), ("dof_indices", np.int32), ("cfg_indices", np.int32), ("axis", np.float64),
+                  ("X_before", np.float64), ("X_com", np.float64), ("inertia_J", np.float64), ("inertia_mass", np.float64), ("inertia_com", np.float64)):
+        a = np.ascontiguousarray(np.asarray(getattr(desc, k), dtype=dt).reshape(-1))
+        keep.append(a)
+        setattr(d, k, a.ctypes.data_as(ctypes.c_void_p))
+    out, size = np.zeros(64, dtype=np.int32), ctypes.c_size_t(0)
+    _lib.check(lib.mh_internal_model_table(ctypes.byref(d), b"scalars", out.ctypes.data_as(ctypes.c_void_p), out.nbytes, ctypes.byref(size)))
+    return int(out[13]), int(out[14])  # (the order of the "scalars" table: tests/test_model_tables_cpu.py)
+
+
+MIXED_KINDS = ("revolute", "prismatic", "sixdof", "fixed", "planar", "spherical")
+MIXED_SEED = 0  # the first seed whose tree holds the three joint kinds below with cond_inf(H) < 1e8 on the rows the tests use (achieved: 1.6e4);
+#                 tests/test_index_map_helpers.py asserts both
+
+
+def mixed_tree(seed=None):
+    """Model (a) of the index-map tests: (system, desc) of a 10-joint random tree over all six joint kinds that holds a spherical, a
+    floating and a planar joint, so that the configuration and the DoF space differ (nq != nv) and quaternions are there to be split."""
+    from mecano_amd.multibody import MultiBodySystem
+    rng = np.random.default_rng(MIXED_SEED if seed is None else seed)
+    sys_ = MultiBodySystem.toMultiBodySystemInput(rt.nextJointTree(rng, 10, MIXED_KINDS)[0].getPredecessor())
+    return sys_, sys_.toModelDesc()
+
+
+def humanoid():
+    """Model (b): (system, desc) of the committed 30-DoF humanoid, whose identity-map form runs the tree-split code object"""
+    sys_ = rt.committedBenchmarkSystems()["humanoid30"]
+    return sys_, sys_.toModelDesc()
+
+
+SCATTERED_MODELS = {"mixed10": mixed_tree, "humanoid30": humanoid}
+SCATTERED_CASES = [("mixed10", 0), ("mixed10", 2), ("humanoid30", 0)]  # (model, holes)
+
+
+def scattered_case(model, holes=0, salt=""):
+    """(system, identity description, scattered description, perm_v, perm_q) of model (a) "mixed10" or (b) "humanoid30", after the engine's
+    own model compiler is found to see what the test means it to see: identity maps on the one, neither identity nor (with holes) dense
+    maps on the other -- so the scattered model cannot take a plan that is reserved for identity maps."""
+    import zlib
+    sys_, d0 = SCATTERED_MODELS[model]()
+    d, pv, pq = scattered_maps(d0, np.random.default_rng(zlib.crc32(f"scattered {model} {holes} {salt}".encode())), holes)
+    assert maps_flags(d0) == (1, 1) and maps_flags(d) == (0, int(holes == 0)), (maps_flags(d0), maps_flags(d))
+    return sys_, d0, d, pv, pq
+
+
+def scattered_model(desc, model):
+    """HipModel of a scattered description.  The humanoid keeps its tree-split code object and the mixed tree has none: kernel_variant
+    names the code object only and reads the same on identity and on scattered maps, so the assertion below says which family of
+    kernels runs, not which plan.  What rules the identity plans out is ident_maps / dense_maps (maps_flags, asserted by scattered_case
+    on a compile of the same description: the engine has no query for the plan a call took)."""
+    from mecano_amd.engine import HipModel
+    hm = HipModel(desc)
+    assert hm.kernel_variant.startswith("topo:" if model == "humanoid30" else "generic"), hm.kernel_variant
+    return hm
+
+
+def poisoned_set(torch, B, shapes, dtype, soa=False):
+    """(outputs, guards) for per-configuration shapes: AoS [B, *shape] with one guard row behind, SoA [prod(shape), B] with B guard entries"""
+    pairs = [poisoned(torch, int(np.prod(s)), (B,), dtype) if soa else poisoned(torch, B, tuple(s), dtype) for s in shapes]
+    return [p[0] for p in pairs], [p[1] for p in pairs]
+
+
+def rows_of(t, B, shape, soa=False):
+    """A device output as fp64 numpy [B, *shape]"""
+    a = (t.t() if soa else t).cpu().numpy().astype(np.float64)
+    return a.reshape((B,) + tuple(shape))
+
+
+def guards_intact(guards, label=""):
+    for k, g in enumerate(guards):
+        if g is not None:
+            assert np.isnan(g.cpu().numpy()).all(), f"{label}: output {k} wrote past its last row"
+
+
+def quaternion_joints(desc):
+    """[(joint, its four quaternion configuration entries in the listing's packed order)] of the floating and spherical joints"""
+    nc = {0: 1, 1: 1, 2: 7, 3: 0, 4: 3, 5: 4}
+    ofs = np.concatenate([[0], np.cumsum([nc[int(t)] for t in desc.joint_type])])
+    return [(j, np.arange(ofs[j], ofs[j] + 4)) for j in range(int(desc.n_joints)) if int(desc.joint_type[j]) in (2, 5)]
+
+
 def bad_outputs(torch, shape, dt=None):
     """The four ways a tensor handed in as ``out`` can be wrong for an output of `shape` and dtype `dt` (fp64), with what the engine raises
     for each: [(what, tensor, exception class)].  The first three are device tensors; none is ever written."""

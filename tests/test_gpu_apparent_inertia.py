@@ -1,11 +1,13 @@
 """mh_apparent_inertia_inverse_f64 / _f32 on the device against the CPU checker (tests/apparent_inertia_check.py, pinned by
 tests/test_apparent_inertia_cpu.py), through the C-ABI (HipModel.apparent_inertia_inverse is the ctypes call) and the calculator mirror."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 import apparent_inertia_check as ac
+import helpers as hp
 from helpers import DistinctRows, check_bad_outputs, check_cover, f32_aba_forward_factor, group_cover, poisoned, record_parity
 from test_apparent_inertia_cpu import CASES, HUMANOID_TARGETS, WELL_CONDITIONED, make_case, states, targets_of
 
@@ -92,6 +94,65 @@ def test_fp32_matches_fp64_checker(torch_cuda, case):
         print(f"{case} fp32 layout {layout}: err / (cond u) = {ratio:.3e}, factor {factor:.3e}, achieved / bound = {ratio / factor:.3e}")
         record_parity(ratio, factor, f"fp32 {case} layout {layout} err / (cond_inf(H) u)")
         assert ratio <= factor
+
+
+@functools.lru_cache(maxsize=None)
+def _scattered_reference(model, dtype_name):
+    """Configurations in the identity description's index space and the checker's W in both block modes: once per model and precision,
+    shared by the layouts, the hole and the re-listing cases, never modified."""
+    from oracle.cpu_oracle import OracleModel
+    sys_, d0 = hp.SCATTERED_MODELS[model]()
+    om, B = OracleModel(d0), 70
+    q = DistinctRows(sys_, 16, seed=81).rows(np.arange(B), np.float32 if dtype_name == "float32" else np.float64)[0]
+    t = list(HUMANOID_TARGETS) + [HUMANOID_TARGETS[1]] if model == "humanoid30" else [d0.n_joints - 1, 4, 2, 4]  # one body named twice
+    poses = ac.random_poses(np.random.default_rng(82), len(t))
+    refs = {coupled: ac.apparent_inertia_inverse(om, q, t, poses, coupled) for coupled in (False, True)}
+    conds = ac.mass_matrix_conds(om, q)
+    assert conds.max() < 1.0e8
+    return q, t, poses, refs, ac.bound_of(om, q, d0.n_joints, False), conds
+
+
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("model,holes,relist", [("mixed10", 0, False), ("mixed10", 2, False), ("humanoid30", 0, False), ("humanoid30", 0, True)])
+def test_scattered_index_maps(torch_cuda, model, holes, relist, layout, dtype_name):
+    """Both block modes on a description whose configuration map sends every entry somewhere else (with holes: two indices owned by no
+    joint, holding 7.0 in q), against the checker on the IDENTITY description: only q moves, W does not.  fp64 under ac.bound_of's per-row
+    bound, fp32 under test_fp32_matches_fp64_checker's f32_aba_forward_factor(n) cond_inf(H) 2^-24 max(1, |ref|_inf).  relist: the
+    scattered description's joints are listed in a random order, parents possibly after their children, and the target list is
+    translated.  The guard row stays poisoned; fed q as the identity description lists it the call misses the reference by more than
+    1e-3."""
+    torch = torch_cuda
+    dtype = getattr(torch, dtype_name)
+    sys_, d0, d, pv, pq = hp.scattered_case(model, holes)
+    q, t, poses, refs, bounds, conds = _scattered_reference(model, dtype_name)
+    if relist:
+        d, order = hp.relisted(d, np.random.default_rng(83))
+        assert any(d.parent[k] > k for k in range(d.n_joints)) and hp.maps_flags(d) == (0, 1)
+        t = [int(np.argsort(order)[j]) for j in t]
+    hm, B, K = hp.scattered_model(d, model) if not relist else model_of(d, None), 70, len(t)
+    is_soa = layout == SOA
+    for coupled in (False, True):
+        shape = (6 * K, 6 * K) if coupled else (K, 6, 6)
+        (W,), guards = hp.poisoned_set(torch, B, [shape], dtype, is_soa)
+        tq = dev(torch, hp.to_q(q, pq, d.nq), dtype)
+        hm.apparent_inertia_inverse(tq.t().contiguous() if is_soa else tq, t, poses, coupled, layout, out=W)
+        torch.cuda.synchronize()
+        hp.guards_intact(guards, "apparent_inertia_inverse")
+        got, ref = hp.rows_of(W, B, shape, is_soa), refs[coupled]
+        assert not np.isnan(got).any()
+        label = f"scattered {model} holes={holes} relist={relist} {'coupled' if coupled else 'diagonal'} layout {layout} {dtype_name}"
+        if dtype_name == "float64":
+            ac.close_rows(got, ref, bounds, label=label)
+        else:
+            rel = np.abs(got - ref).reshape(B, -1).max(axis=1) / np.maximum(1.0, np.abs(ref).reshape(B, -1).max(axis=1))
+            ratio, factor = float((rel / (conds * 2.0 ** -24)).max()), f32_aba_forward_factor(d0.n_joints)
+            record_parity(ratio, factor, label + " err / (cond_inf(H) u)")
+            assert ratio <= factor, f"{label}: {ratio:.3e} > {factor:.3e}"
+        if not holes:
+            unmoved = hm.apparent_inertia_inverse(dev(torch, q, dtype).t().contiguous() if is_soa else dev(torch, q, dtype), t, poses, coupled, layout)
+            torch.cuda.synchronize()
+            hp.assert_misses(hp.rows_of(unmoved, B, shape, is_soa), ref, label + ", q unmoved")
 
 
 @pytest.mark.parametrize("layout", [AOS, SOA])

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import constrained_dynamics_check as cc
+import helpers as hp
 import kinematics_check as kc
 from helpers import DistinctRows, U32, check_cover, close_aba, f32_aba_forward_factor, group_cover, poisoned, record_parity
 from test_constrained_dynamics_cpu import CASES, GRAVITY, duplicate_compliance, make_inputs, model_of, reference, reference_impulse
@@ -155,6 +156,82 @@ def test_matches_checker(torch_cuda, name, layout, dtype_name):
         Hv, Hq = np.einsum("bij,bj->bi", H, v), np.einsum("bij,bj->bi", H, I["qd"][:B])
         scale = np.abs(Hv).max(axis=1) + np.abs(Hq).max(axis=1) + np.abs(JTp).max(axis=1)
         hold_residual(np.abs(Hv - Hq - JTp).max(axis=1), scale, RI["cond_H"][:B], n, u, label + " momentum balance")
+
+
+SCATTERED = [("humanoid30", 0, False), ("humanoid30", 0, True), ("humanoid30", 2, False)]  # (case, holes, joints re-listed)
+
+
+def scattered_description(name, desc, holes, relist, targets, bases=None):
+    """(description on scattered maps, perm_v, perm_q, targets, bases in its listing, order): test_matches_checker's model, targets and rows,
+    with every DoF and configuration entry sent somewhere else; relist: its joints listed in a random order, parents possibly after
+    children.  The unowned-index case of the constraint, contact and joint-limit tests is taken on this humanoid and not on the mixed tree
+    of helpers.mixed_tree, so that the family's own targets, rows, poses, inputs and cached references serve unchanged (its code object
+    then runs with dense_maps off).  The two flags asserted below are what rules the identity plans out: kernel_variant, which the callers
+    assert too, names the code object and reads the same on any maps, and a re-listed description is asked for no variant."""
+    import zlib
+    assert hp.maps_flags(desc) == (1, 1)
+    rng = np.random.default_rng(zlib.crc32(f"scattered {name} {holes} {relist}".encode()))
+    d, pv, pq = hp.scattered_maps(desc, rng, holes)
+    order = np.arange(desc.n_joints)  # joint k of the description handed out is joint order[k] of `desc`
+    if relist:
+        d, order = hp.relisted(d, rng)
+        assert any(d.parent[k] > k for k in range(d.n_joints))
+        inv = np.argsort(order)
+        targets = [int(inv[j]) if j >= 0 else -1 for j in targets]
+        bases = None if bases is None else [int(inv[j]) if j >= 0 else -1 for j in bases]
+    assert hp.maps_flags(d) == (0, int(holes == 0))  # no plan reserved for identity (or dense) maps can be taken
+    return d, pv, pq, targets, bases, order
+
+
+def moved_inputs(torch, I, B, pv, pq, d, order, layout, dtype, keys=("q", "qd", "tau", "f_ext", "a_des", "v_des")):
+    """device_inputs on the scattered description: q through the configuration map, qd and tau through the DoF map, the external wrenches
+    in the listing order of its joints, the rest as it is"""
+    moved = dict(I)
+    if "f_ext" in I:
+        moved["f_ext"] = I["f_ext"][:, order]
+    moved["q"] = hp.to_q(I["q"][:B], pq, d.nq)
+    for k in ("qd", "tau"):
+        if k in I:
+            moved[k] = hp.to_v(I[k][:B], pv, d.nv)
+    D = {k: laid_out(dev(torch, moved[k][:B], dtype), layout) for k in keys if k in moved}
+    D["active"] = None if I.get("active") is None else laid_out(dev(torch, I["active"][:B], torch.int32), layout)
+    return D
+
+
+@pytest.mark.parametrize("dtype_name", ["f64", "f32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("name,holes,relist", SCATTERED)
+def test_scattered_index_maps(torch_cuda, name, holes, relist, layout, dtype_name):
+    """aba_constrained and constraint_impulse on the humanoid with maps that send every DoF and every configuration entry somewhere else (also
+    with two indices of each space owned by no joint, holding 7.0 in every state input, and with its joints re-listed, the target list
+    translated and the external wrenches in the new order), with test_matches_checker's targets, rows, poses and inputs, against ITS references -- the checker on the identity
+    description -- under its bound: close_aba on (qdd, lambda) resp. (qd+, impulse) with cond_inf(KKT).  The state goes in through the
+    maps, qdd and qd+ come back through the DoF map, multipliers and impulses do not move.  Guard rows stay poisoned; read without moving
+    them back qdd and qd+ miss the reference by more than 1e-3."""
+    torch = torch_cuda
+    dtype, u = (torch.float64, U64) if dtype_name == "f64" else (torch.float32, U32)
+    I, R, RI = references(name, dtype_name)
+    sys_, desc, om = model_of(name)
+    d, pv, pq, targets, _, order = scattered_description(name, desc, holes, relist, I["targets"])
+    hm = hip_model(d)
+    assert relist or hm.kernel_variant.startswith("topo:"), hm.kernel_variant
+    B, K, n, nv = 70, len(targets), desc.n_joints, d.nv
+    D, J = moved_inputs(torch, I, B, pv, pq, d, order, layout, dtype), dict(I, targets=targets)
+    label = f"scattered {name} holes={holes} relist={relist} layout={layout} {dtype_name}"
+    for call, ref, x_key, l_key in ((call_constrained, R, "qdd", "lam"), (call_impulse, RI, "qd_next", "impulse")):
+        x, x_rows, x_guard = outputs(torch, B, (nv,), layout, dtype)
+        lam, lam_rows, lam_guard = outputs(torch, B, (K, 6), layout, dtype)
+        call(hm, D, J, layout, (x, lam))
+        torch.cuda.synchronize()
+        assert torch.isnan(x_guard).all() and torch.isnan(lam_guard).all(), f"{label} {x_key}: wrote past the end"
+        raw, l = x_rows.cpu().numpy().astype(np.float64), lam_rows.cpu().numpy().astype(np.float64).reshape(B, K, 6)
+        back, free = hp.from_v(raw, pv)
+        assert not np.isnan(back).any() and not np.isnan(l).any(), f"{label} {x_key}: entries left unwritten"
+        assert x_key == "qdd" or np.all(free == hp.UNOWNED), f"{label}: entries of qd_out no joint owns do not hold those of qd"
+        check_exact_zeros(l, I, B, f"{label} {l_key}")
+        close_aba(np.concatenate([back, l.reshape(B, -1)], axis=1), np.concatenate([ref[x_key][:B], ref[l_key][:B].reshape(B, -1)], axis=1), None, n, u,
+                  label=f"{label} ({x_key}, {l_key})", conds=ref["cond_kkt"][:B])
+        hp.assert_misses(hp.keep_order(raw, pv), ref[x_key][:B], f"{label} {x_key}")
 
 
 def test_nothing_active_is_the_free_forward_dynamics_and_null_arguments_are_zeros(torch_cuda):

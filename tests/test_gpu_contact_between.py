@@ -14,13 +14,15 @@ import numpy as np
 import pytest
 
 import contact_dynamics_check as cd
+import helpers as hp
 import kinematics_check as kc
 import relative_constraints_check as rc
 from helpers import DistinctRows, U32, check_cover, close_aba, f32_aba_forward_factor, f32_forward_tol, group_cover, poisoned
 from test_contact_between_cpu import (AT_REST, BLOCK_A, BLOCK_B, BLOCK_NORMAL, CASES, CONVERGED_CASES, block_closed_form, block_collisions, make_inputs,
                                       model_of, momentum_balance, solve, stick_inside, two_blocks)
 from test_contact_dynamics_cpu import held_to_H, held_to_kkt, mixed_mu, stale_start
-from test_gpu_constrained_dynamics import AOS, B_MAX, BATCHES, INVALID, SOA, U64, dev, hip_model, laid_out, outputs, torch_cuda  # noqa: F401
+from test_gpu_constrained_dynamics import (AOS, B_MAX, BATCHES, INVALID, SOA, U64, dev, hip_model, laid_out, moved_inputs, outputs,
+                                           scattered_description, torch_cuda)  # noqa: F401
 from test_gpu_contact_dynamics import device_inputs, set_path, three_outputs
 
 pytestmark = pytest.mark.gpu
@@ -78,6 +80,47 @@ def test_matches_checker(torch_cuda, name, layout, dtype_name):
         close_aba(r[:, None], R["residual"][:B, None], None, n, u, label=label + " residual", conds=R["cond_kkt"][:B])
         momentum_balance(v, p, I, R, rows, n, u, label)
     assert np.abs(R["impulse"]).max() > 0.1
+
+
+@pytest.mark.parametrize("dtype_name", ["f64", "f32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("holes,relist", [(0, False), (0, True), (2, False)])
+def test_scattered_index_maps(torch_cuda, holes, relist, layout, dtype_name):
+    """mixed_k3 of test_matches_checker (a rooted contact, two between moving bodies) on maps that send every DoF and every configuration
+    entry of the humanoid somewhere else (also with two indices of each space owned by no joint, holding 7.0 in q and qd, and with its
+    joints re-listed and both joint lists translated), against ITS reference -- the checker on the identity description -- under its
+    bound: held_to_kkt and close_aba on the residual.  Both forms of the solve, S resident in LDS and S streamed, each forced.  q and qd go
+    in through the maps, qd+ comes back through the DoF map; impulses and residuals do not move.  Guard rows stay poisoned; read without
+    moving it back qd+ misses the reference by more than 1e-3."""
+    torch = torch_cuda
+    name = "mixed_k3"
+    dtype, u = (torch.float64, U64) if dtype_name == "f64" else (torch.float32, U32)
+    I, R = reference(name, dtype_name)
+    _, desc, om = model_of(name)
+    d, pv, pq, targets, bases, order = scattered_description(name, desc, holes, relist, I["targets"], I["bases"])
+    hm = hip_model(d)
+    assert relist or hm.kernel_variant.startswith("topo:"), hm.kernel_variant
+    B, K, n, nv = 70, len(targets), desc.n_joints, d.nv
+    D = moved_inputs(torch, I, B, pv, pq, d, order, layout, dtype, keys=("q", "qd", "normals", "v_normal"))
+    J, rows = dict(I, targets=targets, bases=bases), slice(0, B)
+    try:
+        for path in (1, 0):
+            label = f"between scattered holes={holes} relist={relist} path={path} layout={layout} {dtype_name}"
+            set_path(hm, path)
+            (qdn, qdn_rows, qdn_guard), (imp, imp_rows, imp_guard), (res, res_rows, res_guard) = three_outputs(torch, B, nv, K, layout, dtype)
+            call(hm, D, J, mixed_mu(K), I["sweeps"], layout, (qdn, imp, res))
+            torch.cuda.synchronize()
+            assert torch.isnan(qdn_guard).all() and torch.isnan(imp_guard).all() and torch.isnan(res_guard).all(), label + ": wrote past the end"
+            raw, p, r = read(qdn_rows, B), read(imp_rows, B, K), read(res_rows, B)
+            v = hp.from_v(raw, pv)[0]
+            assert np.all(hp.from_v(raw, pv)[1] == hp.UNOWNED), label + ": entries of qd_out no joint owns do not hold those of qd"
+            assert not np.isnan(v).any() and not np.isnan(p).any() and not np.isnan(r).any(), label + ": entries left unwritten"
+            assert not p[:, :, :3].any() and not p[I["active"][:B] == 0].any(), label
+            held_to_kkt(v, p, R, rows, n, u, label)
+            close_aba(r[:, None], R["residual"][:B, None], None, n, u, label=label + " residual", conds=R["cond_kkt"][:B])
+            hp.assert_misses(hp.keep_order(raw, pv), R["qd_next"][:B], label + " qd+")
+    finally:
+        set_path(hm, -1)
 
 
 @pytest.mark.parametrize("dtype_name", ["f64", "f32"])

@@ -14,10 +14,12 @@ import numpy as np
 import pytest
 
 import contact_dynamics_check as cd
+import helpers as hp
 import kinematics_check as kc
 from helpers import DistinctRows, U32, check_cover, close_aba, f32_aba_forward_factor, group_cover, poisoned
 from test_contact_dynamics_cpu import CASES, make_inputs, model_of
-from test_gpu_constrained_dynamics import AOS, B_MAX, BATCHES, INVALID, SOA, U64, dev, hip_model, hold_residual, laid_out, outputs, torch_cuda  # noqa: F401
+from test_gpu_constrained_dynamics import (AOS, B_MAX, BATCHES, INVALID, SOA, U64, dev, hip_model, hold_residual, laid_out, moved_inputs, outputs,
+                                           scattered_description, torch_cuda)  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -141,6 +143,48 @@ def test_resident_and_streamed_solves_give_the_same_bits(torch_cuda, name, dtype
         for a, b, c in zip(*got):
             assert torch.equal(a, b) and torch.equal(a, c), f"{name} {dtype_name} layout={layout}: the two paths differ"
     set_path(hm, -1)
+
+
+@pytest.mark.parametrize("dtype_name", ["f64", "f32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("holes,relist", [(0, False), (0, True), (2, False)])
+def test_scattered_index_maps(torch_cuda, holes, relist, layout, dtype_name):
+    """The humanoid of test_matches_checker on maps that send every DoF and every configuration entry somewhere else (also with two indices
+    of each space owned by no joint, holding 7.0 in q and qd, and with its joints re-listed and the targets translated), mu = 0.5, with
+    that test's targets, poses, normals, active and v_normal, against ITS reference -- the checker on the identity description -- under its
+    bound: close_aba on (qd+, impulse) and on the residual with cond_inf(KKT).  Both forms of the solve, S resident in LDS and S streamed,
+    each forced.  q and qd go in through the maps, qd+ comes back through the DoF map; impulses and residuals do not move.  Guard rows
+    stay poisoned; read without moving it back qd+ misses the reference by more than 1e-3."""
+    torch = torch_cuda
+    name, mu = "humanoid30", 0.5
+    dtype, u = (torch.float64, U64) if dtype_name == "f64" else (torch.float32, U32)
+    I, R = reference(name, dtype_name, mu)
+    _, desc, om = model_of(name)
+    d, pv, pq, targets, _, order = scattered_description(name, desc, holes, relist, I["targets"])
+    hm = hip_model(d)
+    assert relist or hm.kernel_variant.startswith("topo:"), hm.kernel_variant
+    B, K, n, nv = 70, len(targets), desc.n_joints, d.nv
+    D = moved_inputs(torch, I, B, pv, pq, d, order, layout, dtype, keys=("q", "qd", "normals", "v_normal"))
+    J = dict(I, targets=targets)
+    try:
+        for path in (1, 0):
+            label = f"scattered holes={holes} relist={relist} path={path} layout={layout} {dtype_name}"
+            set_path(hm, path)
+            (qdn, qdn_rows, qdn_guard), (imp, imp_rows, imp_guard), (res, res_rows, res_guard) = three_outputs(torch, B, nv, K, layout, dtype)
+            call(hm, D, J, mu, SWEEPS[name], layout, (qdn, imp, res))
+            torch.cuda.synchronize()
+            assert torch.isnan(qdn_guard).all() and torch.isnan(imp_guard).all() and torch.isnan(res_guard).all(), label + ": wrote past the end"
+            raw, p = qdn_rows.cpu().numpy().astype(np.float64), imp_rows.cpu().numpy().astype(np.float64).reshape(B, K, 6)
+            v, r = hp.from_v(raw, pv)[0], res_rows.cpu().numpy().astype(np.float64)
+            assert np.all(hp.from_v(raw, pv)[1] == hp.UNOWNED), label + ": entries of qd_out no joint owns do not hold those of qd"
+            assert not np.isnan(v).any() and not np.isnan(p).any() and not np.isnan(r).any(), label + ": entries left unwritten"
+            assert not p[:, :, :3].any() and not p[I["active"][:B] == 0].any(), label
+            close_aba(np.concatenate([v, p.reshape(B, -1)], axis=1), np.concatenate([R["qd_next"][:B], R["impulse"][:B].reshape(B, -1)], axis=1), None,
+                      n, u, label=label + " (qd+, impulse)", conds=R["cond_kkt"][:B])
+            close_aba(r[:, None], R["residual"][:B, None], None, n, u, label=label + " residual", conds=R["cond_kkt"][:B])
+            hp.assert_misses(hp.keep_order(raw, pv), R["qd_next"][:B], label + " qd+")
+    finally:
+        set_path(hm, -1)
 
 
 def test_a_bad_configuration_is_nan_in_its_own_outputs_only(torch_cuda):

@@ -1,11 +1,14 @@
 """mh_rnea_derivatives_* / mh_aba_derivatives_* on the device against the CPU checker (tests/dynamics_derivatives_check.py, pinned by
 tests/test_dynamics_derivatives_cpu.py) and against the device's own neighbours (rnea, aba, gravity_gradient, mass_matrix_inverse),
 through the C-ABI (the HipModel methods are the ctypes calls)."""
+import functools
+
 import numpy as np
 import pytest
 
 import dynamics_derivatives_check as dc
 import gravity_gradient_check as gc
+import helpers as hp
 from helpers import DistinctRows, check_bad_outputs, check_cover, close, close_aba, f32_forward_tol, group_cover, poisoned
 from mecano_amd import random_tools as rt
 from oracle.cpu_oracle import OracleModel
@@ -15,6 +18,7 @@ pytestmark = pytest.mark.gpu
 
 TOL = 1.0e-10  # helpers.close default: relative to max(1, |ref|_inf)
 AOS, SOA = 0, 1
+U32 = 2.0 ** -24
 ROOT_ACC = np.array([0.4, -0.3, 0.2, 1.5, -0.7, 9.0])
 TREE_ROWS = np.array([0, 1, 31, 63, 64, 69])  # (the checker takes seconds per row of the 128-body tree)
 
@@ -389,3 +393,65 @@ def test_calculator_mirrors(torch_cuda):
     H = OracleModel(desc).crba(q)
     for g, r in zip((qdd_d, Dq, Dv, Hinv), ref):
         close_aba(g.cpu().numpy().reshape(B, -1), r.reshape(B, -1), H, 3 * desc.n_joints)
+
+
+# ------------------------------------------------------------------------------------------------ scattered index maps
+@functools.lru_cache(maxsize=None)
+def _scattered_reference(model, dtype_name):
+    """Inputs in the identity description's index space and the checker's outputs on them: computed once per model and precision (the
+    states rounded to it), shared by the layouts and the hole cases, never modified."""
+    sys_, d0 = hp.SCATTERED_MODELS[model]()
+    np_dt = np.float32 if dtype_name == "float32" else np.float64
+    q, qd, qdd, tau = DistinctRows(sys_, 16, seed=41).rows(np.arange(70), np_dt)
+    f = random_wrenches(np.random.default_rng(42), 70, d0.n_joints).astype(np_dt).astype(np.float64)
+    inv = dc.rnea_derivatives(d0, q, qd, qdd, GRAVITY, f)
+    fwd = dc.aba_derivatives(d0, q, qd, tau, GRAVITY, f)
+    conds = np.array([np.linalg.cond(h, np.inf) for h in OracleModel(d0).crba(q)])
+    assert conds.max() < 1.0e8
+    return (q, qd, qdd, tau, f), inv, fwd, conds
+
+
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("model,holes", hp.SCATTERED_CASES)
+def test_scattered_index_maps(torch_cuda, model, holes, layout, dtype_name):
+    """rnea_derivatives and aba_derivatives on a description whose maps send every DoF and every configuration entry somewhere else (the
+    parts of a quaternion apart; with holes, two indices of each space owned by no joint), on moved inputs, against the checker on the
+    IDENTITY description: every output moved back meets this file's own bounds (1e-10 resp. f32_forward_tol(3 n) for the inverse form,
+    close_aba's per-row cond_inf(H) bound for the forward form), the guard rows stay poisoned, and read without moving rows or columns
+    back the same outputs miss the reference by more than 1e-3."""
+    torch = torch_cuda
+    dtype, u = getattr(torch, dtype_name), (U32 if dtype_name == "float32" else 2.0 ** -53)
+    sys_, d0, d, pv, pq = hp.scattered_case(model, holes)
+    hm, B, nv, n = hp.scattered_model(d, model), 70, d.nv, d0.n_joints
+    (q, qd, qdd, tau, f), inv, fwd, conds = _scattered_reference(model, dtype_name)
+    is_soa = layout == SOA
+    lay = (lambda x: soa(torch, x)) if is_soa else (lambda x: x)
+    tq, tqd, tqdd, ttau = (lay(dev(torch, x, dtype)) for x in (hp.to_q(q, pq, d.nq), hp.to_v(qd, pv, nv), hp.to_v(qdd, pv, nv), hp.to_v(tau, pv, nv)))
+    tf = lay(dev(torch, f, dtype))
+    tol = TOL if dtype_name == "float64" else f32_forward_tol(3 * n)
+    # the inverse form
+    outs, guards = hp.poisoned_set(torch, B, [(nv,), (nv, nv), (nv, nv)], dtype, is_soa)
+    hm.rnea_derivatives(tq, tqd, tqdd, GRAVITY, tf, layout, out=tuple(outs))
+    torch.cuda.synchronize()
+    hp.guards_intact(guards, "rnea_derivatives")
+    got = [hp.rows_of(o, B, s, is_soa) for o, s in zip(outs, [(nv,), (nv, nv), (nv, nv)])]
+    close(hp.from_v(got[0], pv)[0], inv[0], tol, label="scattered tau")
+    hp.assert_misses(hp.keep_order(got[0], pv), inv[0], "tau")
+    for k, name in ((1, "dtau_dq"), (2, "dtau_dqd")):
+        close(hp.from_vv(got[k], pv)[0], inv[k], tol, label=f"scattered {name}")
+        hp.assert_misses(hp.keep_order(got[k], pv, (-2,))[:, :, pv], inv[k], f"{name}, rows left where they are")
+        hp.assert_misses(hp.keep_order(got[k], pv, (-1,))[:, pv, :], inv[k], f"{name}, columns left where they are")
+    # the forward form
+    shapes = [(nv,), (nv, nv), (nv, nv), (nv, nv)]
+    outs, guards = hp.poisoned_set(torch, B, shapes, dtype, is_soa)
+    hm.aba_derivatives(tq, tqd, ttau, GRAVITY, tf, layout, out=tuple(outs))
+    torch.cuda.synchronize()
+    hp.guards_intact(guards, "aba_derivatives")
+    got = [hp.rows_of(o, B, s, is_soa) for o, s in zip(outs, shapes)]
+    close_aba(hp.from_v(got[0], pv)[0], fwd[0], None, n, u, label="scattered qdd", conds=conds)
+    hp.assert_misses(hp.keep_order(got[0], pv), fwd[0], "qdd")
+    for k, name, bodies in ((1, "dqdd_dq", 3 * n), (2, "dqdd_dqd", 3 * n), (3, "Hinv", 3 * n)):
+        close_aba(hp.from_vv(got[k], pv)[0].reshape(B, -1), fwd[k].reshape(B, -1), None, bodies, u, label=f"scattered {name}", conds=conds)
+        hp.assert_misses(hp.keep_order(got[k], pv, (-2,))[:, :, pv], fwd[k], f"{name}, rows left where they are")
+        hp.assert_misses(hp.keep_order(got[k], pv, (-1,))[:, pv, :], fwd[k], f"{name}, columns left where they are")

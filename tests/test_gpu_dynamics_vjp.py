@@ -7,10 +7,13 @@ Bounds.  An output entry is a contraction sum_i u_i D_ij, so the project's per-e
 the per-row bound of helpers.close_aba as the forward-dynamics derivative tests apply it to the matrices: 8 sqrt(8 * 3 n) cond_inf(H) u
 max(1, |D_ref|_inf), cond from the oracle's H.  fp32: helpers.f32_forward_tol(3 n) in place of TOL, u = 2^-24 in close_aba's form, the
 checker fed the fp32-rounded inputs.  Every check records achieved / bound (helpers.record_parity)."""
+import functools
+
 import numpy as np
 import pytest
 
 import dynamics_vjp_check as vc
+import helpers as hp
 from helpers import DistinctRows, check_bad_outputs, close_aba, f32_aba_forward_factor, f32_forward_tol, group_cover, poisoned, record_parity
 from mecano_amd import random_tools as rt
 from oracle.cpu_oracle import OracleModel
@@ -258,6 +261,75 @@ def test_unowned_dof_indices_get_zeros(torch_cuda):
                 assert np.array_equal(g[:, place], base[k]), f"output {k}"
             else:
                 held(g[:, place], ref_f[k - 3], bounds[k - 3], f"forward output {k - 3}, wide map")
+
+
+# ------------------------------------------------------------------------------------------------ scattered index maps
+@functools.lru_cache(maxsize=None)
+def _scattered_reference(model, dtype_name):
+    """States and cotangents in the identity description's index space and the checker's outputs on them: once per model and precision,
+    shared by the layouts and the hole cases, never modified."""
+    sys_, d0 = hp.SCATTERED_MODELS[model]()
+    np_dt = np.float32 if dtype_name == "float32" else np.float64
+    q, qd, qdd, tau = DistinctRows(sys_, 16, seed=51).rows(np.arange(70), np_dt)
+    u = cotangent(70, d0.nv, 52).astype(np_dt).astype(np.float64)
+    f = random_wrenches(np.random.default_rng(53), 70, d0.n_joints).astype(np_dt).astype(np.float64)
+    conds = conds_of(d0, q)
+    assert conds.max() < 1.0e8
+    return (q, qd, qdd, tau, u, f), vc.rnea_vjp(d0, q, qd, qdd, u, GRAVITY, f), vc.aba_vjp(d0, q, qd, tau, u, GRAVITY, f), conds
+
+
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("model,holes", hp.SCATTERED_CASES)
+def test_scattered_index_maps(torch_cuda, model, holes, layout, dtype_name):
+    """rnea_vjp and aba_vjp on a description whose maps send every DoF and every configuration entry somewhere else (with holes: two
+    indices of each space owned by no joint, holding 7.0 in every input, the cotangent included), against the checker on the IDENTITY
+    description: the cotangent goes in and every gradient comes back through the DoF map and meets this file's bounds (rnea_bounds /
+    aba_bounds, close_aba for qdd); the gradients at unowned indices are exact zeros, the guard rows stay poisoned; each gradient asked
+    for alone (the other outputs NULL) meets the same bound; read without moving them back the outputs miss the
+    reference by more than 1e-3."""
+    torch = torch_cuda
+    dtype, unit = getattr(torch, dtype_name), (U32 if dtype_name == "float32" else U64)
+    sys_, d0, d, pv, pq = hp.scattered_case(model, holes)
+    hm, B, nv, n = hp.scattered_model(d, model), 70, d.nv, d0.n_joints
+    (q, qd, qdd, tau, u, f), inv, fwd, conds = _scattered_reference(model, dtype_name)
+    is_soa = layout == SOA
+    lay = soa if is_soa else (lambda x: x)
+    tq, tqd, tqdd, ttau, tu = (lay(dev(torch, x, dtype)) for x in
+                               (hp.to_q(q, pq, d.nq), hp.to_v(qd, pv, nv), hp.to_v(qdd, pv, nv), hp.to_v(tau, pv, nv), hp.to_v(u, pv, nv)))
+    tf = lay(dev(torch, f, dtype))
+    *ref_i, scales_i = inv
+    qdd_ref, *ref_f, scales_f = fwd
+    bounds_i = rnea_bounds(u, scales_i, TOL if dtype_name == "float64" else f32_forward_tol(3 * n))
+    bounds_f = aba_bounds(u, scales_f, conds, n, unit)
+
+    def run(method, x3, places, want):
+        outs, guards = hp.poisoned_set(torch, B, [(nv,)] * places, dtype, is_soa)
+        outs = [o if k in want else None for k, o in enumerate(outs)]
+        method(tq, tqd, x3, tu, GRAVITY, tf, layout, out=tuple(outs))
+        torch.cuda.synchronize()
+        hp.guards_intact([g for k, g in enumerate(guards) if k in want], method.__name__)
+        return [None if o is None else hp.rows_of(o, B, (nv,), is_soa) for o in outs]
+
+    got = run(hm.rnea_vjp, tqdd, 3, (0, 1, 2))
+    for k, (g, r, b, name) in enumerate(zip(got, ref_i, bounds_i, ("gq", "gqd", "gqdd"))):
+        back, free = hp.from_v(g, pv)
+        assert not free.any(), name  # exact zeros, and written
+        held(back, r, b, f"scattered {name}")
+        hp.assert_misses(hp.keep_order(g, pv), r, name)
+        alone = hp.from_v(run(hm.rnea_vjp, tqdd, 3, (k,))[k], pv)
+        assert not alone[1].any(), name
+        held(alone[0], r, b, f"scattered {name} alone")
+    got = run(hm.aba_vjp, ttau, 4, (0, 1, 2, 3))
+    close_aba(hp.from_v(got[0], pv)[0], qdd_ref, None, n, unit, label="scattered qdd", conds=conds)
+    for k, (g, r, b, name) in enumerate(zip(got[1:], ref_f, bounds_f, ("gq", "gqd", "gtau")), start=1):
+        back, free = hp.from_v(g, pv)
+        assert not free.any(), name
+        held(back, r, b, f"scattered forward {name}")
+        hp.assert_misses(hp.keep_order(g, pv), r, "forward " + name)
+        alone = hp.from_v(run(hm.aba_vjp, ttau, 4, (k,))[k], pv)
+        assert not alone[1].any(), name
+        held(alone[0], r, b, f"scattered forward {name} alone")
 
 
 # ------------------------------------------------------------------------------------------------ cover of batches

@@ -1,11 +1,13 @@
 """mh_gravity_gradient_f64 / _f32 on the device against the CPU checker (tests/gravity_gradient_check.py, pinned by
 tests/test_gravity_gradient_cpu.py), through the C-ABI (HipModel.gravity_gradient is the ctypes call) and the calculator mirror."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
 
 import gravity_gradient_check as gc
+import helpers as hp
 from helpers import DistinctRows, check_bad_outputs, check_cover, close, f32_forward_tol, group_cover, poisoned
 from test_gravity_gradient_cpu import CASES, GRAVITY, make_case, random_wrenches, states, system_of
 
@@ -277,3 +279,45 @@ def test_calculator_mirror(torch_cuda):
     calc.reset()
     t2, _ = gc.gravity_gradient(desc, q[:1], (0.0, 0.0, -1.0), f1)
     close(calc.getTauMatrix().reshape(-1), t2[0], TOL)
+
+
+# ------------------------------------------------------------------------------------------------ scattered index maps
+@functools.lru_cache(maxsize=None)
+def _scattered_reference(model, dtype_name):
+    """Configurations and wrenches in the identity description's index space and the checker's outputs on them: once per model and
+    precision, shared by the layouts and the hole cases, never modified."""
+    sys_, d0 = hp.SCATTERED_MODELS[model]()
+    np_dt = np.float32 if dtype_name == "float32" else np.float64
+    q = DistinctRows(sys_, 16, seed=43).rows(np.arange(70), np_dt)[0]
+    f = random_wrenches(np.random.default_rng(44), 70, d0.n_joints).astype(np_dt).astype(np.float64)
+    return q, f, gc.gravity_gradient(d0, q, GRAVITY, f)
+
+
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("model,holes", hp.SCATTERED_CASES)
+def test_scattered_index_maps(torch_cuda, model, holes, layout, dtype_name):
+    """The device on a description whose maps send every DoF and every configuration entry somewhere else (with holes: two indices of
+    each space owned by no joint), on moved configurations, against the checker on the IDENTITY description: tau and the gradient moved
+    back meet this file's bounds (1e-10, f32_forward_tol(2 n) in fp32), the guard rows stay poisoned, and with the rows or the columns left
+    where they are the gradient misses the reference by more than 1e-3."""
+    torch = torch_cuda
+    dtype = getattr(torch, dtype_name)
+    sys_, d0, d, pv, pq = hp.scattered_case(model, holes)
+    hm, B, nv = hp.scattered_model(d, model), 70, d.nv
+    q, f, (tau_ref, grad_ref) = _scattered_reference(model, dtype_name)
+    tol = TOL if dtype_name == "float64" else f32_forward_tol(2 * d0.n_joints)
+    is_soa = layout == SOA
+    outs, guards = hp.poisoned_set(torch, B, [(nv,), (nv, nv)], dtype, is_soa)
+    tq, tf = dev(torch, hp.to_q(q, pq, d.nq), dtype), dev(torch, f, dtype)
+    if is_soa:
+        tq, tf = soa(torch, tq), soa(torch, tf)
+    hm.gravity_gradient(tq, GRAVITY, tf, layout, out=tuple(outs))
+    torch.cuda.synchronize()
+    hp.guards_intact(guards, "gravity_gradient")
+    tau, grad = hp.rows_of(outs[0], B, (nv,), is_soa), hp.rows_of(outs[1], B, (nv, nv), is_soa)
+    close(hp.from_v(tau, pv)[0], tau_ref, tol, label="scattered tau")
+    close(hp.from_vv(grad, pv)[0], grad_ref, tol, label="scattered grad")
+    hp.assert_misses(hp.keep_order(tau, pv), tau_ref, "tau")
+    hp.assert_misses(hp.keep_order(grad, pv, (-2,))[:, :, pv], grad_ref, "grad, rows left where they are")
+    hp.assert_misses(hp.keep_order(grad, pv, (-1,))[:, pv, :], grad_ref, "grad, columns left where they are")

@@ -15,9 +15,11 @@ import ctypes
 import numpy as np
 import pytest
 
+import helpers as hp
 import joint_limits_check as jl
 from helpers import DistinctRows, U32, check_cover, close_aba, f32_aba_forward_factor, group_cover, poisoned
-from test_gpu_constrained_dynamics import AOS, B_MAX, BATCHES, INVALID, SOA, U64, dev, hip_model, hold_residual, laid_out, outputs, torch_cuda  # noqa: F401
+from test_gpu_constrained_dynamics import (AOS, B_MAX, BATCHES, INVALID, SOA, U64, dev, hip_model, hold_residual, laid_out, outputs,
+                                           scattered_description, torch_cuda)  # noqa: F401
 from test_joint_limits_cpu import ERP, LOWER, MARGIN, UPPER, make_inputs, model_of
 
 pytestmark = pytest.mark.gpu
@@ -149,6 +151,63 @@ def test_converged_impulses_solve_the_complementarity_problem(torch_cuda, name):
 def set_path(hm, path):
     from mecano_amd import _lib
     _lib.check(_lib.load().mh_internal_limit_path(hm._h, path))
+
+
+def _scattered_reference(dtype_name, sweeps):
+    """The humanoid's first 22 one-DoF joints listed in DESCENDING order (what fp64 can still hold in LDS), 70 configurations: inputs in the
+    identity description's index space and the checker's result on them, once per precision and sweep count, never modified."""
+    key = ("scattered", dtype_name, sweeps)
+    if key not in _REFS:
+        I = make_inputs("humanoid30", 70, 1, np.float64 if dtype_name == "f64" else np.float32, humanoid_joints(22)[::-1])
+        _REFS[key] = (I, check("humanoid30", I, sweeps, 0.0))
+    return _REFS[key]
+
+
+@pytest.mark.parametrize("dtype_name", ["f64", "f32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("holes,relist", [(0, False), (0, True), (2, False)])
+def test_scattered_index_maps(torch_cuda, holes, relist, layout, dtype_name):
+    """The humanoid on maps that send every DoF and every configuration entry somewhere else -- so that a listed joint's configuration
+    index is not its DoF index, which the host resolves one by one before it indexes columns of H^-1 with them -- (also with two indices of
+    each space owned by no joint, holding 7.0 in q and qd, and with the joints re-listed and the list translated), 22 joints listed in
+    descending order, 3 sweeps (nothing has converged: the order of the updates shows), against the checker on the IDENTITY description
+    under hold_parity's bound: close_aba on (qd+, impulse) and on the residual with cond_inf(KKT).  The resident and the streamed form,
+    each forced.  q and qd go in through the maps, qd+ comes back through the DoF map; impulses (one per listed joint, in list order) and
+    residuals do not move.  Guard rows stay poisoned; read without moving it back qd+ misses the reference by more than 1e-3."""
+    torch = torch_cuda
+    name, sweeps, B = "humanoid30", 3, 70
+    dtype, u = (torch.float64, U64) if dtype_name == "f64" else (torch.float32, U32)
+    I, R = _scattered_reference(dtype_name, sweeps)
+    _, desc, om = model_of(name)
+    assert not R["bad"].any() and R["closed"].any() and np.abs(R["impulse"]).max() > 0.1
+    d, pv, pq, joints, _, _ = scattered_description(name, desc, holes, relist, I["joints"])
+    d_idx, c_idx = jl.joint_indices(desc, I["joints"])
+    assert np.any(pv[d_idx] != pq[c_idx]), "every listed joint's configuration index is its DoF index"
+    hm = hip_model(d)
+    assert relist or hm.kernel_variant.startswith("topo:"), hm.kernel_variant
+    L, n, nv = len(joints), desc.n_joints, d.nv
+    q = laid_out(dev(torch, hp.to_q(I["q"], pq, d.nq), dtype), layout)
+    qd = laid_out(dev(torch, hp.to_v(I["qd"], pv, nv), dtype), layout)
+    J = dict(I, joints=joints)
+    try:
+        for path in (1, 0):
+            label = f"scattered holes={holes} relist={relist} path={path} layout={layout} {dtype_name}"
+            set_path(hm, path)
+            (qdn, qdn_rows, qdn_guard), (imp, imp_rows, imp_guard), (res, res_rows, res_guard) = three_outputs(torch, B, nv, L, layout, dtype)
+            call(hm, q, qd, J, sweeps, layout, (qdn, imp, res))
+            torch.cuda.synchronize()
+            assert torch.isnan(qdn_guard).all() and torch.isnan(imp_guard).all() and torch.isnan(res_guard).all(), label + ": wrote past the end"
+            raw, p, r = (t.cpu().numpy().astype(np.float64) for t in (qdn_rows, imp_rows, res_rows))
+            v = hp.from_v(raw, pv)[0]
+            assert np.all(hp.from_v(raw, pv)[1] == hp.UNOWNED), label + ": entries of qd_out no joint owns do not hold those of qd"
+            assert not np.isnan(v).any() and not np.isnan(p).any() and not np.isnan(r).any(), label + ": entries left unwritten"
+            assert not p[~R["closed"]].any() and (R["s"] * p >= 0).all(), label
+            close_aba(np.concatenate([v, p], axis=1), np.concatenate([R["qd_next"], R["impulse"]], axis=1), None, n, u, label=label + " (qd+, impulse)",
+                      conds=R["cond_kkt"])
+            close_aba(r[:, None], R["residual"][:, None], None, n, u, label=label + " residual", conds=R["cond_kkt"])
+            hp.assert_misses(hp.keep_order(raw, pv), R["qd_next"], label + " qd+")
+    finally:
+        set_path(hm, -1)
 
 
 @pytest.mark.parametrize("case,dtype_name", [("humanoid30_l22", "f64"), ("humanoid30", "f32"), ("arm7", "f32")])

@@ -8,6 +8,7 @@ import ctypes
 import numpy as np
 import pytest
 
+import helpers as hp
 import kinematics_check as kc
 from helpers import DistinctRows, check_bad_outputs, check_cover, close, f32_forward_tol, group_cover, poisoned
 from test_kinematics_cpu import HUMANOID_TARGETS, make_case, states, targets_of
@@ -120,6 +121,76 @@ def test_matches_checker(torch_cuda, case, layout, dtype_name):
         torch.cuda.synchronize()
         check_cover(P_rows, P_guard, idx, R["P"][:B].reshape(B, -1), label=label + " poses", **tol)
         check_cover(PA_rows, PA_guard, idx, R["P_all"][:B].reshape(B, -1), label=label + " poses of all bodies", **tol)
+
+
+def scattered_chains(model, desc):
+    """(targets, bases, poses): the humanoid's five chains of the tests above (one body twice, two from a moving foot); on the mixed tree
+    the last body from the root, a body from another branch's body, and the root body from a moving base"""
+    if model == "humanoid30":
+        return chains_of("humanoid30", desc, 5)
+    return [desc.n_joints - 1, 4, -1, 2], [-1, desc.n_joints - 2, 6, -1], kc.random_poses(np.random.default_rng(44), 4)
+
+
+def _scattered_reference(model, dtype_name):
+    """States in the identity description's index space and the checker's outputs on them: once per model and precision, shared by the
+    layouts, the hole and the re-listing cases, never modified."""
+    key = ("scattered", model, dtype_name)
+    if key not in _REFS:
+        sys_, d0 = hp.SCATTERED_MODELS[model]()
+        q, qd = DistinctRows(sys_, 16, seed=71).rows(np.arange(70), np.float32 if dtype_name == "f32" else np.float64)[:2]
+        m = kc.KinModel(d0)
+        t, b, poses = scattered_chains(model, d0)
+        J, c = kc.geometric_jacobian(m, q, t, b, poses, qd)
+        _REFS[key] = dict(q=q, qd=qd, t=t, b=b, poses=poses, J=J, c=c, P=kc.body_poses(m, q, t, poses), P_all=kc.body_poses(m, q))
+    return _REFS[key]
+
+
+@pytest.mark.parametrize("dtype_name", ["f64", "f32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("model,holes,relist", [("mixed10", 0, False), ("mixed10", 2, False), ("humanoid30", 0, False), ("humanoid30", 0, True)])
+def test_scattered_index_maps(torch_cuda, model, holes, relist, layout, dtype_name):
+    """body_poses and geometric_jacobian (with the convective term, chains from the root and from moving bases) on a description whose
+    maps send every DoF and every configuration entry somewhere else (with holes: two indices of each space owned by no joint, holding 7.0
+    in q and qd), against the checker on the IDENTITY description under this file's tolerances.  Only q, qd and the columns of J move;
+    poses and convective terms do not.  relist: the scattered description's joints are listed in a random order, parents possibly after
+    their children -- the joint lists are translated, and the poses of "every body" follow the new listing.  The guard rows stay
+    poisoned; with its columns left where they are J misses the reference by more than 1e-3, and so do the poses read from q unmoved."""
+    torch = torch_cuda
+    dtype = torch.float64 if dtype_name == "f64" else torch.float32
+    sys_, d0, d, pv, pq = hp.scattered_case(model, holes)
+    R = _scattered_reference(model, dtype_name)
+    t, b, order = list(R["t"]), list(R["b"]), np.arange(d0.n_joints)
+    if relist:
+        d, order = hp.relisted(d, np.random.default_rng(72))
+        assert any(d.parent[k] > k for k in range(d.n_joints)) and hp.maps_flags(d) == (0, 1)
+        inv = np.argsort(order)
+        t, b = [int(inv[j]) if j >= 0 else -1 for j in t], [int(inv[j]) if j >= 0 else -1 for j in b]
+    hm, B, K, nv, n = hp.scattered_model(d, model) if not relist else model_of(d), 70, len(t), d.nv, d0.n_joints
+    tol = tolerance(d0, dtype_name)
+    idx = np.arange(B)
+    q, qd = laid_out(dev(torch, hp.to_q(R["q"], pq, d.nq), dtype), layout), laid_out(dev(torch, hp.to_v(R["qd"], pv, nv), dtype), layout)
+    J, J_rows, J_guard = outputs(torch, B, (6 * K, nv), layout, dtype)
+    c, c_rows, c_guard = outputs(torch, B, (K, 6), layout, dtype)
+    P, P_rows, P_guard = outputs(torch, B, (K, 12), layout, dtype)
+    PA, PA_rows, PA_guard = outputs(torch, B, (n, 12), layout, dtype)
+    hm.geometric_jacobian(q, t, b, R["poses"], qd, True, layout, out=(J, c))
+    hm.body_poses(q, t, R["poses"], layout, out=P)
+    hm.body_poses(q, None, None, layout, out=PA)
+    torch.cuda.synchronize()
+    label = f"scattered {model} holes={holes} relist={relist} layout={layout} {dtype_name}"
+    check_cover(c_rows, c_guard, idx, R["c"].reshape(B, -1), label=label + " convective", **tol)
+    check_cover(P_rows, P_guard, idx, R["P"].reshape(B, -1), label=label + " poses", **tol)
+    check_cover(PA_rows, PA_guard, idx, R["P_all"][:, order].reshape(B, -1), label=label + " poses of all bodies", **tol)
+    assert np.isnan(J_guard.cpu().numpy()).all(), label + " J: wrote past the last row"
+    J_host = J_rows.cpu().numpy().astype(np.float64).reshape(B, 6 * K, nv)
+    J_back, _ = hp.from_cols(J_host, pv)
+    assert not np.isnan(J_back).any(), label + " J: owned columns left unwritten"
+    close(J_back, R["J"], label=label + " J", **tol)
+    hp.assert_misses(hp.keep_order(J_host, pv), R["J"], "J, columns left where they are")
+    if not holes:  # the same description fed q as the identity description lists it: the poses must notice
+        hm.body_poses(laid_out(dev(torch, R["q"], dtype), layout), t, R["poses"], layout, out=P)
+        torch.cuda.synchronize()
+        hp.assert_misses(P_rows.cpu().numpy().astype(np.float64).reshape(B, K, 12), R["P"], "poses from q unmoved")
 
 
 def test_tree128_fp32(torch_cuda):

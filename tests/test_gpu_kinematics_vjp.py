@@ -9,10 +9,11 @@ import ctypes
 import numpy as np
 import pytest
 
+import helpers as hp
 import kinematics_check as kc
 import kinematics_vjp_check as kv
 from helpers import DistinctRows, check_bad_outputs, check_cover, close, f32_forward_tol, group_cover, poisoned
-from test_gpu_kinematics import AOS, B_MAX, INVALID, SOA, chains_of, dev, laid_out, model_of
+from test_gpu_kinematics import AOS, B_MAX, INVALID, SOA, scattered_chains, chains_of, dev, laid_out, model_of
 from test_kinematics_cpu import HUMANOID_TARGETS, make_case, states
 from test_kinematics_vjp_cpu import cotangents
 
@@ -104,6 +105,59 @@ def test_matches_checker(torch_cuda, case, layout, dtype_name):
         got = run_three(torch, hm, desc, B, layout, dtype, q, g, ga, w, R["t"], R["b"], R["poses"])
         for (name, rows, guard), ref in zip(got, (R["gq"], R["gq_all"], R["tau"])):
             check_cover(rows, guard, np.arange(B), ref[:B], tolerance(desc, dtype_name), label=f"{case} B={B} K={K} layout={layout} {dtype_name} {name}")
+
+
+def _scattered_reference(model, dtype_name):
+    """Configurations and cotangents in the identity description's index space and the checker's outputs on them: once per model and
+    precision, shared by the layouts, the hole and the re-listing cases, never modified."""
+    key = ("scattered", model, dtype_name)
+    if key not in _REFS:
+        sys_, d0 = hp.SCATTERED_MODELS[model]()
+        B = 70
+        t, b, poses = vjp_chains("humanoid30", d0, 5) if model == "humanoid30" else scattered_chains(model, d0)
+        K = len(t)
+        q = DistinctRows(sys_, 16, seed=73).rows(np.arange(B))[0]
+        g, ga, w = cotangents(B, K, 12, 74), cotangents(B, d0.n_joints, 12, 75), cotangents(B, K, 6, 76)
+        if dtype_name == "f32":
+            q, g, ga, w = (x.astype(np.float32).astype(np.float64) for x in (q, g, ga, w))
+        m = kc.KinModel(d0)
+        _REFS[key] = dict(q=q, g=g, ga=ga, w=w, t=t, b=b, poses=poses, gq=kv.body_poses_vjp(m, q, g, t, poses),
+                          gq_all=kv.body_poses_vjp(m, q, ga), tau=kv.jacobian_transpose(m, q, w, t, b, poses))
+    return _REFS[key]
+
+
+@pytest.mark.parametrize("dtype_name", ["f64", "f32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("model,holes,relist", [("mixed10", 0, False), ("mixed10", 2, False), ("humanoid30", 0, False), ("humanoid30", 0, True)])
+def test_scattered_index_maps(torch_cuda, model, holes, relist, layout, dtype_name):
+    """body_poses_vjp (listed targets and every body) and jacobian_transpose on a description whose maps send every DoF and every
+    configuration entry somewhere else (with holes: two indices of each space owned by no joint, holding 7.0 in q), against the checker on
+    the IDENTITY description under this file's tolerances.  q goes in through the configuration map, the gradients come back through the
+    DoF map; the cotangents follow the target list and do not move.  relist: the scattered description's joints are listed in a random
+    order, parents possibly after their children -- the joint lists are translated and the cotangents of "every body" follow the new
+    listing.  Unowned entries are exact zeros, the guard rows stay poisoned, and read without moving them back the gradients miss the
+    reference by more than 1e-3."""
+    torch = torch_cuda
+    dtype = torch.float64 if dtype_name == "f64" else torch.float32
+    sys_, d0, d, pv, pq = hp.scattered_case(model, holes)
+    R = _scattered_reference(model, dtype_name)
+    t, b, order = list(R["t"]), list(R["b"]), np.arange(d0.n_joints)
+    if relist:
+        d, order = hp.relisted(d, np.random.default_rng(77))
+        assert any(d.parent[k] > k for k in range(d.n_joints)) and hp.maps_flags(d) == (0, 1)
+        inv = np.argsort(order)
+        t, b = [int(inv[j]) if j >= 0 else -1 for j in t], [int(inv[j]) if j >= 0 else -1 for j in b]
+    hm, B = hp.scattered_model(d, model) if not relist else model_of(d), 70
+    q, g, ga, w = (dev(torch, x, dtype) for x in (hp.to_q(R["q"], pq, d.nq), R["g"], R["ga"][:, order], R["w"]))
+    got = run_three(torch, hm, d, B, layout, dtype, q, g, ga, w, t, b, R["poses"])
+    for (name, rows, guard), ref in zip(got, (R["gq"], R["gq_all"], R["tau"])):
+        label = f"scattered {model} holes={holes} relist={relist} layout={layout} {dtype_name} {name}"
+        assert torch.isnan(guard).all(), label + ": wrote past the last row"
+        raw = rows.cpu().numpy().astype(np.float64)
+        back, free = hp.from_v(raw, pv)
+        assert not np.isnan(raw).any() and not free.any(), label  # every entry written, the unowned ones as zeros
+        close(back, ref, tolerance(d0, dtype_name), label=label)
+        hp.assert_misses(hp.keep_order(raw, pv), ref, label)
 
 
 def test_tree128_fp32(torch_cuda):

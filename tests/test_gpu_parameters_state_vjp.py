@@ -14,6 +14,7 @@ import itertools
 import numpy as np
 import pytest
 
+import helpers as hp
 import inertial_parameters_check as ipc
 import parameters_state_vjp_check as sc
 from helpers import DistinctRows, check_bad_outputs, close_aba, f32_aba_forward_factor, f32_forward_tol, group_cover, poisoned, record_parity
@@ -447,6 +448,83 @@ def test_a_bad_row_stays_alone(torch_cuda, layout):
     assert all(np.array_equal(a[keep], b[keep]) for a, b in zip(clean_i, got_i))
     assert all(np.array_equal(a[keep], b[keep]) and np.isfinite(b[keep]).all() for a, b in zip(clean_f, got_f))
     assert all(not np.isfinite(g[k]).all() for g in got_f)
+
+
+# ------------------------------------------------------------------------------------------------ scattered index maps
+@functools.lru_cache(maxsize=None)
+def _scattered_reference(model, single):
+    """States, parameters and cotangents in the identity description's index space and the checker's outputs on them: once per model and
+    precision, shared by the layouts and the hole cases, never modified."""
+    sys_, d0 = hp.SCATTERED_MODELS[model]()
+    B, np_dt = 70, (np.float32 if single else np.float64)
+    q, qd, qdd, tau = DistinctRows(sys_, 16, seed=61).rows(np.arange(B), np_dt)
+    rnd = lambda x: np.asarray(x, dtype=np_dt).astype(np.float64)
+    pi, u, w = rnd(parameters(d0, B, 62)), rnd(cotangent(B, d0.nv, 63)), rnd(cotangent(B, d0.nv, 64))
+    f = rnd(random_wrenches(np.random.default_rng(65), B, d0.n_joints))
+    ref_i = sc.rnea_parameters_state_vjp(d0, q, qd, qdd, pi, u, GRAVITY, f)
+    ref_f = sc.aba_parameters_state_vjp(d0, q, qd, tau, pi, w, GRAVITY, f)
+    assert ref_f[-1][5].max() < 1.0e8  # cond_inf(H(pi_r)) of every row
+    return (q, qd, qdd, tau, pi, u, w, f), ref_i, ref_f
+
+
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("model,holes", hp.SCATTERED_CASES)
+def test_scattered_index_maps(torch_cuda, model, holes, layout, dtype_name):
+    """Both calls on a description whose maps send every DoF and every configuration entry somewhere else (with holes: two indices of each
+    space owned by no joint, holding 7.0 in every input, the cotangent included), a different parameter set in every row, against the
+    checker on the IDENTITY description: the state gradients come back through the DoF map and meet hold_inverse's / hold_forward's
+    bounds, gpi follows the listing order of the joints and does NOT move; the gradients at unowned indices are exact zeros, the guard
+    rows stay poisoned; each output asked for alone (the others NULL) meets the same bound; read without moving them back the state
+    gradients miss the reference by more than 1e-3."""
+    torch = torch_cuda
+    single = dtype_name == "float32"
+    dtype, unit = getattr(torch, dtype_name), (U32 if single else U64)
+    sys_, d0, d, pv, pq = hp.scattered_case(model, holes)
+    hm, B, nv, n = hp.scattered_model(d, model), 70, d.nv, d0.n_joints
+    (q, qd, qdd, tau, pi, u, w, f), ref_i, ref_f = _scattered_reference(model, single)
+    is_soa = layout == SOA
+    put = lambda x: soa(dev(torch, x.reshape(B, -1), dtype)) if is_soa else dev(torch, x.reshape(B, -1), dtype)
+    tq = put(hp.to_q(q, pq, d.nq))
+    tqd, tqdd, ttau, tu, tw = (put(hp.to_v(x, pv, nv)) for x in (qd, qdd, tau, u, w))
+    tpi, tf = put(pi), put(f)
+
+    def run(issue, shapes, want):
+        """[(moved back, unowned entries, as the device wrote it)] of the outputs `want`; gpi ([B, 10 n]) is not moved"""
+        outs, guards = hp.poisoned_set(torch, B, shapes, dtype, is_soa)
+        outs = [o if k in want else None for k, o in enumerate(outs)]
+        issue(tuple(outs))
+        torch.cuda.synchronize()
+        hp.guards_intact([g for k, g in enumerate(guards) if k in want])
+        res = []
+        for o, s in zip(outs, shapes):
+            raw = None if o is None else hp.rows_of(o, B, s, is_soa)
+            res.append(None if o is None else ((raw, raw[:, :0], raw) if s != (nv,) else hp.from_v(raw, pv) + (raw,)))
+        return res
+
+    def check(got, names, hold):
+        for k, g in enumerate(got):
+            if g is not None and names[k] != "qdd":  # (qdd is no gradient: its unowned entries are not written)
+                assert not g[1].any(), names[k]  # exact zeros at unowned indices, and written
+        hold([None if g is None else g[0] for g in got])
+
+    inverse = lambda out: hm.rnea_parameters_state_vjp(tq, tqd, tqdd, tpi, tu, GRAVITY, tf, layout, out=out)
+    forward = lambda out: hm.aba_parameters_state_vjp(tq, tqd, ttau, tpi, tw, GRAVITY, tf, layout, out=out)
+    tol = f32_forward_tol(3 * n) if single else TOL
+    shapes = [(nv,)] * 3 + [(10 * n,)]
+    got = run(inverse, shapes, (0, 1, 2, 3))
+    check(got, INV_NAMES, lambda g: hold_inverse(g, ref_i, u, "scattered", tol))
+    for k in range(4):
+        check(run(inverse, shapes, (k,)), INV_NAMES, lambda g: hold_inverse(g, ref_i, u, f"scattered, {INV_NAMES[k]} alone", tol))
+    for k in range(3):
+        hp.assert_misses(hp.keep_order(got[k][2], pv), ref_i[k], INV_NAMES[k])
+    shapes = [(nv,)] * 4 + [(10 * n,)]
+    got = run(forward, shapes, (0, 1, 2, 3, 4))
+    check(got, FWD_NAMES, lambda g: hold_forward(g, ref_f, w, n, "scattered", unit))
+    for k in range(1, 5):
+        check(run(forward, shapes, (k,)), FWD_NAMES, lambda g: hold_forward(g, ref_f, w, n, f"scattered, {FWD_NAMES[k]} alone", unit))
+    for k in range(4):
+        hp.assert_misses(hp.keep_order(got[k][2], pv), ref_f[k], "forward " + FWD_NAMES[k])
 
 
 # ------------------------------------------------------------------------------------------------ plumbing

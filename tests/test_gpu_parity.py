@@ -32,6 +32,7 @@ def dev(torch, x, dtype=None):
     return torch.tensor(np.ascontiguousarray(x), device="cuda", dtype=dtype or torch.float64)
 
 
+import helpers as hp  # noqa: E402
 from helpers import close, close_aba, f32_aba_backward_tol, f32_aba_forward_factor, f32_forward_tol  # noqa: E402  (logs every achieved error; absolute=True asserts |x - ref| <= tol outright)
 
 
@@ -841,6 +842,79 @@ def test_simulation_step_equals_aba_then_integrate(torch_cuda, B):
         close(nq.cpu().numpy(), r_q, 1e-12), close(nv.cpu().numpy(), r_v, 1e-11)
     finally:
         os.environ.pop("MH_SPEC_SPLIT", None)
+
+
+@pytest.mark.parametrize("model,holes", hp.SCATTERED_CASES)
+def test_integrate_and_step_on_scattered_index_maps(torch_cuda, model, holes):
+    """mh_integrate_f64 / _f32 (both layouts, into poisoned outputs and in place) and mh_aba_integrate_f64 (both layouts into poisoned
+    outputs, and in place) on a description whose maps send every DoF and every configuration entry somewhere else -- the humanoid then
+    cannot take the one-launch step of its identity build -- (with holes: two indices of each space owned by no joint, holding 7.0 in every input),
+    against the oracle on the IDENTITY description under the bounds of test_state_integrator_matches_oracle_and_ballistic (1e-13, 1e-12 for
+    the acceleration, f32_forward_tol(1) in fp32) and test_simulation_step_equals_aba_then_integrate (1e-10 / 1e-12 / 1e-11).  q moves
+    through the configuration map, everything else through the DoF map; unowned entries of the outputs are not written (in place: left
+    as they were), guard rows stay poisoned; read without moving them back the outputs miss the reference by more than 1e-3."""
+    torch = torch_cuda
+    import ctypes
+    from mecano_amd import _lib
+    from oracle.cpu_oracle import OracleModel
+    sys_, d0, d, pv, pq = hp.scattered_case(model, holes)
+    hm, om, B, nv, nq = hp.scattered_model(d, model), OracleModel(d0), 70, d.nv, d.nq
+    g, dt = (0.1, -0.2, -9.81), 1.3e-3
+    rows = hp.DistinctRows(sys_, 16, seed=91)
+    fext = np.random.default_rng(92).uniform(-2, 2, (B, d0.n_joints, 6))
+    moved = lambda q, *vs: (hp.to_q(q, pq, nq),) + tuple(hp.to_v(x, pv, nv) for x in vs)
+    for np_dt, tdt, tols in ((np.float64, torch.float64, (1e-13, 1e-13, 1e-12)), (np.float32, torch.float32, (f32_forward_tol(1),) * 3)):
+        q, qd, qdd, _ = rows.rows(np.arange(B), np_dt)
+        step = float(np_dt(dt))
+        ref = om.integrate(step, q, qd, qdd)
+        for soa in (False, True):
+            lay = (lambda x: x.t().contiguous()) if soa else (lambda x: x)
+            tq, tv, ta = (lay(dev(torch, x, tdt)) for x in moved(q, qd, qdd))
+            outs, guards = hp.poisoned_set(torch, B, [(nq,), (nv,), (nv,)], tdt, soa)
+            hm.integrate(step, tq, tv, ta, _lib.LAYOUT_SOA if soa else _lib.LAYOUT_AOS, out=tuple(outs))
+            in_q, in_v = tq.clone(), tv.clone()
+            hm.integrate(step, in_q, in_v, ta, _lib.LAYOUT_SOA if soa else _lib.LAYOUT_AOS, out=(in_q, in_v))
+            torch.cuda.synchronize()
+            hp.guards_intact(guards, "integrate")
+            got = [hp.rows_of(o, B, s, soa) for o, s in zip(outs, [(nq,), (nv,), (nv,)])]
+            for x, perm, r, tol, name in zip(got, (pq, pv, pv), ref, tols, ("q_next", "qd_next", "qdd_out")):
+                back, free = hp.from_v(x, perm)
+                assert np.isnan(free).all(), name  # entries no joint owns are not written
+                close(back, r, tol, label=f"scattered integrate {name} {np_dt.__name__} soa={soa}")
+                hp.assert_misses(hp.keep_order(x, perm), r, name)
+            for t, perm, r, tol, shape in ((in_q, pq, ref[0], tols[0], (nq,)), (in_v, pv, ref[1], tols[1], (nv,))):
+                back, free = hp.from_v(hp.rows_of(t, B, shape, soa), perm)
+                assert np.all(free == hp.UNOWNED)
+                close(back, r, tol, label=f"scattered integrate in place {np_dt.__name__} soa={soa}")
+    q, qd, _, tau = rows.rows(np.arange(B))
+    r_qdd = om.aba(q, qd, tau, g, fext)
+    r_q, r_v, _ = om.integrate(dt, q, qd, r_qdd)
+    gv, ra = hm._root(g)
+    for soa in (False, True):  # (the C call: HipModel.step allocates its outputs and is AoS only)
+        lay = (lambda x: x.reshape(B, -1).t().contiguous()) if soa else (lambda x: x)
+        tq, tv, tt, tf = (lay(dev(torch, x)) for x in moved(q, qd, tau) + (fext,))
+        (o_a, o_q, o_v), guards = hp.poisoned_set(torch, B, [(nv,), (nq,), (nv,)], torch.float64, soa)
+        opts = hm._options(_lib.LAYOUT_SOA if soa else _lib.LAYOUT_AOS, True, True, torch.cuda.current_stream().cuda_stream, root_acceleration=ra)
+        _lib.check(_lib.load().mh_aba_integrate_f64(hm._h, B, dt, tq.data_ptr(), tv.data_ptr(), tt.data_ptr(), gv, tf.data_ptr(), ctypes.byref(opts),
+                                                    o_a.data_ptr(), o_q.data_ptr(), o_v.data_ptr()))
+        torch.cuda.synchronize()
+        hp.guards_intact(guards, "step")
+        for t, perm, r, tol, name, shape in ((o_a, pv, r_qdd, 1e-10, "qdd", (nv,)), (o_q, pq, r_q, 1e-12, "q_next", (nq,)),
+                                             (o_v, pv, r_v, 1e-11, "qd_next", (nv,))):
+            raw = hp.rows_of(t, B, shape, soa)
+            back, free = hp.from_v(raw, perm)
+            assert np.isnan(free).all(), name
+            close(back, r, tol, label=f"scattered step {name} soa={soa}")
+            hp.assert_misses(hp.keep_order(raw, perm), r, "step " + name)
+    tq, tv, tt = (dev(torch, x) for x in moved(q, qd, tau))
+    rq, rv = q, qd  # three in-place steps against three oracle steps
+    for _ in range(3):
+        a = om.aba(rq, rv, tau, g)
+        rq, rv, _ = om.integrate(dt, rq, rv, a)
+        hm.step(dt, tq, tv, tt, g, inplace=True)
+    (bq, fq), (bv, fv) = hp.from_v(tq.cpu().numpy(), pq), hp.from_v(tv.cpu().numpy(), pv)
+    assert np.all(fq == hp.UNOWNED) and np.all(fv == hp.UNOWNED)
+    close(bq, rq, 1e-11, label="scattered step in place q"), close(bv, rv, 1e-10, label="scattered step in place qd")
 
 
 @pytest.mark.parametrize("kinds", [("planar",), ("spherical",), ("revolute", "prismatic", "planar", "spherical", "sixdof", "fixed")])

@@ -13,13 +13,14 @@ import ctypes
 import numpy as np
 import pytest
 
+import helpers as hp
 import kinematics_check as kc
 import relative_constraints_check as rc
 from helpers import DistinctRows, U32, check_cover, close, close_aba, f32_aba_forward_factor, group_cover, poisoned
 from oracle.cpu_oracle import OracleModel
 from test_constrained_dynamics_cpu import GRAVITY
 from test_gpu_constrained_dynamics import (AOS, BATCHES, B_MAX, INVALID, SOA, U64, check_exact_zeros, dev, hip_model, hold_residual, laid_out,
-                                           outputs, torch_cuda)  # noqa: F401 (torch_cuda is a fixture)
+                                           moved_inputs, outputs, scattered_description, torch_cuda)  # noqa: F401 (torch_cuda is a fixture)
 from test_relative_constraints_cpu import (CASES, P_BASES, P_GRAVITY, P_POSES, P_ROWS, P_TARGETS, make_inputs, model_of, parallelogram,
                                            parallelogram_state, reference, reference_impulse)
 
@@ -108,6 +109,41 @@ def test_matches_checker(torch_cuda, name, layout, dtype_name):
         Hv, Hq = np.einsum("bij,bj->bi", H, v), np.einsum("bij,bj->bi", H, I["qd"][:B])
         scale = np.abs(Hv).max(axis=1) + np.abs(Hq).max(axis=1) + np.abs(JTp).max(axis=1)
         hold_residual(np.abs(Hv - Hq - JTp).max(axis=1), scale, RI["cond_H"][:B], n, u, label + " momentum balance")
+
+
+@pytest.mark.parametrize("dtype_name", ["f64", "f32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("name,holes,relist", [("humanoid_mixed", 0, False), ("humanoid_mixed", 0, True), ("humanoid_mixed", 2, False)])
+def test_scattered_index_maps(torch_cuda, name, holes, relist, layout, dtype_name):
+    """The between-bodies forms on the humanoid with maps that send every DoF and every configuration entry somewhere else (also with two
+    indices of each space owned by no joint, holding 7.0 in every state input, and with its joints re-listed, the target and base lists
+    translated and the external wrenches in the new order), with test_matches_checker's lists, poses and inputs, against ITS references -- the checker on
+    the identity description -- under its bound: close_aba on (qdd, lambda) resp. (qd+, impulse) with cond_inf(KKT).  Guard rows stay
+    poisoned; read without moving them back qdd and qd+ miss the reference by more than 1e-3."""
+    torch = torch_cuda
+    dtype, u = (torch.float64, U64) if dtype_name == "f64" else (torch.float32, U32)
+    I, R, RI = references(name, dtype_name)
+    sys_, desc, om = model_of(name)
+    d, pv, pq, targets, bases, order = scattered_description(name, desc, holes, relist, I["targets"], I["bases"])
+    hm = hip_model(d)
+    assert relist or hm.kernel_variant.startswith("topo:"), hm.kernel_variant
+    B, K, n, nv = 70, len(targets), desc.n_joints, d.nv
+    D, J = moved_inputs(torch, I, B, pv, pq, d, order, layout, dtype), dict(I, targets=targets, bases=bases)
+    label = f"scattered {name} holes={holes} relist={relist} layout={layout} {dtype_name}"
+    for call, ref, x_key, l_key in ((call_constrained, R, "qdd", "lam"), (call_impulse, RI, "qd_next", "impulse")):
+        x, x_rows, x_guard = outputs(torch, B, (nv,), layout, dtype)
+        lam, lam_rows, lam_guard = outputs(torch, B, (K, 6), layout, dtype)
+        call(hm, D, J, layout, (x, lam))
+        torch.cuda.synchronize()
+        assert torch.isnan(x_guard).all() and torch.isnan(lam_guard).all(), f"{label} {x_key}: wrote past the end"
+        raw, l = x_rows.cpu().numpy().astype(np.float64), lam_rows.cpu().numpy().astype(np.float64).reshape(B, K, 6)
+        back, free = hp.from_v(raw, pv)
+        assert not np.isnan(back).any() and not np.isnan(l).any(), f"{label} {x_key}: entries left unwritten"
+        assert x_key == "qdd" or np.all(free == hp.UNOWNED), f"{label}: entries of qd_out no joint owns do not hold those of qd"
+        check_exact_zeros(l, I, B, f"{label} {l_key}")
+        close_aba(np.concatenate([back, l.reshape(B, -1)], axis=1), np.concatenate([ref[x_key][:B], ref[l_key][:B].reshape(B, -1)], axis=1), None, n, u,
+                  label=f"{label} ({x_key}, {l_key})", conds=ref["cond_kkt"][:B])
+        hp.assert_misses(hp.keep_order(raw, pv), ref[x_key][:B], f"{label} {x_key}")
 
 
 def test_parallelogram_known_answer(torch_cuda):

@@ -6,6 +6,7 @@ import functools
 import numpy as np
 import pytest
 
+import helpers as hp
 import step_derivatives_check as sc
 from helpers import check_bad_outputs, close, close_aba, poisoned
 from mecano_amd import random_tools as rt
@@ -471,3 +472,126 @@ def test_calculator_mirror(torch_cuda):
     for g, w in zip(got, want):
         if not torch.equal(g, w):  # (two models: forward dynamics may take another plan)
             close_aba(g.cpu().numpy().reshape(B, -1), w.cpu().numpy().reshape(B, -1), None, 3 * desc.n_joints + 1, U64, conds=conds)
+
+
+# ------------------------------------------------------------------------------------------------ scattered index maps
+SCATTERED_DT = 0.05
+
+
+@functools.lru_cache(maxsize=None)
+def _scattered_reference(model, dtype_name):
+    """States in the identity description's index space, the checker's (qdd, A, B) on them, the oracle's step and cond_inf(H) per row:
+    once per model and precision, shared by the layouts and the hole cases, never modified."""
+    sys_, d0 = hp.SCATTERED_MODELS[model]()
+    np_dt = np.float32 if dtype_name == "float32" else np.float64
+    q, qd, _, tau = hp.DistinctRows(sys_, 16, seed=45).rows(np.arange(B70), np_dt)
+    f = random_wrenches(np.random.default_rng(46), B70, d0.n_joints).astype(np_dt).astype(np.float64)
+    qdd, A, Bm = sc.step_derivatives(d0, SCATTERED_DT, q, qd, tau, GRAVITY, f)
+    om = OracleModel(d0)
+    qn, vn = om.integrate(SCATTERED_DT, q, qd, qdd)[:2]
+    conds = np.array([np.linalg.cond(h, np.inf) for h in om.crba(q)])
+    assert conds.max() < 1.0e8
+    return (q, qd, tau, f), (qdd, qn, vn, A, Bm), conds
+
+
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("model,holes", hp.SCATTERED_CASES)
+def test_scattered_index_maps(torch_cuda, model, holes, layout, dtype_name):
+    """step_derivatives on a description whose maps send every DoF and every configuration entry somewhere else (with holes: two indices
+    of each space owned by no joint, holding 7.0 in every input), on moved states, against the checker on the IDENTITY description.  A and B
+    go back through both copies of the DoF space stacked in them, q_next through the configuration map, qdd and qd_next through the DoF map;
+    bounds: test_fp64_matches_checker's / the fp32 test's (close_aba, 3 n + 1 for the matrices, n for the vectors).  Rows and columns of
+    unowned indices are exact zeros, unowned entries of q_next / qd_next are not written, the guard rows stay poisoned; with the rows or
+    the columns left where they are A and B miss the reference by more than 1e-3; at dt = 0 A is the identity on the owned indices and B
+    is zero, exactly."""
+    torch = torch_cuda
+    dtype, u = getattr(torch, dtype_name), (U32 if dtype_name == "float32" else U64)
+    sys_, d0, d, pv, pq = hp.scattered_case(model, holes)
+    hm, B, nv, nq, n = hp.scattered_model(d, model), B70, d.nv, d.nq, d0.n_joints
+    (q, qd, tau, f), ref, conds = _scattered_reference(model, dtype_name)
+    is_soa = layout == SOA
+    lay = soa if is_soa else (lambda x: x)
+    tq, tqd, ttau = (lay(dev(torch, x, dtype)) for x in (hp.to_q(q, pq, nq), hp.to_v(qd, pv, nv), hp.to_v(tau, pv, nv)))
+    tf = lay(dev(torch, f, dtype))
+    shapes = [(nv,), (nq,), (nv,), (2 * nv, 2 * nv), (2 * nv, nv)]
+    free_v, free_q = hp.unowned(pv, nv), hp.unowned(pq, nq)
+    for dt in (SCATTERED_DT, 0.0):
+        outs, guards = hp.poisoned_set(torch, B, shapes, dtype, is_soa)
+        hm.step_derivatives(dt, tq, tqd, ttau, GRAVITY, tf, layout, out=tuple(outs))
+        torch.cuda.synchronize()
+        hp.guards_intact(guards, f"step_derivatives dt {dt}")
+        qdd, qn, vn, A, Bm = (hp.rows_of(o, B, s, is_soa) for o, s in zip(outs, shapes))
+        assert np.isnan(qn[:, free_q]).all() and np.isnan(vn[:, free_v]).all()  # entries no joint owns are not written
+        (A_back, A_rows, A_cols), (B_back, B_rows, B_cols) = hp.from_step(A, pv), hp.from_step(Bm, pv)
+        assert not A_rows.any() and not A_cols.any() and not B_rows.any() and not B_cols.any()  # exact zeros, and written
+        if dt == 0.0:
+            assert np.array_equal(A_back, np.broadcast_to(np.eye(2 * d0.nv), A_back.shape)) and not B_back.any()
+            assert np.array_equal(hp.from_v(vn, pv)[0], qd.astype(np.float32 if dtype_name == "float32" else np.float64))
+            continue
+        close_aba(hp.from_v(qdd, pv)[0], ref[0], None, n, u, label="scattered qdd", conds=conds)
+        close_aba(hp.from_v(qn, pq)[0], ref[1], None, n, u, label="scattered q_next", conds=conds)
+        close_aba(hp.from_v(vn, pv)[0], ref[2], None, n, u, label="scattered qd_next", conds=conds)
+        close_aba(A_back.reshape(B, -1), ref[3].reshape(B, -1), None, 3 * n + 1, u, label="scattered A", conds=conds)
+        close_aba(B_back.reshape(B, -1), ref[4].reshape(B, -1), None, 3 * n + 1, u, label="scattered B", conds=conds)
+        hp.assert_misses(hp.keep_order(qn, pq), ref[1], "q_next")
+        hp.assert_misses(hp.keep_order(vn, pv), ref[2], "qd_next")
+        for M, r, name in ((A, ref[3], "A"), (Bm, ref[4], "B")):
+            hp.assert_misses(hp.keep_order_step(M, pv, rows=True, cols=False), r, f"{name}, rows left where they are")
+            hp.assert_misses(hp.keep_order_step(M, pv, rows=False, cols=True), r, f"{name}, columns left where they are")
+
+
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("model,holes", hp.SCATTERED_CASES)
+def test_chart_on_scattered_index_maps(torch_cuda, model, holes, layout):
+    """configuration_add (into a fresh output and onto q itself) and configuration_difference on scattered maps against the checker on the
+    IDENTITY description, test_chart_matches_checker_round_trip_and_in_place's 1e-13 absolute; unowned entries of the difference are
+    exact zeros, of the sum not written; read without moving them back both miss the reference by more than 1e-3.  fp32: the round trip
+    (q (+) dq) (-) q = dq of that test under its 64 * 4 * 2^-24 absolute, and the sum against the checker on the fp32-rounded inputs under
+    the same figure (an entry of the sum is one rotation and one addition on |q| <= 4: a few u |q|, far inside it)."""
+    torch = torch_cuda
+    sys_, d0, d, pv, pq = hp.scattered_case(model, holes)
+    hm, m0, B, nv, nq = hp.scattered_model(d, model), sc.StepModel(d0), B70, d.nv, d.nq
+    rows = hp.DistinctRows(sys_, 16, seed=47)
+    q0, q1 = rows.rows(np.arange(B))[0], rows.rows(np.arange(B, 2 * B))[0]
+    dq = np.random.default_rng(48).uniform(-1.0, 1.0, (B, d0.nv))
+    dq[0] *= 1.0e-9
+    is_soa = layout == SOA
+    lay = soa if is_soa else (lambda x: x)
+    tq0, tq1, tdq = (lay(dev(torch, x)) for x in (hp.to_q(q0, pq, nq), hp.to_q(q1, pq, nq), hp.to_v(dq, pv, nv)))
+    (added, diff), guards = hp.poisoned_set(torch, B, [(nq,), (nv,)], torch.float64, is_soa)
+    hm.configuration_add(tq0, tdq, layout, out=added)
+    hm.configuration_difference(tq0, tq1, layout, out=diff)
+    in_place = tq0.clone()
+    assert hm.configuration_add(in_place, tdq, layout, out=in_place) is in_place
+    torch.cuda.synchronize()
+    hp.guards_intact(guards, "chart")
+    added, diff, in_place = hp.rows_of(added, B, (nq,), is_soa), hp.rows_of(diff, B, (nv,), is_soa), hp.rows_of(in_place, B, (nq,), is_soa)
+    add_ref, diff_ref = sc.configuration_add(m0, q0, dq), sc.configuration_difference(m0, q0, q1)
+    (add_back, add_free), (diff_back, diff_free), (place_back, place_free) = hp.from_v(added, pq), hp.from_v(diff, pv), hp.from_v(in_place, pq)
+    assert np.isnan(add_free).all() and not diff_free.any() and np.all(place_free == hp.UNOWNED)
+    close(add_back, add_ref, 1.0e-13, absolute=True, label="scattered add")
+    close(diff_back, diff_ref, 1.0e-13, absolute=True, label="scattered difference")
+    assert np.array_equal(place_back, add_back)
+    hp.assert_misses(hp.keep_order(added, pq), add_ref, "add")
+    hp.assert_misses(hp.keep_order(diff, pv), diff_ref, "difference")
+    # fp32 (mh_configuration_add_f32 / _difference_f32 read both maps too): that test's round trip (q (+) dq) (-) q = dq within its
+    # 64 * 4 u absolute, on the scattered description, and the sum itself against the checker on the fp32-rounded inputs to the same bound
+    f32 = torch.float32
+    q32, dq32 = q0.astype(np.float32).astype(np.float64), dq.astype(np.float32).astype(np.float64)
+    sq, sdq = lay(dev(torch, hp.to_q(q32, pq, nq), f32)), lay(dev(torch, hp.to_v(dq32, pv, nv), f32))
+    (added32, back32), guards = hp.poisoned_set(torch, B, [(nq,), (nv,)], f32, is_soa)
+    hm.configuration_add(sq, sdq, layout, out=added32)
+    torch.cuda.synchronize()
+    assert np.isnan(hp.from_v(hp.rows_of(added32, B, (nq,), is_soa), pq)[1]).all()  # unowned entries of the sum are not written
+    (added32 if not is_soa else added32.t())[:, torch.as_tensor(hp.unowned(pq, nq), device="cuda")] = hp.UNOWNED  # (an input next: finite there)
+    hm.configuration_difference(sq, added32, layout, out=back32)
+    torch.cuda.synchronize()
+    hp.guards_intact(guards, "fp32 chart")
+    added32, back32 = hp.rows_of(added32, B, (nq,), is_soa), hp.rows_of(back32, B, (nv,), is_soa)
+    trip, trip_free = hp.from_v(back32, pv)
+    assert not trip_free.any() and not np.isnan(trip).any()
+    close(trip, dq32, 64 * U32 * 4.0, absolute=True, label="scattered fp32 round trip")
+    close(hp.from_v(added32, pq)[0], sc.configuration_add(m0, q32, dq32), 64 * U32 * 4.0, absolute=True, label="scattered fp32 add")
+    hp.assert_misses(hp.keep_order(back32, pv), dq32, "fp32 round trip")
+    hp.assert_misses(hp.keep_order(added32, pq), sc.configuration_add(m0, q32, dq32), "fp32 add")

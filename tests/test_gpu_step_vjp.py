@@ -13,6 +13,7 @@ import functools
 import numpy as np
 import pytest
 
+import helpers as hp
 import step_vjp_check as svc
 from helpers import DistinctRows, check_bad_outputs, close_aba, f32_aba_forward_factor, group_cover, poisoned, record_parity
 from mecano_amd import random_tools as rt
@@ -281,6 +282,104 @@ def test_unowned_dof_indices_get_zeros_and_are_not_read(torch_cuda):
         for k, (g, r, b) in enumerate(zip(got[1:], ref[1:4], (bA, bA, bB))):
             assert not np.isnan(g).any() and not g[:, free].any(), f"step_vjp output {k}"
             held_rows(g[:, place], r, b, f"step_vjp output {k}, wide map")
+
+
+@functools.lru_cache(maxsize=None)
+def _scattered_reference(model, f32):
+    """States and cotangents in the identity description's index space and the checker's outputs on them: once per model and precision,
+    shared by the layouts and the hole cases, never modified."""
+    sys_, d0 = hp.SCATTERED_MODELS[model]()
+    np_dt = np.float32 if f32 else np.float64
+    dt = float(np_dt(0.05))
+    q, qd, qdd, tau = DistinctRows(sys_, 16, seed=55).rows(np.arange(B70), np_dt)
+    ga, gb = (x.astype(np_dt).astype(np.float64) for x in cotangents(B70, d0.nv, 56))
+    f = random_wrenches(np.random.default_rng(57), B70, d0.n_joints).astype(np_dt).astype(np.float64)
+    conds = conds_of(d0, q)
+    assert conds.max() < 1.0e8
+    return (dt, q, qd, qdd, tau, ga, gb, f, conds, svc.integrate_vjp(d0, dt, qd, qdd, ga, gb), svc.step_vjp(d0, dt, q, qd, tau, ga, gb, GRAVITY, f))
+
+
+@pytest.mark.parametrize("dtype_name", ["float64", "float32"])
+@pytest.mark.parametrize("layout", [AOS, SOA])
+@pytest.mark.parametrize("model,holes", hp.SCATTERED_CASES)
+def test_scattered_index_maps(torch_cuda, model, holes, layout, dtype_name):
+    """integrate_vjp and step_vjp on a description whose maps send every DoF and every configuration entry somewhere else (with holes:
+    two indices of each space owned by no joint, holding 7.0 in every input, the cotangents included), against the checker on the
+    IDENTITY description.  The cotangents go in and every gradient comes back through the DoF map, under this file's bounds (held_entries
+    for the integrator's transpose, check_step's for the step); the gradients at unowned indices are exact zeros, the guard rows stay
+    poisoned; each gradient asked for alone (the other outputs NULL) meets the same bound; read without moving them back the outputs
+    miss the reference by more than 1e-3."""
+    torch = torch_cuda
+    f32 = dtype_name == "float32"
+    dtype, unit = getattr(torch, dtype_name), (U32 if f32 else U64)
+    sys_, d0, d, pv, pq = hp.scattered_case(model, holes)
+    hm, B, nv, n = hp.scattered_model(d, model), B70, d.nv, d0.n_joints
+    dt, q, qd, qdd, tau, ga, gb, f, conds, ref_i, ref_s = _scattered_reference(model, f32)
+    tq = lay(dev(torch, hp.to_q(q, pq, d.nq), dtype), layout)
+    tqd, tqdd, ttau, tga, tgb = (lay(dev(torch, hp.to_v(x, pv, nv), dtype), layout) for x in (qd, qdd, tau, ga, gb))
+    tf = lay(dev(torch, f, dtype), layout)
+    is_soa = layout == SOA
+
+    def run(issue, places, want):
+        outs, guards = hp.poisoned_set(torch, B, [(nv,)] * places, dtype, is_soa)
+        outs = [o if k in want else None for k, o in enumerate(outs)]
+        issue(tuple(outs))
+        torch.cuda.synchronize()
+        hp.guards_intact([g for k, g in enumerate(guards) if k in want])
+        return [None if o is None else hp.from_v(hp.rows_of(o, B, (nv,), is_soa), pv) + (hp.rows_of(o, B, (nv,), is_soa),) for o in outs]
+
+    integrate = lambda out: hm.integrate_vjp(dt, tqd, tqdd, tga, tgb, layout, out=out)
+    step = lambda out: hm.step_vjp(dt, tq, tqd, ttau, tga, tgb, GRAVITY, tf, layout, out=out)
+    *ref, sums = ref_i
+    got = run(integrate, 3, (0, 1, 2))
+    for k, (r, s, name) in enumerate(zip(ref, sums, ("gq", "gqd", "gqdd"))):
+        for (back, free, raw), what in ((got[k], ""), (run(integrate, 3, (k,))[k], " alone")):
+            assert not free.any(), name  # exact zeros, and written
+            held_entries(back, r, s, unit, f"scattered integrate_vjp {name}{what}")
+        hp.assert_misses(hp.keep_order(got[k][2], pv), r, "integrate_vjp " + name)
+    qdd_ref, gq, gqd, gtau, _, (Ainf, Binf) = ref_s
+    bA, bB = step_bounds(ga, gb, conds, n, unit, Ainf, Binf)
+    got = run(step, 4, (0, 1, 2, 3))
+    close_aba(got[0][0], qdd_ref, None, n, unit, label="scattered step_vjp qdd", conds=conds)
+    for k, (r, b, name) in enumerate(zip((gq, gqd, gtau), (bA, bA, bB), ("gq", "gqd", "gtau")), start=1):
+        for (back, free, raw), what in ((got[k], ""), (run(step, 4, (k,))[k], " alone")):
+            assert not free.any(), name
+            held_rows(back, r, b, f"scattered step_vjp {name}{what}")
+        hp.assert_misses(hp.keep_order(got[k][2], pv), r, "step_vjp " + name)
+
+
+@pytest.mark.parametrize("model,holes", hp.SCATTERED_CASES)
+def test_chart_maps_on_scattered_index_maps(torch_cuda, model, holes):
+    """chart_cotangent and chart_pullback (torch operations on the description's index maps, here on device tensors) on scattered maps
+    against the tangent map T of q (+) dq built from its definition on the IDENTITY description (tests/test_step_vjp_cpu.py, whose bound
+    this is: 1e-14 max(1, |ref|_inf)): the cotangent is T^T g_raw; at unit quaternions the pull-back is T g with the quaternion rows
+    taken four times ((2 / |Q|) Q o (g, 0) against the column Q o (e_k, 0) / 2).  q and g_raw live in the configuration space, g in the
+    DoF space; unowned entries hold 7.0 on the way in and exact zeros on the way out; read without moving them back both miss the
+    reference by more than 1e-3."""
+    from test_step_vjp_cpu import tangent_map
+    from mecano_amd import autograd as mha
+    torch = torch_cuda
+    sys_, d0, d, pv, pq = hp.scattered_case(model, holes)
+    hm, B = hp.scattered_model(d, model), B70
+    q = DistinctRows(sys_, 16, seed=58).rows(np.arange(B))[0]
+    rng = np.random.default_rng(59)
+    g_raw, g = rng.uniform(-1.0, 1.0, (B, d0.nq)), rng.uniform(-1.0, 1.0, (B, d0.nv))
+    T = np.stack([tangent_map(d0, q[b]) for b in range(B)])
+    quat_rows = np.array(sorted(c for rows in mha.chart_maps(d0)["quat_q"] for c in rows), dtype=int)
+    assert len(quat_rows) and np.abs(np.linalg.norm(q[:, quat_rows[:4]], axis=1) - 1.0).max() < 1e-12
+    T4 = T.copy()
+    T4[:, quat_rows, :] *= 4.0
+    ref_cot, ref_pull = np.einsum("bqv,bq->bv", T, g_raw), np.einsum("bqv,bv->bq", T4, g)
+    tq = dev(torch, hp.to_q(q, pq, d.nq))
+    cot = hm.chart_cotangent(tq, dev(torch, hp.to_q(g_raw, pq, d.nq))).cpu().numpy()
+    pull = hm.chart_pullback(tq, dev(torch, hp.to_v(g, pv, d.nv))).cpu().numpy()
+    for raw, perm, ref, name in ((cot, pv, ref_cot, "chart_cotangent"), (pull, pq, ref_pull, "chart_pullback")):
+        back, free = hp.from_v(raw, perm)
+        assert not np.isnan(raw).any() and not free.any(), name
+        err, bound = float(np.abs(back - ref).max()), 1.0e-14 * max(1.0, float(np.abs(ref).max()))
+        record_parity(err, bound, f"scattered {name}")
+        assert err <= bound, f"{name}: {err:.3e} > {bound:.3e}"
+        hp.assert_misses(hp.keep_order(raw, perm), ref, name)
 
 
 # ------------------------------------------------------------------------------------------------ 6. cover of batches
