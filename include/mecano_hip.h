@@ -748,6 +748,60 @@ mh_status mh_aba_integrate_vjp_f32(mh_model_t model, int64_t B, double dt, const
                                    const mh_options *opts, float *qdd_out, float *gq_out, float *gqd_out, float *gtau_out);
 
 /*
+ * ---- forward-mode derivatives (JVP) of the dynamics, the integrator and the simulation step: the matrices of mh_rnea_derivatives_*,
+ *      mh_aba_derivatives_* and mh_aba_integrate_derivatives_* times DIRECTIONS, without forming them (no calculator of the reference) ----
+ * The conventions are those of the matrices: dq is a velocity-space step of mh_configuration_add_*, the components of qd, qdd and tau
+ * move by plain increments, external wrenches are held IN THE WORLD, dq_next is the velocity-space step of q_next and qd_next of a SixDoF
+ * joint is in the NEW frame.  Every direction and every tangent output is [B][nv] (MH_LAYOUT_SOA: [nv][B]), with the strides and index
+ * maps of qd.
+ * mh_rnea_jvp_*: dtau_out = (d tau / d q) dq + (d tau / d qd) dqd + H dqdd at (q, qd, qdd).  ONE launch of a run-time-topology kernel, the
+ * tangent of the Newton-Euler recursion: two sweeps, O(n), nv numbers written per configuration.  consider_coriolis,
+ * consider_accelerations and use_root_acceleration are honoured as by mh_rnea_vjp_*: with consider_coriolis = 0 qd and dqd may be NULL and
+ * dqd contributes nothing, with consider_accelerations = 0 qdd may be NULL (H dqdd is formed all the same).
+ * mh_aba_jvp_*: dqdd_out = H^-1 (dtau - (d tau / d q) dq - (d tau / d qd) dqd) at qdd = mh_aba_*(q, qd, tau), which goes to qdd_out
+ * (may be NULL).  Launches composed on opts->stream: forward dynamics (whichever plan mh_aba_* takes, with the caller's switches), the
+ * tangent sweep at (q, qd, qdd) with both switches on, which writes the right-hand side, and forward dynamics at rest on it.  Without dq
+ * and dqd the sweep is dropped and the first launch runs only for qdd_out; dqdd_out then has the bits of mh_aba_vjp_*'s gtau_out for
+ * w = dtau.  Scratch: at most 2 B nv elements of the context (qdd where the caller takes none, and the right-hand side).
+ * mh_integrate_jvp_*: (dq_next_out, dqd_next_out) = the integrator's per-joint tangent map at (qd, qdd) and step dt applied to
+ * (dq, dqd, dqdd); mh_integrate_vjp_* is its transpose.  ONE elementwise launch, no workspace; joint source modes play no part.  At least
+ * one of the two outputs must be given.
+ * mh_aba_integrate_jvp_*: (dq_next_out, dqd_next_out) = A (dq, dqd) + B dtau with the (A, B) of mh_aba_integrate_derivatives_*, and
+ * dqdd_out as mh_aba_jvp_* gives it: exactly mh_aba_jvp_* followed by mh_integrate_jvp_*, four launches, at most 3 B nv elements of
+ * scratch.  At least one of dqdd_out, dq_next_out and dqd_next_out must be given; qdd_out may be NULL.
+ * All: a direction that is NULL is zero and is not read; all directions NULL is MH_ERR_INVALID_ARGUMENT.  All-zero directions give exact
+ * zeros.  Every entry of an output given is written once, zeros at DoF indices no joint owns included (direction entries there are not
+ * read), nothing outside the outputs.  The outputs overlap neither the inputs, directions included, nor each other.  dt may be 0
+ * (dq_next = dq, dqd_next = dqd exactly on owned DoFs) or negative; a dt that is not finite is MH_ERR_INVALID_ARGUMENT, as are
+ * MH_ACCELERATION_SOURCE joints in the model and gravity == NULL without a root acceleration (mh_integrate_jvp_* takes neither).  B = 0 or
+ * nv = 0 returns MH_OK and touches nothing.  Device pointers, asynchronous on opts->stream, layouts, index maps and contexts honoured; the
+ * scratch is what mh_reserve / mh_context_reserve set aside for the reverse-mode calls, after which the calls only enqueue work
+ * (graph-capturable).
+ */
+mh_status mh_rnea_jvp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double gravity[3],
+                          const double *f_ext, const double *dq, const double *dqd, const double *dqdd, const mh_options *opts,
+                          double *dtau_out);
+mh_status mh_rnea_jvp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const double gravity[3],
+                          const float *f_ext, const float *dq, const float *dqd, const float *dqdd, const mh_options *opts,
+                          float *dtau_out);
+mh_status mh_aba_jvp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
+                         const double *f_ext, const double *dq, const double *dqd, const double *dtau, const mh_options *opts,
+                         double *qdd_out, double *dqdd_out);
+mh_status mh_aba_jvp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const double gravity[3],
+                         const float *f_ext, const float *dq, const float *dqd, const float *dtau, const mh_options *opts,
+                         float *qdd_out, float *dqdd_out);
+mh_status mh_integrate_jvp_f64(mh_model_t model, int64_t B, double dt, const double *qd, const double *qdd, const double *dq,
+                               const double *dqd, const double *dqdd, const mh_options *opts, double *dq_next_out, double *dqd_next_out);
+mh_status mh_integrate_jvp_f32(mh_model_t model, int64_t B, double dt, const float *qd, const float *qdd, const float *dq,
+                               const float *dqd, const float *dqdd, const mh_options *opts, float *dq_next_out, float *dqd_next_out);
+mh_status mh_aba_integrate_jvp_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *tau,
+                                   const double gravity[3], const double *f_ext, const double *dq, const double *dqd, const double *dtau,
+                                   const mh_options *opts, double *qdd_out, double *dqdd_out, double *dq_next_out, double *dqd_next_out);
+mh_status mh_aba_integrate_jvp_f32(mh_model_t model, int64_t B, double dt, const float *q, const float *qd, const float *tau,
+                                   const double gravity[3], const float *f_ext, const float *dq, const float *dqd, const float *dtau,
+                                   const mh_options *opts, float *qdd_out, float *dqdd_out, float *dq_next_out, float *dqd_next_out);
+
+/*
  * ---- inverse and forward dynamics with per-configuration inertial parameters: B different robots of one topology and geometry
  *      (domain randomisation, identification by simulation error, payload sweeps; no calculator of the reference evaluates a batch) ----
  * pi (DEVICE) is [B][n_joints][10], MH_LAYOUT_SOA: [10 n_joints][B] (opts->layout, as for every other matrix of the call).  The ten

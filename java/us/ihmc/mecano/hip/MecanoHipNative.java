@@ -193,6 +193,43 @@ public final class MecanoHipNative
    /** the same in fp32 */
    static final MethodHandle ABA_INTEGRATE_VJP_F32 = handle("mh_aba_integrate_vjp_f32", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
                                                                                                ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * Forward-mode derivatives of the inverse dynamics: (model, B, q, qd, qdd, gravity[3] (host), f_ext|NULL, dq|NULL, dqd|NULL, dqdd|NULL,
+    * opts|NULL, dtau_out), vectors [B][nv]; not all three directions NULL.
+    */
+   static final MethodHandle RNEA_JVP = handle("mh_rnea_jvp_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                         ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle RNEA_JVP_F32 = handle("mh_rnea_jvp_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                             ADDRESS, ADDRESS));
+   /**
+    * Forward-mode derivatives of the forward dynamics: (model, B, q, qd, tau, gravity[3] (host), f_ext|NULL, dq|NULL, dqd|NULL, dtau|NULL,
+    * opts|NULL, qdd_out|NULL, dqdd_out), vectors [B][nv]; not all three directions NULL.
+    */
+   static final MethodHandle ABA_JVP = handle("mh_aba_jvp_f64", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                       ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle ABA_JVP_F32 = handle("mh_aba_jvp_f32", status(ADDRESS, JAVA_LONG, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                           ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * Forward-mode derivatives of the integrator: (model, B, dt, qd, qdd, dq|NULL, dqd|NULL, dqdd|NULL, opts|NULL, dq_next_out|NULL,
+    * dqd_next_out|NULL), vectors [B][nv]; not all three directions NULL, not both outputs NULL.
+    */
+   static final MethodHandle INTEGRATE_JVP = handle("mh_integrate_jvp_f64", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                   ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle INTEGRATE_JVP_F32 = handle("mh_integrate_jvp_f32", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                       ADDRESS, ADDRESS, ADDRESS));
+   /**
+    * Forward-mode derivatives of the simulation step: (model, B, dt, q, qd, tau, gravity[3] (host), f_ext|NULL, dq|NULL, dqd|NULL, dtau|NULL,
+    * opts|NULL, qdd_out|NULL, dqdd_out|NULL, dq_next_out|NULL, dqd_next_out|NULL), vectors [B][nv]; not all three directions NULL, not all
+    * three tangents NULL.
+    */
+   static final MethodHandle ABA_INTEGRATE_JVP = handle("mh_aba_integrate_jvp_f64", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                           ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
+   /** the same in fp32 */
+   static final MethodHandle ABA_INTEGRATE_JVP_F32 = handle("mh_aba_integrate_jvp_f32", status(ADDRESS, JAVA_LONG, JAVA_DOUBLE, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS,
+                                                                                               ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS, ADDRESS));
    /** The model's own inertial parameters: (model, pi_out (host double[n_joints][10])), the layout of a row of pi below. */
    static final MethodHandle MODEL_INERTIAL_PARAMETERS = handle("mh_model_inertial_parameters", status(ADDRESS, ADDRESS));
    /**

@@ -26,7 +26,8 @@ ABI_SYMBOLS = [
     "mh_abi_version", "mh_spec_abi_stamp", "mh_build_hash", "mh_spec_sources_hash", "mh_spec_sources_hash_of", "mh_last_error", "mh_device_count", "mh_set_device", "mh_options_default", "mh_model_create", "mh_model_destroy",
     "mh_context_create", "mh_context_destroy", "mh_context_reserve", "mh_model_check",
     "mh_topology_key", "mh_build_code_object", "mh_model_nq", "mh_model_nv", "mh_model_n_joints", "mh_model_kernel_variant", "mh_model_warnings", "mh_model_warning_text", "mh_reserve", "mh_rnea_f64", "mh_aba_f64", "mh_crba_f64", "mh_rnea_aba_f64", "mh_rnea_crba_f64", "mh_regressor_f64", "mh_regressor_f32",
-    "mh_model_set_joint_source_modes", "mh_model_n_acceleration_sources", "mh_aba_locked_f64", "mh_rnea_bodies_f64", "mh_aba_bodies_f64", "mh_rnea_joint_wrenches_f64", "mh_aba_joint_wrenches_f64", "mh_relative_acceleration_f64", "mh_crba_coriolis_f64", "mh_crba_coriolis_f32", "mh_centroidal_f64", "mh_centroidal_f32", "mh_gravity_gradient_f64", "mh_gravity_gradient_f32", "mh_apparent_inertia_inverse_f64", "mh_apparent_inertia_inverse_f32", "mh_body_poses_f64", "mh_body_poses_f32", "mh_geometric_jacobian_f64", "mh_geometric_jacobian_f32", "mh_body_poses_vjp_f64", "mh_body_poses_vjp_f32", "mh_jacobian_transpose_f64", "mh_jacobian_transpose_f32", "mh_mass_matrix_inverse_f64", "mh_mass_matrix_inverse_f32", "mh_aba_constrained_f64", "mh_aba_constrained_f32", "mh_constraint_impulse_f64", "mh_constraint_impulse_f32", "mh_aba_constrained_between_f64", "mh_aba_constrained_between_f32", "mh_constraint_impulse_between_f64", "mh_constraint_impulse_between_f32", "mh_contact_impulse_f64", "mh_contact_impulse_f32", "mh_contact_impulse_between_f64", "mh_contact_impulse_between_f32", "mh_joint_limit_impulse_f64", "mh_joint_limit_impulse_f32", "mh_rnea_derivatives_f64", "mh_rnea_derivatives_f32", "mh_aba_derivatives_f64", "mh_aba_derivatives_f32", "mh_rnea_vjp_f64", "mh_rnea_vjp_f32", "mh_aba_vjp_f64", "mh_aba_vjp_f32", "mh_configuration_add_f64", "mh_configuration_add_f32", "mh_configuration_difference_f64", "mh_configuration_difference_f32", "mh_aba_integrate_derivatives_f64", "mh_aba_integrate_derivatives_f32", "mh_integrate_vjp_f64", "mh_integrate_vjp_f32", "mh_aba_integrate_vjp_f64", "mh_aba_integrate_vjp_f32", "mh_model_inertial_parameters", "mh_rnea_parameters_f64", "mh_rnea_parameters_f32", "mh_aba_parameters_f64", "mh_aba_parameters_f32", "mh_rnea_parameters_vjp_f64", "mh_rnea_parameters_vjp_f32", "mh_aba_parameters_vjp_f64", "mh_aba_parameters_vjp_f32", "mh_rnea_parameters_state_vjp_f64", "mh_rnea_parameters_state_vjp_f32", "mh_aba_parameters_state_vjp_f64", "mh_aba_parameters_state_vjp_f32", "mh_integrate_f64", "mh_aba_integrate_f64", "mh_integrate_f32", "mh_rnea_f32", "mh_aba_f32", "mh_crba_f32", "mh_rnea_aba_f32", "mh_rnea_bodies_f32", "mh_aba_bodies_f32", "mh_aba_locked_f32", "mh_rnea_f64_host", "mh_aba_f64_host", "mh_crba_f64_host", "mh_rnea_f32_host", "mh_aba_f32_host", "mh_crba_f32_host", "mh_rnea_aba_f64_host", "mh_host_alloc", "mh_host_free", "mh_host_register", "mh_host_unregister", "mh_device_alloc", "mh_device_free", "mh_copy_to_device", "mh_copy_to_host", "mh_stream_synchronize", "mh_crba_coriolis_f64_host", "mh_centroidal_f64_host", "mh_timer_create",
+    "mh_model_set_joint_source_modes", "mh_model_n_acceleration_sources", "mh_aba_locked_f64", "mh_rnea_bodies_f64", "mh_aba_bodies_f64", "mh_rnea_joint_wrenches_f64", "mh_aba_joint_wrenches_f64", "mh_relative_acceleration_f64", "mh_crba_coriolis_f64", "mh_crba_coriolis_f32", "mh_centroidal_f64", "mh_centroidal_f32", "mh_gravity_gradient_f64", "mh_gravity_gradient_f32", "mh_apparent_inertia_inverse_f64", "mh_apparent_inertia_inverse_f32", "mh_body_poses_f64", "mh_body_poses_f32", "mh_geometric_jacobian_f64", "mh_geometric_jacobian_f32", "mh_body_poses_vjp_f64", "mh_body_poses_vjp_f32", "mh_jacobian_transpose_f64", "mh_jacobian_transpose_f32", "mh_mass_matrix_inverse_f64", "mh_mass_matrix_inverse_f32", "mh_aba_constrained_f64", "mh_aba_constrained_f32", "mh_constraint_impulse_f64", "mh_constraint_impulse_f32", "mh_aba_constrained_between_f64", "mh_aba_constrained_between_f32", "mh_constraint_impulse_between_f64", "mh_constraint_impulse_between_f32", "mh_contact_impulse_f64", "mh_contact_impulse_f32", "mh_contact_impulse_between_f64", "mh_contact_impulse_between_f32", "mh_joint_limit_impulse_f64", "mh_joint_limit_impulse_f32", "mh_rnea_derivatives_f64", "mh_rnea_derivatives_f32", "mh_aba_derivatives_f64", "mh_aba_derivatives_f32", "mh_rnea_vjp_f64", "mh_rnea_vjp_f32", "mh_aba_vjp_f64", "mh_aba_vjp_f32", "mh_configuration_add_f64", "mh_configuration_add_f32", "mh_configuration_difference_f64", "mh_configuration_difference_f32", "mh_aba_integrate_derivatives_f64", "mh_aba_integrate_derivatives_f32", "mh_integrate_vjp_f64", "mh_integrate_vjp_f32", "mh_aba_integrate_vjp_f64", "mh_aba_integrate_vjp_f32",
+    "mh_rnea_jvp_f64", "mh_rnea_jvp_f32", "mh_aba_jvp_f64", "mh_aba_jvp_f32", "mh_integrate_jvp_f64", "mh_integrate_jvp_f32", "mh_aba_integrate_jvp_f64", "mh_aba_integrate_jvp_f32", "mh_model_inertial_parameters", "mh_rnea_parameters_f64", "mh_rnea_parameters_f32", "mh_aba_parameters_f64", "mh_aba_parameters_f32", "mh_rnea_parameters_vjp_f64", "mh_rnea_parameters_vjp_f32", "mh_aba_parameters_vjp_f64", "mh_aba_parameters_vjp_f32", "mh_rnea_parameters_state_vjp_f64", "mh_rnea_parameters_state_vjp_f32", "mh_aba_parameters_state_vjp_f64", "mh_aba_parameters_state_vjp_f32", "mh_integrate_f64", "mh_aba_integrate_f64", "mh_integrate_f32", "mh_rnea_f32", "mh_aba_f32", "mh_crba_f32", "mh_rnea_aba_f32", "mh_rnea_bodies_f32", "mh_aba_bodies_f32", "mh_aba_locked_f32", "mh_rnea_f64_host", "mh_aba_f64_host", "mh_crba_f64_host", "mh_rnea_f32_host", "mh_aba_f32_host", "mh_crba_f32_host", "mh_rnea_aba_f64_host", "mh_host_alloc", "mh_host_free", "mh_host_register", "mh_host_unregister", "mh_device_alloc", "mh_device_free", "mh_copy_to_device", "mh_copy_to_host", "mh_stream_synchronize", "mh_crba_coriolis_f64_host", "mh_centroidal_f64_host", "mh_timer_create",
     "mh_timer_destroy", "mh_timer_start", "mh_timer_stop", "mh_timer_elapsed_ms",
     "mh_shard_range", "mh_comm_unique_id", "mh_comm_create", "mh_comm_destroy", "mh_comm_size", "mh_comm_broadcast", "mh_comm_broadcast_host",
     "mh_comm_all_gather_rows", "mh_comm_gather_plan", "mh_comm_barrier",
@@ -216,6 +217,14 @@ def _load_locked():
         getattr(lib, f).argtypes = [P, I64, ctypes.c_double, P, P, P, P, opt, P, P, P]
     for f in ("mh_aba_integrate_vjp_f64", "mh_aba_integrate_vjp_f32"):
         getattr(lib, f).argtypes = [P, I64, ctypes.c_double, P, P, P, P, P, P, P, opt, P, P, P, P]
+    for f in ("mh_rnea_jvp_f64", "mh_rnea_jvp_f32"):
+        getattr(lib, f).argtypes = [P, I64, P, P, P, P, P, P, P, P, opt, P]
+    for f in ("mh_aba_jvp_f64", "mh_aba_jvp_f32"):
+        getattr(lib, f).argtypes = [P, I64, P, P, P, P, P, P, P, P, opt, P, P]
+    for f in ("mh_integrate_jvp_f64", "mh_integrate_jvp_f32"):
+        getattr(lib, f).argtypes = [P, I64, ctypes.c_double, P, P, P, P, P, opt, P, P]
+    for f in ("mh_aba_integrate_jvp_f64", "mh_aba_integrate_jvp_f32"):
+        getattr(lib, f).argtypes = [P, I64, ctypes.c_double, P, P, P, P, P, P, P, P, opt, P, P, P, P]
     lib.mh_model_inertial_parameters.argtypes = [P, P]
     for f in ("mh_rnea_parameters_f64", "mh_rnea_parameters_f32", "mh_aba_parameters_f64", "mh_aba_parameters_f32"):
         getattr(lib, f).argtypes = [P, I64, P, P, P, P, P, P, opt, P]

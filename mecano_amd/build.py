@@ -26,7 +26,7 @@ HEADERS = [os.path.join(CSRC, "mh_kernels.h"), os.path.join(CSRC, "mh_device.h")
 LIB_HEADERS = HEADERS + [os.path.join(CSRC, "mh_dfs_kernels.h"), os.path.join(CSRC, "mh_split_kernels.h"),
                          os.path.join(CSRC, "mh_gravity_kernels.h"), os.path.join(CSRC, "mh_response_kernels.h"), os.path.join(CSRC, "mh_minv_kernels.h"),
                          os.path.join(CSRC, "mh_kinematics_kernels.h"), os.path.join(CSRC, "mh_kinematics_vjp_kernels.h"), os.path.join(CSRC, "mh_constraint_kernels.h"), os.path.join(CSRC, "mh_contact_kernels.h"), os.path.join(CSRC, "mh_limit_kernels.h"),
-                         os.path.join(CSRC, "mh_params_kernels.h"), os.path.join(CSRC, "mh_params_vjp_kernels.h"), os.path.join(CSRC, "mh_params_state_vjp_kernels.h"), os.path.join(CSRC, "mh_rnea_deriv_kernels.h"), os.path.join(CSRC, "mh_rnea_vjp_kernels.h"), os.path.join(CSRC, "mh_step_kernels.h"),  # the library's own kernels
+                         os.path.join(CSRC, "mh_params_kernels.h"), os.path.join(CSRC, "mh_params_vjp_kernels.h"), os.path.join(CSRC, "mh_params_state_vjp_kernels.h"), os.path.join(CSRC, "mh_rnea_deriv_kernels.h"), os.path.join(CSRC, "mh_rnea_vjp_kernels.h"), os.path.join(CSRC, "mh_rnea_jvp_kernels.h"), os.path.join(CSRC, "mh_step_kernels.h"),  # the library's own kernels
                          os.path.join(CSRC, "mh_model_tables.h"), os.path.join(CSRC, "mh_launch_plans.h")]  # ... and its host-side model compiler and launch planners
 SPEC_SOURCE = os.path.join(CSRC, "mh_spec.hip")
 SPEC_HEADERS = HEADERS + [os.path.join(CSRC, "mh_spec_kernels.h"), os.path.join(CSRC, "mh_zv_kernels.h")]

@@ -221,6 +221,7 @@ struct DeviceTables
    int *d_minv_owner = nullptr;
    int *d_deriv_slot = nullptr;
    int *d_vjp_slot = nullptr;
+   int *d_jvp_slot = nullptr;
 };
 
 // The switches of the environment (struct Switches: mh_launch_plans.h, whose planners read some of them).
@@ -325,6 +326,9 @@ struct mh_model : ModelTables, DeviceTables, Switches, ContextState
    // mh_rnea_vjp_* / mh_aba_vjp_*: first workspace slot of every body in that kernel's own plan (vjp_slot_plan, mh_launch_plans.h)
    std::vector<int> vjp_slot;
    int vjp_slots = 0;
+   // mh_rnea_jvp_* / mh_aba_jvp_*: the same for the tangent sweep (jvp_slot_plan)
+   std::vector<int> jvp_slot;
+   int jvp_slots = 0;
    SpecLib spec;
    bool spec_minimal = false; // the loaded code object is a minimal (fast) build
    std::string variant = "generic";
@@ -373,7 +377,8 @@ std::vector<DeviceRow> device_rows(mh_model *m, const std::vector<float> &consts
            device_row(m->d_prog_seq, m->prog_seq), device_row(m->d_consts64, m->consts), device_row(m->d_consts32, consts32),
            device_row(m->d_sub_mass64, m->sub_mass), device_row(m->d_sub_mass32, sub_mass32), device_row(m->d_grav_zero_ofs, m->grav_zero_ofs),
            device_row(m->d_grav_zero_cols, m->grav_zero_cols), device_row(m->d_resp_info, m->resp_info),
-           device_row(m->d_minv_owner, m->minv_owner), device_row(m->d_deriv_slot, m->deriv_slot), device_row(m->d_vjp_slot, m->vjp_slot)};
+           device_row(m->d_minv_owner, m->minv_owner), device_row(m->d_deriv_slot, m->deriv_slot), device_row(m->d_vjp_slot, m->vjp_slot),
+           device_row(m->d_jvp_slot, m->jvp_slot)};
 }
 mh_status ensure_bytes(Workspace &w, size_t bytes)
 {
@@ -3194,6 +3199,233 @@ mh_status step_vjp_impl(mh_model_t model, int64_t B, double dt, const T *q, cons
       return st;
    return rnea_vjp_launch<T>(model, B, q, qd, qdd, gravity, f_ext, mu, both_switches_on(o), true, gq_out, gqd_out, nullptr, true);
 }
+// ---- Forward mode (mh_rnea_jvp_kernels.h, mh_step_kernels.h: integrate_jvp_*_kernel): the matrices of the calls above times directions
+// (dq, dqd, dqdd / dtau), none formed.
+// The tangent sweep of the inverse dynamics: one launch in the kernel's own slot plan (fewer slots than rnea_vjp_launch's, which
+// mh_reserve covers), which writes every entry of dtau_out once.  rhs: dtau_out = tau_in - dtau, a NULL tau_in being zero (the forward form
+// below).
+template <typename T>
+mh_status rnea_jvp_launch(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const double *gravity, const T *f_ext, const T *dq,
+                          const T *dqd, const T *dqdd, bool rhs, const T *tau_in, const mh_options &opts, T *dtau_out)
+{
+   LaneSweep<T> S;
+   if (const mh_status st = plan_lane_sweep<T>(model, B, opts, gravity, model->jvp_slots, S); st != MH_OK)
+      return st;
+   mh::JvpArgs<T> G{};
+   mh::Args<T> &A = G.a = S.A;
+   A.q = q, A.qd = qd, A.in3 = qdd, A.fext = f_ext, A.out = dtau_out;
+   G.dq = dq, G.dqd = dqd, G.dqdd = dqdd, G.rhs = rhs, G.tau_in = tau_in;
+   G.slot = model->d_jvp_slot, G.slots = model->jvp_slots;
+   set_unowned(model, G.unowned, G.n_unowned);
+   hipLaunchKernelGGL((mh::rnea_jvp_kernel<T>), dim3(S.L.grid, S.parts), dim3(S.L.block), 0, (hipStream_t)opts.stream, G);
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
+template <typename T>
+mh_status rnea_jvp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *qdd, const double *gravity, const T *f_ext, const T *dq,
+                        const T *dqd, const T *dqdd, const mh_options *opts_in, T *dtau_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: the derivatives of the dynamics take none", model->n_locked);
+   if (!gravity && !opts.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (!dtau_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "dtau_out is NULL");
+   if (!dq && !dqd && !dqdd)
+      return fail(MH_ERR_INVALID_ARGUMENT, "dq, dqd and dqdd are all NULL");
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!q || (opts.consider_coriolis && !qd) || (opts.consider_accelerations && !qdd))
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state pointer (qd may be NULL with consider_coriolis = 0, qdd with consider_accelerations = 0)");
+   {
+      const size_t nq = (size_t)B * model->nq * sizeof(T), nvb = (size_t)B * model->nv * sizeof(T), nf = (size_t)B * model->n * 6 * sizeof(T);
+      const InRange ins[7] = {{"q", q, nq}, {"qd", opts.consider_coriolis ? qd : nullptr, nvb}, {"qdd", opts.consider_accelerations ? qdd : nullptr, nvb},
+                              {"f_ext", f_ext, nf}, {"dq", dq, nvb}, {"dqd", opts.consider_coriolis ? dqd : nullptr, nvb}, {"dqdd", dqdd, nvb}};
+      const OutRange out = {"dtau_out", dtau_out, nvb, 0u};
+      if ((st = check_aliasing("mh_rnea_jvp", ins, 7, &out, 1)) != MH_OK)
+         return st;
+   }
+   return rnea_jvp_launch<T>(model, B, q, qd, qdd, gravity, f_ext, dq, dqd, dqdd, false, nullptr, opts, dtau_out);
+}
+// Forward mode of the forward dynamics: with tau = H qdd + b, dqdd = H^-1 r, r = dtau - (d tau / d q) dq - (d tau / d qd) dqd at
+// (q, qd, qdd).  forward_form with the tangent sweep as its `between`, which writes r into one vector of the context's vjp scratch:
+// three launches (and one memset).  qdd: the caller's, or the vector before r.  Without dq and dqd r is dtau itself, the sweep is dropped
+// and the first launch runs only for qdd_out.
+template <typename T>
+mh_status jvp_form_scratch(mh_model *model, int64_t B, bool sweep, T *qdd_out, T *&qdd, T *&r)
+{
+   qdd = qdd_out, r = nullptr;
+   const int vectors = (sweep ? 1 : 0) + (sweep && !qdd_out ? 1 : 0);
+   if (vectors == 0)
+      return MH_OK;
+   if (const mh_status st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T), vectors)); st != MH_OK)
+      return st;
+   r = (T *)model->vjp.ptr;
+   if (!qdd)
+      qdd = r + (size_t)B * model->nv;
+   return MH_OK;
+}
+template <typename T>
+mh_status aba_jvp_run(mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const double *gravity, const T *f_ext, const T *dq,
+                      const T *dqd, const T *dtau, const mh_options &o, T *qdd_out, T *qdd, T *r, T *dqdd_out)
+{
+   const bool sweep = dq || dqd;
+   const auto tangent = [&] { return rnea_jvp_launch<T>(model, B, q, qd, qdd, gravity, f_ext, dq, dqd, (const T *)nullptr, true, dtau, both_switches_on(o), r); };
+   if (sweep)
+      return forward_form<T>(model, B, qd, tau, gravity, f_ext, (const T *)r, o, true, qdd, dqdd_out, fixed_forward_dynamics<T>(model, B, q), tangent);
+   return forward_form<T>(model, B, qd, tau, gravity, f_ext, dtau, o, qdd_out != nullptr, qdd, dqdd_out, fixed_forward_dynamics<T>(model, B, q), nothing_between);
+}
+template <typename T>
+mh_status aba_jvp_impl(mh_model_t model, int64_t B, const T *q, const T *qd, const T *tau, const double *gravity, const T *f_ext, const T *dq,
+                       const T *dqd, const T *dtau, const mh_options *opts_in, T *qdd_out, T *dqdd_out)
+{
+   mh_options o;
+   mh_status st = begin_call(model, B, opts_in, o);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: the derivatives of the dynamics take none", model->n_locked);
+   if (!gravity && !o.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (!dqdd_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "dqdd_out is NULL");
+   if (!dq && !dqd && !dtau)
+      return fail(MH_ERR_INVALID_ARGUMENT, "dq, dqd and dtau are all NULL");
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!q || !qd || !tau)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state pointer");
+   const size_t nvb = (size_t)B * model->nv * sizeof(T);
+   {
+      const InRange ins[7] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"qd", qd, nvb}, {"tau", tau, nvb}, {"f_ext", f_ext, (size_t)B * model->n * 6 * sizeof(T)},
+                              {"dq", dq, nvb}, {"dqd", dqd, nvb}, {"dtau", dtau, nvb}};
+      const OutRange outs[2] = {{"qdd_out", qdd_out, nvb, 0u}, {"dqdd_out", dqdd_out, nvb, 0u}};
+      if ((st = check_aliasing("mh_aba_jvp", ins, 7, outs, 2)) != MH_OK)
+         return st;
+   }
+   T *qdd, *r;
+   if ((st = jvp_form_scratch<T>(model, B, dq || dqd, qdd_out, qdd, r)) != MH_OK)
+      return st;
+   return aba_jvp_run<T>(model, B, q, qd, tau, gravity, f_ext, dq, dqd, dtau, o, qdd_out, qdd, r, dqdd_out);
+}
+// Forward mode of the integrator: one elementwise launch in the integrator's own launch shape, no workspace.  Every entry of the
+// outputs given is written once.
+template <typename T>
+mh_status integrate_jvp_launch(mh_model_t model, int64_t B, double dt, const T *qd, const T *qdd, const T *dq, const T *dqd, const T *dqdd,
+                               const mh_options &opts, T *dq_next_out, T *dqd_next_out)
+{
+   mh::StepJvpArgs<T> A{};
+   A.m = dev_model<T>(model);
+   A.B = B, A.dt = (T)dt;
+   A.qd = qd, A.qdd = qdd, A.dq = dq, A.dqd = dqd, A.dqdd = dqdd;
+   A.dqn = dq_next_out, A.dqdn = dqd_next_out;
+   set_unowned(model, A.unowned, A.n_unowned);
+   const bool soa = opts.layout == MH_LAYOUT_SOA;
+   set_strides(A.v_bs, A.v_es, soa, B, model->nv);
+   const int block = 256;
+   if (soa)
+   {
+      const int grid = (int)std::max<long>(1, std::min<long>((B + block - 1) / block, (long)model->cu_count * 8));
+      hipLaunchKernelGGL((mh::integrate_jvp_soa_kernel<T>), dim3(grid), dim3(block), 0, (hipStream_t)opts.stream, A);
+   }
+   else
+   { // the integrator's tiles: enough workgroups to cover the device at small B, up to 256 configurations each at large B
+      const int tile = (int)std::max<long>(16, std::min<long>(256, B / ((long)model->cu_count * 4)));
+      const int grid = (int)std::max<long>(1, std::min<long>((B + tile - 1) / tile, (long)model->cu_count * 8));
+      hipLaunchKernelGGL((mh::integrate_jvp_aos_kernel<T>), dim3(grid), dim3(block), ((size_t)model->n * 2 + 2) * sizeof(int), (hipStream_t)opts.stream, A,
+                         tile);
+   }
+   HIP_TRY(hipGetLastError());
+   return MH_OK;
+}
+template <typename T>
+mh_status integrate_jvp_impl(mh_model_t model, int64_t B, double dt, const T *qd, const T *qdd, const T *dq, const T *dqd, const T *dqdd,
+                             const mh_options *opts_in, T *dq_next_out, T *dqd_next_out)
+{
+   mh_options opts;
+   mh_status st = begin_call(model, B, opts_in, opts);
+   if (st != MH_OK)
+      return st;
+   if (nonfinite_bits(dt))
+      return fail(MH_ERR_INVALID_ARGUMENT, "dt is not finite");
+   if (!dq_next_out && !dqd_next_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "dq_next_out and dqd_next_out are both NULL");
+   if (!dq && !dqd && !dqdd)
+      return fail(MH_ERR_INVALID_ARGUMENT, "dq, dqd and dqdd are all NULL");
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!qd || !qdd)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state pointer");
+   {
+      const size_t bv = (size_t)B * model->nv * sizeof(T);
+      const InRange ins[5] = {{"qd", qd, bv}, {"qdd", qdd, bv}, {"dq", dq, bv}, {"dqd", dqd, bv}, {"dqdd", dqdd, bv}};
+      const OutRange outs[2] = {{"dq_next_out", dq_next_out, bv, 0u}, {"dqd_next_out", dqd_next_out, bv, 0u}};
+      if ((st = check_aliasing("mh_integrate_jvp", ins, 5, outs, 2)) != MH_OK)
+         return st;
+   }
+   return integrate_jvp_launch<T>(model, B, dt, qd, qdd, dq, dqd, dqdd, opts, dq_next_out, dqd_next_out);
+}
+// Forward mode of the step x' = integrate(q, qd, aba(q, qd, tau)): aba_jvp_run, then the integrator's tangent kernel on (dq, dqd, dqdd)
+// at that qdd -- four launches (and one memset), exactly mh_aba_jvp_* followed by mh_integrate_jvp_*.  Scratch: r and qdd as in
+// aba_jvp_impl, and dqdd behind them where the caller takes none -- at most three vectors of the context's vjp scratch.
+template <typename T>
+mh_status step_jvp_impl(mh_model_t model, int64_t B, double dt, const T *q, const T *qd, const T *tau, const double *gravity, const T *f_ext,
+                        const T *dq, const T *dqd, const T *dtau, const mh_options *opts_in, T *qdd_out, T *dqdd_out, T *dq_next_out, T *dqd_next_out)
+{
+   mh_options o;
+   mh_status st = begin_call(model, B, opts_in, o);
+   if (st != MH_OK)
+      return st;
+   if (model->n_locked > 0)
+      return fail(MH_ERR_INVALID_ARGUMENT, "%d joint(s) are acceleration sources: the derivatives of the step take none", model->n_locked);
+   if (nonfinite_bits(dt))
+      return fail(MH_ERR_INVALID_ARGUMENT, "dt is not finite");
+   if (!gravity && !o.use_root_acceleration)
+      return fail(MH_ERR_INVALID_ARGUMENT, "gravity is NULL and no root acceleration is set");
+   if (!dqdd_out && !dq_next_out && !dqd_next_out)
+      return fail(MH_ERR_INVALID_ARGUMENT, "dqdd_out, dq_next_out and dqd_next_out are all NULL");
+   if (!dq && !dqd && !dtau)
+      return fail(MH_ERR_INVALID_ARGUMENT, "dq, dqd and dtau are all NULL");
+   if (B == 0 || model->nv == 0)
+      return MH_OK;
+   if (!q || !qd || !tau)
+      return fail(MH_ERR_INVALID_ARGUMENT, "NULL state pointer");
+   const size_t nvb = (size_t)B * model->nv * sizeof(T);
+   {
+      const InRange ins[7] = {{"q", q, (size_t)B * model->nq * sizeof(T)}, {"qd", qd, nvb}, {"tau", tau, nvb}, {"f_ext", f_ext, (size_t)B * model->n * 6 * sizeof(T)},
+                              {"dq", dq, nvb}, {"dqd", dqd, nvb}, {"dtau", dtau, nvb}};
+      const OutRange outs[4] = {{"qdd_out", qdd_out, nvb, 0u}, {"dqdd_out", dqdd_out, nvb, 0u}, {"dq_next_out", dq_next_out, nvb, 0u},
+                                {"dqd_next_out", dqd_next_out, nvb, 0u}};
+      if ((st = check_aliasing("mh_aba_integrate_jvp", ins, 7, outs, 4)) != MH_OK)
+         return st;
+   }
+   // the integrator reads qdd wherever it runs, so the first launch always does: r, qdd and dqdd in this order, whichever is scratch
+   const bool sweep = dq || dqd, integrator = dq_next_out || dqd_next_out;
+   const int vectors = (sweep ? 1 : 0) + (qdd_out ? 0 : 1) + (dqdd_out ? 0 : 1);
+   T *r = nullptr, *qdd = qdd_out, *dqdd = dqdd_out;
+   if (vectors > 0)
+   {
+      if ((st = ensure_bytes(model->vjp, vjp_scratch_bytes(model, B, sizeof(T), vectors))) != MH_OK)
+         return st;
+      T *at = (T *)model->vjp.ptr;
+      const size_t bn = (size_t)B * model->nv;
+      if (sweep)
+         r = at, at += bn;
+      if (!qdd)
+         qdd = at, at += bn;
+      if (!dqdd)
+         dqdd = at;
+   }
+   // (qdd_out as the "caller's wish" of aba_jvp_run: qdd is needed whenever the integrator runs)
+   st = aba_jvp_run<T>(model, B, q, qd, tau, gravity, f_ext, dq, dqd, dtau, o, integrator ? qdd : qdd_out, qdd, r, dqdd);
+   if (st != MH_OK || !integrator)
+      return st;
+   return integrate_jvp_launch<T>(model, B, dt, qd, (const T *)qdd, dq, dqd, (const T *)dqdd, o, dq_next_out, dqd_next_out);
+}
 } // namespace
 
 static void self_check_spec(mh_model *m);
@@ -3466,6 +3698,7 @@ mh_status mh_model_create(const mh_model_desc *d, mh_model_t *model_out)
    }
    m->device = dev;
    m->vjp_slots = vjp_slot_plan(m->meta, m->n, m->vjp_slot);
+   m->jvp_slots = jvp_slot_plan(m->meta, m->n, m->jvp_slot);
    const std::vector<float> c32(m->consts.begin(), m->consts.end()), sm32(m->sub_mass.begin(), m->sub_mass.end());
    for (const DeviceRow &r : device_rows(m, c32, sm32))
    {
@@ -3828,6 +4061,7 @@ mh_status mh_reserve(mh_model_t m, int64_t max_batch)
          {m->resp_slots, std::max<long>(MH_MAX_APPARENT_TARGETS, minv_groups(std::max<int>(m->nv, MH_MAX_INVERSE_COLUMNS)))},
          {m->deriv_slots, std::min(8, m->n)}, // mh_rnea_derivatives_* / mh_aba_derivatives_*: the kernel's own slot plan
          // mh_rnea_vjp_* / mh_aba_vjp_*: likewise; mh_rnea_parameters_state_vjp_* / mh_aba_parameters_state_vjp_* work in the same plan
+         // (mh_rnea_jvp_* / mh_aba_jvp_*: a plan of fewer slots for every body, JS_BODY < VS_BODY and JS_BRANCH < VS_BRANCH, at the same waves)
          {m->vjp_slots, std::min(8, m->n)},
          // mh_body_poses_* / mh_geometric_jacobian_*: pose and twist of every body per lane, up to one wave per target
          {(long)m->n * mh::KIN_SLOTS, MH_MAX_KINEMATIC_TARGETS}};
@@ -4739,6 +4973,52 @@ mh_status mh_aba_integrate_vjp_f32(mh_model_t model, int64_t B, double dt, const
                                    const mh_options *opts, float *qdd_out, float *gq_out, float *gqd_out, float *gtau_out)
 {
    return step_vjp_impl<float>(model, B, dt, q, qd, tau, gravity, f_ext, gq_next, gqd_next, opts, qdd_out, gq_out, gqd_out, gtau_out);
+}
+mh_status mh_rnea_jvp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double gravity[3],
+                          const double *f_ext, const double *dq, const double *dqd, const double *dqdd, const mh_options *opts,
+                          double *dtau_out)
+{
+   return rnea_jvp_impl<double>(model, B, q, qd, qdd, gravity, f_ext, dq, dqd, dqdd, opts, dtau_out);
+}
+mh_status mh_rnea_jvp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *qdd, const double gravity[3],
+                          const float *f_ext, const float *dq, const float *dqd, const float *dqdd, const mh_options *opts,
+                          float *dtau_out)
+{
+   return rnea_jvp_impl<float>(model, B, q, qd, qdd, gravity, f_ext, dq, dqd, dqdd, opts, dtau_out);
+}
+mh_status mh_aba_jvp_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *tau, const double gravity[3],
+                         const double *f_ext, const double *dq, const double *dqd, const double *dtau, const mh_options *opts,
+                         double *qdd_out, double *dqdd_out)
+{
+   return aba_jvp_impl<double>(model, B, q, qd, tau, gravity, f_ext, dq, dqd, dtau, opts, qdd_out, dqdd_out);
+}
+mh_status mh_aba_jvp_f32(mh_model_t model, int64_t B, const float *q, const float *qd, const float *tau, const double gravity[3],
+                         const float *f_ext, const float *dq, const float *dqd, const float *dtau, const mh_options *opts,
+                         float *qdd_out, float *dqdd_out)
+{
+   return aba_jvp_impl<float>(model, B, q, qd, tau, gravity, f_ext, dq, dqd, dtau, opts, qdd_out, dqdd_out);
+}
+mh_status mh_integrate_jvp_f64(mh_model_t model, int64_t B, double dt, const double *qd, const double *qdd, const double *dq,
+                               const double *dqd, const double *dqdd, const mh_options *opts, double *dq_next_out, double *dqd_next_out)
+{
+   return integrate_jvp_impl<double>(model, B, dt, qd, qdd, dq, dqd, dqdd, opts, dq_next_out, dqd_next_out);
+}
+mh_status mh_integrate_jvp_f32(mh_model_t model, int64_t B, double dt, const float *qd, const float *qdd, const float *dq,
+                               const float *dqd, const float *dqdd, const mh_options *opts, float *dq_next_out, float *dqd_next_out)
+{
+   return integrate_jvp_impl<float>(model, B, dt, qd, qdd, dq, dqd, dqdd, opts, dq_next_out, dqd_next_out);
+}
+mh_status mh_aba_integrate_jvp_f64(mh_model_t model, int64_t B, double dt, const double *q, const double *qd, const double *tau,
+                                   const double gravity[3], const double *f_ext, const double *dq, const double *dqd, const double *dtau,
+                                   const mh_options *opts, double *qdd_out, double *dqdd_out, double *dq_next_out, double *dqd_next_out)
+{
+   return step_jvp_impl<double>(model, B, dt, q, qd, tau, gravity, f_ext, dq, dqd, dtau, opts, qdd_out, dqdd_out, dq_next_out, dqd_next_out);
+}
+mh_status mh_aba_integrate_jvp_f32(mh_model_t model, int64_t B, double dt, const float *q, const float *qd, const float *tau,
+                                   const double gravity[3], const float *f_ext, const float *dq, const float *dqd, const float *dtau,
+                                   const mh_options *opts, float *qdd_out, float *dqdd_out, float *dq_next_out, float *dqd_next_out)
+{
+   return step_jvp_impl<float>(model, B, dt, q, qd, tau, gravity, f_ext, dq, dqd, dtau, opts, qdd_out, dqdd_out, dq_next_out, dqd_next_out);
 }
 mh_status mh_rnea_parameters_f64(mh_model_t model, int64_t B, const double *q, const double *qd, const double *qdd, const double *pi,
                                  const double gravity[3], const double *f_ext, const mh_options *opts, double *tau_out)

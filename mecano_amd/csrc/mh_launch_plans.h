@@ -11,6 +11,7 @@
 #include "mh_dfs_kernels.h"
 #include "mh_split_kernels.h"
 #include "mh_rnea_vjp_kernels.h"
+#include "mh_rnea_jvp_kernels.h"
 
 #include <algorithm>
 #include <cassert>
@@ -114,6 +115,19 @@ int vjp_slot_plan(const std::vector<int> &meta, int n, std::vector<int> &slot)
    {
       slot[e] = slots;
       slots += (meta[(size_t)e * mh::MI_STRIDE + mh::MI_FLAGS] & mh::MF_STORE_VA) ? mh::VS_BRANCH : mh::VS_BODY;
+   }
+   return std::max(slots, 1);
+}
+// ---- forward-mode derivatives of the dynamics (mh_rnea_jvp_kernels.h): the same idea -- JS_BODY slots a body, JS_BRANCH for a body with
+// a child that does not directly follow it, which parks v, a, xi, dv and da for that child
+int jvp_slot_plan(const std::vector<int> &meta, int n, std::vector<int> &slot)
+{
+   slot.assign((size_t)std::max(1, n), 0);
+   int slots = 0;
+   for (int e = 0; e < n; e++)
+   {
+      slot[e] = slots;
+      slots += (meta[(size_t)e * mh::MI_STRIDE + mh::MI_FLAGS] & mh::MF_STORE_VA) ? mh::JS_BRANCH : mh::JS_BODY;
    }
    return std::max(slots, 1);
 }

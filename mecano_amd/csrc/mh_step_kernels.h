@@ -7,6 +7,8 @@
 //   step_assemble_soa_kernel         step dt" from d qdd / d q, d qdd / d qd and H^-1 (mh_aba_derivatives_*)
 //   integrate_vjp_aos_kernel /       the transpose of integrate_joint's tangent map applied to cotangents of (dq', dqd'): gq, gqd, gqdd
 //   integrate_vjp_soa_kernel         (mh_integrate_vjp_*, and the integrator's share of mh_aba_integrate_vjp_*)
+//   integrate_jvp_aos_kernel /       integrate_joint's tangent map applied to directions (dq, dqd, dqdd): dq', dqd'
+//   integrate_jvp_soa_kernel         (mh_integrate_jvp_*, and the last launch of mh_aba_integrate_jvp_*)
 //
 // The step of one joint, in joint-local components (pose (R, p), twist (w, v), acceleration (al, a) from forward dynamics; integrate_sixdof):
 //   a_o = a + w x v,  r = dt w + dt^2/2 al,  E = exp(r),  d = dt v + dt^2/2 a_o,  c = v + dt a_o
@@ -452,6 +454,141 @@ __global__ void __launch_bounds__(256) integrate_vjp_aos_kernel(StepVjpArgs<T> A
          const unsigned lc = u / nm, j = (unsigned)lm[u - lc * nm];
          const int *mi = m.meta + j * MI_STRIDE;
          integrate_vjp_joint<T, const int *>(mi[MI_TYPE], m.dof_map + mi[MI_DOF], A, (cfg0 + lc) * A.v_bs, dt, hdd);
+      }
+   }
+}
+
+// ---- Forward mode of the integrator: step_apply itself on directions (dq, dqd, dqdd) of one configuration, per joint, which gives the
+// joint's entries of (dq', dqd') -- the blocks the assembly kernels above apply column by column, here applied once.  Its transpose is
+// integrate_vjp_*.  A 1-DoF joint: dq' = dq + dt dqd + dt^2/2 dqdd, dqd' = dqd + dt dqdd.  At dt = 0 E and J_r are the identity and
+// dq' = dq, dqd' = dqd come out exactly.
+template <typename T>
+struct StepJvpArgs
+{
+   DevModel m;
+   long B;
+   T dt;
+   const T *qd, *qdd;       // [B][nv] in the call's layout (v_bs, v_es)
+   const T *dq, *dqd, *dqdd; // directions; any may be NULL (zero, not read)
+   T *dqn, *dqdn;           // (dq', dqd'); either may be NULL
+   const int *unowned;      // DoF indices no joint owns: zeros
+   int n_unowned;
+   long v_bs, v_es;
+};
+// One multi-DoF joint of one configuration (rows at `at`, element stride es).  di: the joint's entries of the DoF index map.
+template <typename T, class IP>
+MH_DEV void integrate_jvp_joint(int type, IP di, const StepJvpArgs<T> &A, long at, T dt, T hdd)
+{
+   const long es = A.v_es;
+   StepLin<T> L;
+   step_lin_of_joint<T, IP>(type, di, A.qd + at, A.qdd + at, es, dt, hdd, L);
+   const int k = dof_count(type);
+   T x[6], eq[6], ev[6], oq[6], ov[6];
+#pragma unroll
+   for (int i = 0; i < 6; i++)
+   {
+      eq[i] = A.dq && i < k ? A.dq[at + di[i] * es] : T(0);
+      ev[i] = A.dqd && i < k ? A.dqd[at + di[i] * es] : T(0);
+      x[i] = A.dqdd && i < k ? A.dqdd[at + di[i] * es] : T(0);
+   }
+   step_column<T>(type, L, dt, hdd, x, eq, ev, oq, ov);
+#pragma unroll
+   for (int i = 0; i < 6; i++)
+      if (i < k)
+      {
+         const long e = at + di[i] * es;
+         if (A.dqn)
+            A.dqn[e] = oq[i];
+         if (A.dqdn)
+            A.dqdn[e] = ov[i];
+      }
+}
+// a 1-DoF joint: entry e of every vector
+template <typename T>
+MH_DEV void integrate_jvp_one(const StepJvpArgs<T> &A, long e, T dt, T hdd)
+{
+   const T a = A.dq ? A.dq[e] : T(0), b = A.dqd ? A.dqd[e] : T(0), c = A.dqdd ? A.dqdd[e] : T(0);
+   if (A.dqn)
+      A.dqn[e] = a + dt * b + hdd * c;
+   if (A.dqdn)
+      A.dqdn[e] = b + dt * c;
+}
+template <typename T>
+MH_DEV void integrate_jvp_zero(const StepJvpArgs<T> &A, long at)
+{
+   for (int z = 0; z < A.n_unowned; z++)
+   {
+      const long e = at + A.unowned[z] * A.v_es;
+      if (A.dqn)
+         A.dqn[e] = T(0);
+      if (A.dqdn)
+         A.dqdn[e] = T(0);
+   }
+}
+// SoA: lane = configuration, joints looped, the joint's small matrices in registers.
+template <typename T>
+__global__ void __launch_bounds__(256) integrate_jvp_soa_kernel(StepJvpArgs<T> A)
+{
+   const DevModel &m = A.m;
+   const ciptr meta = as_const(m.meta), dof_map = as_const(m.dof_map);
+   const long nlanes = (long)gridDim.x * blockDim.x;
+   const T dt = A.dt, hdd = T(0.5) * A.dt * A.dt;
+   for (long cfg = (long)blockIdx.x * blockDim.x + threadIdx.x; cfg < A.B; cfg += nlanes)
+   {
+      const long at = cfg * A.v_bs;
+      integrate_jvp_zero<T>(A, at);
+      for (int j = 0; j < m.n; j++)
+      {
+         ciptr mi = meta + j * MI_STRIDE;
+         const int type = mi[MI_TYPE];
+         if (type == JT_REVOLUTE || type == JT_PRISMATIC)
+            integrate_jvp_one<T>(A, at + dof_map[mi[MI_DOF]] * A.v_es, dt, hdd);
+         else if (type != JT_FIXED)
+            integrate_jvp_joint<T, ciptr>(type, dof_map + mi[MI_DOF], A, at, dt, hdd);
+      }
+   }
+}
+// AoS: the thread mapping of integrate_vjp_aos_kernel, joint lists in LDS.
+template <typename T>
+__global__ void __launch_bounds__(256) integrate_jvp_aos_kernel(StepJvpArgs<T> A, int tile)
+{
+   extern __shared__ int lds_meta[]; // [n] v index of the 1-DoF joints ; [n] engine index of the others ; counts
+   const DevModel &m = A.m;
+   int *l1_v = lds_meta, *lm = lds_meta + m.n, *cnt = lds_meta + 2 * m.n;
+   if (threadIdx.x == 0)
+   {
+      int n1 = 0, nm = 0;
+      for (int j = 0; j < m.n; j++)
+      {
+         const int type = m.meta[j * MI_STRIDE + MI_TYPE];
+         if (type == JT_REVOLUTE || type == JT_PRISMATIC)
+            l1_v[n1++] = m.dof_map[m.meta[j * MI_STRIDE + MI_DOF]];
+         else if (type != JT_FIXED)
+            lm[nm++] = j;
+      }
+      cnt[0] = n1, cnt[1] = nm;
+   }
+   __syncthreads();
+   const unsigned n1 = (unsigned)cnt[0], nm = (unsigned)cnt[1];
+   const T dt = A.dt, hdd = T(0.5) * A.dt * A.dt;
+   const long ntiles = (A.B + tile - 1) / tile;
+   for (long t = blockIdx.x; t < ntiles; t += gridDim.x)
+   {
+      const long cfg0 = t * tile;
+      const unsigned rows = (unsigned)(A.B - cfg0 < (long)tile ? A.B - cfg0 : (long)tile);
+      if (A.n_unowned > 0)
+         for (unsigned u = threadIdx.x; u < rows; u += blockDim.x)
+            integrate_jvp_zero<T>(A, (cfg0 + u) * A.v_bs);
+      for (unsigned u = threadIdx.x; u < rows * n1; u += blockDim.x)
+      {
+         const unsigned lc = u / n1, k = u - lc * n1;
+         integrate_jvp_one<T>(A, (cfg0 + lc) * A.v_bs + l1_v[k], dt, hdd);
+      }
+      for (unsigned u = threadIdx.x; u < rows * nm; u += blockDim.x)
+      {
+         const unsigned lc = u / nm, j = (unsigned)lm[u - lc * nm];
+         const int *mi = m.meta + j * MI_STRIDE;
+         integrate_jvp_joint<T, const int *>(mi[MI_TYPE], m.dof_map + mi[MI_DOF], A, (cfg0 + lc) * A.v_bs, dt, hdd);
       }
    }
 }

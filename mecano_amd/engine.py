@@ -1063,6 +1063,112 @@ class HipModel:
             ptr(qdd), ptr(gq), ptr(gqd), ptr(gtau)))
         return qdd, gq, gqd, gtau
 
+    def _directions(self, directions, names, vec, dt):
+        """The directions of a forward-mode call: any may be None (zero), not all; shapes and dtype as the state vectors."""
+        if all(t is None for t in directions):
+            raise _lib.MecanoHipError(1, f"{', '.join(names)} are all None")
+        for t, name in zip(directions, names):
+            if t is not None:
+                self._device_tensor(t, dt)
+                if tuple(t.shape) != vec:
+                    raise _lib.MecanoHipError(2, f"direction {name} has shape {tuple(t.shape)}, expected {vec}")
+
+    def rnea_jvp(self, q, qd, qdd, dq, dqd, dqdd, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, consider_coriolis=True,
+                 consider_accelerations=True, out=None):
+        """Forward-mode derivative of the inverse dynamics, one O(n) launch and no matrix: for directions ``dq`` (a velocity-space step
+        of ``configuration_add``), ``dqd``, ``dqdd`` [B, nv] (any may be None for zero, not all), dtau [B, nv] =
+        (d tau / d q) dq + (d tau / d qd) dqd + H dqdd with the matrices of ``rnea_derivatives`` (wrenches held in the world).  SoA:
+        [nv, B].  ``qdd`` may be None with ``consider_accelerations=False``, ``qd`` with ``consider_coriolis=False`` (dqd then contributes
+        nothing and may be None too).  ``out``: the tensor to write into."""
+        given = [t for t in (q, qd if consider_coriolis else None, qdd if consider_accelerations else None) if t is not None]
+        B, dt, sfx, stream = self._device_inputs(given, layout)
+        if (consider_coriolis and qd is None) or (consider_accelerations and qdd is None):
+            raise _lib.MecanoHipError(1, "qd / qdd may be None only with their switch off")
+        if f_ext is not None:
+            self._device_tensor(f_ext, dt)
+        self._check_f_ext(f_ext, B, layout)
+        vec = (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B)
+        self._directions((dq, dqd, dqdd), ("dq", "dqd", "dqdd"), vec, dt)
+        dtau = self._output(out, vec, dt, q.device, "dtau")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, consider_coriolis, consider_accelerations, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_rnea_jvp_{sfx}")(
+            self._h, B, q.data_ptr(), ptr(qd) if consider_coriolis else None, ptr(qdd) if consider_accelerations else None, g, ptr(f_ext),
+            ptr(dq), ptr(dqd), ptr(dqdd), ctypes.byref(opts), dtau.data_ptr()))
+        return dtau
+
+    def aba_jvp(self, q, qd, tau, dq, dqd, dtau, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Forward-mode derivative of the forward dynamics, no matrix: for directions ``dq``, ``dqd``, ``dtau`` [B, nv] (any may be None
+        for zero, not all), (qdd, dqdd) [B, nv] each with dqdd = (d qdd / d q) dq + (d qdd / d qd) dqd + H^-1 dtau (the matrices of
+        ``aba_derivatives``) at qdd = aba(q, qd, tau).  Two forward-dynamics launches and the kernel of ``rnea_jvp`` between them.
+        ``out``: a (qdd, dqdd) tuple to write into; qdd may be None.  A model with acceleration-source joints is refused."""
+        B, dt, sfx, stream = self._device_inputs([q, qd, tau], layout)
+        if f_ext is not None:
+            self._device_tensor(f_ext, dt)
+        self._check_f_ext(f_ext, B, layout)
+        vec = (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B)
+        self._directions((dq, dqd, dtau), ("dq", "dqd", "dtau"), vec, dt)
+        qdd, dqdd = self._outputs(out, (vec, vec), ("qdd", "dqdd"), dt, q.device)
+        if dqdd is None:
+            raise _lib.MecanoHipError(1, "dqdd is None")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, True, True, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_aba_jvp_{sfx}")(
+            self._h, B, q.data_ptr(), qd.data_ptr(), tau.data_ptr(), g, ptr(f_ext), ptr(dq), ptr(dqd), ptr(dtau), ctypes.byref(opts), ptr(qdd),
+            ptr(dqdd)))
+        return qdd, dqdd
+
+    def integrate_jvp(self, dt, qd, qdd, dq, dqd, dqdd, layout=_lib.LAYOUT_AOS, out=None):
+        """Forward-mode derivative of ``integrate``, one elementwise launch: for directions ``dq``, ``dqd``, ``dqdd`` [B, nv] (any may be
+        None for zero, not all), (dq_next, dqd_next) [B, nv]: the integrator's tangent map in the conventions of ``step_derivatives``
+        (dq_next the velocity-space step of q_next); ``integrate_vjp`` is its transpose.  The configuration does not appear.  SoA:
+        [nv, B].  fp64 / fp32.  ``out``: a (dq_next, dqd_next) tuple to write into; either may be None (not computed), not both."""
+        import torch
+        dtp = qd.dtype
+        if dtp not in (torch.float64, torch.float32):
+            raise TypeError("state tensors must be float64 or float32")
+        for t in (qd, qdd):
+            self._device_tensor(t, dtp)
+        B = self._batch(qd, self.nv, layout)
+        if self._batch(qdd, self.nv, layout) != B:
+            raise _lib.MecanoHipError(2, "batch sizes of the state matrices differ")
+        vec = (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B)
+        self._directions((dq, dqd, dqdd), ("dq", "dqd", "dqdd"), vec, dtp)
+        dqn, dqdn = self._outputs(out, (vec, vec), ("dq_next", "dqd_next"), dtp, qd.device)
+        if dqn is None and dqdn is None:
+            raise _lib.MecanoHipError(1, "both outputs are None")
+        opts = self._options(layout, True, True, torch.cuda.current_stream(qd.device).cuda_stream)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        sfx = "f64" if dtp == torch.float64 else "f32"
+        _lib.check(getattr(_lib.load(), f"mh_integrate_jvp_{sfx}")(
+            self._h, B, float(dt), qd.data_ptr(), qdd.data_ptr(), ptr(dq), ptr(dqd), ptr(dqdd), ctypes.byref(opts), ptr(dqn), ptr(dqdn)))
+        return dqn, dqdn
+
+    def step_jvp(self, dt, q, qd, tau, dq, dqd, dtau, gravity=(0.0, 0.0, -9.81), f_ext=None, layout=_lib.LAYOUT_AOS, out=None):
+        """Forward-mode derivative of the simulation step ``aba`` then ``integrate`` with step ``dt``, no matrix: for directions ``dq``,
+        ``dqd``, ``dtau`` [B, nv] (any may be None for zero, not all), (qdd, dqdd, dq_next, dqd_next) [B, nv] each with
+        (dq_next, dqd_next) = A (dq, dqd) + B dtau for the (A, B) of ``step_derivatives``: ``aba_jvp`` followed by ``integrate_jvp``, bit
+        for bit.  SoA: [nv, B].  fp64 / fp32.  ``out``: a (qdd, dqdd, dq_next, dqd_next) tuple to write into; any may be None, not all
+        three tangents.  A model with acceleration-source joints is refused."""
+        B, dtp, sfx, stream = self._device_inputs([q, qd, tau], layout)
+        if f_ext is not None:
+            self._device_tensor(f_ext, dtp)
+        self._check_f_ext(f_ext, B, layout)
+        vec = (B, self.nv) if layout == _lib.LAYOUT_AOS else (self.nv, B)
+        self._directions((dq, dqd, dtau), ("dq", "dqd", "dtau"), vec, dtp)
+        qdd, dqdd, dqn, dqdn = self._outputs(out, (vec, vec, vec, vec), ("qdd", "dqdd", "dq_next", "dqd_next"), dtp, q.device)
+        if dqdd is None and dqn is None and dqdn is None:
+            raise _lib.MecanoHipError(1, "all three tangents are None")
+        g, ra = self._root(gravity)
+        opts = self._options(layout, True, True, stream, root_acceleration=ra)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        _lib.check(getattr(_lib.load(), f"mh_aba_integrate_jvp_{sfx}")(
+            self._h, B, float(dt), q.data_ptr(), qd.data_ptr(), tau.data_ptr(), g, ptr(f_ext), ptr(dq), ptr(dqd), ptr(dtau), ctypes.byref(opts),
+            ptr(qdd), ptr(dqdd), ptr(dqn), ptr(dqdn)))
+        return qdd, dqdd, dqn, dqdn
+
     def _chart_call(self, name, a, b, b_cols, out_cols, layout, out):
         B, dt, sfx, stream = self._device_inputs([a], layout)
         aos = layout == _lib.LAYOUT_AOS
